@@ -10,7 +10,9 @@ Workload at N=1 = BASELINE.json configs[1]: VideoSeal 1.0, 256 bits, 32 frames o
 N > 1: one process per GPU (torchrun), the same batch per GPU (weak scaling), frames sharded over ranks,
 no data-path collective for embedding and one RCCL all-gather of the [32, 257] logits per step for extraction.
 
-Prints ONE JSON line (rank 0) with the driver's contract plus
+Prints ONE JSON line (rank 0) with the driver's contract (metric, value, unit, higher_is_better, dtype, ms_per_step = milliseconds per
+timed step).  --dump-outputs DIR writes what the last timed step returned (imgs_w, logits, ...) to DIR/<name>.npy; the inputs are
+seeded, so two builds can be compared output for output.  A plain run does only that; --full adds
   roofline     -- dominant kernel = the U-Net bottleneck 3x3 conv (384->384 @32x32, 81 % of the embed FLOPs):
                   algorithmic FLOPs per launch / average launch duration measured live with HIP events on the
                   launch stream, against 2500/3 = 833.3 TFLOP/s (dense f16 MFMA peak / 3 partial products of the default
@@ -19,6 +21,8 @@ Prints ONE JSON line (rank 0) with the driver's contract plus
                   FLOP/s over the same ceiling; `shell` = the HBM-bound kernels against 8 TB/s
   cpu_baseline -- the CPU oracle (torch fp32 restatement of the reference path, pinned to the reference by
                   tests/golden) timed on this host's cores on a bounded sample of the same workload
+  value_pipelined -- the same steps again with detect(batch i) under embed(batch i+1) on a second HIP stream
+  configs      -- (default workload) short legs over the other BASELINE configs, the other cards and the training step
 --mode chain = BASELINE configs[2]: 16-frame 768x768 clip -> embed -> JPEG/Crop/Resize/Brightness/Contrast/
 Saturation/Hue at the fixed validation strengths -> detect (the north-star "fused embed -> augment -> extract").
 """
@@ -81,6 +85,22 @@ def synthetic_batch(n, size, device, seed):
 
 
 CHAIN_ARGS = (40, 0.71, 0.71, 0.5, 1.5, 1.5, 0.1)     # JPEG q, Crop, Resize, Brightness, Contrast, Saturation, Hue (augmentation/__init__.py:107-123)
+
+DUMP_FULL_BYTES = 16 << 20      # --dump-outputs: an array up to this size is written whole, a larger one as DUMP_SAMPLE seeded elements
+DUMP_SAMPLE = 1 << 22           # (16 MB of float32 per sampled array; a step returns at most two arrays that large: 64 MB in all is not reached)
+
+
+def dump_outputs(outs, path):
+    """write each tensor of `outs` as path/<name>.npy in float32: whole up to DUMP_FULL_BYTES, else the elements at DUMP_SAMPLE flat indices
+    drawn from a fixed seed (the same indices for every array of the same size, so two builds compare element for element)"""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, t in outs.items():
+        a = t.detach().float()
+        if a.numel() * 4 > DUMP_FULL_BYTES:
+            idx = torch.randint(0, a.numel(), (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(0))
+            a, name = a.reshape(-1)[idx.to(a.device)], name + "_sample"
+        np.save(os.path.join(path, name + ".npy"), a.cpu().numpy())
 
 
 def cpu_baseline(card_path, size, mode, step_size, max_seconds=25.0):
@@ -216,7 +236,15 @@ def parse_args(argv=None):
     ap.add_argument("--dump-preds", default=None, help="rank 0 saves the (gathered) logits of the last timed step to this path (torch.save)")
     ap.add_argument("--no-extra", action="store_true", help="default run only: skip the short legs over the other BASELINE configs "
                     "(video mode, configs[2] chain, configs[3] streaming, configs[4] ChunkySeal detect, the training step)")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true", help="also measure what the headline does not need: per-kernel roofline timers, the pipelined "
+                    "re-run, the CPU baseline and (default workload) the legs over the other BASELINE configs; --no-cpu-baseline / --no-extra / "
+                    "--no-kernel-timers drop parts of it.  Without --full a run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="rank 0 writes what the last timed step returned to DIR/<name>.npy "
+                    "(float32; a fixed seeded sample of an array larger than %d MB)" % (DUMP_FULL_BYTES >> 20))
+    args = ap.parse_args(argv)
+    if not args.full:
+        args.no_cpu_baseline = args.no_kernel_timers = args.no_extra = True
+    return args
 
 
 
@@ -323,6 +351,7 @@ def _run(args, world, rank, dev, dist_on, n_ranks_seen):
         cmodel = CModel(cfg, model.state_dict(), scaling_w=model.blender.scaling_w, scaling_i=model.blender.scaling_i)
 
     aug_timers = []
+    last = {}       # what the last step's embed returned besides the logits (--dump-outputs)
 
     chain_seq = [None]
 
@@ -337,7 +366,7 @@ def _run(args, world, rank, dev, dist_on, n_ranks_seen):
         # Crop.plan() draws its window with torch.randint (geometric.py:128-150): the same window every step, so that --dump-preds and the
         # per-kernel timers see one workload from run to run
         torch.manual_seed(1234)
-        w = model.embed(frames, msgs, is_video=True, lowres_attenuation=args.lowres_attenuation)["imgs_w"]
+        w = last["imgs_w"] = model.embed(frames, msgs, is_video=True, lowres_attenuation=args.lowres_attenuation)["imgs_w"]
         timed = eng_ref[0] is not None and eng_ref[0].shell_timers is not None
         G.TIMERS = aug_timers if timed else None
         try:
@@ -365,7 +394,7 @@ def _run(args, world, rank, dev, dist_on, n_ranks_seen):
                 preds = gather_frame_logits(preds, B * world, align=B)
             return preds
         if cmodel is not None:
-            w = cmodel.embed(frames, msgs, step=(cfg.step_size if is_video else 1), lowres_attenuation=args.lowres_attenuation)
+            w = last["imgs_w"] = cmodel.embed(frames, msgs, step=(cfg.step_size if is_video else 1), lowres_attenuation=args.lowres_attenuation)
             return cmodel.detect(w)
         if args.detect_only:
             preds = model.detect(frames, is_video=True)["preds"]
@@ -376,13 +405,14 @@ def _run(args, world, rank, dev, dist_on, n_ranks_seen):
             s_emb, s_det = _streams(dev)
             s_emb.wait_stream(torch.cuda.current_stream()); s_det.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(s_emb):
-                w = model.embed(frames, msgs, is_video=is_video, lowres_attenuation=args.lowres_attenuation)["imgs_w"]
+                w = last["imgs_w"] = model.embed(frames, msgs, is_video=is_video, lowres_attenuation=args.lowres_attenuation)["imgs_w"]
                 ev = torch.cuda.Event(); ev.record(s_emb)
             with torch.cuda.stream(s_det):
                 s_det.wait_event(ev); w.record_stream(s_det)
                 preds = model.detect(w, is_video=True)["preds"]
         else:
             out = model.embed(frames, msgs, is_video=is_video, lowres_attenuation=args.lowres_attenuation)
+            last.update(out)
             preds = model.detect(out["imgs_w"], is_video=True)["preds"]
         if dist_on:
             preds = gather_frame_logits(preds, B * world, align=B)
@@ -413,6 +443,8 @@ def _run(args, world, rank, dev, dist_on, n_ranks_seen):
         t = torch.tensor([elapsed], device=coll_device(dev), dtype=torch.float64)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:      # before anything else runs a step (the pipelined re-run of --full)
+        dump_outputs(dict(last, preds=preds), args.dump_outputs)
 
     # the same K steps once more with detect(batch i) overlapped with embed(batch i + 1) on a second HIP stream (what a serving loop does
     # with independent batches); reported next to `value`, which stays the sequential number the kernel timers belong to
@@ -640,7 +672,7 @@ def main():
     if default_run:
         # the other BASELINE configs as short legs of the same command, each with its own roofline fractions
         def leg(extra, steps=20, warmup=3):
-            a = parse_args(["--gpus", str(args.gpus), "--steps", str(steps), "--warmup", str(warmup), "--no-cpu-baseline", "--no-extra"] + extra)
+            a = parse_args(["--gpus", str(args.gpus), "--steps", str(steps), "--warmup", str(warmup), "--full", "--no-cpu-baseline", "--no-extra"] + extra)
             # the previous leg's model and workspace are garbage by now, but torch's caching allocator keeps their blocks RESERVED in this process:
             # hand them back before the next leg builds its own (ChunkySeal's 1.8 B parameters + packed images are ~33 GB per rank; with the
             # one-device preflight's eight ranks sharing 288 GB the reserved leftovers of the earlier legs were the difference to an out-of-memory)

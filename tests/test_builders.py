@@ -12,7 +12,6 @@ import torch
 from tests._util import GOLDEN
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference"
 
 # (card whose key list the construction must reproduce, embedder model, extractor model, nbits, hidden_size_multiplier, img_size_proc, attenuation)
 CASES = [("videoseal_1.0", "unet_small2_yuv_quant", "convnext_tiny", 256, 1, 256, "jnd_1_1"),
@@ -108,7 +107,7 @@ def test_builders_accept_plain_dicts_and_refuse_what_is_outside_the_path():
                   get_dummy_augmenter())
 
 
-def test_shim_is_closed_without_a_reference_checkout():
+def test_shim_is_closed_without_a_reference_checkout(tmp_path):
     env = dict(os.environ, PYTHONPATH=ROOT)
     env.pop("VIDEOSEAL_REFERENCE_ROOT", None)
     code = ("import videoseal, importlib\n"
@@ -116,15 +115,59 @@ def test_shim_is_closed_without_a_reference_checkout():
             "    try:\n        importlib.import_module(m); raise SystemExit('resolved ' + m)\n    except ImportError: pass\n"
             "try:\n    videoseal.utils.bool_inst\n    raise SystemExit('attr')\nexcept AttributeError as e: assert 'VIDEOSEAL_REFERENCE_ROOT' in str(e)\n"
             "print('closed')")
-    r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, cwd="/tmp")
+    r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, cwd=str(tmp_path))
     assert r.returncode == 0 and "closed" in r.stdout, r.stdout + r.stderr
 
 
-@pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "videoseal")), reason="no reference checkout in this environment")
-def test_shim_overlays_a_reference_checkout():
+# The overlay runs over a stand-in checkout that the tests write: the layout of facebookresearch/videoseal (train.py next to videoseal/),
+# the files the shim shadows present as well (so "the shim's file wins" is a real choice), and for every module that the recorded import
+# statements of the reference's caller scripts (tests/golden/reference_script_imports.json) took from the checkout a file defining the
+# imported names -- or, where the unmodified checkout's file needed a third-party package that was absent, a file failing with that
+# package's ModuleNotFoundError.
+IMPORTS = os.path.join(GOLDEN, "reference_script_imports.json")
+_SHADOWED = ("models/videoseal.py", "models/embedder.py", "models/extractor.py", "modules/jnd.py", "augmentation/geometric.py",
+             "evals/metrics.py", "utils/cfg.py")
+_UTILS_INIT = ("from .dist import is_main_process  # noqa: F401  (a relative import inside the overlaid package)\n"
+               "def bool_inst(v):\n    return str(v).lower() in ('1', 'true', 'yes', 'y', 't')\n"
+               "def get_sha():\n    return 'unknown'\n"
+               "class Timer:\n    pass\n")
+
+
+def _stand_in_checkout(root):
+    """write the stand-in checkout under `root` and return its path"""
+    files = {"train.py": "", "videoseal/__init__.py": "", "videoseal/utils/__init__.py": _UTILS_INIT,
+             "videoseal/utils/dist.py": "def is_main_process():\n    return True\n", "videoseal/utils/logger.py": "class MetricLogger:\n    pass\n"}
+    for rel in _SHADOWED:
+        files["videoseal/" + rel] = "raise RuntimeError('the shim shadows this file')\n"
+    for m in ("modules/discriminator", "losses/__init__", "losses/videosealloss", "data/__init__", "data/loader", "utils/optim",
+              "utils/tensorboard", "utils/display", "models/baselines"):
+        files[f"videoseal/{m}.py"] = ""
+    names = {}
+    for _, _, mod, name, outcome in json.load(open(IMPORTS))["statements"]:
+        if outcome == "shim":
+            continue
+        rel = "/".join(mod.split("."))
+        rel = rel + "/__init__.py" if os.path.isdir(os.path.join(ROOT, rel)) else rel + ".py"
+        if outcome.startswith("third_party:"):
+            pkg = outcome.split(":", 1)[1]
+            files[rel] = f"raise ModuleNotFoundError(\"No module named '{pkg}'\", name='{pkg}')\n"
+        elif name is not None and rel != "videoseal/utils/__init__.py":
+            names.setdefault(rel, set()).add(name)
+    for rel, ns in names.items():
+        files[rel] = "".join(f"def {n}(*args, **kwargs):\n    return None\n" for n in sorted(ns))
+    for rel, text in files.items():
+        path = os.path.join(root, rel)
+        os.makedirs(os.path.dirname(path), exist_ok=True)
+        with open(path, "w") as f:
+            f.write(text)
+    return str(root)
+
+
+def test_shim_overlays_a_reference_checkout(tmp_path):
     """VIDEOSEAL_REFERENCE_ROOT: modules the shim does not define (train.py:55-72: videoseal.utils.dist / logger, utils.bool_inst, ...) come
     from the checkout; everything on the embed / extract path stays this package"""
-    env = dict(os.environ, PYTHONPATH=ROOT, VIDEOSEAL_REFERENCE_ROOT=REF)
+    ref = _stand_in_checkout(tmp_path / "checkout")
+    env = dict(os.environ, PYTHONPATH=ROOT, VIDEOSEAL_REFERENCE_ROOT=ref)
     code = ("import videoseal, videoseal_amd\n"
             "import videoseal.utils as utils\n"
             "import videoseal.utils.dist as udist\n"
@@ -135,92 +178,76 @@ def test_shim_overlays_a_reference_checkout():
             "from videoseal.modules.jnd import JND\n"
             "from videoseal.augmentation.augmenter import Augmenter\n"
             "from videoseal.evals.metrics import bit_accuracy, psnr\n"
-            "assert udist.__file__.startswith('" + REF + "') and ulogger.__file__.startswith('" + REF + "')\n"
+            "assert udist.__file__.startswith('" + ref + "') and ulogger.__file__.startswith('" + ref + "')\n"
             "assert utils.bool_inst('yes') is True and callable(utils.get_sha)\n"
             "assert callable(udist.is_main_process) and hasattr(ulogger, 'MetricLogger')\n"
             "assert Videoseal is videoseal_amd.Videoseal and build_embedder is videoseal_amd.builders.build_embedder and b2 is build_embedder\n"
             "assert JPEG is videoseal_amd.augmentation.JPEG and JND is videoseal_amd.model.JND and Augmenter is videoseal_amd.augmentation.Augmenter\n"
             "assert bit_accuracy is videoseal_amd.metrics.bit_accuracy\n"
-            "import importlib.util as iu\n"          # (importing these needs torchvision / lpips / timm, which the checkout's own code depends on)
+            "import importlib.util as iu\n"
             "for m in ('videoseal.modules.discriminator', 'videoseal.losses.videosealloss', 'videoseal.data.loader', 'videoseal.utils.optim',\n"
             "          'videoseal.utils.tensorboard', 'videoseal.utils.display', 'videoseal.models.baselines'):\n"
-            "    assert iu.find_spec(m).origin.startswith('" + REF + "'), m\n"
+            "    assert iu.find_spec(m).origin.startswith('" + ref + "'), m\n"
             "for m in ('videoseal.models.videoseal', 'videoseal.models.embedder', 'videoseal.models.extractor', 'videoseal.modules.jnd',\n"
             "          'videoseal.augmentation.geometric', 'videoseal.evals.metrics', 'videoseal.utils.cfg'):\n"
             "    assert iu.find_spec(m).origin.startswith('" + ROOT + "'), m\n"
             "print('overlay ok')")
-    r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, cwd="/tmp")
+    r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, cwd=str(tmp_path))
     assert r.returncode == 0 and "overlay ok" in r.stdout, r.stdout + r.stderr
 
 
 _CLOSURE = r'''
-import ast, importlib, json, os, sys
-ref = os.environ["VIDEOSEAL_REFERENCE_ROOT"]
-files = {"train.py": None, "inference_streaming.py": None, "inference_av.py": None,
-         "videoseal/evals/full.py": "videoseal.evals", "videoseal/evals/speed.py": "videoseal.evals"}
-resolved, third_party, broken = [], {}, []
+import importlib, json, os, sys
+ref, root = os.environ["VIDEOSEAL_REFERENCE_ROOT"], os.environ["PYTHONPATH"]
+outcome = {}
 def third(e):
     while e is not None:
         if isinstance(e, ModuleNotFoundError) and e.name and not e.name.startswith("videoseal"):
             return e.name
         e = e.__cause__ or e.__context__
     return None
-for rel, pkg in files.items():
-    tree = ast.parse(open(os.path.join(ref, rel)).read())
-    for node in ast.walk(tree):
-        wants = []
-        if isinstance(node, ast.Import):
-            wants = [(a.name, None) for a in node.names if a.name.split(".")[0] == "videoseal"]
-        elif isinstance(node, ast.ImportFrom):
-            mod = node.module or ""
-            if node.level:
-                base = pkg.split(".")[: len(pkg.split(".")) - (node.level - 1)] if pkg else None
-                if base is None:
-                    continue
-                mod = ".".join(base + ([mod] if mod else []))
-            if mod.split(".")[0] == "videoseal":
-                wants = [(mod, a.name) for a in node.names]
-        for mod, name in wants:
-            tag = f"{rel}:{node.lineno} {mod}" + (f".{name}" if name else "")
-            try:
-                m = importlib.import_module(mod)
-                if name is not None and not hasattr(m, name):
-                    importlib.import_module(mod + "." + name)          # `from pkg import submodule`
-                resolved.append(tag)
-            except BaseException as e:
-                t = third(e)
-                if t:
-                    third_party.setdefault(t, []).append(tag)
-                else:
-                    broken.append(tag + " -> " + repr(e))
+def where(obj):
+    f = getattr(obj, "__file__", None) or getattr(sys.modules.get(getattr(obj, "__module__", None) or ""), "__file__", None) or ""
+    return "shim" if f.startswith(root + os.sep) else "checkout" if f.startswith(ref + os.sep) else "elsewhere: " + f
+for rel, line, mod, name, _ in json.load(open(sys.argv[1]))["statements"]:
+    tag = f"{rel}:{line} {mod}" + (f".{name}" if name else "")
+    try:
+        m = importlib.import_module(mod)
+        if name is not None and not hasattr(m, name):
+            m, name = importlib.import_module(mod + "." + name), None          # `from pkg import submodule`
+        outcome[tag] = where(m if name is None else getattr(m, name))
+    except BaseException as e:
+        t = third(e)
+        outcome[tag] = ("third_party:" + t) if t else ("broken: " + repr(e))
 import videoseal_amd, videoseal.evals.metrics as M, videoseal.utils.cfg as C, videoseal.models as MD
 own = {"Videoseal": MD.Videoseal is videoseal_amd.Videoseal, "bit_accuracy": M.bit_accuracy is videoseal_amd.metrics.bit_accuracy,
        "ssim": M.ssim is videoseal_amd.metrics.ssim, "accuracy": M.accuracy is videoseal_amd.metrics.accuracy,
        "setup_model_from_checkpoint": C.setup_model_from_checkpoint is videoseal_amd.cfg.setup_model_from_checkpoint,
        "setup_model": C.setup_model is videoseal_amd.cfg.setup_model}
-print("CLOSURE " + json.dumps({"resolved": resolved, "third_party": third_party, "broken": broken, "own": own}))
+print("CLOSURE " + json.dumps({"outcome": outcome, "own": own}))
 '''
 
 
-@pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "videoseal")), reason="no reference checkout in this environment")
-def test_every_videoseal_import_of_the_reference_scripts_resolves_through_the_overlay():
+def test_every_videoseal_import_of_the_reference_scripts_resolves_through_the_overlay(tmp_path):
     """import closure of the callers the shim claims to carry: every `import videoseal...` / `from videoseal... import name` statement of
-    train.py, inference_streaming.py, inference_av.py, evals/full.py and evals/speed.py is parsed out of the checkout and resolved through
-    the overlay.  A statement may fail only because a THIRD-PARTY package of the checkout's own code is absent here (printed); the path's
-    names must be this package's objects."""
-    import json
-    env = dict(os.environ, PYTHONPATH=ROOT, VIDEOSEAL_REFERENCE_ROOT=REF)
-    r = subprocess.run([sys.executable, "-c", _CLOSURE], env=env, capture_output=True, text=True, cwd="/tmp")
+    train.py, inference_streaming.py, inference_av.py, evals/full.py and evals/speed.py, as recorded from the checkout in
+    tests/golden/reference_script_imports.json, resolves through the overlay to where it resolved over the unmodified checkout: this
+    package's object, the checkout's file, or a missing third-party package of the checkout's own code.  No statement may break, and the
+    path's names must be this package's objects."""
+    ref = _stand_in_checkout(tmp_path / "checkout")
+    env = dict(os.environ, PYTHONPATH=ROOT, VIDEOSEAL_REFERENCE_ROOT=ref)
+    r = subprocess.run([sys.executable, "-c", _CLOSURE, IMPORTS], env=env, capture_output=True, text=True, cwd=str(tmp_path))
     line = [l for l in r.stdout.splitlines() if l.startswith("CLOSURE ")]
     assert r.returncode == 0 and line, r.stdout[-2000:] + r.stderr[-4000:]
     res = json.loads(line[0][8:])
-    print("third-party packages missing here:", {k: len(v) for k, v in res["third_party"].items()})
-    assert not res["broken"], "\n".join(res["broken"])
+    want = {f"{rel}:{ln} {mod}" + (f".{name}" if name else ""): out for rel, ln, mod, name, out in json.load(open(IMPORTS))["statements"]}
+    assert len(want) == 60 and res["outcome"].keys() == want.keys()
+    wrong = {k: (res["outcome"][k], v) for k, v in want.items() if res["outcome"][k] != v}
+    assert not wrong, wrong
     assert all(res["own"].values()), res["own"]
     must = ["train.py:65 videoseal.evals.metrics.accuracy", "train.py:65 videoseal.evals.metrics.iou", "train.py:65 videoseal.evals.metrics.ssim",
             "train.py:67 videoseal.models.build_extractor", "videoseal/evals/full.py:53 videoseal.utils.cfg.setup_model_from_checkpoint",
             "videoseal/evals/speed.py:34 videoseal.utils.cfg.setup_model_from_checkpoint", "videoseal/evals/full.py:46 videoseal.evals.metrics.msssim",
             "videoseal/evals/full.py:46 videoseal.evals.metrics.bd_rate", "videoseal/evals/full.py:46 videoseal.evals.metrics.vmaf_on_tensor",
             "inference_streaming.py:20 videoseal.evals.metrics.bit_accuracy"]
-    missing = [m for m in must if m not in res["resolved"]]
-    assert not missing, (missing, res["third_party"])
+    assert all(res["outcome"][m] in ("shim", "checkout") for m in must), {m: res["outcome"][m] for m in must}

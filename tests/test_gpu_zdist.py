@@ -396,9 +396,9 @@ def test_bench_stream_leg_with_two_ranks_on_one_gpu_gathers_the_single_process_l
 
 @pytest.mark.gpu
 def test_bench_default_legs_with_two_ranks_on_one_gpu(tmp_path):
-    """the DEFAULT command of the driver's scaling run (`bench.py --gpus 2 --steps K --warmup W`: image-mode headline, weak scaling, plus the
+    """the driver's scaling run with --full (`bench.py --gpus 2 --steps K --warmup W --full`: image-mode headline, weak scaling, plus the
     stream_1024 and ChunkySeal legs that run at every rank count) with two ranks on one device: exits cleanly with one line"""
-    line = _bench_two_ranks_one_gpu(["--steps", "2", "--warmup", "1", "--no-kernel-timers"], tmp_path)
+    line = _bench_two_ranks_one_gpu(["--steps", "2", "--warmup", "1", "--full", "--no-kernel-timers"], tmp_path)
     assert line["n_gpus"] == 2 and line["n_ranks_seen"] == 2 and line["scaling"] == "weak" and line["cpu_baseline"] is None
     assert line["shards"] == [[0, 32], [32, 64]] and line["config"]["batch_per_gpu"] == 32
     legs = line["configs"]
@@ -411,11 +411,11 @@ def test_bench_default_legs_with_two_ranks_on_one_gpu(tmp_path):
 
 @pytest.mark.gpu
 def test_bench_eight_ranks_on_one_gpu_preflight(tmp_path):
-    """the driver's 8-GPU command (`bench.py --gpus 8 --steps K --warmup W`, one rank per GPU under torch.distributed.run) with EIGHT Python ranks
+    """the driver's 8-GPU command with --full (`bench.py --gpus 8 --steps K --warmup W --full`, one rank per GPU under torch.distributed.run) with EIGHT Python ranks
     on the one device the build has (gloo group, VS_BENCH_COLLECTIVE): all eight build the model, take the shards [[0, 128], ..., [896, 1024]] of the
     1024-frame clip, gather, and exit with ONE line; the ChunkySeal leg builds 1.8 B random parameters in every rank.  The line carries the
     host side of a rank (peak RSS, start-up seconds; max over ranks) -- recorded in DESIGN.md section 8.  (videoseal/utils/dist.py:210-213)"""
-    line = _bench_two_ranks_one_gpu(["--steps", "1", "--warmup", "1", "--no-kernel-timers"], tmp_path, timeout=2400, ranks=8)
+    line = _bench_two_ranks_one_gpu(["--steps", "1", "--warmup", "1", "--full", "--no-kernel-timers"], tmp_path, timeout=2400, ranks=8)
     assert line["n_gpus"] == 8 and line["n_ranks_seen"] == 8 and line["scaling"] == "weak"
     assert line["shards"] == [[32 * r, 32 * r + 32] for r in range(8)] and line["allgather_ms"] > 0
     st = [v for k, v in line["configs"].items() if k.startswith("stream_1024")][0]

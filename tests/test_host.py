@@ -158,57 +158,24 @@ def test_metrics_match_oracle():
     assert bit_accuracy(pix, torch.randint(0, 2, (2, 8))).shape == (2,)
 
 
-def _reference_metrics_module():
-    """the checkout's own evals/metrics.py, executed as a file (its `pytorch_msssim` import is absent here: a dummy module stands in, so
-    only the functions that do not touch it are usable)"""
-    import importlib.util
-    import sys
-    import types
-    path = "/root/reference/videoseal/evals/metrics.py"
-    if not os.path.isfile(path):
-        pytest.skip("no reference checkout in this environment")
-    added = "pytorch_msssim" not in sys.modules and importlib.util.find_spec("pytorch_msssim") is None
-    if added:
-        sys.modules["pytorch_msssim"] = types.ModuleType("pytorch_msssim")
-    try:
-        spec = importlib.util.spec_from_file_location("_ref_metrics_for_test", path)
-        mod = importlib.util.module_from_spec(spec)
-        spec.loader.exec_module(mod)
-    finally:
-        if added:
-            sys.modules.pop("pytorch_msssim", None)
-    return mod
-
-
 def test_mask_and_message_metrics_equal_the_reference_functions():
-    """train.py:65,649,667-670 / evals/full.py:46: accuracy, iou, linf, pvalue, capacity, bit_accuracy(+_1msg, masked) against the
-    unmodified evals/metrics.py on seeded inputs incl. empty masks / empty unions"""
-    R = _reference_metrics_module()
+    """train.py:65,649,667-670 / evals/full.py:46: accuracy, iou, linf, pvalue, capacity, bit_accuracy(+_1msg, masked) against what the
+    unmodified evals/metrics.py returned on the same seeded inputs incl. empty masks / empty unions (tests/golden/reference_metrics.npz,
+    written by tests/golden/make_golden_metrics.py): equal values and dtypes"""
+    import importlib.util
+    import numpy as np
     from videoseal_amd import metrics as M
-    g = torch.Generator().manual_seed(5)
-    preds = torch.randn(5, 1, 12, 9, generator=g)
-    targets = (torch.rand(5, 1, 12, 9, generator=g) > 0.6).float()
-    targets[3] = 0
-    preds[3] = -1.0                                                      # empty union for label 1
-    for thr in (0.0, 0.3):
-        assert torch.equal(M.accuracy(preds, targets, thr), R.accuracy(preds, targets, thr))
-        for label in (0, 1):
-            assert torch.equal(M.iou(preds.clone(), targets, thr, label), R.iou(preds.clone(), targets, thr, label))
-    a, b = torch.rand(2, 3, 20, 20, generator=g), torch.rand(2, 3, 20, 20, generator=g)
-    assert torch.equal(M.linf(a, b), R.linf(a, b)) and torch.equal(M.psnr(a, b), R.psnr(a, b)) and torch.equal(M.psnr(a, b, True), R.psnr(a, b, True))
-    bits = torch.randint(0, 2, (4, 32), generator=g)
-    logits = (bits.float() * 2 - 1) * torch.rand(4, 32, generator=g) + 0.4 * torch.randn(4, 32, generator=g)
-    logits[1] = bits[1].float() * 2 - 1                                  # a perfect row: p log p at 0
-    assert torch.equal(M.bit_accuracy(logits, bits), R.bit_accuracy(logits, bits))
-    assert torch.equal(M.pvalue(logits, bits), R.pvalue(logits, bits))
-    assert torch.equal(M.capacity(logits, bits), R.capacity(logits, bits))
-    pix = torch.randn(3, 8, 6, 6, generator=g)
-    tb = torch.randint(0, 2, (3, 8), generator=g)
-    mask = (torch.rand(3, 1, 6, 6, generator=g) > 0.5).float()
-    mask[:] = mask[0]                                                    # (masked_select + view needs equal counts, as in the reference)
-    assert torch.equal(M.bit_accuracy(pix, tb, mask), R.bit_accuracy(pix, tb, mask))
-    assert torch.equal(M.bit_accuracy_1msg(pix, tb), R.bit_accuracy_1msg(pix, tb))
-    assert torch.equal(M.bit_accuracy_1msg(pix, tb, mask), R.bit_accuracy_1msg(pix, tb, mask))
+    spec = importlib.util.spec_from_file_location("make_golden_metrics", os.path.join(ROOT, "tests", "golden", "make_golden_metrics.py"))
+    G = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(G)
+    z = np.load(os.path.join(ROOT, "tests", "golden", "reference_metrics.npz"))
+    x = {k[3:]: torch.from_numpy(z[k]) for k in z.files if k.startswith("in_")}
+    got = G.metric_outputs(M, x)
+    want = {k[4:]: torch.from_numpy(z[k]) for k in z.files if k.startswith("out_")}
+    assert got.keys() == want.keys() and len(want) == 15
+    for k, v in want.items():
+        g = torch.as_tensor(got[k])
+        assert g.dtype == v.dtype and torch.equal(g, v), (k, g, v)
 
 
 def test_ssim_and_msssim_against_an_independent_float64_evaluation():

@@ -9,15 +9,15 @@ REF=$PWD/videoseal_amd/csrc/build_ab/libvideoseal_hip_ref.so
 [ -f $REF ] || { echo "no $REF"; exit 1; }
 for m in image video chain; do
   extra=""; [ $m != image ] && extra="--mode $m"
-  python bench.py --no-cpu-baseline --no-extra $extra > $O/${m}_new.json 2>/dev/null
-  VIDEOSEAL_LIB=$REF python bench.py --no-cpu-baseline --no-extra $extra > $O/${m}_ref.json 2>/dev/null
-  python bench.py --no-cpu-baseline --no-extra $extra > $O/${m}_new2.json 2>/dev/null
-  VIDEOSEAL_LIB=$REF python bench.py --no-cpu-baseline --no-extra $extra > $O/${m}_ref2.json 2>/dev/null
+  python bench.py --full --no-cpu-baseline --no-extra $extra > $O/${m}_new.json 2>/dev/null
+  VIDEOSEAL_LIB=$REF python bench.py --full --no-cpu-baseline --no-extra $extra > $O/${m}_ref.json 2>/dev/null
+  python bench.py --full --no-cpu-baseline --no-extra $extra > $O/${m}_new2.json 2>/dev/null
+  VIDEOSEAL_LIB=$REF python bench.py --full --no-cpu-baseline --no-extra $extra > $O/${m}_ref2.json 2>/dev/null
 done
-python bench.py --no-cpu-baseline --mode stream --steps 3 --warmup 1 > $O/stream_new.json 2>/dev/null
-VIDEOSEAL_LIB=$REF python bench.py --no-cpu-baseline --mode stream --steps 3 --warmup 1 > $O/stream_ref.json 2>/dev/null
-python bench.py --no-cpu-baseline --detect-only --steps 30 --warmup 3 > $O/detect_new.json 2>/dev/null
-VIDEOSEAL_LIB=$REF python bench.py --no-cpu-baseline --detect-only --steps 30 --warmup 3 > $O/detect_ref.json 2>/dev/null
+python bench.py --full --no-cpu-baseline --mode stream --steps 3 --warmup 1 > $O/stream_new.json 2>/dev/null
+VIDEOSEAL_LIB=$REF python bench.py --full --no-cpu-baseline --mode stream --steps 3 --warmup 1 > $O/stream_ref.json 2>/dev/null
+python bench.py --full --no-cpu-baseline --detect-only --steps 30 --warmup 3 > $O/detect_new.json 2>/dev/null
+VIDEOSEAL_LIB=$REF python bench.py --full --no-cpu-baseline --detect-only --steps 30 --warmup 3 > $O/detect_ref.json 2>/dev/null
 python - <<PY
 import json,glob
 for f in sorted(glob.glob("$O/*.json")):

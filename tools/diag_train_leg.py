@@ -19,12 +19,12 @@ def show(tag):
 
 if "--train-first" in sys.argv:
     show("fresh process")
-bench.run(bench.parse_args([]))
+bench.run(bench.parse_args(["--full"]))
 legs = [("video", ["--mode", "video"], 5, 2), ("chain", ["--mode", "chain"], 5, 2), ("stream", ["--mode", "stream", "--frames", "1024"], 2, 1),
         ("chunkyseal", ["--card", "chunkyseal", "--size", "1024", "--batch", "16", "--detect-only"], 3, 1), ("pixelseal", ["--card", "pixelseal"], 5, 2),
         ("videoseal_0.0", ["--card", "videoseal_0.0"], 5, 2)]
 for name, extra, k, w in legs:
-    bench.run(bench.parse_args(["--steps", str(k), "--warmup", str(w), "--no-cpu-baseline", "--no-extra"] + extra))
+    bench.run(bench.parse_args(["--steps", str(k), "--warmup", str(w), "--full", "--no-cpu-baseline", "--no-extra"] + extra))
 show("after the default run's legs")
 show("again")
 gc.collect(); torch.cuda.empty_cache()

@@ -29,11 +29,13 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def compile_s(src):
     if src.endswith(".s"):
         return open(src).read()
-    out = os.path.join(tempfile.gettempdir(), os.path.basename(src) + ".s")
-    cmd = ["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", f"-I{ROOT}/include", f"-I{ROOT}/videoseal_amd/csrc", "-S",
-           "--cuda-device-only", src, "-o", out]
-    subprocess.run(cmd, check=True, stderr=subprocess.DEVNULL)
-    return open(out).read()
+    with tempfile.TemporaryDirectory() as tmp:      # (a private directory: another user's or a concurrent run's .s of the same name)
+        out = os.path.join(tmp, os.path.basename(src) + ".s")
+        cmd = ["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", f"-I{ROOT}/include", f"-I{ROOT}/videoseal_amd/csrc", "-S",
+               "--cuda-device-only", src, "-o", out]
+        subprocess.run(cmd, check=True, stderr=subprocess.DEVNULL)
+        with open(out) as f:
+            return f.read()
 
 
 def kernels(text, sub):
