@@ -409,6 +409,27 @@ int64_t vs_percep_partial_doubles(int F, int H, int W);
 int vs_percep_mse(const float* imgs, const float* imgs_w, int F, int H, int W, int yuv, double* partial, float* loss, void* stream);
 int vs_percep_mse_grad(const float* imgs, const float* imgs_w, int F, int H, int W, int yuv, float upstream, float* d_imgs_w, void* stream);
 
+/* ---- SSIM / MS-SSIM and JND perceptual terms, and the SSIM / MS-SSIM metrics (csrc/ssim.hip; losses/ssim.py, losses/jndloss.py, modules/jnd.py).
+ * Frames are P = F * C independent fp32 planes [P][H][W]; window: 11 taps (win11, a HOST array: losses/ssim.py:16-30, sigma 1.5, fp32), 'valid'
+ * filtering -> maps of (H - 10) x (W - 10), K = (0.01, 0.03).  H or W < 11, P <= 0 or a null pointer -> VS_ERR_BAD_ARG without a launch.
+ * vs_ssim_stats: out[p] = mean of the SSIM map of plane p, out[P + p] = mean of its contrast-structure map (losses/ssim.py:91-107), doubles;
+ *   partial = vs_ssim_partial_doubles(P, H, W) doubles.  Per-block sums in double finished in a fixed order: two calls are bit-identical.
+ * vs_ssim_grad: dy [P][H][W] = d/dy of sum_p (g_ssim[p] * mean SSIM_p + g_cs[p] * mean cs_p) (device arrays of P floats; the 1 / ((H-10)(W-10)) is
+ *   applied inside), plus, when g_coarse is not NULL, 0.25 * g_coarse[p][(r + H % 2) / 2][(c + W % 2) / 2]: the adjoint of vs_avgpool2_pad applied
+ *   to the gradient of the next coarser MS-SSIM level (losses/ssim.py:232-239).  A gather: no reduction.  The gradient w.r.t. x is not built.
+ * vs_avgpool2_pad: F.avg_pool2d(kernel 2, padding side % 2), zeros counted (losses/ssim.py:237-239), of x and y -> [P][(H + H%2)/2][(W + W%2)/2].
+ * vs_jnd_loss / vs_jnd_loss_grad: mean((|imgs_w - imgs| - hmap)^2) over [F][3][H][W], hmap [F][1][H][W] = vs_jnd_heatmap(imgs) (jndloss.py:27-31;
+ *   JND() defaults, modules/jnd.py:14-26, 80-108), and upstream * d loss / d imgs_w = 2 (|d| - h) sign(d) / N with sign(0) = 0;
+ *   partial = vs_jnd_loss_partial_doubles(F, H, W) doubles. */
+int64_t vs_ssim_partial_doubles(int P, int H, int W);
+int vs_ssim_stats(const float* x, const float* y, int P, int H, int W, float data_range, const float* win11, double* partial, double* out, void* stream);
+int vs_ssim_grad(const float* x, const float* y, const float* g_ssim, const float* g_cs, const float* g_coarse, int P, int H, int W, float data_range,
+                 const float* win11, float* dy, void* stream);
+int vs_avgpool2_pad(const float* x, const float* y, int P, int H, int W, float* xo, float* yo, void* stream);
+int64_t vs_jnd_loss_partial_doubles(int F, int H, int W);
+int vs_jnd_loss(const float* imgs, const float* imgs_w, const float* hmap, int F, int H, int W, double* partial, float* loss, void* stream);
+int vs_jnd_loss_grad(const float* imgs, const float* imgs_w, const float* hmap, int F, int H, int W, float upstream, float* d_imgs_w, void* stream);
+
 /* Bilinear x2 (align_corners=False) of cat(x, skip*skip_scale) along channels.  unet.py:186-191 + common.py:46. */
 int vs_upcat2x(const float* x, int C1, int64_t ld1, const float* skip, int C2, int64_t ld2, float skip_scale,
                int B, int H, int W, float* out, int64_t out_ld, void* stream);

@@ -8,6 +8,7 @@ autograd only carries the graph.  Nodes:
   DetectTrainFn   frames at the working size + detector parameters -> logits     (extractor.py:154-167)
   CropFlipFn, ResizeFn, MaskBlendFn, ColorFn, SteFn                              the augmentations between the two (augmenter.py:154-194)
   PercepLossFn, DecodeLossFn                                                     the generator-side loss terms (videosealloss.py:121-156)
+  SsimStatsFn, JndLossFn                                                         the 'ssim' / 'msssim' / 'jnd' perceptual terms (losses/ssim.py, jndloss.py)
 Parameters enter the two network nodes as explicit inputs, so `.grad` accumulation, `torch.autograd.grad(loss, last_layer)` and DDP hooks work as
 with any nn.Module.  The operands the backward needs live in the engine's workspace (tagged "tr."), owned by the LAST training forward of the
 model: a backward through an older graph raises instead of reading overwritten buffers.  No CPU path: without the library or a GPU this raises.
@@ -459,10 +460,203 @@ class DecodeLossFn(torch.autograd.Function):
         return d * up, None, None
 
 
+# ---- SSIM / MS-SSIM / JND terms (csrc/ssim.hip; losses/ssim.py, losses/jndloss.py)
+from .metrics import _MS_WEIGHTS as MS_WEIGHTS                 # noqa: E402  (losses/ssim.py:222-223; one copy, in metrics.py)
+# modules/jnd.py:29-45: 5x5 luminance taps, Sobel x, Sobel y -- the host array vs_jnd_heatmap takes (fixed, not weights of a checkpoint)
+_JND_TAPS = (1, 1, 1, 1, 1, 1, 2, 2, 2, 1, 1, 2, 0, 2, 1, 1, 2, 2, 2, 1, 1, 1, 1, 1, 1,
+             -1, 0, 1, -2, 0, 2, -1, 0, 1,
+             1, 2, 1, 0, 0, 0, -1, -2, -1)
+_host_cache: dict = {}
+
+
+def _win11():
+    """the 11-tap window of losses/ssim.py:16-30 in fp32, as the host array the kernels take"""
+    if "win" not in _host_cache:
+        import ctypes as C
+        from .metrics import _gauss_window
+        w = _gauss_window(11, 1.5, torch.zeros(1))
+        _host_cache["win"] = (C.c_float * 11)(*[float(v) for v in w])
+    return _host_cache["win"]
+
+
+def _jnd_taps():
+    if "jnd" not in _host_cache:
+        import ctypes as C
+        _host_cache["jnd"] = (C.c_float * 43)(*[float(v) for v in _JND_TAPS])
+    return _host_cache["jnd"]
+
+
+def _ms_weights(dev) -> torch.Tensor:
+    key = ("msw", str(dev))
+    if key not in _host_cache:              # one upload per device: the loss itself never touches the host
+        _host_cache[key] = torch.tensor(MS_WEIGHTS, dtype=torch.float64, device=dev).view(-1, 1, 1)
+    return _host_cache[key]
+
+
+def avgpool2_pad(x: torch.Tensor, y: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """F.avg_pool2d(kernel 2, padding side % 2) of both frames in one launch (losses/ssim.py:237-239)"""
+    F_, Cc, H, W = x.shape
+    xo = torch.empty(F_, Cc, (H + H % 2) // 2, (W + W % 2) // 2, device=x.device, dtype=torch.float32)
+    yo = torch.empty_like(xo)
+    N.check(N.lib().vs_avgpool2_pad(N.ptr(x), N.ptr(y), F_ * Cc, H, W, N.ptr(xo), N.ptr(yo), N.stream()), "vs_avgpool2_pad")
+    return xo, yo
+
+
+def ssim_pyramid(x: torch.Tensor, y: torch.Tensor, levels: int = 1, data_range: float = 1.0):
+    """per-plane means of the SSIM and contrast-structure maps at `levels` dyadic scales: (ssim [L, F, C], cs [L, F, C]) in float64 on the device,
+    and the pyramid [(x_l, y_l)] the adjoint needs.  x, y: [F, C, H, W] fp32 contiguous device tensors."""
+    if x.dim() != 4 or x.shape != y.shape:
+        raise ValueError(f"SSIM: two [F, C, H, W] tensors of equal shape, got {tuple(x.shape)} and {tuple(y.shape)}")
+    L = N.lib()
+    F_, Cc = x.shape[:2]
+    P = F_ * Cc
+    out = torch.empty(levels, 2, F_, Cc, device=x.device, dtype=torch.float64)
+    pyr = []
+    for lv in range(levels):
+        H, W = x.shape[-2:]
+        if min(H, W) < 11:
+            raise ValueError(f"SSIM on the HIP path needs sides of at least 11 pixels, got {H} x {W}")
+        part = torch.empty(int(L.vs_ssim_partial_doubles(P, H, W)), device=x.device, dtype=torch.float64)
+        N.check(L.vs_ssim_stats(N.ptr(x), N.ptr(y), P, H, W, float(data_range), _win11(), N.ptr(part), N.ptr(out[lv]), N.stream()), "vs_ssim_stats")
+        pyr.append((x, y))
+        if lv < levels - 1:
+            x, y = avgpool2_pad(x, y)
+    return out[:, 0], out[:, 1], pyr
+
+
+def ssim_grad(x, y, g_ssim, g_cs, g_coarse=None, data_range: float = 1.0) -> torch.Tensor:
+    """vs_ssim_grad: d/dy of sum_planes (g_ssim * mean SSIM + g_cs * mean cs) [+ the pooled-level gradient g_coarse through the 2 x 2 mean]"""
+    F_, Cc, H, W = y.shape
+    d = torch.empty_like(y)
+    N.check(N.lib().vs_ssim_grad(N.ptr(x), N.ptr(y), N.ptr(g_ssim), N.ptr(g_cs), N.ptr(g_coarse), F_ * Cc, H, W, float(data_range), _win11(), N.ptr(d),
+                                 N.stream()), "vs_ssim_grad")
+    return d
+
+
+class SsimStatsFn(torch.autograd.Function):
+    """(imgs, imgs_w) -> (ssim [L, F, C], cs [L, F, C]), float64: the per-plane statistics of losses/ssim.py:91-107 at L dyadic levels (L = 1: SSIM;
+    L = 5: the factors of MS-SSIM, losses/ssim.py:232-239).  The pyramid of the forward is KEPT for the backward (4/3 of the two frames), which runs
+    vs_ssim_grad from the coarsest level up, each level adding the pooled gradient of the one below in the same store.  Gradient w.r.t. imgs_w only."""
+
+    @staticmethod
+    def forward(ctx, imgs, imgs_w, levels, data_range):
+        s, c, pyr = ssim_pyramid(N.f32c(imgs), N.f32c(imgs_w), int(levels), float(data_range))
+        ctx.save_for_backward(*[t for pair in pyr for t in pair])
+        ctx.data_range = float(data_range)
+        return s, c
+
+    @staticmethod
+    def backward(ctx, g_ssim, g_cs):
+        saved = ctx.saved_tensors
+        gs, gc = g_ssim.to(torch.float32).contiguous(), g_cs.to(torch.float32).contiguous()
+        g = None
+        for lv in reversed(range(len(saved) // 2)):
+            g = ssim_grad(saved[2 * lv], saved[2 * lv + 1], gs[lv], gc[lv], g, ctx.data_range)
+        return None, g, None, None
+
+
+def ssim_loss(imgs: torch.Tensor, imgs_w: torch.Tensor) -> torch.Tensor:
+    """losses/ssim.py:251-291 `SSIM()`: -mean over images and channels"""
+    s, _ = SsimStatsFn.apply(imgs, imgs_w, 1, 1.0)
+    return (-s[0].mean()).float()
+
+
+def msssim_loss(imgs: torch.Tensor, imgs_w: torch.Tensor) -> torch.Tensor:
+    """losses/ssim.py:294-334 `MSSSIM()`: -mean(prod_l relu(f_l)^w_l), f = cs at the first four levels, ssim at the fifth"""
+    if min(imgs_w.shape[-2:]) <= 160:
+        raise AssertionError("Image size should be larger than 160 due to the 4 downsamplings in ms-ssim")
+    s, c = SsimStatsFn.apply(imgs, imgs_w, len(MS_WEIGHTS), 1.0)
+    f = torch.relu(torch.cat([c[:-1], s[-1:]], dim=0))
+    return (-torch.prod(f ** _ms_weights(f.device), dim=0).mean()).float()
+
+
+class JndLossFn(torch.autograd.Function):
+    """losses/jndloss.py:27-31 (loss_type 0): mean((|imgs_w - imgs| - h)^2), h = the JND heat-map of imgs' luminance repeated over the channels
+    (modules/jnd.py:80-108, `JND()` defaults); gradient with respect to imgs_w"""
+
+    @staticmethod
+    def forward(ctx, imgs, imgs_w):
+        a, b = N.f32c(imgs), N.f32c(imgs_w)
+        F_, Cc, H, W = a.shape
+        if Cc != 3 or b.shape != a.shape:
+            raise ValueError("jnd term: [F, 3, H, W] frames of equal shape")
+        L = N.lib()
+        h = torch.empty(F_, 1, H, W, device=a.device, dtype=torch.float32)
+        N.check(L.vs_jnd_heatmap(N.ptr(a), F_, H, W, 3 * H * W, H * W, W, 1, _jnd_taps(), N.ptr(h), N.stream()), "vs_jnd_heatmap")
+        part = torch.empty(int(L.vs_jnd_loss_partial_doubles(F_, H, W)), device=a.device, dtype=torch.float64)
+        loss = torch.empty(1, device=a.device, dtype=torch.float32)
+        N.check(L.vs_jnd_loss(N.ptr(a), N.ptr(b), N.ptr(h), F_, H, W, N.ptr(part), N.ptr(loss), N.stream()), "vs_jnd_loss")
+        ctx.save_for_backward(a, b, h)
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, up):
+        a, b, h = ctx.saved_tensors
+        F_, _, H, W = a.shape
+        d = torch.empty_like(b)
+        N.check(N.lib().vs_jnd_loss_grad(N.ptr(a), N.ptr(b), N.ptr(h), F_, H, W, 1.0, N.ptr(d), N.stream()), "vs_jnd_loss_grad")
+        return None, d.mul_(up)
+
+
+# ---- the grammar of losses/perceptual.py:73-113
+HIP_PERCEP_TERMS = ("none", "mse", "yuv", "ssim", "msssim", "jnd")
+
+
+_WEIGHT_FILE_TERMS = ("lpips", "dists", "watson_vgg", "watson_dft")
+_REFERENCE_TERMS = HIP_PERCEP_TERMS + _WEIGHT_FILE_TERMS + ("jnd2", "focal")     # the names losses/perceptual.py:20-55 builds
+
+
+def parse_percep_loss(kind: str):
+    """The strings of losses/perceptual.py:84-113: one name -> (None, [name]); terms joined by '+', each optionally 'weight_name' ->
+    ([1.0, 0.1], [a, b]).  Everything the reference rejects is a ValueError here too and is reported first: an unknown name, a weight on
+    a single term ('0.5_ssim' is no name), a term with two underscores (so 'watson_vgg' cannot be a term of a sum there), a weight that
+    is no number.  What the reference accepts and this path lacks is a NotImplementedError that says why."""
+    terms = kind.split("+")
+    single = len(terms) == 1
+    weights, names = [], []
+    for term in terms:
+        if single or "_" not in term:
+            w, name = 1.0, term
+        else:
+            if term.count("_") != 1:
+                raise ValueError(f"perceptual loss term {term!r}: expected 'weight_name'")
+            w, name = term.split("_")
+        if name not in _REFERENCE_TERMS:
+            raise ValueError(f"Loss type {name} not supported.")
+        weights.append(w)
+        names.append(name)
+    weights = [float(w) for w in weights]
+    for name in names:
+        if name in _WEIGHT_FILE_TERMS:
+            raise NotImplementedError(f"perceptual loss {name!r} is a pretrained network: its weight file is not part of this repository "
+                                      f"(losses/perceptual.py:14-53); the HIP path has {', '.join(HIP_PERCEP_TERMS)}")
+        if name == "focal":
+            raise NotImplementedError("perceptual loss 'focal' needs a 2-D FFT, which the HIP path does not have (losses/focal.py)")
+    return (None if single else weights), names
+
+
+def _percep_term(imgs, imgs_w, name: str) -> torch.Tensor:
+    if name == "none":
+        return torch.zeros(1, device=imgs_w.device, requires_grad=True)
+    if name in ("mse", "yuv"):
+        return PercepLossFn.apply(imgs, imgs_w, name == "yuv")
+    if name == "ssim":
+        return ssim_loss(imgs, imgs_w)
+    if name == "msssim":
+        return msssim_loss(imgs, imgs_w)
+    if name == "jnd":
+        return JndLossFn.apply(imgs, imgs_w)
+    raise ValueError("Loss type 2 not supported. Use 0 or 1")        # jnd2 (jndloss.py:32-33)
+
+
 def percep_loss(imgs: torch.Tensor, imgs_w: torch.Tensor, kind: str = "mse") -> torch.Tensor:
-    if kind not in ("mse", "yuv"):
-        raise NotImplementedError(f"perceptual loss {kind!r}: the HIP path has 'mse' and 'yuv' (the others need pretrained networks)")
-    return PercepLossFn.apply(imgs, imgs_w, kind == "yuv")
+    weights, names = parse_percep_loss(kind)
+    if weights is None:
+        return _percep_term(imgs, imgs_w, names[0])
+    total = 0
+    for w, n in zip(weights, names):
+        total = total + w * _percep_term(imgs, imgs_w, n).mean()
+    return total
 
 
 def decoding_loss(preds: torch.Tensor, msgs: torch.Tensor, temperature: float = 1.0) -> torch.Tensor:

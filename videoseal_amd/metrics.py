@@ -5,8 +5,10 @@ and evals/full.py:46 import next to them -- mask metrics (`accuracy`, `iou`), me
 `bit_accuracy_1msg`) and the structural-similarity scores.  The reference takes `ssim` / `msssim` from the third-party package
 `pytorch_msssim` (evals/metrics.py:20, 38-54; absent from this image and not vendored in the checkout): restated here from its
 published algorithm (Wang et al. 2004 / 2003: 11-tap Gaussian window, sigma 1.5, K = (0.01, 0.03), 'valid' filtering, five scales
-with weights 0.0448 / 0.2856 / 0.3001 / 0.2363 / 0.1333) -- parity unpinned against that package, pinned against an independent
-float64 scipy evaluation in tests/test_host.py.
+with weights 0.0448 / 0.2856 / 0.3001 / 0.2363 / 0.1333).  The reference checkout vendors that algorithm in losses/ssim.py: this
+restatement is pinned against the unmodified file (tests/golden/make_golden_ssim.py, tests/test_oracle_ssim.py: equal in float64) and
+against an independent float64 scipy evaluation in tests/test_host.py.  Device fp32 inputs run on the HIP statistics kernel
+(csrc/ssim.hip: one streaming pass per scale instead of ten grouped convolutions); `LAST_SSIM_BACKEND` says which path a call took.
 """
 import math
 
@@ -124,16 +126,49 @@ def _ssim_cs(x, y, data_range, win, k1=0.01, k2=0.03):
     return ssim_map.flatten(2).mean(-1), cs_map.flatten(2).mean(-1)
 
 
+LAST_SSIM_BACKEND = None      # "hip" or "torch": which path the last ssim / msssim call took
+
+
+def _on_hip_path(x: torch.Tensor, y: torch.Tensor) -> bool:
+    """device fp32 4-D inputs that nobody differentiates go to the HIP statistics kernel (csrc/ssim.hip); everything else -- CPU tensors,
+    float64, inputs that require a gradient -- keeps the torch code below"""
+    return (x.is_cuda and y.is_cuda and x.dtype == torch.float32 and y.dtype == torch.float32 and x.dim() == 4 and x.shape == y.shape
+            and not (torch.is_grad_enabled() and (x.requires_grad or y.requires_grad)))
+
+
+def _hip_factors(x, y, levels, data_range):
+    from . import autograd as AG
+    from .native import f32c
+    with torch.no_grad():
+        s, c, _ = AG.ssim_pyramid(f32c(x), f32c(y), levels, data_range)      # (a side shorter than 11: ValueError)
+    return s, c
+
+
 def ssim(x: torch.Tensor, y: torch.Tensor, data_range: float = 1.0) -> torch.Tensor:
-    """evals/metrics.py:38-45 (`pytorch_msssim.ssim(..., size_average=False)`): one score per image, B x C x H x W in [0, data_range]."""
+    """evals/metrics.py:38-45 (`pytorch_msssim.ssim(..., size_average=False)`): one score per image, B x C x H x W in [0, data_range].
+    On the HIP path a side shorter than 11 raises ValueError (the reference skips the filter along that axis with a warning: not built)."""
+    global LAST_SSIM_BACKEND
+    if _on_hip_path(x, y):
+        LAST_SSIM_BACKEND = "hip"
+        s, _ = _hip_factors(x, y, 1, data_range)
+        return s[0].mean(1).float()
+    LAST_SSIM_BACKEND = "torch"
     s, _ = _ssim_cs(x, y, data_range, _gauss_window(11, 1.5, x))
     return s.mean(1)
 
 
 def msssim(x: torch.Tensor, y: torch.Tensor, data_range: float = 1.0) -> torch.Tensor:
     """evals/metrics.py:47-54 (`pytorch_msssim.ms_ssim(..., size_average=False)`): five dyadic scales, sides must exceed 160."""
+    global LAST_SSIM_BACKEND
     if min(x.shape[-2:]) <= (11 - 1) * 2 ** 4:
         raise AssertionError("Image size should be larger than 160 due to the 4 downsamplings in ms-ssim")
+    if _on_hip_path(x, y):
+        LAST_SSIM_BACKEND = "hip"
+        s, c = _hip_factors(x, y, len(_MS_WEIGHTS), data_range)
+        f = torch.relu(torch.cat([c[:-1], s[-1:]], dim=0))
+        from .autograd import _ms_weights
+        return torch.prod(f ** _ms_weights(x.device), dim=0).mean(1).float()
+    LAST_SSIM_BACKEND = "torch"
     win = _gauss_window(11, 1.5, x)
     factors = []
     for level in range(len(_MS_WEIGHTS)):

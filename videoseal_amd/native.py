@@ -35,6 +35,7 @@ EXPORTS = [
     "vs_msg_table_grad", "vs_outc_tanh_bwd", "vs_relu_bwd",
     "vs_resize_nchw_bwd", "vs_embed_tail_bwd", "vs_tail_key_reduce", "vs_aug_crop_flip_bwd", "vs_mask_mul", "vs_aug_color_bwd_scratch_floats",
     "vs_aug_color_bwd", "vs_clamp01_bwd", "vs_nhwc_to_nchw_scaled", "vs_percep_partial_doubles", "vs_percep_mse", "vs_percep_mse_grad",
+    "vs_ssim_partial_doubles", "vs_ssim_stats", "vs_ssim_grad", "vs_avgpool2_pad", "vs_jnd_loss_partial_doubles", "vs_jnd_loss", "vs_jnd_loss_grad",
     "vs_split_block", "vs_check_finite", "vs_absmax", "vs_resblock_thin", "vs_resblock_thin_supported", "vs_cnx_block_supported", "vs_cnx_block_image_bytes", "vs_cnx_block",
 ]
 
@@ -200,6 +201,11 @@ def lib() -> C.CDLL:
         "vs_nhwc_to_nchw_scaled": [P, I, I, I, I, I64, F, P, P],
         "vs_percep_mse": [P, P, I, I, I, I, P, P, P],
         "vs_percep_mse_grad": [P, P, I, I, I, I, F, P, P],
+        "vs_ssim_stats": [P, P, I, I, I, F, P, P, P, P],
+        "vs_ssim_grad": [P, P, P, P, P, I, I, I, F, P, P, P],
+        "vs_avgpool2_pad": [P, P, I, I, I, P, P, P],
+        "vs_jnd_loss": [P, P, P, I, I, I, P, P, P],
+        "vs_jnd_loss_grad": [P, P, P, I, I, I, F, P, P],
         "vs_split_block": [P, I, I64, I, I, F, P, P, P],
         "vs_check_finite": [P, I64, P, P],
         "vs_absmax": [P, I64, P, P],
@@ -220,7 +226,7 @@ def lib() -> C.CDLL:
     L.vs_h264_proxy_workspace_bytes.argtypes = [I, I, I]
     L.vs_vit_attention_bwd_scratch_floats.restype = C.c_int64
     L.vs_vit_attention_bwd_scratch_floats.argtypes = [I, I, I, I, I]
-    for name in ("vs_aug_color_bwd_scratch_floats", "vs_percep_partial_doubles"):
+    for name in ("vs_aug_color_bwd_scratch_floats", "vs_percep_partial_doubles", "vs_ssim_partial_doubles", "vs_jnd_loss_partial_doubles"):
         getattr(L, name).restype = C.c_int64
         getattr(L, name).argtypes = [I, I, I]
     L.vs_cnx_block_image_bytes.restype = C.c_int64

@@ -819,8 +819,9 @@ class EmbedderBackward:
 
 class GeneratorStep:
     """One accumulation step of train.py:626-643 with the generator branch of `VideosealLoss` (videosealloss.py:111-192, optimizer_idx 0)
-    computed on the HIP path end to end: differentiable forward (autograd.py) -> perceptual ('mse' / 'yuv') and decoding terms
-    (vs_percep_mse, vs_bce_logits) -> adaptive weights through `get_last_layer()` (videosealloss.py:72-107: one backward probe per term that
+    computed on the HIP path end to end: differentiable forward (autograd.py) -> perceptual ('mse', 'yuv', 'ssim', 'msssim', 'jnd' and
+    their weighted sums 'a+0.1_b'; 'lpips', 'dists', 'watson_*' need weight files and 'focal' an FFT: not built) and decoding terms
+    (vs_percep_mse, vs_ssim_stats / vs_ssim_grad, vs_jnd_loss, vs_bce_logits) -> adaptive weights through `get_last_layer()` (videosealloss.py:72-107: one backward probe per term that
     stops at the output convolution) -> backward into `.grad` of every embedder and detector parameter.  The discriminator term is a second
     trainable network outside this path (disc_weight = 0, what train.py itself uses for lambda_d = 0); the detection term needs a per-pixel
     mask head, which the ConvNeXt / ViT extractors of the shipped cards do not have (the reference's BCE raises on the shape mismatch too).
@@ -832,8 +833,9 @@ class GeneratorStep:
                  balanced: bool = True, total_norm: float = 0.0, temperature: float = 1.0):
         if detect_weight > 0:
             raise NotImplementedError("detect_weight > 0: the per-frame extractors predict no mask map (videosealloss.py:140-147 needs [b,1,h,w] logits)")
-        if percep_weight > 0 and percep_loss not in ("mse", "yuv"):
-            raise NotImplementedError(f"perceptual loss {percep_loss!r}: 'mse' and 'yuv' run on the HIP path (the rest are pretrained networks)")
+        if percep_weight > 0:
+            from . import autograd as AG
+            AG.parse_percep_loss(percep_loss)          # every string of losses/perceptual.py:84-113 whose terms the HIP path has; raises otherwise
         self.model, self.percep_loss, self.temperature = model, percep_loss, float(temperature)
         self.percep_weight, self.decode_weight, self.balanced, self.total_norm = percep_weight, decode_weight, balanced, total_norm
 
