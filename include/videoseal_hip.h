@@ -633,6 +633,38 @@ int vs_jpeg_roundtrip(const float* src, float* dst, int F, int H, int W, int qua
 int64_t vs_h264_proxy_workspace_bytes(int F, int H, int W);
 int vs_h264_proxy_roundtrip(const float* src, float* dst, int F, int H, int W, int qp, int rgb_mode, void* workspace, void* stream);
 
+/* ---- Pixel-wise extractor head (csrc/pixel_head.hip; modules/pixel_decoder.py:43-83 with upscale stages of 2 / 4 and `pixelwise: True`,
+ * losses/videosealloss.py:138-167, evals/metrics.py:150-206).  Deterministic: no atomics, fixed-order partial sums finished in double.
+ * vs_pixel_upgather: Upsample group at factor f in {2, 4} from the per-tap products z = v W on the LOW-resolution map ([B][H][W][z_ld], columns
+ *   (tap, channel), z_ld >= 9 Co: one vs_conv_gemm launch): 9-tap x 4-neighbour gather through bilinear (align_corners=False) interpolation
+ *   and ReflectionPad2d(1), LayerNorm over Co (biased variance, eps), activation -> [B][fH][fW][out_ld].  lnw = lnb = NULL stores the raw
+ *   gather (what the training forward keeps for vs_layernorm_bwd).  Co % 4 == 0 and Co <= 256, else VS_ERR_UNSUPPORTED
+ *   (vs_pixel_upgather_supported answers 1 / 0).
+ * vs_pixel_upgather_bwd: the adjoint of the raw gather, dg [B][fH][fW][dg_ld] -> dz [B][H][W][dz_ld] (9 Co columns written), as a gather.
+ * vs_pixel_linear: x NHWC [B * HW][ld] times w [K][C] plus bias (may be NULL), optional sigmoid -> NCHW [B][K][HW] (K needs no padding;
+ *   16-byte stores where HW % 4 == 0).  C % 4 == 0 and C <= 64, else VS_ERR_UNSUPPORTED.
+ * vs_pixel_linear_bwd: from dpreds [B][K][HW] (times y (1 - y) when y, the sigmoid output, is given): dx NHWC [B * HW][dx_ld], dw [K][C],
+ *   db [K]; dx or dw / db may be NULL.  partial: vs_pixel_linear_bwd_partial_floats floats (needed for dw).
+ * vs_pixel_bce: loss[0] = detection loss (mean BCE-with-logits of channel 0 against masks [B][HW]), loss[1] = decoding loss (mean BCE-with-logits
+ *   of channels 1.. divided by temperature against msgs [msg_rows][K - 1], msg_rows 1 or B, over the pixels with a non-zero mask; NaN when none is
+ *   selected), dpreds [B][K][HW] = w_det d loss[0] + w_dec d loss[1], every element written.  partial: vs_pixel_bce_partial_doubles doubles.
+ * vs_pixel_vote: votes[b][k] = pixels of frame b with a non-zero mask (all pixels when masks is NULL) and preds[b][k][p] > threshold,
+ *   nsel[b] = selected pixels; preds is [B][K][HW] with `batch_stride` floats between frames (a channel slice of a wider tensor). */
+int vs_pixel_upgather_supported(int Co, int f);
+int vs_pixel_upgather(const float* z, int64_t z_ld, int B, int H, int W, int Co, int f, const float* lnw, const float* lnb, float eps, int act,
+                      float* out, int64_t out_ld, void* stream);
+int vs_pixel_upgather_bwd(const float* dg, int64_t dg_ld, int B, int H, int W, int Co, int f, float* dz, int64_t dz_ld, void* stream);
+int vs_pixel_linear(const float* x, int64_t ld, int B, int64_t HW, int C, const float* w, const float* bias, int K, int sigmoid, float* out,
+                    void* stream);
+int64_t vs_pixel_linear_bwd_partial_floats(int64_t rows, int K, int C);
+int vs_pixel_linear_bwd(const float* dpreds, const float* y, const float* x, int64_t ld, int B, int64_t HW, int C, const float* w, int K, float* dx,
+                        int64_t dx_ld, float* dw, float* db, float* partial, void* stream);
+int64_t vs_pixel_bce_partial_doubles(int B, int K, int64_t HW);
+int vs_pixel_bce(const float* preds, const float* masks, const int32_t* msgs, int msg_rows, int B, int K, int64_t HW, float temperature, float w_det,
+                 float w_dec, float* dpreds, double* partial, float* loss, void* stream);
+int vs_pixel_vote(const float* preds, int64_t batch_stride, const float* masks, int B, int K, int64_t HW, float threshold, int32_t* votes,
+                  int32_t* nsel, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,213 @@
+"""Whole models whose extractor ends in the pixel-wise head (tests/golden/pixel_head_model.npz: the unmodified reference in float64, see
+tests/golden/make_golden_pixel_head.py::model_cases): `detect` in its image and video form and `extract_message` for every aggregation, for
+a tiny ConvNeXt-V2 spec with the head [4, 4, 2] ([F, 17, 64, 64] maps at the 64^2 processing size) and a tiny ViT spec with [4, 2, 2];
+DetectorStep and GeneratorStep on the ConvNeXt model against the reference's float64 loss.backward(); a chain that pools.  Logits: 4 x the reference's own fp32 error against float64,
+floor 1e-6; thresholded decisions through tests/_util.assert_decisions with its default margin and min_sure.  And the per-frame head of the
+released cards after this change: same path, same logits as the recorded run."""
+import dataclasses
+import json
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from oracle.inputs import synthetic_frames
+from oracle.weights import make_state_dict, tiny_spec
+from tests import _pixel_head_util as U
+from tests._util import DECISION_MARGIN, assert_decisions, load_golden
+from tests.test_gpu_e2e import cfg_of, make_model
+from videoseal_amd import native as N
+from videoseal_amd.model import aggregate_bits, build_model
+
+pytestmark = pytest.mark.gpu
+
+G = load_golden("pixel_head_model")
+E = G["meta"]["e"]
+MEASURED = {}
+
+
+def _record(key, **kw):
+    """with VS_PIXEL_HEAD_MODEL_PARITY_OUT=<file> the measured errors are merged into that file (the committed profiles/pixel_head_parity.json holds the operator
+    and loss cases of tests/test_gpu_pixel_head.py only: the model-level figures of this file are not in it yet)"""
+    MEASURED[key] = {k: float(v) for k, v in kw.items()}
+    path = os.environ.get("VS_PIXEL_HEAD_MODEL_PARITY_OUT")
+    if path:
+        have = json.load(open(path)) if os.path.exists(path) else {}
+        have.update(MEASURED)
+        with open(path, "w") as f:
+            json.dump(have, f, indent=1, sort_keys=True)
+
+
+@pytest.fixture(scope="module", params=["cnx", "vit"])
+def pw(request):
+    tag = request.param
+    spec = U.model_specs()[tag]
+    sd = U.model_state_dict(spec, tag)
+    cfg = dataclasses.replace(cfg_of(spec), head_stages=list(U.MODEL_STAGES[tag]), head_pixelwise=True)
+    m = build_model(cfg)
+    res = m.load_state_dict(sd, strict=True)          # the reference's names and shapes, `linear.weight` [1+nbits, c, 1, 1] included
+    assert not res.missing_keys and not res.unexpected_keys
+    n, h, w, seed = U.MODEL_FRAMES
+    imgs = synthetic_frames(n, h, w, seed=seed)
+    want = np.array(G["meta"]["sums"][tag])
+    got = U.checksum(imgs, *[sd[k] for k in sorted(sd) if k.startswith("detector.pixel_decoder.")])
+    assert np.allclose(got, want, rtol=1e-9, atol=1e-9), "the seeded inputs differ from the ones the fixture was made with"
+    return tag, spec, m.eval().to("cuda"), imgs
+
+
+@pytest.mark.parametrize("is_video", [True, False], ids=["video", "image"])
+def test_detect_returns_the_reference_maps(pw, is_video):
+    tag, spec, model, imgs = pw
+    key = f"{tag}.preds_{'vid' if is_video else 'img'}"
+    preds = model.detect(imgs.cuda(), is_video=is_video)["preds"]
+    assert tuple(preds.shape) == tuple(int(v) for v in G[key + ".shape"]) and preds.shape[1] == spec.nbits + 1
+    stats = G[key + ".stats"]
+    flat = preds.double().cpu().flatten()
+    sub = flat[::int(stats[3])]
+    gold = torch.from_numpy(G[key])
+    err = float((sub - gold).abs().max())
+    bound = max(4 * E[key], 1e-6)
+    print(f"{key}: max |hip - float64| = {err:.3e} (reference fp32: {E[key]:.3e}, bound {bound:.3e})")
+    _record(key, err=err, e_ref=E[key], bound=bound)
+    assert torch.isfinite(flat).all() and err <= bound
+    assert_decisions(sub.float(), gold.float(), what=key)
+    if tag == "cnx":
+        assert tuple(preds.shape[-2:]) == (spec.img_size, spec.img_size)
+    assert model.pixelwise and model.detect(imgs[:0].cuda(), is_video=is_video)["preds"].shape == (0,) + tuple(preds.shape[1:])
+
+
+def test_extract_message_for_every_aggregation(pw):
+    tag, spec, model, imgs = pw
+    preds = model.detect(imgs.cuda(), is_video=True, interpolation={"mode": "bilinear", "align_corners": False, "antialias": False})["preds"]
+    for a in U.AGGREGATIONS:
+        want = torch.from_numpy(G[f"{tag}.msg_{a}"])
+        got = model.extract_message(imgs.cuda(), aggregation=a).cpu()
+        assert got.shape == want.shape and got.dtype == torch.bool
+        sure = (aggregate_bits(preds[:, 1:], a).squeeze().unsqueeze(0).abs() > DECISION_MARGIN).cpu()
+        assert int((~sure).sum()) <= max(1, int(0.001 * want.numel())), f"{a}: {int((~sure).sum())} values inside the margin"
+        assert torch.equal(got[sure], want[sure]), f"{a}: {int((got != want)[sure].sum())} decisions differ from the reference"
+
+
+def test_row_interfaces_refuse_pixelwise_models(pw):
+    tag, spec, model, imgs = pw
+    from videoseal_amd.dist import gather_frame_logits
+    from videoseal_amd.streaming import embed_detect_chunks
+    with pytest.raises(NotImplementedError, match="rows of logits"):
+        model.detect_u8(torch.zeros(2, 64, 64, 3, dtype=torch.uint8, device="cuda"))
+    with pytest.raises(NotImplementedError, match="rows of logits"):
+        embed_detect_chunks(model, imgs.cuda(), torch.zeros(1, spec.nbits))
+    with pytest.raises(NotImplementedError, match="rows of logits"):
+        gather_frame_logits(torch.zeros(2, 17, 8, 8), 2)
+
+
+def test_pooled_chain_with_a_factor_one_stage_and_sigmoid():
+    """[4, 2, 1] / `pixelwise: False` / sigmoid_output on 64 channels: two gather stages, the 3 x 3 conv path of a factor-1 stage, the mean over
+    the pixels, Linear and sigmoid -- all on HIP kernels -- against the reference's PixelDecoder"""
+    from tests.test_gpu_kernels import Eng, to_nhwc
+    from videoseal_amd import pixel_head as PH
+    sd = U.head_tensors(64, U.POOLED_CHAIN, 16, seed=17)
+    x = U.chain_input(3, 5)[:, :64].contiguous()
+    lin = sd["pixel_decoder.linear.weight"].reshape(17, -1)
+    want = np.array(G["meta"]["sums"]["pooled_chain"])
+    got = U.checksum(x, *[lin if k.endswith("linear.weight") else v for k, v in sd.items()])
+    assert np.allclose(got, want, rtol=1e-9, atol=1e-9)
+    xa = to_nhwc(x)
+    for eng in (Eng(use_split=True, arith=3), Eng(use_split=False, arith=3)):
+        P = PH.pack_head(lambda k: sd[k].cuda(), "pixel_decoder", 64, U.POOLED_CHAIN, xa.ld, False, True)
+        out = PH.head_forward(eng, xa, P, "t.pooled")
+        assert out.shape == (U.B, 17)
+        err = float((out.double().cpu().flatten() - torch.from_numpy(G["pooled_chain.out"])).abs().max())
+        bound = max(4 * E["pooled_chain.out"], 1e-6)
+        print(f"pooled_chain: max |hip - float64| = {err:.3e} (reference fp32: {E['pooled_chain.out']:.3e}, bound {bound:.3e})")
+        _record("pooled_chain.out@" + ("split" if eng.use_split else "f32"), err=err, e_ref=E["pooled_chain.out"], bound=bound)
+        assert err <= bound
+
+
+# ---- training (tests/golden/make_golden_pixel_head.py::train_cases): the loss values as tests/test_gpu_train.py compares its log entries
+# ((3e-3 for a scale, 2e-4 otherwise) x max(1, |value|)), every detector gradient within 3e-3 of the tensor's largest element, the detector tolerance of that file
+def _train_model():
+    from videoseal_amd import augmentation as A
+    spec = U.model_specs()["cnx"]
+    cfg = dataclasses.replace(cfg_of(spec), head_stages=list(U.MODEL_STAGES["cnx"]), head_pixelwise=True)
+    m = build_model(cfg)
+    m.load_state_dict(U.model_state_dict(spec, "cnx"), strict=True)
+    m.augmenter = A.Augmenter(masks={"kind": "given"}, augs={"identity": 1}, augs_params={}, num_augs=1)
+    return spec, m.to("cuda").train()
+
+
+def _check_grads(case, named):
+    names = [str(n) for n in G[f"train.{case}.names"]]
+    have = dict(named)
+    worst = 0.0
+    for i, k in enumerate(names):
+        assert k in have and have[k] is not None, f"no gradient for {k}"
+        gmax = float(G[f"train.{case}.gmax"][i])
+        err = float((U.grad_sub(have[k]).cpu() - torch.from_numpy(G[f"train.{case}.g{i}"])).abs().max())
+        worst = max(worst, err / gmax)
+        assert err <= 3e-3 * gmax, f"{case} {k}: {err:.3e} > 3e-3 x {gmax:.3e}"
+    assert [k for k in names if "pixel_decoder" in k], names
+    print(f"train.{case}: {len(names)} detector gradients, worst element error / max|g| = {worst:.3e}")
+    _record(f"train.{case}.grads", worst_rel=worst, bound=3e-3)
+
+
+def test_detector_step_on_the_pixelwise_model():
+    from videoseal_amd.training import DetectorStep
+    spec, model = _train_model()
+    imgs, masks, msgs = U.train_inputs(spec.nbits)
+    ref = G["meta"]["train"]["det"]
+    loss, preds, grads = DetectorStep(model).step(imgs.cuda(), msgs, masks=masks.cuda(), detect_weight=1.0, decode_weight=1.0)
+    assert preds.shape == (imgs.shape[0], spec.nbits + 1, 64, 64)
+    print(f"train.det: loss {float(loss):.7f} (reference {ref['loss']:.7f})")
+    tol = 2e-4 * max(1.0, abs(ref["loss"]))
+    _record("train.det.loss", err=abs(float(loss) - ref["loss"]), bound=tol)
+    assert abs(float(loss) - ref["loss"]) <= tol
+    _check_grads("det", [(k, p.grad) for k, p in model.named_parameters()])
+    with pytest.raises(ValueError):
+        DetectorStep(model).step(imgs.cuda(), msgs, masks=masks[..., :32, :32].contiguous().cuda(), detect_weight=1.0, accumulate=False)
+    with pytest.raises(ValueError):
+        DetectorStep(model).step(imgs.cuda(), msgs, accumulate=False)
+
+
+def test_generator_step_with_detection_and_masked_decoding_terms():
+    from videoseal_amd.training import GeneratorStep
+    spec, model = _train_model()
+    imgs, masks, msgs = U.train_inputs(spec.nbits)
+    ref = G["meta"]["train"]["gen"]["log"]
+    step = GeneratorStep(model, detect_weight=1, decode_weight=1, percep_loss="mse")
+    torch.manual_seed(7)
+    total, log, outputs = step.step(imgs.cuda(), masks.cuda(), msgs)
+    assert [k for k in log if k.startswith("loss_")] == ["loss_percep", "loss_detect", "loss_decode"]         # the reference's dict order
+    for k in ("loss_percep", "loss_detect", "loss_decode", "scale_percep", "scale_detect", "scale_decode", "total_loss"):
+        got, want = float(log[k]), ref[k]
+        tol = (3e-3 if k.startswith("scale_") else 2e-4) * max(1.0, abs(want))
+        print(f"train.gen {k}: {got:.7e} (reference {want:.7e})")
+        _record(f"train.gen.{k}", err=abs(got - want), bound=tol)
+        assert abs(got - want) <= tol, k
+    _check_grads("gen", [(k, p.grad) for k, p in model.named_parameters()])
+    assert all(p.grad is not None and torch.isfinite(p.grad).all() for k, p in model.named_parameters() if k.startswith("embedder.") and p.requires_grad)
+    # a mask whose size differs from the maps, and the per-frame extractors, go on raising
+    with pytest.raises(ValueError):
+        step.losses(imgs.cuda(), dict(outputs, masks=masks[..., :32, :32].contiguous().cuda()))
+    plain = make_model(tiny_spec(), make_state_dict(tiny_spec(), seed=3))
+    with pytest.raises(NotImplementedError, match="no mask map"):
+        GeneratorStep(plain, detect_weight=1.0)
+
+
+def test_per_frame_head_is_unchanged():
+    """upscale_stages [1] / pixelwise False: the engine packs and runs the pooled head it always did (no `phead` entry, vs_pool_linear) and the
+    logits of the recorded tiny case hold at that case's existing tolerance, decisions exact"""
+    spec = tiny_spec()
+    model = make_model(spec, make_state_dict(spec, seed=3))
+    g = load_golden("tiny_img")
+    meta = g["meta"]
+    imgs = synthetic_frames(meta["n"], meta["h"], meta["w"], seed=meta["seed"], kind=meta["kind"])
+    clean = model.detect(imgs.cuda(), is_video=meta["is_video"])["preds"]
+    eng = model._engine()
+    assert not eng.pixel_head and "phead" not in eng.X and "head_conv" in eng.X and not model.pixelwise
+    assert clean.shape == (meta["n"], spec.nbits + 1)
+    gclean = torch.from_numpy(g["preds_clean"])
+    assert (clean.cpu() - gclean).abs().max() < 1e-4
+    assert ((clean.cpu() > 0) == (gclean > 0)).all()
+    again = model.detect(imgs.cuda(), is_video=meta["is_video"])["preds"]
+    assert torch.equal(clean, again)

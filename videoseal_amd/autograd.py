@@ -460,6 +460,33 @@ class DecodeLossFn(torch.autograd.Function):
         return d * up, None, None
 
 
+class PixelLossFn(torch.autograd.Function):
+    """videosealloss.py:138-167 on the [B, 1+nbits, H, W] maps of a pixel-wise extractor (vs_pixel_bce): `which` = 'detect' (BCE-with-logits of
+    channel 0 against the mask) or 'decode' (BCE-with-logits of channels 1.. / temperature against the bits over the pixels the mask selects)"""
+
+    @staticmethod
+    def forward(ctx, preds, masks, msgs_i32, temperature, which):
+        from .pixel_head import pixel_bce
+        det = which == "detect"
+        loss, d = pixel_bce(preds, masks, msgs_i32, temperature=temperature, w_det=1.0 if det else 0.0, w_dec=0.0 if det else 1.0)
+        ctx.save_for_backward(d)
+        return loss[0 if det else 1]
+
+    @staticmethod
+    def backward(ctx, up):
+        (d,) = ctx.saved_tensors
+        return d * up, None, None, None, None
+
+
+def pixel_loss(preds, masks, msgs, temperature: float = 1.0, which: str = "decode"):
+    if which not in ("detect", "decode"):
+        raise ValueError(which)
+    m = msgs.to(preds.device)
+    if m.is_floating_point():
+        m = m > 0.5
+    return PixelLossFn.apply(preds, masks.to(preds.device), m.to(torch.int32).contiguous(), float(temperature), which)
+
+
 # ---- SSIM / MS-SSIM / JND terms (csrc/ssim.hip; losses/ssim.py, losses/jndloss.py)
 from .metrics import _MS_WEIGHTS as MS_WEIGHTS                 # noqa: E402  (losses/ssim.py:222-223; one copy, in metrics.py)
 # modules/jnd.py:29-45: 5x5 luminance taps, Sobel x, Sobel y -- the host array vs_jnd_heatmap takes (fixed, not weights of a checkpoint)

@@ -11,7 +11,9 @@ embed_dim back into it exactly like the reference does (train.py copies and logs
     optimizer over list(embedder.parameters()) + list(extractor.parameters())                      # train.py:330
 
 Architectures outside the hot path ('vae', 'hidden', 'patchmixer', 'dvmark' embedders; 'dino2', 'hidden', 'dvmark'
-extractors; pixel-wise decoders) raise NotImplementedError instead of building something else.
+extractors; pixel decoders that up-scale by anything but bilinear interpolation, by factors other than 1 / 2 / 4 or to a stage width that is no
+multiple of 4) raise NotImplementedError instead of building something else.  The pixel-wise heads of configs/extractor.yaml (`convnext_tiny_pw`,
+`convnext_base_pw`, `sam_small_pw`: upscale_stages [4, 4, 2] / [4, 2, 2], `pixelwise: True`) are built.
 """
 from __future__ import annotations
 
@@ -21,7 +23,7 @@ from typing import Any
 
 import yaml
 
-from .layout import ModelCfg
+from .layout import ModelCfg, head_cfg
 from .model import Embedder, Extractor
 
 CONFIG_DIR = Path(__file__).resolve().parent / "configs"
@@ -98,14 +100,13 @@ def build_extractor(name, cfg, img_size, nbits) -> Extractor:
         enc, pd = _need(cfg, "encoder", name), _need(cfg, "pixel_decoder", name)
         enc["img_size"] = img_size            # extractor.py:172-173
         pd["nbits"] = nbits
-        _check_pixel_decoder(pd)
         if not _get(enc, "qkv_bias", True) or _get(enc, "temporal_attention", False) or not _get(enc, "use_abs_pos", True):
             raise NotImplementedError("ViT extractor: qkv_bias and absolute position embeddings are required, temporal attention is not built")
         mc = ModelCfg(nbits=int(nbits), img_size=int(img_size), extractor="sam", vit_dim=int(enc["embed_dim"]), vit_depth=int(enc["depth"]),
                       vit_heads=int(enc["num_heads"]), vit_patch=int(enc["patch_size"]), vit_window=int(_get(enc, "window_size", 0)),
                       vit_global=[int(i) for i in _get(enc, "global_attn_indexes", [])], vit_out=int(enc["out_chans"]),
                       vit_mlp_ratio=float(_get(enc, "mlp_ratio", 4.0)), vit_rel_pos=bool(_get(enc, "use_rel_pos", False)),
-                      dims=[0, 0, 0, int(enc["out_chans"])], depths=[0, 0, 0, 0])
+                      dims=[0, 0, 0, int(enc["out_chans"])], depths=[0, 0, 0, 0], **head_cfg(pd, int(enc["out_chans"])))
         if int(_get(pd, "embed_dim", mc.vit_out)) != mc.vit_out:
             raise ValueError(f"pixel_decoder.embed_dim {pd['embed_dim']} != encoder.out_chans {mc.vit_out}")
         return Extractor(mc)
@@ -116,19 +117,9 @@ def build_extractor(name, cfg, img_size, nbits) -> Extractor:
             multiplier = sqrt(nbits / 128)
             enc["dims"] = [int(dim * multiplier) for dim in enc["dims"]]
         pd["embed_dim"] = enc["dims"][-1]     # extractor.py:202
-        _check_pixel_decoder(pd)
         mc = ModelCfg(nbits=int(nbits), img_size=int(img_size), extractor="convnext", dims=[int(v) for v in enc["dims"]],
-                      depths=[int(v) for v in enc["depths"]], stem_stride=int(_get(enc, "stem_stride", 4)))
+                      depths=[int(v) for v in enc["depths"]], stem_stride=int(_get(enc, "stem_stride", 4)), **head_cfg(pd, int(enc["dims"][-1])))
         return Extractor(mc)
     if any(name.startswith(k) for k in ("dino2", "hidden", "dvmark")):
         raise NotImplementedError(f"Model {name}: only the ConvNeXt-V2 and SAM-style ViT extractors are built on the HIP path")
     raise NotImplementedError(f"Model {name} not implemented")
-
-
-def _check_pixel_decoder(pd) -> None:
-    if list(_get(pd, "upscale_stages", [1])) != [1] or _get(pd, "pixelwise", False):
-        raise NotImplementedError("pixel decoder: only upscale_stages [1], pixelwise False")
-    if str(_get(pd, "upscale_type", "bilinear")) != "bilinear":
-        raise NotImplementedError("pixel decoder: only upscale_type 'bilinear'")
-    if _get(pd, "sigmoid_output", False):
-        raise NotImplementedError("pixel decoder: sigmoid_output")

@@ -54,6 +54,9 @@ class CModel:
         if cfg.extractor != "convnext" or cfg.unet_norm != "batch":
             raise NotImplementedError("the model-level C-ABI covers the released cards (BatchNorm/ReLU U-Net + ConvNeXt-V2 extractor); "
                                       "the legacy videoseal_0.0 family runs through the operator-level entry points (videoseal_amd.engine)")
+        if list(cfg.head_stages) != [1] or cfg.head_pixelwise or cfg.head_sigmoid:
+            raise NotImplementedError("the model-level C-ABI passes [F, 1+nbits] rows of logits: extractors with up-scaling stages or a pixel-wise "
+                                      "head run through the operator-level entry points (videoseal_amd.engine, csrc/pixel_head.hip)")
         self.cfg = cfg
         c = ModelCfgC()
         c.nbits, c.hidden, c.img_size, c.in_ch, c.out_ch, c.yuv = cfg.nbits, cfg.hidden, cfg.img_size, cfg.in_ch, cfg.out_ch, int(cfg.yuv)

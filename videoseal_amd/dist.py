@@ -34,6 +34,8 @@ def all_shards(n_frames: int, world: int, align: int = 16) -> List[Tuple[int, in
 def gather_frame_logits(local: torch.Tensor, n_frames: int, align: int = 16, group=None) -> torch.Tensor:
     """all-gather of ragged per-rank [f_local, k] logits into the full [n_frames, k] matrix (frame order kept).
     Ranks pad to the largest shard so a single fixed-size all_gather is issued."""
+    if local.dim() != 2:
+        raise NotImplementedError(f"gather_frame_logits passes [f, 1+nbits] rows of logits, got {tuple(local.shape)} (the maps of a pixel-wise detector)")
     if not (dist.is_available() and dist.is_initialized()):
         return local
     world, rank = dist.get_world_size(group), dist.get_rank(group)

@@ -471,12 +471,7 @@ class HipEngine:
                                    gamma=g(p + ".grn.gamma").float().reshape(-1).contiguous(), beta=padvec(g(p + ".grn.beta"), rup(ld4, 16)),
                                    pw2=ConvW(w2, g(p + ".pwconv2.bias").float().contiguous(), Cc, 1, 1, cp2)))
             X["stages"].append(blocks)
-        pd = "detector.pixel_decoder"
-        wh, cph = pack_conv(g(pd + ".output_upscaling.0.upsample_block.2.weight"), self._xld(d[-1]))
-        X["head_conv"] = ConvW(wh, None, d[-1], 3, 3, cph)
-        X["head_ln"] = (g(pd + ".output_upscaling.0.upsample_block.3.weight").float().contiguous(), g(pd + ".output_upscaling.0.upsample_block.3.bias").float().contiguous())
-        X["lin_w"] = g(pd + ".linear.weight").float().contiguous()
-        X["lin_b"] = g(pd + ".linear.bias").float().contiguous()
+        self._pack_head(g, X, d[-1])
         self.X = X
         self._sd_now = None
 
@@ -1344,8 +1339,36 @@ class HipEngine:
                     self.conv(hh, blk["pw2"], cur, res=cur, a_mul=A_MUL_GRN, **kwa2)
         return self._pixel_decoder(cur, X)
 
+    @property
+    def pixel_head(self) -> bool:
+        """the extractor ends in a chain of up-scaling stages and / or the per-pixel linear layer (csrc/pixel_head.hip) instead of the pooled head"""
+        c = self.cfg
+        return list(c.head_stages) != [1] or bool(c.head_pixelwise) or bool(c.head_sigmoid)
+
+    @property
+    def preds_owned(self) -> bool:
+        """extractor_forward returns a fresh tensor the caller owns (the maps of a pixel-wise head: 0.8 GB at 32 x 97 x 256^2, not worth a copy)
+        instead of a view of an engine buffer that the next pass overwrites"""
+        return self.pixel_head and bool(self.cfg.head_pixelwise)
+
+    def _pack_head(self, g, X, e: int) -> None:
+        pd = "detector.pixel_decoder"
+        if self.pixel_head:
+            from . import pixel_head as PH
+            X["phead"] = PH.pack_head(g, pd, e, self.cfg.head_stages, self._xld(e), self.cfg.head_pixelwise, self.cfg.head_sigmoid)
+            return
+        wh, cph = pack_conv(g(pd + ".output_upscaling.0.upsample_block.2.weight"), self._xld(e))
+        X["head_conv"] = ConvW(wh, None, e, 3, 3, cph)
+        X["head_ln"] = (g(pd + ".output_upscaling.0.upsample_block.3.weight").float().contiguous(), g(pd + ".output_upscaling.0.upsample_block.3.bias").float().contiguous())
+        X["lin_w"] = g(pd + ".linear.weight").float().contiguous()
+        X["lin_b"] = g(pd + ".linear.bias").float().contiguous()
+
     def _pixel_decoder(self, cur: Act, X) -> torch.Tensor:
-        """pixel_decoder.py:61-83 with upscale_stages [1]: reflect-pad conv3x3 -> LayerNorm(cf) -> GELU -> mean(H, W) -> Linear."""
+        """pixel_decoder.py:61-83 with upscale_stages [1]: reflect-pad conv3x3 -> LayerNorm(cf) -> GELU -> mean(H, W) -> Linear; any other head
+        (a chain of stages, `pixelwise`: [B, 1+nbits, S, S] logits) runs in pixel_head.head_forward."""
+        if "phead" in X:
+            from . import pixel_head as PH
+            return PH.head_forward(self, cur, X["phead"])
         c, L, st, B = self.cfg, self.lib, N.stream(), cur.B
         d = [cur.C]
         hc = self.new_act("head.c", B, cur.H, cur.W, d[-1])
@@ -1397,12 +1420,7 @@ class HipEngine:
         wn2, cp2 = pack_conv(g(ie + ".neck.2.weight"), self._xld(c.vit_out))
         V["neck2"] = ConvW(wn2, None, c.vit_out, 3, 3, cp2)
         V["neck3"] = (g(ie + ".neck.3.weight").float().contiguous(), g(ie + ".neck.3.bias").float().contiguous())
-        pd = "detector.pixel_decoder"
-        wh, cph = pack_conv(g(pd + ".output_upscaling.0.upsample_block.2.weight"), self._xld(c.vit_out))
-        V["head_conv"] = ConvW(wh, None, c.vit_out, 3, 3, cph)
-        V["head_ln"] = (g(pd + ".output_upscaling.0.upsample_block.3.weight").float().contiguous(), g(pd + ".output_upscaling.0.upsample_block.3.bias").float().contiguous())
-        V["lin_w"] = g(pd + ".linear.weight").float().contiguous()
-        V["lin_b"] = g(pd + ".linear.bias").float().contiguous()
+        self._pack_head(g, V, c.vit_out)
         self.X = V
         self._sd_now = None
 

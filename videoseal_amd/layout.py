@@ -53,6 +53,9 @@ class ModelCfg:
     vit_out: int = 384
     vit_mlp_ratio: float = 4.0
     vit_rel_pos: bool = True
+    head_stages: List[int] = field(default_factory=lambda: [1])      # pixel_decoder.upscale_stages: factors 1 / 2 / 4 (pixel_decoder.py:43-49)
+    head_pixelwise: bool = False                                      # True: [F, 1+nbits, S, S] logits from a 1 x 1 conv instead of the pooled Linear
+    head_sigmoid: bool = False                                        # pixel_decoder.sigmoid_output
 
     @property
     def zc(self) -> List[int]:
@@ -64,6 +67,50 @@ class ModelCfg:
 
 
 _JND_MODES = {"jnd_1_1": (1, 1), "jnd_3_3": (3, 3), "jnd_1_3": (1, 3), "jnd_3_1": (3, 1)}
+
+
+def stage_width(c_in: int, f: int, what: str = "") -> int:
+    """width behind one up-scaling stage, or NotImplementedError with the reason: the one copy of the rule of csrc/pixel_head.hip"""
+    if f not in (1, 2, 4):
+        raise NotImplementedError(f"pixel decoder: {what}upscale factor {f}: only 1, 2 and 4 are built")
+    co = int(c_in) // f
+    if co <= 0 or co % 4:
+        raise NotImplementedError(f"pixel decoder: {what}a stage of width {c_in} // {f} = {co} is not a multiple of 4 (the HIP kernels move 4 channels at a time)")
+    if f > 1 and co > 256:
+        raise NotImplementedError(f"pixel decoder: {what}stage width {co} > 256 at factor {f}")
+    return co
+
+
+def head_cfg(pd, embed_dim: int) -> dict:
+    """the pixel decoder's keys as ModelCfg fields; NotImplementedError, with the reason, for what the HIP path does not build: up-scaling by
+    'nearest' / 'conv' / 'pixelshuffle', factors other than 1 / 2 / 4 and stage widths that are no multiple of 4 (csrc/pixel_head.hip)"""
+    get = (lambda k, dflt: dflt if pd.get(k) is None else pd.get(k))
+    ut = str(get("upscale_type", "bilinear"))
+    if ut != "bilinear":
+        raise NotImplementedError(f"pixel decoder: upscale_type '{ut}': only 'bilinear' is built")
+    stages = [int(f) for f in get("upscale_stages", [1])]
+    pixelwise = bool(get("pixelwise", False))
+    if stages != [1] or pixelwise:          # (the per-frame head of the released cards takes any width, as before)
+        c = int(embed_dim)
+        for f in stages:
+            c = stage_width(c, f, f"upscale_stages {stages} on {embed_dim} channels: ")
+    sigmoid = bool(get("sigmoid_output", False))
+    if pixelwise or sigmoid:                # the layer that vs_pixel_linear computes (per pixel, or on the pooled row when a sigmoid follows)
+        c = int(embed_dim)
+        for f in stages:
+            c //= f
+        if c > 64:
+            raise NotImplementedError(f"pixel decoder: a {'pixel-wise' if pixelwise else 'sigmoid_output'} linear layer on {c} channels: the kernel "
+                                      f"takes at most 64 (upscale_stages {stages} on {embed_dim} channels)")
+    return dict(head_stages=stages, head_pixelwise=pixelwise, head_sigmoid=sigmoid)
+
+
+def head_widths(c: ModelCfg) -> List[int]:
+    e, out = (c.vit_out if c.extractor == "sam" else c.dims[-1]), []
+    for f in c.head_stages:
+        e //= f
+        out.append(e)
+    return out
 
 
 def cfg_from_card(card: dict) -> ModelCfg:
@@ -85,10 +132,6 @@ def cfg_from_card(card: dict) -> ModelCfg:
     norm_ = "batch" if norm_.startswith("batch") else ("rms" if norm_.startswith("rms") else norm_)
     if (act_, norm_) not in (("relu", "batch"), ("silu", "rms")):
         raise NotImplementedError(f"U-Net activation/normalization '{act_}'/'{norm_}': relu + batch (released cards) or silu + rms (legacy card)")
-    if list(e["pixel_decoder"].get("upscale_stages", [1])) != [1] or e["pixel_decoder"].get("pixelwise", False):
-        raise NotImplementedError("pixel decoder: only upscale_stages [1], pixelwise False")
-    if str(e["pixel_decoder"].get("upscale_type", "bilinear")) != "bilinear":
-        raise NotImplementedError("pixel decoder: only upscale_type 'bilinear'")
     nbits = int(a["nbits"])
     mult = a.get("hidden_size_multiplier", 2)
     vit = {}
@@ -120,7 +163,7 @@ def cfg_from_card(card: dict) -> ModelCfg:
         mults=[int(v) for v in u["z_channels_mults"]], num_blocks=int(u["num_blocks"]), last_tanh=bool(u.get("last_tanh", True)),
         depths=depths, dims=dims, stem_stride=int(e["encoder"].get("stem_stride", 4)),
         jnd_in=jnd[0], jnd_out=jnd[1], checkpoint_path=str(card.get("checkpoint_path", "")),
-        unet_act=act_, unet_norm=norm_, **vit,
+        unet_act=act_, unet_norm=norm_, **vit, **head_cfg(e["pixel_decoder"], dims[-1]),
     )
 
 
@@ -214,9 +257,12 @@ def _vit_entries(c: ModelCfg) -> Iterator[Entry]:
 
 
 def _pixel_decoder_entries(c: ModelCfg, e: int) -> Iterator[Entry]:
-    yield "pixel_decoder.output_upscaling.0.upsample_block.2.weight", (e, e, 3, 3), "param"
-    yield from _norm_affine("pixel_decoder.output_upscaling.0.upsample_block.3", e)
-    yield "pixel_decoder.linear.weight", (c.nbits + 1, e), "param"
+    """pixel_decoder.py:43-55: one Upsample group per stage (e -> e // f), then nn.Linear, or a 1 x 1 nn.Conv2d when pixel-wise"""
+    for i, f in enumerate(c.head_stages):
+        yield f"pixel_decoder.output_upscaling.{i}.upsample_block.2.weight", (e // f, e, 3, 3), "param"
+        yield from _norm_affine(f"pixel_decoder.output_upscaling.{i}.upsample_block.3", e // f)
+        e //= f
+    yield "pixel_decoder.linear.weight", ((c.nbits + 1, e, 1, 1) if c.head_pixelwise else (c.nbits + 1, e)), "param"
     yield "pixel_decoder.linear.bias", (c.nbits + 1,), "param"
 
 
@@ -245,11 +291,7 @@ def detector_entries(c: ModelCfg) -> Iterator[Entry]:
             yield p + ".grn.beta", (1, 1, 1, 4 * ch), "param"
             yield p + ".pwconv2.weight", (ch, 4 * ch), "param"
             yield p + ".pwconv2.bias", (ch,), "param"
-    e = d[-1]
-    yield "pixel_decoder.output_upscaling.0.upsample_block.2.weight", (e, e, 3, 3), "param"
-    yield from _norm_affine("pixel_decoder.output_upscaling.0.upsample_block.3", e)
-    yield "pixel_decoder.linear.weight", (c.nbits + 1, e), "param"
-    yield "pixel_decoder.linear.bias", (c.nbits + 1,), "param"
+    yield from _pixel_decoder_entries(c, d[-1])
 
 
 class ParamTree(nn.Module):

@@ -9,6 +9,8 @@ with weights 0.0448 / 0.2856 / 0.3001 / 0.2363 / 0.1333).  The reference checkou
 restatement is pinned against the unmodified file (tests/golden/make_golden_ssim.py, tests/test_oracle_ssim.py: equal in float64) and
 against an independent float64 scipy evaluation in tests/test_host.py.  Device fp32 inputs run on the HIP statistics kernel
 (csrc/ssim.hip: one streaming pass per scale instead of ten grouped convolutions); `LAST_SSIM_BACKEND` says which path a call took.
+`bit_accuracy` / `bit_accuracy_1msg` send device fp32 pixel-wise (4-D) predictions through the pixel-vote kernel (csrc/pixel_head.hip);
+`LAST_VOTE_BACKEND` says which path such a call took.
 """
 import math
 
@@ -23,8 +25,39 @@ def psnr(x: torch.Tensor, y: torch.Tensor, is_video: bool = False) -> torch.Tens
     return 20 * math.log10(255.0) - 10 * torch.log10(torch.mean(delta ** 2, dim=dims))
 
 
+LAST_VOTE_BACKEND = None      # "hip" or "torch": which path the last bit_accuracy / bit_accuracy_1msg call on 4-D predictions took
+
+
+def _vote_on_hip(preds: torch.Tensor, mask) -> bool:
+    """device fp32 4-D predictions go through the pixel-vote kernel (csrc/pixel_head.hip: one read of the logits); everything else keeps the torch code"""
+    return (preds.dim() == 4 and preds.is_cuda and preds.dtype == torch.float32 and preds.numel() > 0 and preds.shape[-2] * preds.shape[-1] < 2 ** 24
+            and (mask is None or (torch.is_tensor(mask) and mask.is_cuda and mask.dim() == 4 and mask.shape[1] == 1
+                                  and mask.shape[0] in (1, preds.shape[0]) and mask.shape[-2:] == preds.shape[-2:])))
+
+
+def _hip_votes(preds, mask, threshold):
+    """(votes [B, K], nsel [B]) as int64, or None when the frames select different numbers of pixels: the reference's
+    `masked_select(...).view(bsz, nbits, -1)` then regroups the selected values across frames, which only the torch code reproduces"""
+    from .pixel_head import pixel_vote
+    with torch.no_grad():
+        votes, nsel = pixel_vote(preds, mask, threshold)
+    if mask is not None and not bool((nsel == nsel[0]).all()):
+        return None
+    return votes.long(), nsel.long()
+
+
 def bit_accuracy(preds: torch.Tensor, targets: torch.Tensor, mask: torch.Tensor = None, threshold: float = 0.0) -> torch.Tensor:
     """fraction of bits where (pred > threshold) == (target > 0.5); pixel-wise predictions are majority-voted first."""
+    global LAST_VOTE_BACKEND
+    if _vote_on_hip(preds, mask):
+        vn = _hip_votes(preds, mask, threshold)
+        if vn is not None:
+            LAST_VOTE_BACKEND = "hip"
+            votes, nsel = vn
+            voted = (votes.double() / nsel.double()[:, None]) > 0.5          # the mean of the 0 / 1 decisions in double, as `.mean(dtype=float)`
+            return (voted == (targets > 0.5)).float().mean(dim=-1)
+    if preds.dim() == 4:
+        LAST_VOTE_BACKEND = "torch"
     preds = preds > threshold
     if preds.dim() == 4:
         bsz, nbits, h, w = preds.size()
@@ -39,7 +72,20 @@ def bit_accuracy(preds: torch.Tensor, targets: torch.Tensor, mask: torch.Tensor 
 
 
 def bit_accuracy_1msg(preds: torch.Tensor, targets: torch.Tensor, masks: torch.Tensor = None, threshold: float = 0.0) -> torch.Tensor:
-    """evals/metrics.py:180-206: per-pixel bit accuracy averaged over the (unmasked) pixels of each image; preds B x K x H x W."""
+    """evals/metrics.py:180-206: per-pixel bit accuracy averaged over the (unmasked) pixels of each image; preds B x K x H x W.
+    Return value as the reference's: with `masks` a HOST tensor (the reference builds it from `.item()` values, so this form synchronises on
+    either path), without masks a tensor on the predictions' device."""
+    global LAST_VOTE_BACKEND
+    if _vote_on_hip(preds, masks):
+        from .pixel_head import pixel_vote
+        LAST_VOTE_BACKEND = "hip"
+        with torch.no_grad():
+            votes, nsel = pixel_vote(preds, masks, threshold)
+        votes, nsel = votes.long(), nsel.long()[:, None]
+        hits = torch.where(targets.to(votes.device) > 0.5, votes, nsel - votes).sum(dim=1)        # whole numbers below 2^24 x K: exact
+        acc = (hits.double() / (nsel[:, 0] * preds.shape[1]).double()).float()      # the exact ratio of two whole numbers, rounded once
+        return acc if masks is None else acc.cpu()                                                 # (the masked form returns a host tensor)
+    LAST_VOTE_BACKEND = "torch"
     hit = ((preds > threshold) == (targets > 0.5)[:, :, None, None]).float()
     if masks is None:
         return hit.mean(dim=(1, 2, 3))

@@ -134,7 +134,8 @@ class Extractor(nn.Module):
         with torch.cuda.device(eng.dev):
             x = N.f32c(imgs.to(eng.dev))
             rgb, _ = eng.resize_pre(x, (x.shape[-2], x.shape[-1]), False, want_rgb=True, mul=2.0, add=-1.0, tag="det.in")
-            return eng.extractor_forward(rgb).clone().to(imgs.device)
+            p = eng.extractor_forward(rgb)
+            return (p if eng.preds_owned else p.clone()).to(imgs.device)
 
 
 class Blender(nn.Module):
@@ -202,7 +203,7 @@ def _msgs_i32(msgs: torch.Tensor, dev) -> torch.Tensor:
 
 
 _EXTRACTOR_FIELDS = ("depths", "dims", "stem_stride", "extractor", "vit_dim", "vit_depth", "vit_heads", "vit_patch", "vit_window", "vit_global",
-                     "vit_out", "vit_mlp_ratio", "vit_rel_pos")
+                     "vit_out", "vit_mlp_ratio", "vit_rel_pos", "head_stages", "head_pixelwise", "head_sigmoid")
 
 
 def merge_cfg(embedder: "Embedder", detector: "Extractor", **own) -> ModelCfg:
@@ -364,6 +365,28 @@ class Wam(nn.Module):
         ent["g"].replay()
         return ent["out"]
 
+    @property
+    def pixelwise(self) -> bool:
+        """the detector predicts [F, 1+nbits, S, S] maps (pixel_decoder.pixelwise) instead of one row of logits per frame"""
+        return bool(getattr(self.detector.cfg, "head_pixelwise", False))
+
+    def _empty_preds_shape(self) -> tuple:
+        """shape of `preds` for a clip without frames: the maps of a pixel-wise head are the latent grid times the product of its factors"""
+        c = self.detector.cfg
+        k = self.embedder.cfg.nbits + 1
+        if not self.pixelwise:
+            return (0, k)
+        S = int(self.img_size)
+        side = S // c.vit_patch if c.extractor == "sam" else ((S - 4) // c.stem_stride + 1) // 8
+        for f in c.head_stages:
+            side *= int(f)
+        return (0, k, side, side)
+
+    def _per_frame_rows_only(self, what: str) -> None:
+        if self.pixelwise:
+            raise NotImplementedError(f"{what} passes [F, 1+nbits] rows of logits: a pixel-wise detector predicts [F, 1+nbits, S, S] maps "
+                                      f"(use detect / extract_message)")
+
     def _detect_frames(self, eng: HipEngine, fr: torch.Tensor, S, antialias: bool) -> torch.Tensor:
         def run(si):
             rgb, _ = eng.resize_pre(si["fr"], S, antialias, want_rgb=True, mul=2.0, add=-1.0, tag="det.in")
@@ -374,7 +397,8 @@ class Wam(nn.Module):
             out = self._graphed(key(), {"fr": fr}, run, rekey=key)["preds"].clone()
             eng.note_guard()           # the captured vs_check_finite has run: deliver its flag like an eager steady-state pass does
             return out
-        return run({"fr": fr})["preds"].clone()
+        p = run({"fr": fr})["preds"]
+        return p if eng.preds_owned else p.clone()      # (the maps of a pixel-wise head are already the caller's: no second 0.8 GB pass)
 
     # ---- core of embed: one chunk of frames on the device
     def _embed_frames(self, eng: HipEngine, fr: torch.Tensor, msgs_i32: torch.Tensor, out: torch.Tensor, *, step: int,
@@ -522,7 +546,7 @@ class Wam(nn.Module):
         eng = self._engine()
         aa = _antialias_flag(interpolation)
         if imgs.shape[0] == 0:
-            return {"preds": imgs.new_zeros((0, self.embedder.cfg.nbits + 1))}
+            return {"preds": imgs.new_zeros(self._empty_preds_shape())}
         with torch.cuda.device(eng.dev):
             x = N.f32c(imgs.to(eng.dev))
             return {"preds": self._detect_frames(eng, x, (self.img_size, self.img_size), aa).to(imgs.device)}
@@ -542,7 +566,6 @@ class Wam(nn.Module):
         """(embedder, detector) have parameters that want gradients in the current autograd mode"""
         if not torch.is_grad_enabled():
             return False, False
-        cfg = self.embedder.cfg
         emb = any(p.requires_grad for p in self.embedder.parameters())
         det = any(p.requires_grad for p in self.detector.parameters())
         return emb, det
@@ -716,7 +739,7 @@ class Videoseal(Wam):
             return super().detect(imgs) if interpolation is None else super().detect(imgs, interpolation)
         if imgs.shape[0] == 0:
             self._engine()
-            return {"preds": imgs.new_zeros((0, self.embedder.cfg.nbits + 1))}
+            return {"preds": imgs.new_zeros(self._empty_preds_shape())}
         return {"preds": self._detect_clip(imgs, interpolation)}
 
     # ---- uint8 RGB24 clips, the data format on either side of the path in inference_streaming.py
@@ -743,6 +766,7 @@ class Videoseal(Wam):
         """inference_streaming.py:119-125 (`detect_video_clip`): uint8 [F,H,W,3] -> {'preds': [F, 1+nbits]}."""
         if clip.dtype != torch.uint8 or clip.dim() != 4 or clip.shape[-1] != 3:
             raise ValueError("detect_u8 wants a uint8 RGB24 clip [F, H, W, 3]")
+        self._per_frame_rows_only("detect_u8")
         if clip.shape[0] == 0:
             self._engine()
             return {"preds": torch.zeros((0, self.embedder.cfg.nbits + 1), device=clip.device)}

@@ -37,6 +37,8 @@ EXPORTS = [
     "vs_aug_color_bwd", "vs_clamp01_bwd", "vs_nhwc_to_nchw_scaled", "vs_percep_partial_doubles", "vs_percep_mse", "vs_percep_mse_grad",
     "vs_ssim_partial_doubles", "vs_ssim_stats", "vs_ssim_grad", "vs_avgpool2_pad", "vs_jnd_loss_partial_doubles", "vs_jnd_loss", "vs_jnd_loss_grad",
     "vs_split_block", "vs_check_finite", "vs_absmax", "vs_resblock_thin", "vs_resblock_thin_supported", "vs_cnx_block_supported", "vs_cnx_block_image_bytes", "vs_cnx_block",
+    "vs_pixel_upgather_supported", "vs_pixel_upgather", "vs_pixel_upgather_bwd", "vs_pixel_linear", "vs_pixel_linear_bwd_partial_floats", "vs_pixel_linear_bwd",
+    "vs_pixel_bce_partial_doubles", "vs_pixel_bce", "vs_pixel_vote",
 ]
 
 
@@ -213,6 +215,13 @@ def lib() -> C.CDLL:
         "vs_resblock_thin_supported": [I, I, I],
         "vs_cnx_block": [P, P, I, I64, I, I, F, F, P, I64, P, P, I64, P, I64, P, P],
         "vs_cnx_block_supported": [I, I64, I],
+        "vs_pixel_upgather_supported": [I, I],
+        "vs_pixel_upgather": [P, I64, I, I, I, I, I, P, P, F, I, P, I64, P],
+        "vs_pixel_upgather_bwd": [P, I64, I, I, I, I, I, P, I64, P],
+        "vs_pixel_linear": [P, I64, I, I64, I, P, P, I, I, P, P],
+        "vs_pixel_linear_bwd": [P, P, P, I64, I, I64, I, P, I, P, I64, P, P, P, P],
+        "vs_pixel_bce": [P, P, P, I, I, I, I64, F, F, F, P, P, P, P],
+        "vs_pixel_vote": [P, I64, P, I, I, I64, F, P, P, P],
     }
     for name, args in sig.items():
         fn = getattr(L, name)
@@ -237,6 +246,10 @@ def lib() -> C.CDLL:
                        ("vs_colreduce_partial_floats", [I, I64, I64]), ("vs_bn_bwd_partial_floats", [I64, I64])):
         getattr(L, name).restype = C.c_int64
         getattr(L, name).argtypes = args
+    L.vs_pixel_linear_bwd_partial_floats.restype = C.c_int64
+    L.vs_pixel_linear_bwd_partial_floats.argtypes = [I64, I, I]
+    L.vs_pixel_bce_partial_doubles.restype = C.c_int64
+    L.vs_pixel_bce_partial_doubles.argtypes = [I, I, I64]
     L.vs_sizeof_conv_desc.restype = C.c_int
     L.vs_sizeof_tail_desc.restype = C.c_int
     if L.vs_version() != 3:

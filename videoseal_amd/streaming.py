@@ -47,6 +47,9 @@ def embed_detect_chunks(model, frames: torch.Tensor, msgs: torch.Tensor, chunk: 
     """frames [F,3,H,W] fp32 or uint8 [F,H,W,3] on the device -> logits [F, 1+nbits].  `sink(first_frame, imgs_w_chunk)` receives
     every watermarked chunk in clip order (e.g. to hand it to an encoder); it is called on the embed stream's timeline.
     group: chunks per U-Net pass (None = default_group; 1 = the literal per-chunk calls); det_batch: frames per extractor pass (None = DET_BATCH)."""
+    if getattr(model, "pixelwise", False):
+        raise NotImplementedError("embed_detect_chunks passes [F, 1+nbits] rows of logits: a pixel-wise detector predicts [F, 1+nbits, S, S] maps "
+                                  "(use model.detect)")
     u8 = frames.dtype == torch.uint8
     step = int(model.step_size)
     if group is None:

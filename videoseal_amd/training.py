@@ -44,6 +44,11 @@ class DetectorStep:
     `grad_scale` (= 1 / accumulation_steps in train.py:641)."""
 
     def __init__(self, model):
+        c = model.embedder.cfg
+        self.pixel_head = list(c.head_stages) != [1] or bool(c.head_pixelwise) or bool(c.head_sigmoid)
+        if self.pixel_head and (not c.head_pixelwise or c.head_sigmoid or any(f not in (2, 4) for f in c.head_stages)):
+            raise NotImplementedError("DetectorStep: of the heads with up-scaling stages, the training step covers the pixel-wise ones of the reference's "
+                                      "configurations (factors 2 / 4, `pixelwise: True`, no sigmoid_output)")
         self.model = model
         self.vit = model.embedder.cfg.extractor == "sam"       # the legacy card's SAM-style ViT (vit.py:14-144): _forward_vit / _backward_vit
         self._ones: Dict[int, torch.Tensor] = {}
@@ -309,6 +314,8 @@ class DetectorStep:
 
     def _head_forward(self, eng: HipEngine, cur: Act, X, S) -> torch.Tensor:
         """pixel decoder (pixel_decoder.py:61-83, upscale_stages [1]): reflect-pad conv3x3 as patch matrix + GEMM, LayerNorm, GELU, mean, Linear"""
+        if self.pixel_head:
+            return self._pixel_head_forward(eng, cur, X, S)
         c, L, st, B = eng.cfg, eng.lib, N.stream(), cur.B
         Cl = cur.C
         g = eng._g
@@ -332,8 +339,45 @@ class DetectorStep:
         S.update(last=cur, cols=cols, hc=hc, z=z, hl=hl)
         return logits
 
+    def _pixel_head_forward(self, eng: HipEngine, cur: Act, X, S) -> torch.Tensor:
+        """the chained, pixel-wise head (pixel_decoder.py:61-83 with stages of 2 / 4): per stage the low-resolution per-tap GEMM, the raw gather,
+        LayerNorm and GELU, all kept; then the per-pixel linear layer -> [B, 1+nbits, H, W]"""
+        from . import pixel_head as PH
+        P = X["phead"]
+        keep = []
+        for i, s in enumerate(P["stages"]):
+            out, raw, ln = PH.stage_forward(eng, cur, s["gemm"], s["lnw"], s["lnb"], s["f"], f"tr.ph{i}", keep_raw=True)
+            keep.append(dict(x=cur, raw=raw, ln=ln))
+            cur = out
+        preds = torch.empty(cur.B, P["lin_w"].shape[0], cur.H, cur.W, device=eng.dev, dtype=torch.float32)
+        PH.linear_forward(cur, P["lin_w"], P["lin_b"], False, preds)
+        S.update(ph_keep=keep, ph_last=cur)
+        return preds
+
+    def _pixel_head_backward(self, eng: HipEngine, S, dpreds: torch.Tensor, X, G, want_params: bool) -> Act:
+        """fills the `detector.pixel_decoder.*` gradients from d preds [B, 1+nbits, H, W]; returns the gradient of the head's input map"""
+        from . import pixel_head as PH
+        P, pd, g = X["phead"], "detector.pixel_decoder", eng._g
+        last = S["ph_last"]
+        if tuple(dpreds.shape) != (last.B, P["lin_w"].shape[0], last.H, last.W):
+            raise ValueError(f"gradient of shape {tuple(dpreds.shape)} for predictions [{last.B}, {P['lin_w'].shape[0]}, {last.H}, {last.W}]")
+        dcur, dlw, dlb = PH.linear_backward(last, P["lin_w"], dpreds, None, want_params=want_params)
+        if want_params:
+            G[pd + ".linear.weight"], G[pd + ".linear.bias"] = dlw, dlb
+        for i in reversed(range(len(P["stages"]))):
+            s, k = P["stages"][i], S["ph_keep"][i]
+            pre = f"{pd}.output_upscaling.{i}.upsample_block."
+            dcur, Gs = PH.stage_backward(eng, k["x"], g(pre + "2.weight").float(), s["lnw"], k["raw"], k["ln"], dcur, s["f"], f"tr.phb{i}",
+                                         want_params=want_params)
+            G[pre + "3.weight"], G[pre + "3.bias"] = Gs["lnw"], Gs["lnb"]
+            if want_params:
+                G[pre + "2.weight"] = Gs["conv"]
+        return dcur
+
     def _head_backward(self, eng: HipEngine, S, dlogits: torch.Tensor, X, G, want_params: bool) -> Act:
         """pixel decoder backward: fills the `detector.pixel_decoder.*` gradients, returns the gradient of its input map"""
+        if self.pixel_head:
+            return self._pixel_head_backward(eng, S, dlogits, X, G, want_params)
         c, L, st = eng.cfg, eng.lib, N.stream()
         pd = "detector.pixel_decoder"
         hl, z, hc, cols, cur = S["hl"], S["z"], S["hc"], S["cols"], S["last"]
@@ -462,7 +506,9 @@ class DetectorStep:
 
     # ------------------------------------------------------------------ public
     def step(self, imgs_aug: torch.Tensor, msgs: torch.Tensor, temperature: float = 1.0, grad_scale: float = 1.0,
-             accumulate: bool = True):
+             accumulate: bool = True, masks: Optional[torch.Tensor] = None, detect_weight: float = 0.0, decode_weight: float = 1.0):
+        """masks / detect_weight / decode_weight: for a pixel-wise extractor, whose loss is detect_weight x detection + decode_weight x masked
+        decoding loss on its [B, 1+nbits, H, W] maps (vs_pixel_bce); `masks` [B, 1, H, W] must have the size of the maps (ValueError otherwise)"""
         model = self.model
         eng = model._engine()
         eng.begin_training_pass()
@@ -479,21 +525,36 @@ class DetectorStep:
             m = msgs.to(eng.dev).to(torch.int32).contiguous()
             if m.dim() != 2 or m.shape[1] != k or m.shape[0] not in (1, B):
                 raise ValueError(f"msgs must be [{B} or 1, {k}]")
+            if self.pixel_head:
+                from . import pixel_head as PH
+                if masks is None:
+                    raise ValueError("a pixel-wise extractor needs the masks [B, 1, H, W] its decoding loss is taken over")
+                terms, dlogits = PH.pixel_bce(logits, masks.to(eng.dev), m, temperature=temperature, w_det=float(detect_weight) * float(grad_scale),
+                                              w_dec=float(decode_weight) * float(grad_scale))
+                loss = (detect_weight * terms[0] if detect_weight else 0.0) + (decode_weight * terms[1] if decode_weight else 0.0)
+                grads = self._backward(eng, S, dlogits)
+                self._accumulate(model, grads, accumulate)
+                return loss, logits, grads
             dlogits = torch.empty_like(logits)
             loss = torch.empty(1, device=eng.dev, dtype=torch.float32)
             N.check(eng.lib.vs_bce_logits(N.ptr(logits), N.ptr(m), m.shape[0], B, k, float(temperature), float(grad_scale), N.ptr(dlogits),
                                           N.ptr(loss), N.stream()), "vs_bce_logits")
             grads = self._backward(eng, S, dlogits)
-        if accumulate:
-            params = dict(model.named_parameters())
-            for name, gten in grads.items():
-                prm = params[name]
-                gten = gten.reshape(prm.shape)
-                if prm.grad is None:
-                    prm.grad = gten.clone()
-                else:
-                    prm.grad.add_(gten)
+        self._accumulate(model, grads, accumulate)
         return loss[0], logits, grads
+
+    @staticmethod
+    def _accumulate(model, grads, accumulate: bool) -> None:
+        if not accumulate:
+            return
+        params = dict(model.named_parameters())
+        for name, gten in grads.items():
+            prm = params[name]
+            gten = gten.reshape(prm.shape)
+            if prm.grad is None:
+                prm.grad = gten.clone()
+            else:
+                prm.grad.add_(gten)
 
 
 class EmbedderBackward:
@@ -824,20 +885,24 @@ class GeneratorStep:
     (vs_percep_mse, vs_ssim_stats / vs_ssim_grad, vs_jnd_loss, vs_bce_logits) -> adaptive weights through `get_last_layer()` (videosealloss.py:72-107: one backward probe per term that
     stops at the output convolution) -> backward into `.grad` of every embedder and detector parameter.  The discriminator term is a second
     trainable network outside this path (disc_weight = 0, what train.py itself uses for lambda_d = 0); the detection term needs a per-pixel
-    mask head, which the ConvNeXt / ViT extractors of the shipped cards do not have (the reference's BCE raises on the shape mismatch too).
+    mask head, which the ConvNeXt / ViT extractors of the shipped cards do not have (the reference's BCE raises on the shape mismatch too).  The
+    pixel-wise extractors (`*_pw`) have that head on the HIP path for inference, and `vs_pixel_bce` computes the detection and the masked decoding
+    term with their gradient on `[B, 1+nbits, H, W]` logits: with such a detector `losses()` has `detect` and the masked `decode` in the reference's
+    order (percep, detect, decode), and a mask of another size than the maps raises ValueError.
 
     The reference's own loss object works as well -- `model(imgs, masks)` returns graph-carrying tensors -- this class is the same step
     without ATen in the loss."""
 
     def __init__(self, model, percep_loss: str = "mse", percep_weight: float = 1.0, decode_weight: float = 0.0, detect_weight: float = 0.0,
                  balanced: bool = True, total_norm: float = 0.0, temperature: float = 1.0):
-        if detect_weight > 0:
+        if detect_weight > 0 and not getattr(model, "pixelwise", False):
             raise NotImplementedError("detect_weight > 0: the per-frame extractors predict no mask map (videosealloss.py:140-147 needs [b,1,h,w] logits)")
         if percep_weight > 0:
             from . import autograd as AG
             AG.parse_percep_loss(percep_loss)          # every string of losses/perceptual.py:84-113 whose terms the HIP path has; raises otherwise
         self.model, self.percep_loss, self.temperature = model, percep_loss, float(temperature)
         self.percep_weight, self.decode_weight, self.balanced, self.total_norm = percep_weight, decode_weight, balanced, total_norm
+        self.detect_weight = detect_weight
 
     def losses(self, imgs: torch.Tensor, outputs: dict):
         from . import autograd as AG
@@ -845,8 +910,14 @@ class GeneratorStep:
         dev = outputs["imgs_w"].device
         if self.percep_weight > 0:
             losses["percep"], weights["percep"] = AG.percep_loss(imgs.to(dev), outputs["imgs_w"], self.percep_loss), self.percep_weight
-        if self.decode_weight > 0:
-            losses["decode"], weights["decode"] = AG.decoding_loss(outputs["preds"], outputs["msgs"], self.temperature), self.decode_weight
+        preds = outputs["preds"]
+        if preds.dim() == 4:          # pixel-wise extractor: detection on channel 0, decoding over the pixels the mask selects (videosealloss.py:138-167)
+            if self.detect_weight > 0:
+                losses["detect"], weights["detect"] = AG.pixel_loss(preds, outputs["masks"], outputs["msgs"], self.temperature, "detect"), self.detect_weight
+            if self.decode_weight > 0:
+                losses["decode"], weights["decode"] = AG.pixel_loss(preds, outputs["masks"], outputs["msgs"], self.temperature, "decode"), self.decode_weight
+        elif self.decode_weight > 0:
+            losses["decode"], weights["decode"] = AG.decoding_loss(preds, outputs["msgs"], self.temperature), self.decode_weight
         return losses, weights
 
     def scales(self, losses: dict, weights: dict):
