@@ -665,6 +665,44 @@ int vs_pixel_bce(const float* preds, const float* masks, const int32_t* msgs, in
 int vs_pixel_vote(const float* preds, int64_t batch_stride, const float* masks, int B, int K, int64_t HW, float threshold, int32_t* votes,
                   int32_t* nsel, void* stream);
 
+/* ---- PatchGAN discriminator of the adversarial term (csrc/disc.hip; modules/discriminator.py:89-148, losses/videosealloss.py:16-31, 128-135,
+ * 192-214).  The dense 4 x 4 convolutions and their backward-data products are vs_conv_gemm launches (KH = KW = 4; vs_pack_conv with transpose = 1
+ * and padding 2 for the backward; vs_dilate2 in front of it for the stride-2 layers).  Deterministic: fixed-order partial sums, no atomics.
+ * vs_disc_input: frames [B][3][H][W] -> the rows [B * H * W][4] of layer 1: (r, g, b, 0), or (m0 . rgb, 0, 0, 0) when m0 (3 device floats: row 0
+ *   of the rgb2yuv matrix) is given.  vs_disc_input_bwd: the adjoint, d rows -> d imgs [B][3][H][W] (every element written).
+ * vs_groupnorm_lrelu: groups = 4: GroupNorm over (C / 4, HW) per frame and group (biased variance, eps), per-channel affine, LeakyReLU(slope) on
+ *   NHWC rows [B][HW][ld] in one pass; writes mean / rstd [B][4] (doubles) for the backward.  C % 16 == 0 and C / 4 a divisor of 256.  groups = 0: plain
+ *   LeakyReLU (gamma .. rstd and partial may be NULL).  Pad columns of the output row are zeroed.  partial: vs_groupnorm_partial_doubles doubles.
+ * vs_groupnorm_lrelu_bwd: from dy, the saved pre-norm x and mean / rstd: dx, dgamma [C], dbeta [C] (the slope of LeakyReLU taken from the sign
+ *   of the normalised, affine value); groups = 0: dx = dy * (x > 0 ? 1 : slope).
+ * vs_conv4x4_wgrad: dw[n][tap * ld + c] = sum over the output pixels of dy[b, oy, ox, n] * x[b, oy * stride + ky - 1, ox * stride + kx - 1, c]
+ *   (zero padding 1, stride 1 | 2) straight from the NHWC image x [B][H][W][ld], on the fp32 matrix cores, without a patch matrix; N = 1 (the
+ *   last layer; dy may then be dense, dy_ld = 1) runs a reduction kernel.  ld % 4 == 0 and ld <= 1024 (vs_conv4x4_wgrad_supported).
+ *   partial: vs_conv4x4_wgrad_partial_floats floats.
+ * vs_conv4x4_n1 / vs_conv4x4_n1_bwd: the last layer (ld channels -> 1, stride 1, padding 1): w [16 * ld] in (tap, channel) order, bias 1 float or
+ *   NULL, out dense [B][H - 1][W - 1]; the backward maps dy [B][H - 1][W - 1] to dx [B][H][W][ld]; vs_conv4x4_n1_bias_grad: db[0] = the sum
+ *   of the n values of dy (fp64, fixed order).
+ * vs_disc_loss: hinge = 0: out[0] = -mean(fake), dfake = -gscale / n_fake (real may be NULL).  hinge = 1: out[0] = 0.5 (mean relu(1 - real) +
+ *   mean relu(1 + fake)) with dreal / dfake = gscale * its gradient.  out[1], out[2] = mean(real), mean(fake); out has 4 floats.  dreal / dfake
+ *   may be NULL. */
+int vs_disc_input(const float* imgs, int B, int H, int W, const float* m0, float* rows, void* stream);
+int vs_disc_input_bwd(const float* drows, int B, int H, int W, const float* m0, float* dimgs, void* stream);
+int64_t vs_groupnorm_partial_doubles(int B, int HW, int C);
+int vs_groupnorm_lrelu(const float* x, int64_t ld, int B, int HW, int C, int groups, const float* gamma, const float* beta, float eps, float slope,
+                       double* partial, double* mean, double* rstd, float* out, int64_t out_ld, void* stream);
+int vs_groupnorm_lrelu_bwd(const float* dy, int64_t dy_ld, const float* x, int64_t ld, int B, int HW, int C, int groups, const float* gamma,
+                           const float* beta, const double* mean, const double* rstd, float slope, double* partial, float* dx, int64_t dx_ld,
+                           float* dgamma, float* dbeta, void* stream);
+int vs_conv4x4_wgrad_supported(int N, int64_t ld, int stride);
+int64_t vs_conv4x4_wgrad_partial_floats(int N, int64_t ld, int B, int H, int W, int stride);
+int vs_conv4x4_wgrad(const float* dy, int64_t dy_ld, int N, const float* x, int64_t ld, int B, int H, int W, int stride, float* partial, float* dw,
+                     void* stream);
+int vs_conv4x4_n1(const float* x, int64_t ld, int B, int H, int W, const float* w, const float* bias, float* out, void* stream);
+int vs_conv4x4_n1_bwd(const float* dy, int B, int H, int W, int64_t ld, const float* w, float* dx, void* stream);
+int vs_conv4x4_n1_bias_grad(const float* dy, int64_t n, float* db, void* stream);
+int vs_disc_loss(const float* real, int64_t n_real, const float* fake, int64_t n_fake, int hinge, float gscale, float* dreal, float* dfake,
+                 float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -39,6 +39,8 @@ EXPORTS = [
     "vs_split_block", "vs_check_finite", "vs_absmax", "vs_resblock_thin", "vs_resblock_thin_supported", "vs_cnx_block_supported", "vs_cnx_block_image_bytes", "vs_cnx_block",
     "vs_pixel_upgather_supported", "vs_pixel_upgather", "vs_pixel_upgather_bwd", "vs_pixel_linear", "vs_pixel_linear_bwd_partial_floats", "vs_pixel_linear_bwd",
     "vs_pixel_bce_partial_doubles", "vs_pixel_bce", "vs_pixel_vote",
+    "vs_disc_input", "vs_disc_input_bwd", "vs_groupnorm_partial_doubles", "vs_groupnorm_lrelu", "vs_groupnorm_lrelu_bwd", "vs_conv4x4_wgrad_supported",
+    "vs_conv4x4_wgrad_partial_floats", "vs_conv4x4_wgrad", "vs_conv4x4_n1", "vs_conv4x4_n1_bwd", "vs_conv4x4_n1_bias_grad", "vs_disc_loss",
 ]
 
 
@@ -222,6 +224,16 @@ def lib() -> C.CDLL:
         "vs_pixel_linear_bwd": [P, P, P, I64, I, I64, I, P, I, P, I64, P, P, P, P],
         "vs_pixel_bce": [P, P, P, I, I, I, I64, F, F, F, P, P, P, P],
         "vs_pixel_vote": [P, I64, P, I, I, I64, F, P, P, P],
+        "vs_disc_input": [P, I, I, I, P, P, P],
+        "vs_disc_input_bwd": [P, I, I, I, P, P, P],
+        "vs_groupnorm_lrelu": [P, I64, I, I, I, I, P, P, F, F, P, P, P, P, I64, P],
+        "vs_groupnorm_lrelu_bwd": [P, I64, P, I64, I, I, I, I, P, P, P, P, F, P, P, I64, P, P, P],
+        "vs_conv4x4_wgrad_supported": [I, I64, I],
+        "vs_conv4x4_wgrad": [P, I64, I, P, I64, I, I, I, I, P, P, P],
+        "vs_conv4x4_n1": [P, I64, I, I, I, P, P, P, P],
+        "vs_conv4x4_n1_bwd": [P, I, I, I, I64, P, P, P],
+        "vs_conv4x4_n1_bias_grad": [P, I64, P, P],
+        "vs_disc_loss": [P, I64, P, I64, I, F, P, P, P, P],
     }
     for name, args in sig.items():
         fn = getattr(L, name)
@@ -250,6 +262,10 @@ def lib() -> C.CDLL:
     L.vs_pixel_linear_bwd_partial_floats.argtypes = [I64, I, I]
     L.vs_pixel_bce_partial_doubles.restype = C.c_int64
     L.vs_pixel_bce_partial_doubles.argtypes = [I, I, I64]
+    L.vs_groupnorm_partial_doubles.restype = C.c_int64
+    L.vs_groupnorm_partial_doubles.argtypes = [I, I, I]
+    L.vs_conv4x4_wgrad_partial_floats.restype = C.c_int64
+    L.vs_conv4x4_wgrad_partial_floats.argtypes = [I, I64, I, I, I, I]
     L.vs_sizeof_conv_desc.restype = C.c_int
     L.vs_sizeof_tail_desc.restype = C.c_int
     if L.vs_version() != 3:

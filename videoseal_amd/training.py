@@ -883,8 +883,9 @@ class GeneratorStep:
     computed on the HIP path end to end: differentiable forward (autograd.py) -> perceptual ('mse', 'yuv', 'ssim', 'msssim', 'jnd' and
     their weighted sums 'a+0.1_b'; 'lpips', 'dists', 'watson_*' need weight files and 'focal' an FFT: not built) and decoding terms
     (vs_percep_mse, vs_ssim_stats / vs_ssim_grad, vs_jnd_loss, vs_bce_logits) -> adaptive weights through `get_last_layer()` (videosealloss.py:72-107: one backward probe per term that
-    stops at the output convolution) -> backward into `.grad` of every embedder and detector parameter.  The discriminator term is a second
-    trainable network outside this path (disc_weight = 0, what train.py itself uses for lambda_d = 0); the detection term needs a per-pixel
+    stops at the output convolution) -> backward into `.grad` of every embedder and detector parameter.  With `disc_weight > 0` the adversarial
+    term -mean(D(imgs_w)) of videosealloss.py:128-135 joins them between `percep` and `detect` (discriminator.py: NLayerDiscriminator, frozen in this
+    step; its own hinge update is `DiscriminatorStep`); the default disc_weight = 0 keeps it out.  The detection term needs a per-pixel
     mask head, which the ConvNeXt / ViT extractors of the shipped cards do not have (the reference's BCE raises on the shape mismatch too).  The
     pixel-wise extractors (`*_pw`) have that head on the HIP path for inference, and `vs_pixel_bce` computes the detection and the masked decoding
     term with their gradient on `[B, 1+nbits, H, W]` logits: with such a detector `losses()` has `detect` and the masked `decode` in the reference's
@@ -894,7 +895,17 @@ class GeneratorStep:
     without ATen in the loss."""
 
     def __init__(self, model, percep_loss: str = "mse", percep_weight: float = 1.0, decode_weight: float = 0.0, detect_weight: float = 0.0,
-                 balanced: bool = True, total_norm: float = 0.0, temperature: float = 1.0):
+                 balanced: bool = True, total_norm: float = 0.0, temperature: float = 1.0, disc_weight: float = 0.0, disc_start: int = 0,
+                 disc_num_layers: int = 2, disc_in_channels: int = 3, discriminator=None, disc_loss: str = "hinge", use_actnorm: bool = False):
+        if disc_weight > 0:
+            from .discriminator import check_disc_loss
+            check_disc_loss(disc_loss)
+            if use_actnorm:
+                raise NotImplementedError("use_actnorm=True: ActNorm is not built on the HIP path (discriminator.py)")
+        # the discriminator is built on first use (`disc()`), on the device of the frames: constructing the step touches no device
+        self.disc_weight, self.disc_start, self.disc_num_layers, self.disc_in_channels = float(disc_weight), int(disc_start), disc_num_layers, disc_in_channels
+        self.discriminator = discriminator
+        self.global_step = 0
         if detect_weight > 0 and not getattr(model, "pixelwise", False):
             raise NotImplementedError("detect_weight > 0: the per-frame extractors predict no mask map (videosealloss.py:140-147 needs [b,1,h,w] logits)")
         if percep_weight > 0:
@@ -904,12 +915,35 @@ class GeneratorStep:
         self.percep_weight, self.decode_weight, self.balanced, self.total_norm = percep_weight, decode_weight, balanced, total_norm
         self.detect_weight = detect_weight
 
+    def disc(self, device=None):
+        """the discriminator of the adversarial term, built on first use (NLayerDiscriminator(disc_in_channels, n_layers=disc_num_layers) with the
+        reference's initialisation, videosealloss.py:63-64) unless one was passed in"""
+        if self.discriminator is None:
+            from .discriminator import NLayerDiscriminator
+            self.discriminator = NLayerDiscriminator(input_nc=self.disc_in_channels, n_layers=self.disc_num_layers)
+        if device is not None and next(self.discriminator.parameters()).device != torch.device(device):
+            self.discriminator.to(device)
+        return self.discriminator
+
     def losses(self, imgs: torch.Tensor, outputs: dict):
         from . import autograd as AG
         losses, weights = {}, {}
         dev = outputs["imgs_w"].device
         if self.percep_weight > 0:
             losses["percep"], weights["percep"] = AG.percep_loss(imgs.to(dev), outputs["imgs_w"], self.percep_loss), self.percep_weight
+        if self.disc_weight > 0:      # videosealloss.py:128-135: -mean(D(imgs_w)) with the discriminator frozen; present with weight 0 before disc_start
+            from .discriminator import adopt_weight, generator_disc_loss
+            D = self.disc(dev)
+            frozen = [p for p in D.parameters() if p.requires_grad]
+            for p in frozen:
+                p.requires_grad_(False)
+            try:
+                logits_fake = D(outputs["imgs_w"])
+            finally:
+                for p in frozen:
+                    p.requires_grad_(True)
+            losses["disc"] = generator_disc_loss(logits_fake)
+            weights["disc"] = adopt_weight(1.0, self.global_step, self.disc_start) * self.disc_weight
         preds = outputs["preds"]
         if preds.dim() == 4:          # pixel-wise extractor: detection on channel 0, decoding over the pixels the mask selects (videosealloss.py:138-167)
             if self.detect_weight > 0:
@@ -934,8 +968,10 @@ class GeneratorStep:
         return {k: (w / tot) * n / (1e-12 + gn) for (k, w), gn in zip(weights.items(), norms)}
 
     def step(self, imgs: torch.Tensor, masks: torch.Tensor, msgs: Optional[torch.Tensor] = None, is_video: bool = False,
-             accumulation_steps: int = 1):
-        """returns (total_loss, log, outputs); gradients are accumulated into `.grad` scaled by 1 / accumulation_steps (train.py:641)"""
+             accumulation_steps: int = 1, global_step: int = 0):
+        """returns (total_loss, log, outputs); gradients are accumulated into `.grad` scaled by 1 / accumulation_steps (train.py:641).  `global_step`
+        is the step counter that `disc_start` is compared with (videosealloss.py:132)."""
+        self.global_step = int(global_step)
         outputs = self.model(imgs, masks, msgs, is_video=is_video)
         losses, weights = self.losses(imgs, outputs)
         scales = self.scales(losses, weights)
@@ -944,3 +980,32 @@ class GeneratorStep:
         log = {"total_loss": total.detach(), **{f"loss_{k}": v.detach() for k, v in losses.items()},
                **{f"scale_{k}": torch.as_tensor(v).detach() for k, v in scales.items()}}
         return total.detach(), log, outputs
+
+
+class DiscriminatorStep:
+    """The discriminator update of train.py:626-643 (videosealloss.py:192-214, optimizer_idx 1, `cond = None`): hinge loss of the patch logits of the
+    detached real and watermarked frames, gradients ADDED to `.grad` of the discriminator's parameters only.  GroupNorm is per frame, so both halves go
+    through the network as one batch of 2 B frames."""
+
+    def __init__(self, discriminator, disc_start: int = 0, disc_loss: str = "hinge"):
+        from .discriminator import check_disc_loss
+        check_disc_loss(disc_loss)
+        self.discriminator, self.disc_start = discriminator, int(disc_start)
+
+    def step(self, imgs: torch.Tensor, imgs_w: torch.Tensor, global_step: int = 0, accumulation_steps: int = 1, cond=None):
+        """returns (d_loss, log) with the reference's log keys: disc_loss, disc_factor, logits_real, logits_fake"""
+        from .discriminator import adopt_weight, disc_loss_raw
+        if cond is not None:
+            raise NotImplementedError("a `cond` tensor is not built on the HIP path (videosealloss.py:199-203): train.py never passes one")
+        D = self.discriminator
+        dev = next(D.parameters()).device
+        B = imgs.shape[0]
+        both = torch.cat([imgs.detach().to(dev), imgs_w.detach().to(dev)], 0)
+        logits = D(both)
+        factor = adopt_weight(1.0, int(global_step), self.disc_start)
+        out, dr, df = disc_loss_raw(logits[:B], logits[B:], hinge=True, gscale=factor / accumulation_steps)
+        if logits.requires_grad:
+            logits.backward(torch.cat([dr, df], 0))
+        d_loss = factor * out[0]
+        log = {"disc_loss": d_loss.detach(), "disc_factor": factor, "logits_real": out[1], "logits_fake": out[2]}
+        return d_loss.detach(), log
