@@ -233,7 +233,8 @@ int vs_scale_shift_act(const float* x, int64_t rows, int C, int64_t ld, const fl
  * train.py:517-523, 626-643).  Backward-DATA products are vs_conv_gemm launches on transposed weights; these are the rest.  All NHWC
  * fp32, leading dimensions multiples of 4, reductions deterministic (fixed order, fp64 across chunks).
  * vs_gemm_wgrad: dw[n][k] = sum_rows dy[row][n] * x[row][k] (dense [N][K]); partial = vs_gemm_wgrad_partial_floats floats.
- * vs_dwconv7: depthwise 7x7 pad 3 (+ bias) (+ add), w = [49][ld]; flip = 1 uses tap 48 - t: the backward-data pass (convnext.py:43).
+ * vs_dwconv7: depthwise 7x7 pad 3 (+ bias) (+ add), w = [49][ld], bias = [ld] (both read in whole float4 over the ld lanes: entries [C, ld) must be
+ *   there, and zero); flip = 1 uses tap 48 - t: the backward-data pass (convnext.py:43).
  * vs_dwconv7_wgrad: dw[49][ld] of the same; partial = vs_dwconv7_wgrad_partial_floats.
  * vs_layernorm_bwd: LayerNorm over C (biased variance): dx, d weight, d bias; stats = 2 * rows floats (mean, rstd out); partial =
  *   vs_colreduce_partial_floats(1, rows, ld).
@@ -298,7 +299,10 @@ int vs_bce_logits(const float* preds, const int32_t* msgs, int msg_rows, int B, 
 /* ---- backward building blocks of the U-Net embedder under model.train() (csrc/bwd_unet.hip; the generator side of train.py:626-643).
  * vs_bn_mean_rstd: batch statistics from the (all-reduced) moment vector of vs_bn_partial_sums.  vs_bn_relu_bwd_sums / _apply: BatchNorm
  *   on batch statistics (+ the ReLU that follows it) backward in two halves -- sums = [sum g xhat | sum g | rows] (2 * 4 ceil(C/4) + 1
- *   doubles) is what SyncBatchNorm all-reduces between them; dgamma / dbeta are the local sums.  vs_dilate2 + the forward conv on flipped
+ *   doubles) is what SyncBatchNorm all-reduces between them; dgamma / dbeta are the local sums.  mean / rstd / scale / shift: 4 ceil(C/4) floats
+ *   each, 16-byte aligned -- vs_bn_relu_bwd_sums reads them in whole float4 (what the entries [C, 4 ceil(C/4)) hold reaches the pad lanes of `sums` only);
+ *   vs_bn_mean_rstd writes ld entries of mean and of rstd ([C, ld) as zeros) from sums = 2 * ld + 1 doubles.  partial of vs_bn_relu_bwd_sums:
+ *   vs_bn_bwd_partial_floats(rows, 4 ceil(C/4)) floats (the kernel strides its partial sums by 4 ceil(C/4), whatever the tensors' ld).  vs_dilate2 + the forward conv on flipped
  *   weights = backward-data of the stride-2 down convs; vs_im2col3x3_strided: their patch matrix (zero padding 1) for vs_gemm_wgrad.
  * vs_upcat2x_bwd: adjoint of vs_upcat2x.  vs_msg_table_grad: the message embedding table.  vs_outc_tanh_bwd: adjoint of vs_outc_tanh
  *   (dv = [rows][4] dense, for the weight / bias gradients). */

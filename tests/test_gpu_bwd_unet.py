@@ -18,7 +18,7 @@ pytestmark = pytest.mark.gpu
 from oracle import videoseal_ref as R  # noqa: E402
 from oracle.inputs import synthetic_frames, synthetic_msgs  # noqa: E402
 from oracle.weights import make_state_dict, spec_from_card, tiny_spec  # noqa: E402
-from tests.test_gpu_bwd import _lib, _padded, _rand  # noqa: E402
+from tests.test_gpu_bwd import ENV_SHAPES, _lib, _padded, _rand, cpu_autograd, envelope, group_err, hard_matrix  # noqa: E402
 from tests.test_gpu_e2e import make_model  # noqa: E402
 from tests.test_oracle_golden import CARDS  # noqa: E402
 
@@ -63,6 +63,63 @@ def test_bn_relu_bwd(rows, C, ld):
     assert (dx[:, C:] == 0).all()
     assert (dg - gam.grad).abs().max() <= 5e-5 * gam.grad.abs().max()
     assert (db - bet.grad).abs().max() <= 5e-5 * bet.grad.abs().max()
+
+
+@pytest.mark.parametrize("rows,C,ld", ENV_SHAPES)
+def test_bn_relu_bwd_chain_fp64_envelope(rows, C, ld):
+    """vs_bn_partial_sums -> vs_bn_finish_sums / vs_bn_mean_rstd -> vs_bn_relu_bwd_sums -> vs_bn_relu_bwd_apply on hard channels (mean 30 and
+    std 0.5: E[x^2] - mean^2 cancels four digits; a constant channel: variance 0; a single 4e3 outlier; a channel of magnitude 1e-3, below
+    sqrt(eps)) against float64 autograd of relu(batch_norm(training=True)) on the CPU, per channel (see tests/test_gpu_bwd.py for the metric
+    and the yardstick).
+    ReLU decisions: an element whose float64 pre-activation lies within the fp32 rounding of raw * scale + shift of zero -- tau = 4 U (|raw *
+    scale| + |mean * scale| + |beta|): scale, shift and the multiply-add each round once -- may legitimately fall on either side, so such
+    elements are left out of the dx comparison; at most 0.1 % of the elements may be (ATen's fp32 run flips none on these inputs).  beta of
+    the constant channel, whose pre-activation IS beta, is set away from zero."""
+    L, st = _lib()
+    g = torch.Generator().manual_seed(60)
+    raw = hard_matrix(rows, C, 61, "cols")
+    gam, bet, dy = 1 + 0.5 * torch.rand(C, generator=g), 0.3 * torch.randn(C, generator=g), torch.randn(rows, C, generator=g)
+    bet[1] = 0.25
+
+    def autograd(dt):
+        rr, gg, bb = (t.to(dt).requires_grad_(True) for t in (raw, gam, bet))
+        pre = F.batch_norm(rr, None, None, gg, bb, training=True, eps=1e-5)
+        F.relu(pre).backward(dy.to(dt))
+        return rr.grad, gg.grad, bb.grad, pre.detach()
+    r64, r32 = cpu_autograd(autograd)
+    rd = raw.double()
+    mean64, var64 = rd.mean(0), rd.var(0, unbiased=False)
+    rstd64 = 1 / torch.sqrt(var64 + 1e-5)
+    sc64 = gam.double() * rstd64
+    tau = 4 * 2.0 ** -24 * ((rd * sc64).abs() + (mean64 * sc64).abs() + bet.double().abs())
+    keep = (r64[3].abs() > tau).double()
+    assert 1 - float(keep.mean()) <= 1e-3
+    assert torch.equal(r32[3] > 0, r64[3] > 0)                   # the yardstick itself takes every ReLU decision of the reference
+    ra, dya = _padded(raw.cuda(), ld), _padded(dy.cuda(), ld)
+    part = torch.empty(int(L.vs_bn_partial_doubles(rows, ld)), dtype=torch.float64, device="cuda")
+    sums = torch.empty(2 * ld + 1, dtype=torch.float64, device="cuda")
+    N.check(L.vs_bn_partial_sums(N.ptr(ra), rows, C, ld, N.ptr(part), N.ptr(sums), st), "vs_bn_partial_sums")
+    v = torch.zeros(4, ld, device="cuda")
+    gp, bp = _padded(gam.cuda()[None], ld)[0].contiguous(), _padded(bet.cuda()[None], ld)[0].contiguous()
+    N.check(L.vs_bn_finish_sums(N.ptr(sums), C, ld, N.ptr(gp), N.ptr(bp), 1e-5, 0.1, None, None, N.ptr(v[0]), N.ptr(v[1]), st), "vs_bn_finish_sums")
+    N.check(L.vs_bn_mean_rstd(N.ptr(sums), C, ld, 1e-5, N.ptr(v[2]), N.ptr(v[3]), st), "vs_bn_mean_rstd")
+    ldp = (C + 3) // 4 * 4
+    bpart = torch.empty(int(L.vs_bn_bwd_partial_floats(rows, ldp)), device="cuda")
+    bsums = torch.empty(2 * ldp + 1, dtype=torch.float64, device="cuda")
+    dg, db = torch.empty(C, device="cuda"), torch.empty(C, device="cuda")
+    N.check(L.vs_bn_relu_bwd_sums(N.ptr(ra), ld, N.ptr(dya), ld, N.ptr(v[2]), N.ptr(v[3]), N.ptr(v[0]), N.ptr(v[1]), 1, rows, C, N.ptr(bpart), N.ptr(bsums),
+                                  N.ptr(dg), N.ptr(db), st), "vs_bn_relu_bwd_sums")
+    dx = torch.full((rows, ld), 7.0, device="cuda")
+    N.check(L.vs_bn_relu_bwd_apply(N.ptr(ra), ld, N.ptr(dya), ld, N.ptr(v[2]), N.ptr(v[3]), N.ptr(v[0]), N.ptr(v[1]), 1, N.ptr(bsums), rows, C, N.ptr(dx),
+                                   ld, st), "vs_bn_relu_bwd_apply")
+    assert (dx[:, C:] == 0).all()
+    # the forward statistics: mean and rstd are single correctly-rounded-or-nearly values, the yardstick is one fp32 rounding (2^-24, the floor)
+    envelope(f"bn_relu_bwd chain rows={rows} C={C} ld={ld}", [
+        ("mean/chan", group_err(v[2][:C], mean64, None), 0.0),
+        ("rstd/chan", group_err(v[3][:C], rstd64, None), 0.0),
+        ("dx/chan", group_err(dx[:, :C], r64[0], 0, keep), group_err(r32[0], r64[0], 0, keep)),
+        ("dgamma/ch", group_err(dg, r64[1], None), group_err(r32[1], r64[1], None)),
+        ("dbeta/ch", group_err(db, r64[2], None), group_err(r32[2], r64[2], None))])
 
 
 @pytest.mark.parametrize("B,H,W,C,ld", [(2, 8, 8, 4, 4), (1, 9, 7, 6, 8), (2, 5, 6, 8, 8)])
@@ -283,3 +340,32 @@ def test_rmsnorm_act_bwd_and_act_bwd(rows, C, act):
     dz = torch.full((rows, C), 7.0, device="cuda")
     N.check(L.vs_act_bwd(N.ptr(zd), C, N.ptr(dy), C, rows, C, code, N.ptr(dz), C, st), "vs_act_bwd")
     assert (dz - z.grad).abs().max() <= 2e-6 * z.grad.abs().max() + 1e-7
+
+
+@pytest.mark.parametrize("rows,C,ld,act", [(37, 20, 20, "silu"), (301, 132, 160, "gelu"), (67, 1100, 1100, "relu")])
+def test_rmsnorm_act_bwd_fp64_envelope(rows, C, ld, act):
+    """vs_rmsnorm_act_bwd on hard rows (mean 30 and std 0.5: the projection g - n (n . g) removes the dominant common component; a constant
+    row; a single 4e3 outlier that carries the norm alone; a row of magnitude 1e-3) against float64 autograd on the CPU, per row for dx and per
+    channel for d gamma (the column sums of `term`, summed in float64 like the caller does).  The entry point requires C % 4 == 0: 18 and 130
+    of the other envelope tests become 20 and 132.  The ReLU case has no ambiguous decision: the sign of u = n sqrt(C) gamma is the sign of
+    x * gamma in any precision."""
+    L, st = N.lib(), N.stream()
+    fn = {"silu": F.silu, "relu": F.relu, "gelu": F.gelu}[act]
+    code = {"silu": N.ACT_SILU, "relu": N.ACT_RELU, "gelu": N.ACT_GELU}[act]
+    g = torch.Generator().manual_seed(62)
+    x = hard_matrix(rows, C, 63, "rows")
+    gamma, dy = 1 + 0.3 * torch.randn(C, generator=g), torch.randn(rows, C, generator=g)
+
+    def autograd(dt):
+        xx, gg = x.to(dt).requires_grad_(True), gamma.to(dt).requires_grad_(True)
+        fn(F.normalize(xx, dim=1) * (C ** 0.5) * gg).backward(dy.to(dt))
+        return xx.grad, gg.grad
+    r64, r32 = cpu_autograd(autograd)
+    xa, dya, gd = _padded(x.cuda(), ld), _padded(dy.cuda(), ld), gamma.cuda()
+    dx = torch.full((rows, ld), 7.0, device="cuda")
+    term = torch.full((rows, ld), 7.0, device="cuda")
+    N.check(L.vs_rmsnorm_act_bwd(N.ptr(xa), rows, C, ld, N.ptr(gd), code, N.ptr(dya), ld, N.ptr(dx), ld, N.ptr(term), ld, st), "vs_rmsnorm_act_bwd")
+    assert (dx[:, C:] == 0).all() and (term[:, C:] == 0).all()
+    envelope(f"rmsnorm_act_bwd {act} rows={rows} C={C} ld={ld}", [
+        ("dx/row", group_err(dx[:, :C], r64[0], 1), group_err(r32[0], r64[0], 1)),
+        ("dgamma/ch", group_err(term[:, :C].double().sum(0), r64[1], None), group_err(r32[1], r64[1], None))])

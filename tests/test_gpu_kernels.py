@@ -1164,21 +1164,7 @@ def test_resblock_thin_fused_kernel_32_channels(shape):
 # around a tensor reach the result, and must not write outside the output.  Every operand sits between two guard areas poisoned with signalling
 # patterns: NaN around the inputs (a value read past either end that reaches an accumulator makes the output NaN or different), a sentinel
 # around the output (a store outside the tensor changes it).  The unguarded launch of the same case is the expected value, bit for bit.
-GUARD = 4096        # floats on either side (16 KiB: more than any tile's halo)
-
-
-def _guarded(t: torch.Tensor, fill: float):
-    flat = t.contiguous().flatten()
-    buf = torch.full((GUARD + flat.numel() + GUARD,), fill, device=t.device, dtype=t.dtype)
-    buf[GUARD:GUARD + flat.numel()] = flat
-    return buf, buf[GUARD:GUARD + flat.numel()].view(t.shape)
-
-
-def _guards_intact(buf: torch.Tensor, fill: float) -> bool:
-    lo, hi = buf[:GUARD], buf[-GUARD:]
-    if fill != fill:
-        return bool(torch.isnan(lo).all() and torch.isnan(hi).all())
-    return bool((lo == fill).all() and (hi == fill).all())
+from tests._guards import GUARD, _guarded, _guards_intact  # noqa: E402,F401  (moved to tests/_guards.py; re-exported for the suites that import them from here)
 
 
 REDZONE_CONV = [c for c in CONV_CASES if c[-1] in (10, 11, 12, 15, 0x40, 0x43, 0x44, 0x45, 14)]

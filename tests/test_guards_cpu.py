@@ -1,0 +1,73 @@
+"""The red-zone helpers of tests/_guards.py on CPU tensors: a test that relies on a sentinel is only as good as the sentinel check."""
+import pytest
+import torch
+
+from tests._guards import GUARD, _guarded, _guards_intact, scratch, scratch_sentinel
+
+NAN = float("nan")
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.float64])
+@pytest.mark.parametrize("fill", [NAN, -7.0])
+@pytest.mark.parametrize("shape", [(1,), (3, 5), (2, 3, 7)])
+def test_guarded_view_aliases_the_buffer_between_two_intact_bands(dtype, fill, shape):
+    t = torch.arange(1, 1 + torch.Size(shape).numel(), dtype=dtype).view(shape)
+    buf, view = _guarded(t, fill)
+    assert buf.numel() == 2 * GUARD + t.numel() and view.shape == t.shape and torch.equal(view, t)
+    assert view.data_ptr() == buf.data_ptr() + GUARD * buf.element_size()
+    assert _guards_intact(buf, fill)
+    view.mul_(2)                                           # writes through the view land in the buffer, not in the bands
+    assert torch.equal(buf[GUARD:GUARD + t.numel()].view(shape), 2 * t) and _guards_intact(buf, fill)
+
+
+# (a NaN written into a NaN band is indistinguishable by value: NaN bands surround inputs, which kernels only read)
+@pytest.mark.parametrize("fill,value", [(NAN, 0.0), (NAN, 1.0), (NAN, float("inf")), (-7.0, 0.0), (-7.0, 1.0), (-7.0, NAN), (-7.0, float("inf")),
+                                        (-7.0, 7.0)])
+@pytest.mark.parametrize("where", ["one before", "one after", "first of the low band", "last of the high band"])
+def test_a_single_foreign_element_in_either_band_is_detected(fill, where, value):
+    buf, view = _guarded(torch.zeros(5), fill)
+    idx = {"one before": GUARD - 1, "one after": GUARD + 5, "first of the low band": 0, "last of the high band": buf.numel() - 1}[where]
+    buf[idx] = value
+    assert not _guards_intact(buf, fill)
+
+
+def test_nan_sentinels_compare_as_sentinels_and_finite_sentinels_reject_nan():
+    buf, _ = _guarded(torch.zeros(3), NAN)
+    assert _guards_intact(buf, NAN)                        # NaN != NaN must not read as "damaged"
+    assert not _guards_intact(buf, -7.0)                   # ... and a NaN band is not a -7 band
+    buf, _ = _guarded(torch.zeros(3), -7.0)
+    assert _guards_intact(buf, -7.0) and not _guards_intact(buf, NAN) and not _guards_intact(buf, 7.0)
+    buf[GUARD - 1] = torch.nextafter(torch.tensor(-7.0), torch.tensor(-8.0))     # one ulp off the sentinel
+    assert not _guards_intact(buf, -7.0)
+
+
+@pytest.mark.parametrize("dtype,fill", [(torch.float32, NAN), (torch.float32, 0.0), (torch.float64, NAN), (torch.float64, 0.0),
+                                        (torch.uint8, 0xFF), (torch.uint8, 0)])
+@pytest.mark.parametrize("nelem", [0, 1, 3, 7, 1025])
+def test_scratch_has_exactly_the_requested_elements_aligned_between_sentinels(dtype, fill, nelem):
+    buf, view = scratch(nelem, dtype, fill, device="cpu")
+    sent = scratch_sentinel(dtype)
+    assert view.numel() == nelem and view.dtype == dtype and buf.numel() == nelem + 2 * GUARD
+    if nelem:                                              # (an empty view has no address)
+        assert view.data_ptr() % 16 == 0
+        assert view.data_ptr() == buf.data_ptr() + GUARD * buf.element_size()
+    assert _guards_intact(buf, sent)
+    if fill != fill:
+        assert torch.isnan(view).all()
+    else:
+        assert (view == fill).all()
+    assert (buf[:GUARD] == sent).all() and (buf[GUARD + nelem:] == sent).all()       # the bands touch the view: nothing in between
+    view.fill_(1)                                          # a kernel that stays inside leaves the bands alone
+    assert _guards_intact(buf, sent)
+    buf[GUARD - 1] = 1                                     # one element before the view
+    assert not _guards_intact(buf, sent)
+    buf[GUARD - 1] = sent
+    buf[GUARD + nelem] = 1                                 # one element after the view
+    assert not _guards_intact(buf, sent)
+
+
+def test_scratch_detects_a_nan_written_outside_a_nan_filled_interior():
+    buf, view = scratch(6, torch.float32, NAN, device="cpu")
+    assert _guards_intact(buf, scratch_sentinel(torch.float32))
+    buf[GUARD + 6] = NAN                                   # what a reducer's stray NaN store would leave
+    assert not _guards_intact(buf, scratch_sentinel(torch.float32))
