@@ -1,6 +1,7 @@
 #!/usr/bin/env python
 """Upsample groups of the VideoSeal 1.0 U-Net at B = 32 (levels 0..2): fused one-kernel form vs cat2 + 9-tap GEMM + gather, HIP-event
-times.  GPU box only."""
+times; gather + LN and the fused kernel in both forms of the gather -- 2 x 2 blocks (csrc/upconv_gather.h, the default) and per pixel
+(vs_debug_set key 9 = 1) --, alternating in one process.  GPU box only."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -38,12 +39,25 @@ for (H, C1, C2, Co) in ((32, 384, 384, 64), (64, 64, 64, 32), (128, 32, 32, 16))
     cat = lambda: N.check(L.vs_cat2_scale(N.ptr(xa.t), C1, xa.ld, N.ptr(sa.t), C2, sa.ld, 2 ** -0.5, lc.rows, N.ptr(lc.t), lc.ld, st), "cat")
     gemm = lambda: eng.conv(lc, cw, z)
     gath = lambda: N.check(L.vs_upconv_gather_ln(N.ptr(z.t), z.ld, B, H, H, Co, N.ptr(lw), N.ptr(lb), 1e-6, 1, N.ptr(out.t), out.ld, st), "g")
-    t = [timeit(f) for f in (cat, gemm, gath)]
-    line = f"{H}^2 {C1}+{C2}->{Co}: cat {t[0]:6.1f}  gemm9 {t[1]:6.1f}  gather+LN {t[2]:6.1f}  = {sum(t):6.1f} us"
+    def both_forms(fn):
+        """(blocked, per-pixel) best times of two alternating rounds"""
+        best = [1e9, 1e9]
+        for _ in range(2):
+            for form in (0, 1):
+                L.vs_debug_set(9, form)
+                try:
+                    best[form] = min(best[form], timeit(fn))
+                finally:
+                    L.vs_debug_set(9, 0)
+        return best
+    t = [timeit(f) for f in (cat, gemm)]
+    tg = both_forms(gath)
+    t.append(tg[0])
+    line = f"{H}^2 {C1}+{C2}->{Co}: cat {t[0]:6.1f}  gemm9 {t[1]:6.1f}  gather+LN {tg[0]:6.1f} (per pixel {tg[1]:6.1f})  = {sum(t):6.1f} us"
     if L.vs_upconv_fused_supported(C1, C2, Co):
         fu = lambda: N.check(L.vs_upconv_fused(N.ptr(xa.t), C1, xa.ld, N.ptr(sa.t), C2, sa.ld, 2 ** -0.5, N.ptr(cw.split), B, H, H, Co,
                                                N.ptr(lw), N.ptr(lb), 1e-6, 1, N.ptr(out.t), out.ld, cw.arith, 16.0, 1.0 / (16.0 * cw.w_mul), st), "f")
-        tf = timeit(fu)
+        tf, tfp = both_forms(fu)
         io = (x.numel() + sk.numel() + out.rows * Co) * 4
-        line += f" | fused {tf:6.1f} us ({io / tf / 1e6:5.0f} GB/s of in+out)"
+        line += f" | fused {tf:6.1f} us (per pixel {tfp:6.1f}; {io / tf / 1e3:5.0f} GB/s of in+out)"
     print(line, flush=True)

@@ -7,6 +7,7 @@
 #include <cstring>
 
 #include "conv_common.h"
+#include "upconv_gather.h"
 
 namespace {
 
@@ -665,6 +666,8 @@ __global__ __launch_bounds__(256) void upcat2x_kernel(const float* __restrict__ 
 // vs_conv_gemm; this kernel does the 9-tap x 4-neighbour gather, the per-pixel LayerNorm and the activation.  The x2 up-sampled
 // concat (384 MB per launch at 64^2 x 768 channels x 32 frames) is never materialised.
 // Thread = (output pixel, group of CG channels); the TPP = Co / CG lanes of a pixel are adjacent and reduce with xor shuffles.
+// (The per-pixel form: since the blocked kernel below it runs only under the development switch VS_DBG_UPCONV_FORM = 1 and is what the
+// blocked form is compared with, bit for bit.)
 template <int CG>
 __global__ __launch_bounds__(256) void upconv_gather_ln_kernel(const float* __restrict__ z, int64_t zld, int H, int W, int Co,
                                                                int tpp_log2, const float* __restrict__ lnw,
@@ -748,6 +751,79 @@ __global__ __launch_bounds__(256) void upconv_gather_ln_kernel(const float* __re
     for (int e = 0; e < 4; ++e) o[e] = vs_apply_act(wv[e] * ((acc[j][e] - mean) / den) + bv[e], act);
     *reinterpret_cast<f32x4*>(orow + 4 * j) = o;
   }
+}
+
+// The same, blocked (upconv_gather.h): thread = (low-resolution cell, group of CG channels) produces the cell's 2 x 2 output pixels from 49
+// shared z loads instead of 4 x 36 -- every pixel still receives its own 36 terms in the order of the kernel above, so the outputs are the
+// same bit for bit (tests/test_gpu_upconv_block.py).  The LayerNorm reduces over the same TPP adjacent lanes, once per pixel.
+template <int CG>
+__global__ __launch_bounds__(256) void upconv_gather_ln_blk_kernel(const float* __restrict__ z, int64_t zld, int H, int W, int Co,
+                                                                   int tpp_log2, const float* __restrict__ lnw,
+                                                                   const float* __restrict__ lnb, float eps, int act,
+                                                                   float* __restrict__ out, int64_t old, int64_t ncell, int nblk) {
+  const int per = (nblk + 7) >> 3;           // XCD-aware order, as above
+  const int64_t vb = (int64_t)(blockIdx.x & 7) * per + (blockIdx.x >> 3);
+  const int64_t gid = vb * 256 + threadIdx.x;
+  const int64_t cq = gid >> tpp_log2;
+  const int g = (int)(gid & ((1 << tpp_log2) - 1));
+  const bool live = cq < ncell && vb < nblk;
+  const int64_t cell = live ? cq : 0;        // dead lanes still take part in the shuffles
+  constexpr int NV = CG / 4;
+  f32x4 lwv[NV], lbv[NV];
+#pragma unroll
+  for (int j = 0; j < NV; ++j) {
+    lwv[j] = *reinterpret_cast<const f32x4*>(lnw + g * CG + 4 * j);
+    lbv[j] = *reinterpret_cast<const f32x4*>(lnb + g * CG + 4 * j);
+  }
+  const int x = (int)(cell % W);
+  const int64_t t0 = cell / W;
+  const int y = (int)(t0 % H);
+  const int64_t b = t0 / H;
+  UpAxis ay, ax;
+  upconv_axis(y, H, ay);
+  upconv_axis(x, W, ax);
+  f32x4 acc[2][2][NV];
+#pragma unroll
+  for (int p = 0; p < 2; ++p)
+#pragma unroll
+    for (int q = 0; q < 2; ++q)
+#pragma unroll
+      for (int j = 0; j < NV; ++j) acc[p][q][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  upconv_gather_2x2<NV, int64_t>(z + b * H * W * zld + g * CG, (int64_t)W * zld, zld, Co, ay, ax, acc);
+  float mean[2][2], den[2][2];
+#pragma unroll
+  for (int p = 0; p < 2; ++p)
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+      float s = 0.f;
+#pragma unroll
+      for (int j = 0; j < NV; ++j) s += (acc[p][q][j][0] + acc[p][q][j][1]) + (acc[p][q][j][2] + acc[p][q][j][3]);
+      for (int o = 1; o < (1 << tpp_log2); o <<= 1) s += __shfl_xor(s, o, 64);
+      mean[p][q] = s / (float)Co;
+      float v = 0.f;
+#pragma unroll
+      for (int j = 0; j < NV; ++j)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) { const float dl = acc[p][q][j][e] - mean[p][q]; v += dl * dl; }
+      for (int o = 1; o < (1 << tpp_log2); o <<= 1) v += __shfl_xor(v, o, 64);
+      den[p][q] = sqrtf(v / (float)Co + eps);
+    }
+  if (!live) return;
+  const int64_t W2 = 2 * (int64_t)W;
+#pragma unroll
+  for (int p = 0; p < 2; ++p)
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+      float* orow = out + (((b * 2 * H + 2 * y + p) * W2) + 2 * x + q) * old + g * CG;
+#pragma unroll
+      for (int j = 0; j < NV; ++j) {
+        const f32x4 wv = lwv[j], bv = lbv[j];
+        f32x4 o;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) o[e] = vs_apply_act(wv[e] * ((acc[p][q][j][e] - mean[p][q]) / den[p][q]) + bv[e], act);
+        *reinterpret_cast<f32x4*>(orow + 4 * j) = o;
+      }
+    }
 }
 
 // 3x3 / stride 1 / pad 1 patch matrix of a SMALL map: out[m][t*ld + c] = in[b][p(y+ky-1)][p(x+kx-1)][c], p = reflect or zero padding.
@@ -1500,16 +1576,24 @@ extern "C" int vs_upconv_gather_ln(const float* z, int64_t z_ld, int B, int H, i
   const int cg = Co >= 64 ? 16 : Co / 4;
   int tl = 0;
   while ((cg << tl) < Co) ++tl;
-  const int64_t npix = (int64_t)B * 4 * H * W;
-  const int64_t nblk64 = cdiv64(npix << tl, 256);
+  // thread = (2 x 2 block of output pixels, channel group); development switch: thread = (output pixel, channel group), the first form
+  const bool blocked = vs_debug_get(VS_DBG_UPCONV_FORM) != 1;
+  const int64_t nitem = (int64_t)B * H * W * (blocked ? 1 : 4);
+  const int64_t nblk64 = cdiv64(nitem << tl, 256);
   VS_REQUIRE(nblk64 < (1 << 30));
   const int nblk = (int)nblk64;
   const int grid = ((nblk + 7) / 8) * 8;
   hipStream_t st = (hipStream_t)stream;
-#define VS_UPG(CG_) hipLaunchKernelGGL(upconv_gather_ln_kernel<CG_>, dim3(grid), dim3(256), 0, st, z, z_ld, H, W, Co, tl, lnw, lnb, eps, act, out, out_ld, npix, nblk)
-  if (cg == 4) VS_UPG(4);
-  else if (cg == 8) VS_UPG(8);
-  else VS_UPG(16);
+#define VS_UPG(KERN_, CG_) hipLaunchKernelGGL(KERN_<CG_>, dim3(grid), dim3(256), 0, st, z, z_ld, H, W, Co, tl, lnw, lnb, eps, act, out, out_ld, nitem, nblk)
+  if (blocked) {
+    if (cg == 4) VS_UPG(upconv_gather_ln_blk_kernel, 4);
+    else if (cg == 8) VS_UPG(upconv_gather_ln_blk_kernel, 8);
+    else VS_UPG(upconv_gather_ln_blk_kernel, 16);
+  } else {
+    if (cg == 4) VS_UPG(upconv_gather_ln_kernel, 4);
+    else if (cg == 8) VS_UPG(upconv_gather_ln_kernel, 8);
+    else VS_UPG(upconv_gather_ln_kernel, 16);
+  }
 #undef VS_UPG
   return vs_launch_status();
 }

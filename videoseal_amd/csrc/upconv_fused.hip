@@ -11,11 +11,13 @@
 //      three bf16 planes and stored to LDS next to the chunk of the pre-split weights ([3][9*Co][K] bf16); wave w multiplies
 //      row block w by all NB column blocks;
 //   2. accumulators -> z tile in LDS [100][9*Co (+4)] (the staging buffers are dead by then and are reused);
-//   3. gather + LayerNorm + activation: 4 lanes per output pixel, Co/4 channels each, two quad shuffles, 16-byte stores.
+//   3. gather + LayerNorm + activation: 4 lanes per low-resolution cell, Co/4 channels each, produce the cell's 2 x 2 output pixels from 49
+//      shared z reads (upconv_gather.h; the per-pixel form read 36 per pixel), two quad shuffles per pixel, 16-byte stores.
 #include <algorithm>
 #include <cstdlib>
 
 #include "conv_common.h"
+#include "upconv_gather.h"
 
 namespace {
 
@@ -94,7 +96,7 @@ __global__ __launch_bounds__(256, (NB <= 5 ? 2 : 1)) void upconv_fused_kernel(co
     }
   };
   fetch_b(0);
-  for (int kg = 0; kg < ((abl & 1) ? 0 : K); kg += KG * BK) {      // abl: tools/bench_upconv.py ablations (1: no GEMM, 2: no gather)
+  for (int kg = 0; kg < ((abl & 1) ? 0 : K); kg += KG * BK) {      // abl: tools/bench_upconv.py ablations (1: no GEMM, 2: no gather; 4: per-pixel gather)
     f32x4 ra[KG][2];
 #pragma unroll
     for (int c = 0; c < KG; ++c) {
@@ -171,6 +173,63 @@ __global__ __launch_bounds__(256, (NB <= 5 ? 2 : 1)) void upconv_fused_kernel(co
   }
   const int H2 = 2 * H, W2 = 2 * W;
   const float invC = 1.0f / (float)Co;
+  if (!(abl & 4)) {
+    // 2 x 2 blocks (upconv_gather.h): the quad of lanes takes one low-resolution cell -- 64 cells, one pass of the 256 threads -- and reads 49
+    // z vectors for its four pixels instead of 4 x 36; per pixel the terms, their order and the LayerNorm are those of the per-pixel loop below
+    if (abl & 2) return;
+    const int cy = tid >> 5, cx = (tid >> 2) & (UT - 1);
+    const int yc = y0 + 1 + cy, xc = x0 + 1 + cx;          // low-resolution cell
+    const bool live = yc < H && xc < W;
+    UpAxis ay, ax;
+    upconv_axis(min(yc, H - 1), H, ay);
+    upconv_axis(min(xc, W - 1), W, ax);
+#pragma unroll
+    for (int p = 0; p < 2; ++p)
+#pragma unroll
+      for (int k = 0; k < 3; ++k)
+#pragma unroll
+        for (int a = 0; a < 2; ++a) { ay.s[p][k][a] -= y0; ax.s[p][k][a] -= x0; }     // tile-relative
+    f32x4 v[2][2][NV];
+#pragma unroll
+    for (int p = 0; p < 2; ++p)
+#pragma unroll
+      for (int q = 0; q < 2; ++q)
+#pragma unroll
+        for (int j = 0; j < NV; ++j) v[p][q][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    upconv_gather_2x2<NV, int>(Z + q4 * CG, UH * ZS, ZS, Co, ay, ax, v);
+#pragma unroll
+    for (int p = 0; p < 2; ++p)
+#pragma unroll
+      for (int q = 0; q < 2; ++q) {
+        float s = 0.f;
+#pragma unroll
+        for (int j = 0; j < NV; ++j) s += (v[p][q][j][0] + v[p][q][j][1]) + (v[p][q][j][2] + v[p][q][j][3]);
+        s += __shfl_xor(s, 1, 64);
+        s += __shfl_xor(s, 2, 64);
+        const float mean = s * invC;
+        float var = 0.f;
+#pragma unroll
+        for (int j = 0; j < NV; ++j)
+#pragma unroll
+          for (int e = 0; e < 4; ++e) { const float dl = v[p][q][j][e] - mean; var += dl * dl; }
+        var += __shfl_xor(var, 1, 64);
+        var += __shfl_xor(var, 2, 64);
+        const float den = sqrtf(var * invC + eps);
+        if (live) {
+          float* orow = out + (((int64_t)b * H2 + 2 * yc + p) * W2 + 2 * xc + q) * old + q4 * CG;
+#pragma unroll
+          for (int j = 0; j < NV; ++j) {
+            const f32x4 wv = lwv[j], bv = lbv[j];
+            f32x4 o;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) o[e] = vs_apply_act(wv[e] * ((v[p][q][j][e] - mean) / den) + bv[e], act);
+            *reinterpret_cast<f32x4*>(orow + 4 * j) = o;
+          }
+        }
+      }
+    return;
+  }
+  // per-pixel form (development switch VS_DBG_UPCONV_FORM = 1): what the blocked form is compared with, bit for bit
   for (int it = tid >> 2; it < ((abl & 2) ? 0 : 4 * UT * UT); it += 64) {
     const int oy = it / (2 * UT), ox = it % (2 * UT);
     const int Y = (y0 + 1) * 2 + oy, X = (x0 + 1) * 2 + ox;
@@ -253,8 +312,9 @@ int launch_fused(const float* x, int C1, int64_t ld1, const float* skip, int C2,
   const int64_t nblk = (int64_t)B * tiles_x * tiles_y;
   if (nblk >= (1 << 30)) return VS_ERR_UNSUPPORTED;
   static const int abl = [] { const char* e = getenv("VS_UPCONV_ABL"); return e ? atoi(e) : 0; }();
+  const int form = vs_debug_get(VS_DBG_UPCONV_FORM) == 1 ? 4 : 0;      // abl bit 4: per-pixel phase 3
   hipLaunchKernelGGL(kern, dim3((unsigned)((nblk + 7) / 8 * 8)), dim3(256), smem, st, x, C1, ld1, skip, C2, ld2, s,
-                     static_cast<const unsigned short*>(wsplit), H, W, Co, lnw, lnb, eps, act, out, old, tiles_x, tiles_y, (int)nblk, abl, a_mul, acc_mul);
+                     static_cast<const unsigned short*>(wsplit), H, W, Co, lnw, lnb, eps, act, out, old, tiles_x, tiles_y, (int)nblk, abl | form, a_mul, acc_mul);
   return vs_launch_status();
 }
 
