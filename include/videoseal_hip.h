@@ -541,6 +541,47 @@ typedef struct vs_tail_desc {
 int vs_embed_tail(const vs_tail_desc_t* d, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * NV12 frames: what a hardware decoder (or ffmpeg in its native pixel format) hands over, 1.5 bytes per pixel.
+ * Layout.  A clip is uint8 [F][3H/2][W], H and W even.  Rows 0 .. H-1 of a frame are luma; rows H .. 3H/2-1 are the chroma plane: bytes 2j
+ *   and 2j+1 of chroma row i are Cb and Cr of the 2 x 2 pixel block (2i .. 2i+1, 2j .. 2j+1).  Consecutive bytes of a row are adjacent; rows
+ *   lie `pitch` bytes apart (any value >= W, no alignment asked), frames `frame_stride` bytes apart (>= pitch * 3H/2).
+ * Colour.  Kr/Kb = 0.299/0.114 (BT.601) or 0.2126/0.0722 (BT.709), Kg = 1-Kr-Kb;  Y = Kr R + Kg G + Kb B,  Cb = (B-Y)/(2(1-Kb)),
+ *   Cr = (R-Y)/(2(1-Kr)).  Limited range codes: Y -> 16 + 219 Y, C -> 128 + 224 C; full range: Y -> 255 Y, C -> 128 + 255 C.  The host builds
+ *   the forward 3 x 4 affine rgb2yuv12 ((R,G,B,1) in [0,1] -> codes, row-major) in float64, inverts it in float64 (yuv2rgb12) and passes both
+ *   as HOST arrays of 12 floats; the kernels know no presets.
+ * Chroma.  Up: every pixel of a 2 x 2 block uses the block's (Cb, Cr).  Down: the mean of the block's four per-pixel values, then one rounding.
+ * Range and rounding.  After NV12 -> RGB every channel is clamped to [0, 1] before anything else uses it.  Output codes are
+ *   floor(clamp(v, 0, 255) + 0.5), v in code units; there is no intermediate rounding to RGB24.
+ *
+ * vs_resize_pre_nv12: vs_resize_pre on such frames (conversion and clamp per source pixel in front of the filter); dst_rgb / dst_y / ymat3
+ *   as there.
+ * vs_embed_tail_nv12: vs_embed_tail on the converted, clamped pixel (key-frame expansion in all three video modes, Cd 1 and 3, attenuate 0 /
+ *   1 with hmap_lowres / 1 with the full-resolution JND, scaling_i, scaling_w), then RGB -> YUV, the 2 x 2 chroma mean and the rounding.
+ *   The members up to `variant` are those of vs_tail_desc_t: clamp must be 1, io_u8 is ignored; variant 0 = default (the row-streaming
+ *   kernel where it applies: W >= 2 S_w, H >= 2 S_h, standard JND taps; the 16-row tile kernel elsewhere), 1 = tile kernel, 4 = row-streaming
+ *   kernel (VS_ERR_UNSUPPORTED where it does not apply).  preds_w != NULL and attenuate = 2 answer VS_ERR_UNSUPPORTED.  Bytes of `out`
+ *   between W and dst_pitch are never written.
+ */
+typedef struct vs_tail_nv12_desc {
+  const void* imgs; void* out; float* preds_w;
+  const float* delta; const float* hmap_lowres; const float* taps43;   /* taps43: HOST pointer */
+  int32_t F, H, W, S_h, S_w, Cd;
+  int32_t step, video_mode, total_key;
+  int32_t attenuate, clamp, antialias;
+  float scaling_i, scaling_w;
+  int32_t io_u8;
+  int32_t variant;
+  int64_t src_pitch, src_frame_stride;      /* bytes */
+  int64_t dst_pitch, dst_frame_stride;      /* bytes */
+  float yuv2rgb12[12], rgb2yuv12[12];
+} vs_tail_nv12_desc_t;
+int vs_sizeof_tail_nv12_desc(void);         /* sizeof(vs_tail_nv12_desc_t) */
+int vs_resize_pre_nv12(const unsigned char* src, int B, int H, int W, int64_t pitch, int64_t frame_stride, const float* yuv2rgb12, int oh,
+                       int ow, int antialias, float* dst_rgb, float mul, float add, float* dst_y, int y_step, const float* ymat3,
+                       void* stream);
+int vs_embed_tail_nv12(const vs_tail_nv12_desc_t* d, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * Model-level entry points (the granularity a non-Python host would bind): an opaque model built from the card numbers
  * (utils/cfg.py:88-154, embedder.py:243-262, extractor.py:189-208) and the reference state_dict (cfg.py:147-150:
  * checkpoint['model'], HOST fp32 tensors by their reference names, loaded like strict=False: unknown names are ignored,
@@ -553,6 +594,9 @@ int vs_embed_tail(const vs_tail_desc_t* d, void* stream);
  *                     one message for the clip) or ceil(frames/step) (image mode: step = 1); preds_w optional.
  *   vs_model_detect = Wam.detect / Videoseal.detect (wam.py:206-234): resize -> ConvNeXt-V2 -> logits [frames][1+nbits].
  * io_u8 = 1: imgs / imgs_w are uint8 RGB24 [frames][H][W][3] (inference_streaming.py:26,31), conversions fused.
+ * io_u8 = 2: imgs / imgs_w are uint8 NV12 [frames][3H/2][W] (see vs_resize_pre_nv12), contiguous (pitch = W), H and W even, conversions fused;
+ *            BT.709 limited range unless vs_model_set_nv12_color has stored another pair of affines (the one mutation of a model: call it
+ *            before the model is shared between threads).  preds_w is not available with NV12 frames (VS_ERR_UNSUPPORTED).
  * Chunking over long clips, frame aggregation (videoseal.py:390-428) and message generation stay with the caller. */
 typedef struct vs_model vs_model_t;
 typedef struct vs_model_cfg {
@@ -576,6 +620,10 @@ int vs_model_embed(vs_model_t* m, const void* imgs, const int32_t* msgs, int n_m
                    int64_t ws_bytes, void* stream);
 int vs_model_detect(vs_model_t* m, const void* imgs, int frames, int H, int W, int antialias, int io_u8, float* logits, void* ws,
                     int64_t ws_bytes, void* stream);
+/* colour affines of io_u8 = 2 (HOST arrays of 12 floats, row-major 3 x 4: codes -> RGB in [0,1] and its inverse, see vs_resize_pre_nv12) */
+int vs_model_set_nv12_color(vs_model_t* m, const float* yuv2rgb12, const float* rgb2yuv12);
+/* the pair a fresh model holds (BT.709 limited range), written to two HOST arrays of 12 floats; needs no GPU */
+int vs_nv12_default_color(float* yuv2rgb12, float* rgb2yuv12);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Augmentations (videoseal/augmentation/valuemetric.py, geometric.py, utils/image.py).  Frames are NCHW fp32 [F][3][H][W]

@@ -41,6 +41,8 @@ def _bind(L):
     L.vs_model_embed.restype = I
     L.vs_model_detect.argtypes = [P, P, I, I, I, I, I, P, P, I64, P]
     L.vs_model_detect.restype = I
+    L.vs_model_set_nv12_color.argtypes = [P, P, P]
+    L.vs_model_set_nv12_color.restype = I
     L._model_api_bound = True
 
 
@@ -95,11 +97,30 @@ class CModel:
             self._ws = torch.empty(need, dtype=torch.uint8, device="cuda")
         return self._ws
 
+    def set_nv12_color(self, matrix: str = "bt709", full_range: bool = False) -> None:
+        """colour choice of the NV12 clips (io_u8 = 2) of later calls; a fresh model reads BT.709 limited range"""
+        from .nv12 import color_affine
+        fwd, inv = color_affine(matrix, full_range)
+        dec = (C.c_float * 12)(*[float(v) for v in inv.reshape(-1)])
+        enc = (C.c_float * 12)(*[float(v) for v in fwd.reshape(-1)])
+        N.check(self._L.vs_model_set_nv12_color(self._h, dec, enc), "vs_model_set_nv12_color")
+
+    @staticmethod
+    def _frames(imgs: torch.Tensor):
+        """(contiguous frames, F, H, W, io_u8): fp32 NCHW -> 0, uint8 RGB24 [F,H,W,3] -> 1, uint8 NV12 [F,3H/2,W] -> 2"""
+        if imgs.dtype == torch.uint8 and imgs.dim() == 3:
+            from .nv12 import check_clip
+            F_, H, W = check_clip(imgs)
+            return imgs.contiguous(), F_, H, W, 2
+        if imgs.dtype == torch.uint8:
+            x = imgs.contiguous()
+            return x, x.shape[0], x.shape[1], x.shape[2], 1
+        x = N.f32c(imgs)
+        return x, x.shape[0], x.shape[2], x.shape[3], 0
+
     def embed(self, imgs: torch.Tensor, msgs: torch.Tensor, *, step: int = 1, video_mode: int = 0, lowres_attenuation: bool = False,
               antialias: bool = True, want_preds_w: bool = False):
-        u8 = imgs.dtype == torch.uint8                 # RGB24 [F,H,W,3] in and out
-        x = imgs.contiguous() if u8 else N.f32c(imgs)
-        F_, H, W = (x.shape[0], x.shape[1], x.shape[2]) if u8 else (x.shape[0], x.shape[2], x.shape[3])
+        x, F_, H, W, u8 = self._frames(imgs)           # uint8 clips (RGB24 [F,H,W,3] or NV12 [F,3H/2,W]) come back in their own format
         m = msgs.to(device=x.device, dtype=torch.int32).contiguous()
         out = torch.empty_like(x)
         pw = torch.empty(F_, self.cfg.out_ch, H, W, device=x.device) if want_preds_w else None
@@ -109,9 +130,7 @@ class CModel:
         return (out, pw) if want_preds_w else out
 
     def detect(self, imgs: torch.Tensor, antialias: bool = True) -> torch.Tensor:
-        u8 = imgs.dtype == torch.uint8
-        x = imgs.contiguous() if u8 else N.f32c(imgs)
-        F_, H, W = (x.shape[0], x.shape[1], x.shape[2]) if u8 else (x.shape[0], x.shape[2], x.shape[3])
+        x, F_, H, W, u8 = self._frames(imgs)
         logits = torch.empty(F_, self.cfg.nbits + 1, device=x.device)
         ws = self._workspace(F_, H, W, 1)
         N.check(self._L.vs_model_detect(self._h, N.ptr(x), F_, H, W, int(antialias), int(u8), N.ptr(logits), N.ptr(ws), ws.numel(), N.stream()),

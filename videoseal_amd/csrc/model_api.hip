@@ -59,6 +59,7 @@ struct vs_model {
   std::vector<Blk> stages[4];
   float ymat[3];
   float taps43[43];
+  float yuv2rgb12[12], rgb2yuv12[12];      // NV12 colour affines (io_u8 = 2): BT.709 limited range until vs_model_set_nv12_color
   int arith = 3;                 // arithmetic of the split planes (vs_conv_desc_t::arith)
   bool ok = true;
 };
@@ -735,20 +736,24 @@ struct Runner {
     if (live()) chk(vs_pool_linear(hl.p, B, hl.H * hl.W, hl.C, hl.ld, m->lin_w, m->lin_b, c.nbits + 1, logits, st));
   }
   // model.py::_embed_frames_eager
-  void resize(const void* imgs, bool u8, int F, int H, int W, int S, int antialias, float* rgb, float mul, float add, float* key, int step,
+  // io: 0 = fp32 NCHW, 2 = NV12 (contiguous: pitch = W), any other value = RGB24
+  void resize(const void* imgs, int io, int F, int H, int W, int S, int antialias, float* rgb, float mul, float add, float* key, int step,
               const float* ymat) {
     if (!live()) return;
-    if (u8) chk(vs_resize_pre_u8(static_cast<const unsigned char*>(imgs), F, H, W, S, S, antialias, rgb, mul, add, key, step, ymat, st));
+    const bool u8 = io != 0;
+    if (io == 2) chk(vs_resize_pre_nv12(static_cast<const unsigned char*>(imgs), F, H, W, W, (int64_t)W * (H / 2 * 3), m->yuv2rgb12, S, S, antialias,
+                                        rgb, mul, add, key, step, ymat, st));
+    else if (u8) chk(vs_resize_pre_u8(static_cast<const unsigned char*>(imgs), F, H, W, S, S, antialias, rgb, mul, add, key, step, ymat, st));
     else chk(vs_resize_pre(static_cast<const float*>(imgs), F, 3, H, W, S, S, antialias, rgb, mul, add, key, step, ymat, st));
   }
-  void embed(const void* imgs, bool u8, const int32_t* msgs, int n_msgs, int F, int H, int W, int step, int video_mode, int lowres, int antialias,
+  void embed(const void* imgs, int io, const int32_t* msgs, int n_msgs, int F, int H, int W, int step, int video_mode, int lowres, int antialias,
              void* out, float* preds_w) {
     const vs_model_cfg_t& c = m->c;
     const int S = c.img_size, nk = (F + step - 1) / step;
     const bool att = c.attenuate != 0;
     Act rgb{nullptr, F, S, S, 3, 4}, key = act(nk, S, S, c.in_ch, 4);
     if (att && lowres) rgb = act(F, S, S, 3, 4);
-    resize(imgs, u8, F, H, W, S, antialias, (att && lowres) ? rgb.p : nullptr, 1.0f, 0.0f, key.p, step, c.yuv ? m->ymat : nullptr);
+    resize(imgs, io, F, H, W, S, antialias, (att && lowres) ? rgb.p : nullptr, 1.0f, 0.0f, key.p, step, c.yuv ? m->ymat : nullptr);
     int Sh = 0, Sw = 0;
     float* delta = embedder(key, msgs, n_msgs, Sh, Sw);
     float* hmap = nullptr;
@@ -756,6 +761,22 @@ struct Runner {
       hmap = alloc((int64_t)F * S * S);
       if (live()) chk(vs_jnd_heatmap(rgb.p, F, S, S, (int64_t)S * S * 4, 1, (int64_t)S * 4, 4, m->taps43, hmap, st));
     }
+    if (io == 2) {
+      vs_tail_nv12_desc_t n;
+      std::memset(&n, 0, sizeof(n));
+      n.imgs = imgs; n.out = out; n.preds_w = preds_w; n.delta = delta; n.hmap_lowres = hmap; n.taps43 = m->taps43;
+      n.F = F; n.H = H; n.W = W; n.S_h = Sh; n.S_w = Sw; n.Cd = c.out_ch;
+      n.step = step; n.video_mode = video_mode; n.total_key = nk;
+      n.attenuate = att ? 1 : 0; n.clamp = c.clamp; n.antialias = antialias;
+      n.scaling_i = c.scaling_i; n.scaling_w = c.scaling_w;
+      n.src_pitch = n.dst_pitch = W;
+      n.src_frame_stride = n.dst_frame_stride = (int64_t)W * (H / 2 * 3);
+      std::memcpy(n.yuv2rgb12, m->yuv2rgb12, sizeof(n.yuv2rgb12));
+      std::memcpy(n.rgb2yuv12, m->rgb2yuv12, sizeof(n.rgb2yuv12));
+      if (live()) chk(vs_embed_tail_nv12(&n, st));
+      return;
+    }
+    const bool u8 = io != 0;
     vs_tail_desc_t d;
     std::memset(&d, 0, sizeof(d));
     d.imgs = imgs; d.out = out; d.preds_w = preds_w; d.delta = delta; d.hmap_lowres = hmap; d.taps43 = m->taps43;
@@ -766,15 +787,17 @@ struct Runner {
     d.io_u8 = u8 ? 1 : 0;
     if (live()) chk(vs_embed_tail(&d, st));
   }
-  void detect(const void* imgs, bool u8, int F, int H, int W, int antialias, float* logits) {
+  void detect(const void* imgs, int io, int F, int H, int W, int antialias, float* logits) {
     const int S = m->c.img_size;
     Act rgb = act(F, S, S, 3, 4);
-    resize(imgs, u8, F, H, W, S, antialias, rgb.p, 2.0f, -1.0f, nullptr, 1, nullptr);
+    resize(imgs, io, F, H, W, S, antialias, rgb.p, 2.0f, -1.0f, nullptr, 1, nullptr);
     extractor(rgb, logits);
   }
 };
 
 }  // namespace
+
+static void nv12_default_color(float* yuv2rgb12, float* rgb2yuv12);
 
 extern "C" int vs_model_create(const vs_model_cfg_t* cfg, const vs_tensor_t* tensors, int ntensors, vs_model_t** out) {
   VS_REQUIRE(cfg && tensors && ntensors > 0 && out);
@@ -787,6 +810,7 @@ extern "C" int vs_model_create(const vs_model_cfg_t* cfg, const vs_tensor_t* ten
   vs_model* m = new vs_model();
   m->c = *cfg;
   m->arith = cfg->arith == 2 || cfg->arith == 3 ? cfg->arith : vs_default_arith();
+  nv12_default_color(m->yuv2rgb12, m->rgb2yuv12);
   for (int i = 0; i <= cfg->nlev; ++i) {
     m->zc.push_back(cfg->zc[i]);
     if (cfg->zc[i] % 4) { delete m; return VS_ERR_UNSUPPORTED; }
@@ -887,6 +911,48 @@ extern "C" int vs_model_create(const vs_model_cfg_t* cfg, const vs_tensor_t* ten
   return VS_OK;
 }
 
+// BT.709 limited range, the expressions of videoseal_amd/nv12.py::color_affine in the same order: the forward affine in double, its inverse by
+// cofactors in double (no contraction into fused multiply-adds: numpy has none), both rounded to fp32 once -- the same 24 floats, bit for bit
+static void nv12_default_color(float* yuv2rgb12, float* rgb2yuv12) {
+#pragma clang fp contract(off)
+  const double kr = 0.2126, kb = 0.0722, kg = 1.0 - kr - kb, ys = 219.0, cs = 224.0;
+  const double k[3] = {kr, kg, kb}, off[3] = {16.0, 128.0, 128.0};
+  double a[3][3];
+  for (int j = 0; j < 3; ++j) {
+    a[0][j] = ys * k[j];
+    a[1][j] = cs * (((j == 2 ? 1.0 : 0.0) - k[j]) / (2.0 * (1.0 - kb)));
+    a[2][j] = cs * (((j == 0 ? 1.0 : 0.0) - k[j]) / (2.0 * (1.0 - kr)));
+  }
+  double cof[3][3];
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j)
+      cof[i][j] = a[(i + 1) % 3][(j + 1) % 3] * a[(i + 2) % 3][(j + 2) % 3] - a[(i + 1) % 3][(j + 2) % 3] * a[(i + 2) % 3][(j + 1) % 3];
+  const double det = a[0][0] * cof[0][0] + a[0][1] * cof[0][1] + a[0][2] * cof[0][2];
+  for (int i = 0; i < 3; ++i) {
+    double inv[3];
+    for (int j = 0; j < 3; ++j) {
+      inv[j] = cof[j][i] / det;
+      yuv2rgb12[4 * i + j] = (float)inv[j];
+      rgb2yuv12[4 * i + j] = (float)a[i][j];
+    }
+    yuv2rgb12[4 * i + 3] = (float)(-(inv[0] * off[0] + inv[1] * off[1] + inv[2] * off[2]));
+    rgb2yuv12[4 * i + 3] = (float)off[i];
+  }
+}
+
+extern "C" int vs_nv12_default_color(float* yuv2rgb12, float* rgb2yuv12) {
+  VS_REQUIRE(yuv2rgb12 && rgb2yuv12);
+  nv12_default_color(yuv2rgb12, rgb2yuv12);
+  return VS_OK;
+}
+
+extern "C" int vs_model_set_nv12_color(vs_model_t* m, const float* yuv2rgb12, const float* rgb2yuv12) {
+  VS_REQUIRE(m && yuv2rgb12 && rgb2yuv12);
+  std::memcpy(m->yuv2rgb12, yuv2rgb12, sizeof(m->yuv2rgb12));
+  std::memcpy(m->rgb2yuv12, rgb2yuv12, sizeof(m->rgb2yuv12));
+  return VS_OK;
+}
+
 extern "C" void vs_model_destroy(vs_model_t* m) {
   if (!m) return;
   for (void* d : m->dev) (void)hipFree(d);
@@ -896,9 +962,9 @@ extern "C" void vs_model_destroy(vs_model_t* m) {
 extern "C" int64_t vs_model_workspace_bytes(const vs_model_t* m, int frames, int H, int W, int step) {
   if (!m || frames <= 0 || H <= 0 || W <= 0 || step < 1) return -1;
   Runner e{const_cast<vs_model_t*>(m), nullptr, 0, 0, nullptr};
-  e.embed(nullptr, false, nullptr, 1, frames, H, W, step, 0, 1, 1, nullptr, nullptr);
+  e.embed(nullptr, 0, nullptr, 1, frames, H, W, step, 0, 1, 1, nullptr, nullptr);
   Runner dt{const_cast<vs_model_t*>(m), nullptr, 0, 0, nullptr};
-  dt.detect(nullptr, false, frames, H, W, 1, nullptr);
+  dt.detect(nullptr, 0, frames, H, W, 1, nullptr);
   return std::max(e.used, dt.used) + 256;
 }
 
@@ -911,7 +977,11 @@ extern "C" int vs_model_embed(vs_model_t* m, const void* imgs, const int32_t* ms
   VS_REQUIRE(video_mode >= 0 && video_mode <= 2);
   Runner r{m, static_cast<char*>(ws), ws_bytes, 0, stream};
   if (io_u8) VS_REQUIRE(m->c.clamp);
-  r.embed(imgs, io_u8 != 0, msgs, n_msgs, frames, H, W, step, video_mode, lowres_attenuation, antialias, imgs_w, preds_w);
+  if (io_u8 == 2) {
+    VS_REQUIRE(!(H & 1) && !(W & 1));
+    if (preds_w) return VS_ERR_UNSUPPORTED;
+  }
+  r.embed(imgs, io_u8, msgs, n_msgs, frames, H, W, step, video_mode, lowres_attenuation, antialias, imgs_w, preds_w);
   return r.rc;
 }
 
@@ -919,6 +989,7 @@ extern "C" int vs_model_detect(vs_model_t* m, const void* imgs, int frames, int 
                                int64_t ws_bytes, void* stream) {
   VS_REQUIRE(m && imgs && logits && ws && frames > 0 && H > 0 && W > 0 && ((uintptr_t)ws & 255) == 0);
   Runner r{m, static_cast<char*>(ws), ws_bytes, 0, stream};
-  r.detect(imgs, io_u8 != 0, frames, H, W, antialias, logits);
+  if (io_u8 == 2) VS_REQUIRE(!(H & 1) && !(W & 1));
+  r.detect(imgs, io_u8, frames, H, W, antialias, logits);
   return r.rc;
 }

@@ -393,7 +393,7 @@ class Wam(nn.Module):
             return {"preds": eng.extractor_forward(rgb)}
         if self.use_graphs and not torch.cuda.is_current_stream_capturing():
             def key():           # the arithmetic is part of the key: network-wide split AND the layers the calibration pinned to the exact split
-                return ("det", fr.dtype, tuple(fr.shape), tuple(S), antialias, id(eng), eng.arith_net["X"], tuple(sorted(eng.layer_arith.items())))
+                return ("det", fr.dtype, tuple(fr.shape), eng.nv12_color if fr.dim() == 3 else None, tuple(S), antialias, id(eng), eng.arith_net["X"], tuple(sorted(eng.layer_arith.items())))
             out = self._graphed(key(), {"fr": fr}, run, rekey=key)["preds"].clone()
             eng.note_guard()           # the captured vs_check_finite has run: deliver its flag like an eager steady-state pass does
             return out
@@ -406,7 +406,7 @@ class Wam(nn.Module):
                       fwd_order: bool = False, tail_span: int = 0) -> None:
         bn_train = self.embedder.training
         if self.use_graphs and not bn_train and not torch.cuda.is_current_stream_capturing():
-            key = ("emb", fr.dtype, tuple(fr.shape), tuple(msgs_i32.shape), step, video_mode, antialias, lowres, preds_w is not None, self.img_size,
+            key = ("emb", fr.dtype, tuple(fr.shape), eng.nv12_color if fr.dim() == 3 else None, tuple(msgs_i32.shape), step, video_mode, antialias, lowres, preds_w is not None, self.img_size,
                    self.clamp, float(self.blender.scaling_i), float(self.blender.scaling_w), self.attenuation is not None, fwd_order, tail_span, id(eng), eng.arith_net["E"])
             ent = self._graphs.get(key)
             if ent is None:
@@ -771,6 +771,47 @@ class Videoseal(Wam):
             self._engine()
             return {"preds": torch.zeros((0, self.embedder.cfg.nbits + 1), device=clip.device)}
         return {"preds": self._detect_clip(clip.contiguous(), interpolation)}
+
+    # ---- uint8 NV12 clips (videoseal_amd/nv12.py): what a hardware decoder hands over, 1.5 bytes per pixel each way
+    def _nv12_clip(self, clip: torch.Tensor, what: str, matrix: str, full_range: bool) -> HipEngine:
+        from .nv12 import MATRICES, check_clip
+        check_clip(clip, what)
+        if matrix not in MATRICES:
+            raise ValueError(f"{what}: matrix must be one of {sorted(MATRICES)}, got {matrix!r}")
+        eng = self._engine()
+        eng.nv12_color = (matrix, bool(full_range))
+        return eng
+
+    @torch.no_grad()
+    def embed_nv12(self, clip: torch.Tensor, msgs: torch.Tensor = None, interpolation: dict = None, lowres_attenuation: bool = True,
+                   matrix: str = "bt709", full_range: bool = False) -> dict:
+        """clip uint8 [F, 3H/2, W] (NV12: H luma rows, then H/2 rows of interleaved CbCr per 2 x 2 block; H, W even; last stride 1, any row
+        pitch >= W and frame stride -- a pitched decoder surface is a strided view, not a copy) -> {'imgs_w': contiguous uint8
+        [F, 3H/2, W], 'msgs'}.  Means: NV12 -> RGB fp32 (nv12.nv12_to_rgb: the block's chroma for its four pixels, clamp to [0, 1]) ->
+        embed(..., is_video=True) -> RGB -> NV12 (nv12.rgb_to_nv12: mean of the block's four chroma values, codes =
+        floor(clamp(v, 0, 255) + 0.5)), with both conversions fused into the resize and tail kernels: no RGB or fp32 frame is written.
+        `matrix` is "bt601" or "bt709", `full_range` selects 0..255 codes instead of 16..235 / 16..240.  Needs clamp=True."""
+        eng = self._nv12_clip(clip, "embed_nv12", matrix, full_range)
+        if not self.clamp:
+            raise NotImplementedError("NV12 output needs clamp=True (codes are undefined outside [0, 1])")
+        if msgs is None:
+            msgs = self.get_random_msg()
+        else:
+            assert msgs.shape[0] == 1, "Message should be unique"
+        if clip.shape[0] == 0 or clip.numel() == 0:
+            return {"imgs_w": clip.clone().contiguous(), "msgs": msgs[0:1].repeat(len(clip), 1)}
+        out = self._embed_clip(clip, msgs, interpolation, lowres_attenuation)
+        return {"imgs_w": out, "msgs": msgs[0:1].repeat(len(clip), 1)}
+
+    @torch.no_grad()
+    def detect_nv12(self, clip: torch.Tensor, interpolation: dict = None, matrix: str = "bt709", full_range: bool = False) -> dict:
+        """clip uint8 [F, 3H/2, W] (see embed_nv12) -> {'preds': [F, 1+nbits]}: detect(nv12.nv12_to_rgb(clip), is_video=True) with the
+        conversion fused into the resize kernel."""
+        self._nv12_clip(clip, "detect_nv12", matrix, full_range)
+        self._per_frame_rows_only("detect_nv12")
+        if clip.shape[0] == 0:
+            return {"preds": torch.zeros((0, self.embedder.cfg.nbits + 1), device=clip.device)}
+        return {"preds": self._detect_clip(clip, interpolation)}
 
     def extract_message(self, imgs: torch.Tensor, aggregation: str = "avg",
                         interpolation: dict = {"mode": "bilinear", "align_corners": False, "antialias": False}) -> torch.Tensor:

@@ -23,7 +23,7 @@ VIDEO_MODES = {"repeat": 0, "alternate": 1, "interpolate": 2}
 
 EXPORTS = [
     "vs_version", "vs_arch", "vs_error_string", "vs_sizeof_conv_desc", "vs_sizeof_tail_desc", "vs_debug_set",
-    "vs_model_create", "vs_model_destroy", "vs_model_workspace_bytes", "vs_model_embed", "vs_model_detect", "vs_conv_gemm", "vs_to_planes", "vs_to_planes_affine", "vs_layernorm_act", "vs_layernorm_patch2x2", "vs_stem_conv_ln", "vs_rmsnorm_act", "vs_vit_attention", "vs_dwconv7_ln", "vs_dwconv7_ln_planes", "vs_grn_scale", "vs_grn_scale_from_partials", "vs_grn_scale_from_straddle_partials", "vs_grn_apply",
+    "vs_model_create", "vs_model_destroy", "vs_model_workspace_bytes", "vs_model_embed", "vs_model_detect", "vs_model_set_nv12_color", "vs_nv12_default_color", "vs_conv_gemm", "vs_to_planes", "vs_to_planes_affine", "vs_layernorm_act", "vs_layernorm_patch2x2", "vs_stem_conv_ln", "vs_rmsnorm_act", "vs_vit_attention", "vs_dwconv7_ln", "vs_dwconv7_ln_planes", "vs_grn_scale", "vs_grn_scale_from_partials", "vs_grn_scale_from_straddle_partials", "vs_grn_apply",
     "vs_upcat2x", "vs_upconv_supported", "vs_upconv_gather_ln", "vs_cat2_scale", "vs_msg_pre", "vs_upconv_fused_supported", "vs_upconv_fused_preferred", "vs_upconv_fused", "vs_im2col3x3", "vs_msg_latent", "vs_broadcast_channels", "vs_outc_tanh", "vs_pool_linear", "vs_resize_pre", "vs_resize_pre_u8",
     "vs_jnd_heatmap", "vs_embed_tail", "vs_aug_color_scratch_floats", "vs_aug_color", "vs_aug_color_chain", "vs_aug_crop_resize_color", "vs_aug_crop_flip", "vs_aug_warp", "vs_resize_nchw",
     "vs_gaussian_blur", "vs_median_filter", "vs_jpeg_workspace_bytes", "vs_jpeg_roundtrip", "vs_h264_proxy_workspace_bytes", "vs_h264_proxy_roundtrip",
@@ -41,6 +41,7 @@ EXPORTS = [
     "vs_pixel_bce_partial_doubles", "vs_pixel_bce", "vs_pixel_vote",
     "vs_disc_input", "vs_disc_input_bwd", "vs_groupnorm_partial_doubles", "vs_groupnorm_lrelu", "vs_groupnorm_lrelu_bwd", "vs_conv4x4_wgrad_supported",
     "vs_conv4x4_wgrad_partial_floats", "vs_conv4x4_wgrad", "vs_conv4x4_n1", "vs_conv4x4_n1_bwd", "vs_conv4x4_n1_bias_grad", "vs_disc_loss",
+    "vs_sizeof_tail_nv12_desc", "vs_resize_pre_nv12", "vs_embed_tail_nv12",
 ]
 
 
@@ -77,6 +78,14 @@ class TailDesc(C.Structure):
         ("step", C.c_int32), ("video_mode", C.c_int32), ("total_key", C.c_int32),
         ("attenuate", C.c_int32), ("clamp", C.c_int32), ("antialias", C.c_int32),
         ("scaling_i", C.c_float), ("scaling_w", C.c_float), ("io_u8", C.c_int32), ("variant", C.c_int32),
+    ]
+
+
+class TailNv12Desc(C.Structure):
+    """mirror of vs_tail_nv12_desc_t: TailDesc's members, pitches / frame strides in bytes and the two colour affines"""
+    _fields_ = TailDesc._fields_ + [
+        ("src_pitch", C.c_int64), ("src_frame_stride", C.c_int64), ("dst_pitch", C.c_int64), ("dst_frame_stride", C.c_int64),
+        ("yuv2rgb12", C.c_float * 12), ("rgb2yuv12", C.c_float * 12),
     ]
 
 
@@ -141,6 +150,9 @@ def lib() -> C.CDLL:
         "vs_resize_pre_u8": [P, I, I, I, I, I, I, P, F, F, P, I, P, P],
         "vs_jnd_heatmap": [P, I, I, I, I64, I64, I64, I64, P, P, P],
         "vs_embed_tail": [C.POINTER(TailDesc), P],
+        "vs_nv12_default_color": [P, P],
+        "vs_resize_pre_nv12": [P, I, I, I, I64, I64, P, I, I, I, P, F, F, P, I, P, P],
+        "vs_embed_tail_nv12": [C.POINTER(TailNv12Desc), P],
         "vs_aug_color": [P, P, I, I, I, I, F, P, P],
         "vs_aug_crop_flip": [P, P, I, I, I, I, I, I, I, I, P],
         "vs_aug_color_chain": [P, P, I, I, I, I, C.POINTER(C.c_int), C.POINTER(C.c_float), P, P],
@@ -268,10 +280,12 @@ def lib() -> C.CDLL:
     L.vs_conv4x4_wgrad_partial_floats.argtypes = [I, I64, I, I, I, I]
     L.vs_sizeof_conv_desc.restype = C.c_int
     L.vs_sizeof_tail_desc.restype = C.c_int
+    L.vs_sizeof_tail_nv12_desc.restype = C.c_int
     if L.vs_version() != 3:
         raise NativeError(f"{LIB_PATH} has ABI version {L.vs_version()}, this binding is written for 3: rebuild (make -C videoseal_amd/csrc)")
-    if L.vs_sizeof_conv_desc() != C.sizeof(ConvDesc) or L.vs_sizeof_tail_desc() != C.sizeof(TailDesc):
-        raise NativeError("ctypes mirrors of vs_conv_desc_t / vs_tail_desc_t are out of date with the shared library")
+    if L.vs_sizeof_conv_desc() != C.sizeof(ConvDesc) or L.vs_sizeof_tail_desc() != C.sizeof(TailDesc) or \
+            L.vs_sizeof_tail_nv12_desc() != C.sizeof(TailNv12Desc):
+        raise NativeError("ctypes mirrors of vs_conv_desc_t / vs_tail_desc_t / vs_tail_nv12_desc_t are out of date with the shared library")
     _lib = L
     return L
 
