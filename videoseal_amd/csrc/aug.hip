@@ -135,12 +135,15 @@ __global__ __launch_bounds__(64) void gray_finish_kernel(const float* __restrict
 // augmenter.py:175: imgs_aug = imgs_w * m + imgs * (1 - m), m = [F][1][H][W] broadcast over the C planes of a frame
 __global__ __launch_bounds__(256) void mask_blend_kernel(const float* __restrict__ iw, const float* __restrict__ im,
                                                          const float* __restrict__ m, float* __restrict__ dst, int Cc, int64_t plane) {
+#pragma clang fp contract(off)      // ATen rounds each product: HIP's __fmul_rn / __fadd_rn are a plain '*' / '+' that hipcc contracted into an fma here (1 ulp off in 3e-4 of the elements)
   const int64_t pl = blockIdx.y;                 // frame * Cc + channel
   const float* mk = m + (pl / Cc) * plane;
   const int64_t o = pl * plane;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < plane; i += (int64_t)gridDim.x * 256) {
     const float w = mk[i];
-    dst[o + i] = __fadd_rn(__fmul_rn(iw[o + i], w), __fmul_rn(im[o + i], __fsub_rn(1.f, w)));   // no fma contraction: ATen rounds each product
+    const float t0 = iw[o + i] * w;
+    const float t1 = im[o + i] * (1.f - w);
+    dst[o + i] = t0 + t1;
   }
 }
 // valuemetric.py:188-191: image + noise * std (the noise itself is the caller's torch.randn_like draw)
@@ -202,8 +205,8 @@ __global__ __launch_bounds__(256) void resize_nchw_kernel(const float* __restric
   const float* s = src + (int64_t)blockIdx.z * H * W;
   const Taps ty = make_taps(oy, H, oh, antialias), tx = make_taps(ox, W, ow, antialias);
   float acc = 0.f;
-  constexpr int MAXW = 12;
-  if (tx.n <= MAXW) {        // the column weights once per output (they were re-evaluated -- a triangle and a division each -- for every row of the window)
+  constexpr int MAXW = LONG_TAPS;
+  if (tx.n <= MAXW && ty.n <= MAXW) {        // the column weights once per output (they were re-evaluated -- a triangle and a division each -- for every row of the window)
     float wx[MAXW];
 #pragma unroll
     for (int j = 0; j < MAXW; ++j) wx[j] = j < tx.n ? tap_w(tx, j) : 0.f;
@@ -215,13 +218,15 @@ __global__ __launch_bounds__(256) void resize_nchw_kernel(const float* __restric
         if (jx < tx.n) r = __builtin_fmaf(wx[jx], row[jx], r);
       acc = __builtin_fmaf(tap_w(ty, jy), r, acc);
     }
-  } else {
+  } else {                   // long filters on either axis: compensated sums (resize_taps.h)
+    CompSum a;
     for (int jy = 0; jy < ty.n; ++jy) {
       const float* row = s + (int64_t)(ty.lo + jy) * W + tx.lo;
-      float r = 0.f;
-      for (int jx = 0; jx < tx.n; ++jx) r = __builtin_fmaf(tap_w(tx, jx), row[jx], r);
-      acc = __builtin_fmaf(tap_w(ty, jy), r, acc);
+      CompSum r;
+      for (int jx = 0; jx < tx.n; ++jx) r.add(tap_w(tx, jx), row[jx]);
+      a.add(tap_w(ty, jy), r.value());
     }
+    acc = a.value();
   }
   dst[((int64_t)blockIdx.z * oh + oy) * ow + ox] = acc;
 }
@@ -231,7 +236,7 @@ __global__ __launch_bounds__(256) void resize_nchw_kernel(const float* __restric
 // window of all three planes is staged once in LDS by coalesced loads (resize_nchw_kernel reads every tap from global memory: L1-bound at 0.14
 // of the HBM rate), and each output pixel evaluates the SAME taps in the SAME order as resize_nchw_kernel on the cropped tensor -- horizontal
 // sums first, then the vertical one -- followed by apply_color on its three channel values: bit-identical to the separate launches.
-constexpr int CRC_MAXW = 12;      // taps per axis whose weights are tabulated per tile (anti-aliased down-scaling up to 5.5 x)
+constexpr int CRC_MAXW = LONG_TAPS;      // taps per axis whose weights are tabulated per tile (anti-aliased down-scaling up to 5.5 x)
 
 __global__ __launch_bounds__(256) void crop_resize_color_kernel(const float* __restrict__ src, float* __restrict__ dst, int H, int W, int i0, int j0,
                                                                 int ch, int cw, int oh, int ow, int antialias, int win_h, int win_w, ColorChain cc) {
@@ -318,18 +323,18 @@ __global__ __launch_bounds__(256) void crop_resize_color_kernel(const float* __r
       a2 = __builtin_fmaf(wyj, r2, a2);
     }
     v[0] = a0; v[1] = a1; v[2] = a2;
-  } else {          // longer filters: the weights as resize_nchw_kernel evaluates them
+  } else {          // longer filters: the weights and the compensated sums as resize_nchw_kernel evaluates them
     const Taps ty = make_taps(oy, ch, oh, antialias), tx = make_taps(ox, cw, ow, antialias);
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-      float acc = 0.f;
+      CompSum a;
       for (int jy = 0; jy < ty.n; ++jy) {
         const float* row = crc_win + (c * win_h + (loy + jy)) * win_w + lox;
-        float r = 0.f;
-        for (int jx = 0; jx < tx.n; ++jx) r = __builtin_fmaf(tap_w(tx, jx), row[jx], r);
-        acc = __builtin_fmaf(tap_w(ty, jy), r, acc);
+        CompSum r;
+        for (int jx = 0; jx < tx.n; ++jx) r.add(tap_w(tx, jx), row[jx]);
+        a.add(tap_w(ty, jy), r.value());
       }
-      v[c] = acc;
+      v[c] = a.value();
     }
   }
   for (int k = 0; k < cc.n; ++k) apply_color(cc.op[k], cc.factor[k], 0.f, v[0], v[1], v[2]);

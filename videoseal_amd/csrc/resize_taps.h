@@ -77,6 +77,25 @@ __device__ __forceinline__ float tap_w(const Taps& t, int j) {
   return j == 0 ? 1.f - t.l1 : t.l1;
 }
 
+// Long filters: more taps on an axis than any tabulated or staged form holds (anti-aliased down-scaling beyond 5.5 x).  A serial fma chain over n
+// taps loses up to n / 2 ulp -- 64 x 64 -> 1 x 1 of a constant frame came back 2 ulp off, 10 x 2^-24 of the output after x * 2 - 1 --, so past
+// LONG_TAPS taps on either axis the resize kernels carry the rounding errors of both sums along (the product's through an fma, the sum's through
+// Knuth's two-sum) and add them at the end: the horizontal sums first, then the vertical one, each within an ulp of the exact sum.
+constexpr int LONG_TAPS = 12;
+struct CompSum {
+  float s = 0.f, c = 0.f;
+  __device__ __forceinline__ void add(const float w, const float v) {
+#pragma clang fp contract(off)
+    const float p = w * v;
+    const float e = __builtin_fmaf(w, v, -p);
+    const float t = s + p;
+    const float bp = t - s;
+    c += ((s - (t - bp)) + (p - bp)) + e;
+    s = t;
+  }
+  __device__ __forceinline__ float value() const { return s + c; }
+};
+
 // Adjoint side: the outputs o whose tap window can contain input index i lie in [o_lo, o_hi] (a conservative superset; the caller
 // rebuilds make_taps(o) and tests lo <= i < lo + n, which keeps the weights bit-identical to the forward pass).
 __device__ __forceinline__ void adjoint_range(int i, int in, int out, bool antialias, int& o_lo, int& o_hi) {

@@ -128,6 +128,20 @@ __global__ __launch_bounds__(256) void resize_pre_kernel(const T* __restrict__ s
 #pragma unroll
       for (int c = 0; c < 3; ++c) acc[c] = __builtin_fmaf(wy, r[c], acc[c]);
     }
+  } else if (tx.n > LONG_TAPS || ty.n > LONG_TAPS) {        // long filters: compensated sums (resize_taps.h)
+    CompSum a3[3];
+    for (int jy = 0; jy < ty.n; ++jy) {
+      const float wy = tap_w(ty, jy);
+      const int64_t row = (int64_t)(ty.lo + jy) * W + tx.lo;
+      CompSum r3[3];
+      for (int jx = 0; jx < tx.n; ++jx) {
+        const float wx = tap_w(tx, jx);
+        for (int c = 0; c < 3; ++c)
+          if (c < C) r3[c].add(wx, Px<T>::ld(base, plane, c, row + jx));
+      }
+      for (int c = 0; c < 3; ++c) a3[c].add(wy, r3[c].value());
+    }
+    for (int c = 0; c < 3; ++c) acc[c] = a3[c].value();
   } else {
     for (int jy = 0; jy < ty.n; ++jy) {
       const float wy = tap_w(ty, jy);
@@ -948,6 +962,27 @@ __global__ __launch_bounds__(256) void resize_pre_nv12_kernel(const unsigned cha
 #pragma unroll
       for (int c = 0; c < 3; ++c) acc[c] = __builtin_fmaf(wy, r[c], acc[c]);
     }
+  } else if (tx.n > LONG_TAPS || ty.n > LONG_TAPS) {        // long filters: compensated sums, as resize_pre_kernel
+    CompSum a3[3];
+    for (int jy = 0; jy < ty.n; ++jy) {
+      const float wy = tap_w(ty, jy);
+      const int yy = ty.lo + jy;
+      const unsigned char* yr = base + (int64_t)yy * pitch;
+      const unsigned char* cr_ = cbase + (int64_t)(yy >> 1) * pitch;
+      CompSum r3[3];
+      for (int jx = 0; jx < tx.n; ++jx) {
+        const float wx = tap_w(tx, jx);
+        const int xx = tx.lo + jx;
+        float rgb[3];
+        nv12_rgb(dec, (float)yr[xx], (float)cr_[xx & ~1], (float)cr_[xx | 1], rgb);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) r3[c].add(wx, rgb[c]);
+      }
+#pragma unroll
+      for (int c = 0; c < 3; ++c) a3[c].add(wy, r3[c].value());
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) acc[c] = a3[c].value();
   } else {
     for (int jy = 0; jy < ty.n; ++jy) {
       const float wy = tap_w(ty, jy);
