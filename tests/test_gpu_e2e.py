@@ -900,3 +900,37 @@ def test_pipelined_convnext_block_kernel_equals_the_serial_one_bit_for_bit(vs10)
     finally:
         eng.lib.vs_cnx_block = orig
     assert torch.equal(p_pipe, p_serial), float((p_pipe - p_serial).abs().max())
+
+
+def test_convnext_blocks_whose_frames_straddle_an_apply_workgroup_take_the_per_layer_path(vs10):
+    """96 x 96 frames: stage 0 has 576 pixels per frame, no multiple of the 128 pixels an apply workgroup of csrc/convnext_fused.hip shares one GRN
+    scale row for (2304 rows and HW % 64 == 0: the older gate accepted it and part of the waves read the neighbouring frame's scale).
+    vs_cnx_block_supported refuses it, the engine's gate calls that function: no fused launch, and the logits are the unfused path's bits"""
+    spec, sd, model = vs10
+    imgs = synthetic_frames(4, 96, 96, seed=79).cuda()
+    eng = model._engine()
+    if eng.arith_net["X"] != 2 or not eng.fused_blocks:
+        pytest.skip("2 x f16 arithmetic with fused blocks only")
+    assert eng.lib.vs_cnx_block_supported(96, 4 * 576, 576) == 0 and eng.lib.vs_cnx_block_supported(96, 4 * 4096, 4096) == 1
+    calls = []
+    orig = eng.lib.vs_cnx_block
+
+    class Spy:
+        def __call__(self, *a):
+            calls.append(a[5])
+            return orig(*a)
+    try:
+        eng.lib.vs_cnx_block = Spy()
+        p1 = model.detector(imgs).clone()
+    finally:
+        eng.lib.vs_cnx_block = orig
+    assert not calls
+    eng.fused_blocks = False
+    try:
+        p0 = model.detector(imgs).clone()
+    finally:
+        eng.fused_blocks = True
+    assert torch.isfinite(p1).all() and torch.equal(p1, p0)
+    with torch.no_grad():
+        ref = R.extractor_forward(sd, spec, imgs.cpu())
+    assert (p1.cpu() - ref).abs().max() < 1e-4

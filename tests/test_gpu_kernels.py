@@ -398,7 +398,10 @@ def test_conv_grn_transform_and_residual(eng, tile):
     wt, cp = pack_conv(w[:, :, None, None].to(DEV), K)
     ra = Act(res.to(DEV).contiguous(), B, HW, 1, Nn, Nn)
     shp = torch.zeros(cp); shp[:K] = sh
-    eng.conv(ha, ConvW(wt, bias.to(DEV), Nn, 1, 1, cp), ra, res=ra, a_scale=sc.to(DEV).contiguous(), a_scale_ld=K, a_shift=shp.to(DEV), tile_hint=tile)
+    # vs_conv_desc_t: a_scale is read up to CinP entries per row -- the last row's chunk K .. CinP - 1 lies behind the [B][K] array and must be
+    # memory of this tensor (zeros), not whatever an earlier test left in the allocator (a NaN there times the zeroed activation is a NaN)
+    scp = torch.zeros(B * K + cp - K); scp[:B * K] = sc.reshape(-1)
+    eng.conv(ha, ConvW(wt, bias.to(DEV), Nn, 1, 1, cp), ra, res=ra, a_scale=scp.to(DEV), a_scale_ld=K, a_shift=shp.to(DEV), tile_hint=tile)
     torch.cuda.synchronize()
     assert rel_err(ra.t.cpu().view(B, HW, Nn), ref) < 2e-5
 

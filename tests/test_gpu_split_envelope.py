@@ -8,9 +8,10 @@ split operands on the CPU (one thread); the assertion is  max r <= SPLIT_MARGIN 
 ratio measured on an MI355X and never more than 8 (profiles/split_fp64_envelope.txt lists every case).  tests/test_split_contract_cpu.py shows
 without a GPU that a low plane flushed to zero or a product dropped on the last K chunk exceeds that cap on each of these shapes.
 
-Not here: the fused kernels with on-chip intermediates (convnext_fused, resblock_thin, upconv_fused) and attention -- their bit-identity and oracle
-tests (tests/test_gpu_kernels.py, test_gpu_fwd.py) tie them to the kernels pinned here -- and range-guard / overflow behaviour
-(tests/test_gpu_e2e.py, test_guards_cpu.py)."""
+The fused kernels with on-chip intermediates (convnext_fused, resblock_thin) are held to the same metric, carried through the on-chip stage, in
+tests/test_gpu_fused_envelope.py.  Not here and not there: upconv_fused -- its z is never observable behind the LayerNorm; it keeps the
+arithmetic-3 envelope of tests/test_gpu_fwd_envelope.py and the bit-identity tests of tests/test_gpu_upconv_block.py -- attention
+(tests/test_gpu_fwd_envelope.py), and range-guard / overflow behaviour of whole networks (tests/test_gpu_e2e.py, test_guards_cpu.py)."""
 import os
 import subprocess
 import sys

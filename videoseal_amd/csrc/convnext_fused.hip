@@ -108,7 +108,7 @@ __global__ __launch_bounds__(256) void cnx_block_kernel(const CnxArgs a) {
   constexpr int NST = 3;                                    // weight stages: block hb + 2 is in flight while block hb is multiplied (an L2 round trip is
                                                             // about as long as one block's arithmetic: with two stages every iteration waited for its DMA)
   __shared__ __attribute__((aligned(16))) unsigned char smem[NST * BLK_KB * 1024];
-  __shared__ __attribute__((aligned(16))) float s_scale[STATS ? 4 : 4 * C];      // GRN scale of the workgroup's frame (its 128 * PB pixels lie in one frame)
+  __shared__ __attribute__((aligned(16))) float s_scale[STATS ? 4 : 4 * C];      // GRN scale of the workgroup's frame (its 128 * PB pixels lie in one frame: vs_cnx_block_supported)
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int r32 = lane & 31, hf = lane >> 5;
@@ -595,10 +595,13 @@ int launch_cnx(const CnxArgs& a, bool stats, bool serial, hipStream_t st) {
 
 }  // namespace
 
+// Frames of whole apply workgroups only: the apply launch takes 128 pixels per workgroup (PB = 1 for both channel counts) and stages ONE row of
+// the GRN scale for them, so a frame boundary inside a workgroup would give part of its waves the neighbouring frame's scale (HW = 64, 96 or 192:
+// tests/test_gpu_fused_envelope.py).  The statistics launch at C = 96 takes 256 pixels per workgroup and knows no frames.
 extern "C" int vs_cnx_block_supported(int C, int64_t rows, int HW) {
   if (C != 96 && C != 192) return 0;
   const int pb = C == 96 ? 2 : 1;
-  return (rows % (128 * pb) == 0 && HW % (32 * pb) == 0) ? 1 : 0;
+  return (rows % (128 * pb) == 0 && HW % 128 == 0) ? 1 : 0;
 }
 
 extern "C" int64_t vs_cnx_block_image_bytes(int C) { return (int64_t)(4 * C / 32) * ((C / 16) * 2 + (C / 32) * 4 + 1) * 1024; }
