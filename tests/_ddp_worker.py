@@ -12,7 +12,7 @@ import torch.distributed as dist
 def batch_and_model():
     from oracle.weights import make_state_dict, tiny_spec
     from oracle.inputs import synthetic_frames, synthetic_msgs
-    from tests.test_gpu_e2e import make_model
+    from tests._model import make_model
     import videoseal_amd.augmentation as G
     spec = tiny_spec()
     model = make_model(spec, make_state_dict(spec, seed=3))
@@ -40,7 +40,7 @@ def extract_job(rank: int, world: int, out_path: str) -> None:
     """frames sharded over the ranks (contiguous 16-aligned ranges), embed locally, ONE all-gather of the logits (videoseal_amd/dist.py)"""
     from oracle.inputs import synthetic_frames, synthetic_msgs
     from oracle.weights import make_state_dict, tiny_spec
-    from tests.test_gpu_e2e import make_model
+    from tests._model import make_model
     from videoseal_amd.dist import embed_sharded, extract_message_sharded, gather_frame_logits, shard_range
     spec = tiny_spec()
     model = make_model(spec, make_state_dict(spec, seed=3))

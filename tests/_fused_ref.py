@@ -31,7 +31,6 @@ import torch.nn.functional as F
 
 from tests import _split_ref as R
 
-CAP = 8.0
 # Twice the largest ratio  max r / max(max r_ref, 1)  measured on an MI355X over every case of tests/test_gpu_fused_envelope.py
 # (profiles/fused_fp64_envelope.txt lists them), never more than CAP: a kernel that needs more has a defect.
 FUSED_MARGIN = 4.218          # 2 x 2.109, the largest ratio measured: vs_resblock_thin 1 -> 16 -> 16 in the 3 x bf16 arithmetic on B = 2 maps of 9 x 1
@@ -48,10 +47,6 @@ def gelu64(x):
 def ratio_units(got, S, unit):
     """r = |got - S| / max(unit, tiny) per element (float64)"""
     return (got.double() - S).abs() / unit.clamp_min(R.TINY)
-
-
-def outside(r_defect, r_ref):
-    return not r_defect <= CAP * max(r_ref, 1.0)
 
 
 def stage(a, w, arith, a_mul=A_MUL, pad=0):
@@ -148,13 +143,13 @@ def cnx_first(o, drop_tail=False):
     S1 = r.S
     if drop_tail:
         S1 = S1 - r.acc * _rows(F.conv2d(r.la[:, -16:], r.hw[:, -16:]))
-    f = SimpleNamespace(u1=R.U24 * (r.P + o.b1.double().abs()), w_mul=r.w_mul)
+    f = SimpleNamespace(u1=R.U32 * (r.P + o.b1.double().abs()), w_mul=r.w_mul)
     f.g = gelu64(S1 + o.b1.double())
     f.g32 = R.one_thread(lambda: F.gelu(r.ref32 + o.b1))
     G, H4 = o.rows // 32, 4 * o.C
     f.part = (f.g * f.g).view(G, 32, H4).sum(1)
     d = GELU_LIP * f.u1
-    f.part_unit = R.U24 * f.part + (2.0 * f.g.abs() * d + d * d).view(G, 32, H4).sum(1)
+    f.part_unit = R.U32 * f.part + (2.0 * f.g.abs() * d + d * d).view(G, 32, H4).sum(1)
     f.part32 = R.one_thread(lambda: (f.g32 * f.g32).view(G, 32, H4).sum(1))
     return f
 
@@ -175,7 +170,7 @@ def cnx_second(o, f, w2, *, rows64=None, rows32=None, u_scale=None, bias2=None, 
     b2 = torch.zeros(o.C) if bias2 is None else bias2
     rs = torch.zeros(o.rows, o.C) if res is None else res
     e.S = r.S + b2.double() + rs.double()
-    e.unit = R.U24 * (r.P + b2.double().abs() + rs.double().abs()) + (u_v + fmt) @ w2.double().abs()[:, :, 0, 0].t()
+    e.unit = R.U32 * (r.P + b2.double().abs() + rs.double().abs()) + (u_v + fmt) @ w2.double().abs()[:, :, 0, 0].t()
     if want_ref:
         v32 = R.one_thread(lambda: f.g32 * rows32 + o.beta)
         if zero is not None:
@@ -201,7 +196,7 @@ def grn_scale64(part, gamma, B, unit_part=None):
         return scale
     u_ss = unit_part.view(B, -1, part.shape[1]).sum(1)
     u_gx = torch.where(gx > 0, u_ss / (2 * gx).clamp_min(R.TINY), u_ss.sqrt())
-    u = gamma.double().abs() * (u_gx / m + gx * u_gx.mean(1, keepdim=True) / (m * m)) + R.U24 * (1 + (gamma.double() * gx / m).abs())
+    u = gamma.double().abs() * (u_gx / m + gx * u_gx.mean(1, keepdim=True) / (m * m)) + R.U32 * (1 + (gamma.double() * gx / m).abs())
     return scale, u
 
 
@@ -296,7 +291,7 @@ def rb_chain(o, arith, *, padded_conv0=False, halo_shift=False, zero=None, want_
     r0 = stage(o.x, o.w0, arith, A_MUL, pad=2)
     inside = _ring_mask(r0.S)
     t = F.relu(r0.S + bc(o.b0.double()))
-    u_t = R.U24 * (r0.P + bc(o.b0.double().abs()))
+    u_t = R.U32 * (r0.P + bc(o.b0.double().abs()))
     if not padded_conv0:
         t = t * inside
     u_t = u_t * inside
@@ -312,7 +307,7 @@ def rb_chain(o, arith, *, padded_conv0=False, halo_shift=False, zero=None, want_
         S1, P1 = r1.S, r1.P
     e.S = F.relu(S1 + bc(o.b1.double())) + rr.S + bc(o.br.double())
     if P1 is not None:
-        e.unit = (R.U24 * (P1 + bc(o.b1.double().abs()) + rr.P + bc(o.br.double().abs())) + F.conv2d(u_t + fmt, o.w1.double().abs()))
+        e.unit = (R.U32 * (P1 + bc(o.b1.double().abs()) + rr.P + bc(o.br.double().abs())) + F.conv2d(u_t + fmt, o.w1.double().abs()))
     if want_ref and not halo_shift:
         t32 = R.one_thread(lambda: F.relu(r0.ref32 + bc(o.b0)) * inside)
         if zero is not None:

@@ -10,7 +10,7 @@ if ROOT not in sys.path:
 import torch  # noqa: E402
 
 from tests import _fwd_ref as R  # noqa: E402
-from tests.test_gpu_fwd_envelope import attention_launch  # noqa: E402
+from tests._gpu import attention_launch  # noqa: E402
 
 if __name__ == "__main__":
     torch.save([attention_launch(c) for c in R.ATTN_MFMA_CASES], sys.argv[1])

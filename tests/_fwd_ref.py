@@ -1,39 +1,25 @@
 """fp64 envelopes of the FORWARD normalisation, GRN and attention kernels: formulas, hard inputs, cases and the metric shared by
 tests/test_fwd_contract_cpu.py (the envelope has teeth; no GPU) and tests/test_gpu_fwd_envelope.py (every kernel against it).
 
-As in the backward envelopes (tests/test_gpu_bwd.py, whose helpers are imported, not copied): the reference is the formula in float64 on the CPU
+As in the backward envelopes (tests/test_gpu_bwd.py; the rule and its helpers are tests/_envelope.py's): the reference is the formula in float64 on the CPU
 from the same fp32 input values, the error is taken PER GROUP -- max |got - ref| over the group / max |ref| over the group, worst group: a row
 (pixel) for LayerNorm and RMSNorm, a (frame, channel) element for the GRN scale, a (token, head) slice of hd values for attention -- and the
 yardstick is the same formula in float32 on the CPU (one thread), written out the way the modelled project writes it (common.py:147-179,
 vit.py:302-360), NOT a fused ATen kernel such as F.layer_norm, whose cascade summation is a stricter algorithm than the one specified.
 A kernel may exceed the yardstick by FWD_FP64_MARGIN; no element is excluded from any case."""
+import functools
 import math
 
 import torch
 import torch.nn.functional as F
 
-from tests.test_gpu_bwd import U32, cpu_autograd, group_err, hard_matrix  # noqa: F401  (re-exported to the two test files)
+from tests._envelope import check_rows, cpu_autograd, group_err, hard_matrix
 
 # Twice the largest ratio hip / max(aten-fp32, 2^-24) measured on an MI355X over every case of tests/test_gpu_fwd_envelope.py
 # (profiles/fwd_fp64_envelope.txt lists them), never more than 8: a kernel that needs more has a defect.
 FWD_FP64_MARGIN = 5.76         # 2 x 2.882, the largest ratio measured: vs_layernorm_act small<16> at rows = 301, C = 50, no activation (one thread adds the row's 50 values in order)
-CAP = 8.0                      # the standing rule itself: what the CPU contract test uses ("with any margin up to the cap")
 EPS = 1e-6
-
-def envelope(case, rows):
-    """rows: (name, hip error, fp32 yardstick error).  Prints every figure, then asserts hip <= FWD_FP64_MARGIN * max(aten, U32) for each."""
-    bad = []
-    for name, hip, aten in rows:
-        ratio = hip / max(aten, U32)
-        print(f"FWD-ENVELOPE {case:<58s} {name:<10s} hip {hip:.3e}  aten-fp32 {aten:.3e}  ratio {ratio:6.3f}")
-        if not ratio <= FWD_FP64_MARGIN:
-            bad.append((name, hip, aten, ratio))
-    assert not bad, (case, bad)
-
-
-def outside(defect_err, yard_err):
-    """True when an error falls outside the envelope at the cap: the yardstick's own ratio is 1, no margin up to 8 admits the defect"""
-    return not defect_err <= CAP * max(yard_err, U32)
+envelope = functools.partial(check_rows, "FWD-ENVELOPE", 58, "aten-fp32", FWD_FP64_MARGIN)
 
 
 def ACT(act):

@@ -2,66 +2,25 @@
 colour ops, resizes, blur, median, warp, blends, temporal ops): formulas, hard frames, cases and the metric shared by
 tests/test_img_contract_cpu.py (the envelope has teeth; no GPU) and tests/test_gpu_img_envelope.py (every kernel against it).
 
-As in tests/_fwd_ref.py: the reference is the formula in float64 on the CPU from the same fp32 input values and the same fp32 coefficient values
-the kernel receives, the yardstick is the same formula in float32 on the CPU.  The error is taken PER (case, frame kind):
+As in tests/_fwd_ref.py (the rule and the metrics frame_err / cand_err are tests/_envelope.py's): the reference is the formula in float64 on the
+CPU from the same fp32 input values and the same fp32 coefficient values the kernel receives, the yardstick is the same formula in float32 on the CPU.  The error is taken PER (case, frame kind):
 max |got - ref64| / max(max |ref64|, tiny) over the whole output, against the yardstick's figure for the same frame kind -- every kind has its own
 line, so that noise's larger yardstick cannot hide an error on a structured frame.  A kernel may exceed the yardstick by IMG_FP64_MARGIN; no element
 is excluded from any case: where the operation is discontinuous (nearest warp at a .5 boundary, the JND luminance mask at la = 127) a pixel inside a
 band whose width follows from the fp32 coordinate error gets a candidate set instead (nearest_check, cand_err)."""
+import functools
 import math
 
 import torch
 import torch.nn.functional as F
 
-from tests.test_gpu_bwd import U32, group_err  # noqa: F401  (re-exported to the two test files)
+from tests._envelope import check_rows, one_thread
 
 # Twice the largest ratio hip / max(yardstick, 2^-24) measured on an MI355X over every line of tests/test_gpu_img_envelope.py
 # (profiles/img_fp64_envelope.txt lists them), never more than 8: a kernel that needs more has a defect (DESIGN.md section 5).
-CAP = 8.0                      # the standing rule itself: what the CPU contract test uses ("with any margin up to the cap")
 IMG_FP64_MARGIN = 8.0          # min(2 x 4.328, cap): the largest ratio measured is vs_aug_warp bilinear, rotate 45 on 8 x 300, `ramp` (996 lines)
-TINY = 1e-30
 F32, F64 = torch.float32, torch.float64
-
-
-def frame_err(got, ref):
-    """max |got - ref| / max(max |ref|, tiny) over the whole tensor"""
-    got, ref = got.detach().double().cpu(), ref.detach().double().cpu()
-    assert got.shape == ref.shape, (got.shape, ref.shape)
-    return float((got - ref).abs().max() / max(float(ref.abs().max()), TINY))
-
-
-def cand_err(got, own, other, amb):
-    """frame_err where a pixel of the mask `amb` may match either `own` or `other` (the two sides of a discontinuity); every other pixel must match `own`"""
-    got, own, other = got.detach().double().cpu(), own.double(), other.double()
-    d = (got - own).abs()
-    d = torch.where(amb.expand_as(d), torch.minimum(d, (got - other).abs()), d)
-    return float(d.max() / max(float(own.abs().max()), TINY))
-
-
-def envelope(case, rows):
-    """rows: (frame kind, hip error, fp32 yardstick error).  Prints every figure, then asserts hip <= IMG_FP64_MARGIN * max(yard, U32) for each."""
-    bad = []
-    for name, hip, yard in rows:
-        ratio = hip / max(yard, U32)
-        print(f"IMG-ENVELOPE {case:<58s} {name:<10s} hip {hip:.3e}  cpu-fp32 {yard:.3e}  ratio {ratio:6.3f}")
-        if not ratio <= IMG_FP64_MARGIN:
-            bad.append((name, hip, yard, ratio))
-    assert not bad, (case, bad)
-
-
-def outside(defect_err, yard_err):
-    """True when an error falls outside the envelope at the cap: the yardstick's own ratio is 1, no margin up to 8 admits the defect"""
-    return not defect_err <= CAP * max(yard_err, U32)
-
-
-def one_thread(fn):
-    """fn() with ATen on one thread: the summation order of its reductions (and the yardstick with it) must not depend on the host's core count"""
-    n = torch.get_num_threads()
-    torch.set_num_threads(1)
-    try:
-        return fn()
-    finally:
-        torch.set_num_threads(n)
+envelope = functools.partial(check_rows, "IMG-ENVELOPE", 58, "cpu-fp32", IMG_FP64_MARGIN)
 
 
 def f32(v):

@@ -16,9 +16,9 @@ from types import SimpleNamespace
 import torch
 import torch.nn.functional as F
 
+from tests._envelope import U32, one_thread
 from videoseal_amd.engine import split_bf16x3, split_f16x2
 
-U24 = 2.0 ** -24
 TINY = 1e-300
 F16_MIN_NORMAL = 2.0 ** -14
 # Twice the largest ratio  max r / max(max r_ref, 1)  measured on an MI355X over every case of tests/test_gpu_split_envelope.py
@@ -64,16 +64,6 @@ def _conv32(x, w, stride, pad, reflect):
     if pad:
         x = F.pad(x, (pad, pad, pad, pad), mode="reflect" if reflect else "constant")
     return F.conv2d(x, w, stride=stride)
-
-
-def one_thread(fn):
-    """ATen's summation order must not depend on the number of cores the host grants"""
-    n = torch.get_num_threads()
-    torch.set_num_threads(1)
-    try:
-        return fn()
-    finally:
-        torch.set_num_threads(n)
 
 
 def ideal(a, w, arith, a_mul=16.0, w_mul=None, *, stride=1, pad=0, reflect=False, extras=False):
@@ -142,7 +132,7 @@ def epilogue(v, P=None, bias=None, act=0, res=None):
 
 def units(got, S, P):
     """r = |got - S| / max(2^-24 P, tiny) per element (float64)"""
-    return (got.double() - S).abs() / (U24 * P).clamp_min(TINY)
+    return (got.double() - S).abs() / (U32 * P).clamp_min(TINY)
 
 
 def old_criterion_accepts(got, ref) -> bool:

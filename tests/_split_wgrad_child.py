@@ -10,7 +10,7 @@ if ROOT not in sys.path:
 import torch  # noqa: E402
 
 from tests import _split_ref as R  # noqa: E402
-from tests.test_gpu_split_envelope import wgrad_gemm_launch  # noqa: E402
+from tests._gpu import wgrad_gemm_launch  # noqa: E402
 
 if __name__ == "__main__":
     torch.save([wgrad_gemm_launch(c) for c in R.WGRAD_GEMM_CASES], sys.argv[1])

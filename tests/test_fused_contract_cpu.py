@@ -12,6 +12,7 @@ import torch
 
 from tests import _fused_ref as Q
 from tests import _split_ref as R
+from tests._envelope import outside
 
 
 def rmax(got, S, unit, skip=None):
@@ -82,7 +83,7 @@ def test_cnx_yardstick_is_finite_and_the_seeded_defects_fall_outside(shape, cnx_
         r = {k: rmax(bad[k][0], S, unit) for k, (S, unit, _) in good.items()}
         print(f"FUSED-TEETH cnx_block {shape}: {name}: " + ", ".join(f"{k} {v:.1f}" for k, v in r.items())
               + f"; older criterion on randn operands {'ACCEPTS' if cnx_old_criterion[name] else 'rejects'} it")
-        assert any(Q.outside(r[k], r_ref[k]) for k in r), (name, r, r_ref)
+        assert any(outside(r[k], r_ref[k], 1.0) for k in r), (name, r, r_ref)
 
 
 @pytest.mark.parametrize("shape", Q.CNX_SHAPES, ids=str)
@@ -138,15 +139,15 @@ def test_resblock_yardstick_is_finite_and_the_seeded_defects_fall_outside(p, rb_
             msg += f", t through tap {tap} {rt:.2f}"
             if tap == 0:
                 padded = rmax(Q.rb_chain(q, arith, padded_conv0=True, want_ref=False).S, et.S, et.unit)
-                assert Q.outside(padded, rt), (padded, rt)
+                assert outside(padded, rt, 1.0), (padded, rt)
     else:
         padded = rmax(Q.rb_chain(o, arith, padded_conv0=True, want_ref=False).S, e.S, e.unit)
-        assert Q.outside(padded, r_ref), (padded, r_ref)
+        assert outside(padded, r_ref, 1.0), (padded, r_ref)
     print(msg)
     print(f"FUSED-TEETH resblock_thin {p}: t outside the image = conv0 of padded data {padded:.3g} (older criterion on randn operands "
           f"{'ACCEPTS' if rb_old_criterion['padded_conv0'] else 'rejects'} it), halo ring shifted by one pixel {shift:.3g} "
           f"({'ACCEPTS' if rb_old_criterion['halo_shift'] else 'rejects'})")
-    assert Q.outside(shift, r_ref), (shift, r_ref)
+    assert outside(shift, r_ref, 1.0), (shift, r_ref)
 
 
 @pytest.mark.parametrize("p", [(f, m) for f in ((16, 2, 1), (16, 2, 16), (32, 2, 20)) for m in ((2, 7, 15), (2, 17, 33))], ids=str)

@@ -6,6 +6,7 @@ and a softmax without the maximum on those tests' own randn inputs (single-plane
 import pytest
 import torch
 
+from tests import _envelope as E
 from tests import _fwd_ref as R
 
 # what "meaningful" means for the yardstick: fp32 round-off times the condition of the hard rows -- mean 30 / std 0.5 loses log2(60) = 6 bits in
@@ -24,23 +25,23 @@ def test_layernorm_defects_fall_outside_the_envelope(case, act):
     tag, rows, C, ld, _ = case
     x, w, b = R.ln_inputs(rows, C)
     r64, r32 = R.ln_ref(x, w, b, act)
-    yard = R.group_err(r32, r64, 1)
-    one = R.group_err(R.ln_ref(x, w, b, act, one_pass=True)[1], r64, 1)
+    yard = E.group_err(r32, r64, 1)
+    one = E.group_err(R.ln_ref(x, w, b, act, one_pass=True)[1], r64, 1)
     print(f"TEETH layernorm {tag} C={C} act={act}: yardstick {yard:.3e}, one-pass variance {one:.3e}")
     assert yard < LN_YARD
-    assert R.outside(one, yard)
+    assert E.outside(one, yard)
     # ... and on a mean-30 row alone (row 0).  The outlier row (2) is listed, not asserted: its variance is the outlier's own square over C,
     # E[x^2] exceeds E[x]^2 by a factor of about C there and the one-pass form cancels nothing -- that row is hard for the MEAN (a sum of
     # 30s next to 4e3) and for a kernel that loses the small elements, not for this defect
     bad = R.ln_ref(x, w, b, act, one_pass=True)[1]
     for row in (0, 2):
-        y1, d1 = R.group_err(r32[row:row + 1], r64[row:row + 1], 1), R.group_err(bad[row:row + 1], r64[row:row + 1], 1)
+        y1, d1 = E.group_err(r32[row:row + 1], r64[row:row + 1], 1), E.group_err(bad[row:row + 1], r64[row:row + 1], 1)
         print(f"TEETH layernorm {tag} C={C} act={act}: row {row}: yardstick {y1:.3e}, one-pass variance {d1:.3e}")
-        assert row == 2 or R.outside(d1, y1), (row, d1, y1)
+        assert row == 2 or E.outside(d1, y1), (row, d1, y1)
     if ld > C:
-        wrong = R.group_err(R.ln_ref(x, w, b, act, div=ld)[1], r64, 1)
+        wrong = E.group_err(R.ln_ref(x, w, b, act, div=ld)[1], r64, 1)
         print(f"TEETH layernorm {tag} C={C} act={act}: variance / ld {wrong:.3e}")
-        assert R.outside(wrong, yard)
+        assert E.outside(wrong, yard)
 
 
 def _producer_cases():
@@ -72,11 +73,11 @@ def test_layernorm_behind_a_producer_one_pass_variance_falls_outside_the_envelop
     fp32 rounding then costs as much as the one-pass variance and the figure is listed, not asserted -- the variant without it is the hard one"""
     tag, ref, hard = case
     r64, r32 = ref()
-    yard = R.group_err(r32, r64, -1)
-    one = R.group_err(ref(one_pass=True)[1], r64, -1)
+    yard = E.group_err(r32, r64, -1)
+    one = E.group_err(ref(one_pass=True)[1], r64, -1)
     print(f"TEETH {tag}: yardstick {yard:.3e}, one-pass variance {one:.3e}")
     assert yard < LN_YARD
-    assert R.outside(one, yard) or not hard
+    assert E.outside(one, yard) or not hard
 
 
 @pytest.mark.parametrize("case", R.RMS_CASES)
@@ -84,7 +85,7 @@ def test_rmsnorm_yardstick_is_meaningful(case):
     rows, C = case
     x, gamma, add = R.rms_inputs(rows, C)
     r64, r32 = R.rms_ref(x, gamma, add)
-    yard = R.group_err(r32, r64, 1)
+    yard = E.group_err(r32, r64, 1)
     print(f"TEETH rmsnorm rows={rows} C={C}: yardstick {yard:.3e}")
     assert yard < 1e-6
     assert torch.equal(r64[R.RMS_ZERO_ROW], add[R.RMS_ZERO_ROW].double()) and torch.equal(r32[R.RMS_ZERO_ROW], add[R.RMS_ZERO_ROW])
@@ -95,11 +96,11 @@ def test_grn_mean_over_ld_falls_outside_the_envelope(case):
     B, HW, C, ld = case
     h, gamma, beta = R.grn_inputs(B, HW, C)
     r64, r32 = R.grn_ref(h, gamma)
-    yard = R.group_err(r32, r64, None)
-    wrong = R.group_err(R.grn_ref(h, gamma, div=ld)[1], r64, None)
+    yard = E.group_err(r32, r64, None)
+    wrong = E.group_err(R.grn_ref(h, gamma, div=ld)[1], r64, None)
     print(f"TEETH grn B={B} HW={HW} C={C} ld={ld}: yardstick {yard:.3e}, mean over ld {wrong:.3e}")
     assert ld > C and yard < 1e-5
-    assert R.outside(wrong, yard)
+    assert E.outside(wrong, yard)
 
 
 ATTN_ALL = R.ATTN_VALU_CASES + R.ATTN_MFMA_CASES
@@ -119,11 +120,11 @@ def test_attention_defects_fall_outside_the_envelope(case):
         print(f"TEETH attention {cfg} rel={rel} {mode}: " + ", ".join(f"{n} {d:.3e} (yardstick {y:.3e})" for n, d, y in lines))
         if mode == "plane2":          # listed only: 2^-16 of a probability is at the yardstick's own level on these inputs
             continue
-        assert R.outside(lines[0][1], lines[0][2]), (mode, lines[0])
+        assert E.outside(lines[0][1], lines[0][2]), (mode, lines[0])
         if mode == "nomax":
             assert not torch.isfinite(bad).all()          # exp overflows on the peaked rows
         if mode == "plane":                               # every head on its own line, whatever its V holds
-            assert all(R.outside(d, y) for n, d, y in lines), lines
+            assert all(E.outside(d, y) for n, d, y in lines), lines
 
 
 def test_uniform_query_is_the_mean_of_v():

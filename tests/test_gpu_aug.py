@@ -10,7 +10,7 @@ from oracle import videoseal_ref as R  # noqa: E402
 from oracle.inputs import synthetic_frames, synthetic_msgs  # noqa: E402
 from oracle.weights import make_state_dict, tiny_spec  # noqa: E402
 from tests._util import assert_decisions  # noqa: E402
-from tests.test_gpu_e2e import make_model  # noqa: E402
+from tests._model import make_model  # noqa: E402
 
 CHAIN_MARGIN = 2e-5       # through the augmentation chain: measured logit error 2.2e-6 (profiles/r06a_decision_margins.txt)
 from videoseal_amd import augmentation as G  # noqa: E402

@@ -14,25 +14,12 @@ pytestmark = pytest.mark.gpu
 
 from oracle.weights import make_state_dict, tiny_spec  # noqa: E402
 from tests._util import load_golden, projection_vector  # noqa: E402
-from tests.test_gpu_e2e import make_model  # noqa: E402
+from tests._cases import CARDS  # noqa: E402
+from tests._envelope import ENV_SHAPES, bwd_envelope as envelope, cpu_autograd, group_err, hard_matrix  # noqa: E402
+from tests._gpu import _lib, _padded, _rand  # noqa: E402
+from tests._model import hip_forward, make_model  # noqa: E402
 
 from videoseal_amd import native as N  # noqa: E402
-
-
-def _lib():
-    return N.lib(), N.stream()
-
-
-def _rand(*shape, seed=0, scale=1.0):
-    g = torch.Generator().manual_seed(seed)
-    return (torch.randn(*shape, generator=g) * scale).cuda()
-
-
-def _padded(t, ld):
-    """[rows, C] -> [rows, ld] with zero pad lanes"""
-    out = torch.zeros(t.shape[0], ld, device=t.device)
-    out[:, : t.shape[1]] = t
-    return out
 
 
 @pytest.mark.parametrize("rows,n,k,ldn,ldk", [(1000, 20, 36, 20, 36), (4100, 96, 384, 96, 384), (64, 257 - 1, 16, 256, 16), (7, 5, 70, 8, 72),
@@ -287,63 +274,7 @@ def test_head_pieces_and_the_decoding_loss():
 # inputs are hard on purpose and the error is taken PER GROUP: max |got - ref| over a row (or channel) divided by max |ref| over the same row,
 # worst row.  The yardstick is ATen's own fp32 CPU autograd of the formula, on the same inputs in the same metric: the HIP kernel may exceed
 # it by FP64_MARGIN, which covers a different but legitimate summation order.  The margin is twice the largest ratio measured on an MI355X
-# (profiles/bwd_fp64_envelope.txt lists every case), and may never exceed 8: a kernel that needs more has a defect.
-FP64_MARGIN = 6.94          # 2 x 3.468, the largest ratio measured: d bias of vs_layernorm_bwd at rows = 301, C = 130 (64-row fp32 chunks vs ATen's order)
-ENV_SHAPES = [(37, 18, 20), (301, 130, 160), (67, 1100, 1100)]          # (rows, C, ld): C % 4 != 0 twice, ld > 4 ceil(C / 4) once
-U32 = 2.0 ** -24            # floor of the yardstick: the final rounding of an fp32 result is unavoidable even where ATen happens to be exact
-
-
-def hard_matrix(rows, C, seed, groups):
-    """[rows][C] float32 (CPU), fixed seed.  groups = "rows": every row is a group of mean 30 and std 0.5, row 1 is constant (variance 0), row 2
-    holds a single 4e3 outlier, row 3 has magnitude 1e-3; groups = "cols": the same for the columns (channels)"""
-    g = torch.Generator().manual_seed(seed)
-    x = 30.0 + 0.5 * torch.randn(rows, C, generator=g)
-    if groups == "rows":
-        x[1] = 30.25
-        x[2, C // 2] = 4e3
-        x[3] = 1e-3 * torch.randn(C, generator=g)
-    else:
-        x[:, 1] = 30.25
-        x[rows // 2, 2] = 4e3
-        x[:, 3] = 1e-3 * torch.randn(rows, generator=g)
-    return x
-
-
-def cpu_autograd(fn):
-    """(float64 reference, ATen float32 yardstick) of `fn(dtype)` on the CPU.  One thread: the summation order of ATen's reductions -- and with it
-    the yardstick, whose worst channel is a cancelling sum -- would otherwise change with the number of cores the host happens to grant"""
-    n = torch.get_num_threads()
-    torch.set_num_threads(1)
-    try:
-        return fn(torch.float64), fn(torch.float32)
-    finally:
-        torch.set_num_threads(n)
-
-
-def group_err(got, ref, dim, keep=None):
-    """worst group of max |got - ref| / max |ref|, groups = slices along `dim` (dim = None: every element is its own group); `keep`: mask of the
-    elements that take part.  A group whose reference is all zero must be reproduced exactly."""
-    got, ref = got.detach().double().cpu(), ref.detach().double().cpu()
-    d, m = (got - ref).abs(), ref.abs()
-    if keep is not None:
-        d, m = d * keep, m * keep
-    if dim is not None:
-        d, m = d.amax(dim), m.amax(dim)
-    e = torch.where(m > 0, d / m.clamp_min(1e-300), torch.where(d > 0, torch.full_like(d, float("inf")), torch.zeros_like(d)))
-    return float(e.max())
-
-
-def envelope(case, rows):
-    """rows: (name, hip error, ATen fp32 error).  Prints every figure, then asserts hip <= FP64_MARGIN * max(aten, U32) for each."""
-    bad = []
-    for name, hip, aten in rows:
-        ratio = hip / max(aten, U32)
-        print(f"ENVELOPE {case:<44s} {name:<10s} hip {hip:.3e}  aten-fp32 {aten:.3e}  ratio {ratio:6.3f}")
-        if not ratio <= FP64_MARGIN:
-            bad.append((name, hip, aten, ratio))
-    assert not bad, (case, bad)
-
-
+# (profiles/bwd_fp64_envelope.txt lists every case), and may never exceed 8: a kernel that needs more has a defect (tests/_envelope.py).
 @pytest.mark.parametrize("rows,C,ld", ENV_SHAPES)
 def test_layernorm_bwd_fp64_envelope(rows, C, ld):
     L, st = _lib()
@@ -437,7 +368,6 @@ def test_colmean_and_pool_gelu_bwd_fp64_envelope(rows, C, ld):
 
 # ---------------------------------------------------------------------------------------------------------- end to end
 def _train_forward(model, spec, meta):
-    from tests.test_gpu_fwd import hip_forward
     full = dict(meta, bn_train=True, video_mode="repeat", lowres=False, scaling_i=spec.scaling_i)
     return hip_forward(model, spec, full)
 
@@ -500,7 +430,6 @@ def test_detector_step_full_size_architecture_matches_oracle_autograd():
     from oracle import videoseal_ref as R
     from oracle.inputs import synthetic_frames, synthetic_msgs
     from oracle.weights import spec_from_card
-    from tests.test_oracle_golden import CARDS
     from videoseal_amd.training import DetectorStep
     spec = spec_from_card(os.path.join(CARDS, "videoseal_1.0.yaml"))
     sd = make_state_dict(spec, seed=0)
@@ -602,7 +531,6 @@ def test_detector_step_vit_extractor_matches_oracle_autograd(which):
     from oracle import videoseal_ref as R
     from oracle.inputs import synthetic_frames, synthetic_msgs
     from oracle.weights import legacy_tiny_spec, spec_from_card
-    from tests.test_oracle_golden import CARDS
     from videoseal_amd.training import DetectorStep
     spec = legacy_tiny_spec() if which == "tiny" else spec_from_card(os.path.join(CARDS, "videoseal_0.0.yaml"))
     sd = make_state_dict(spec, seed=5)

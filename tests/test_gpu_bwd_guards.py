@@ -14,7 +14,7 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
-from tests.test_gpu_scratch_contracts import _L, _contract, r4  # noqa: E402
+from tests._gpu import _contract, _lib as _L, r4  # noqa: E402
 
 from videoseal_amd import native as N  # noqa: E402
 

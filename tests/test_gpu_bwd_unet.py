@@ -18,9 +18,10 @@ pytestmark = pytest.mark.gpu
 from oracle import videoseal_ref as R  # noqa: E402
 from oracle.inputs import synthetic_frames, synthetic_msgs  # noqa: E402
 from oracle.weights import make_state_dict, spec_from_card, tiny_spec  # noqa: E402
-from tests.test_gpu_bwd import ENV_SHAPES, _lib, _padded, _rand, cpu_autograd, envelope, group_err, hard_matrix  # noqa: E402
-from tests.test_gpu_e2e import make_model  # noqa: E402
-from tests.test_oracle_golden import CARDS  # noqa: E402
+from tests._cases import CARDS  # noqa: E402
+from tests._envelope import ENV_SHAPES, bwd_envelope as envelope, cpu_autograd, group_err, hard_matrix  # noqa: E402
+from tests._gpu import _lib, _MaskedF, _padded, _rand, hip_relu_masks  # noqa: E402
+from tests._model import make_model  # noqa: E402
 
 from videoseal_amd import native as N  # noqa: E402
 
@@ -199,47 +200,6 @@ def test_msg_table_outc_and_relu_adjoints():
     dz = torch.full((50, 8), 7.0, device="cuda")
     N.check(L.vs_relu_bwd(N.ptr(za), 8, N.ptr(dya), 8, 50, 6, N.ptr(dz), 8, st), "vs_relu_bwd")
     assert torch.equal(dz[:, :6], dy * (z > 0)) and (dz[:, 6:] == 0).all()
-
-
-class _MaskedF:
-    """stands in for torch.nn.functional inside oracle.videoseal_ref: relu(x) = x * mask_i with the i-th ReLU decision of the HIP forward"""
-
-    def __init__(self, masks):
-        self.masks, self.i = masks, 0
-
-    def __getattr__(self, k):
-        return getattr(F, k)
-
-    def relu(self, x):
-        m = self.masks[self.i]
-        self.i += 1
-        assert m.shape == x.shape, (self.i, m.shape, x.shape)
-        return x * m
-
-
-def hip_relu_masks(model, saved):
-    """the ReLU decisions of EmbedderBackward.forward_keep in the order oracle.videoseal_ref.unet_forward calls F.relu"""
-    eng = model._engine()
-    L, st = eng.lib, N.stream()
-
-    def nchw(act, t=None):
-        tt = act.t if t is None else t
-        return (tt.view(act.B, act.H, act.W, act.ld)[..., : act.C].permute(0, 3, 1, 2) > 0).float().cpu()
-
-    def block(rec):
-        raw1, s1 = rec["raw1"], rec["s1"]
-        tmp = torch.empty_like(raw1.t)
-        N.check(L.vs_scale_shift_act(N.ptr(raw1.t), raw1.rows, (raw1.C + 3) // 4 * 4, raw1.ld, N.ptr(s1["scale"]), N.ptr(s1["shift"]), N.ACT_RELU, None, 0,
-                                     N.ptr(tmp), raw1.ld, st), "vs_scale_shift_act")
-        return [nchw(rec["t"]), nchw(raw1, tmp)]
-    masks = block(saved["inc"])
-    for d in saved["downs"]:
-        masks += block(d["rb"])
-    for rec in saved["bott"]:
-        masks += block(rec)
-    for u in saved["ups"]:
-        masks += [nchw(u["z"])] + block(u["rb"])
-    return masks
 
 
 def _embedder_case(spec, sd, n, seed, masked=True):

@@ -20,7 +20,7 @@ import torch.nn.functional as F
 
 from tests import _disc_util as U
 from tests._util import load_golden
-from tests.test_gpu_kernels import _guarded, _guards_intact
+from tests._guards import _guarded, _guards_intact
 
 from videoseal_amd import native as N
 from videoseal_amd.discriminator import GN_EPS, SLOPE, NLayerDiscriminator, disc_loss_raw, generator_disc_loss
@@ -343,7 +343,7 @@ def test_hinge_update_matches_the_reference(case):
 def _step_setup(meta, monkeypatch):
     from oracle.inputs import synthetic_frames, synthetic_msgs
     from oracle.weights import make_state_dict, tiny_spec
-    from tests.test_gpu_e2e import make_model
+    from tests._model import make_model
     from videoseal_amd import augmentation as G
     monkeypatch.setenv("VIDEOSEAL_CONV", "bf16x3")            # the embedder and the extractor on the exact split as well
     spec = tiny_spec()

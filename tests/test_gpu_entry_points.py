@@ -11,6 +11,8 @@ pytestmark = pytest.mark.gpu
 
 from oracle import augment as A  # noqa: E402
 from oracle.inputs import synthetic_frames  # noqa: E402
+from tests._envelope import U32 as U  # noqa: E402  (unit round-off of float32)
+from tests._gpu import _lib  # noqa: E402
 from tests._guards import _guarded, _guards_intact  # noqa: E402
 
 from videoseal_amd import native as N  # noqa: E402
@@ -18,12 +20,7 @@ from videoseal_amd import native as N  # noqa: E402
 NAN, INF = float("nan"), float("inf")
 FLT_MAX = torch.finfo(torch.float32).max
 DENORM = 1e-42                       # a float32 denormal (min normal = 1.18e-38)
-U = 2.0 ** -24                       # unit round-off of float32
 SENT = 0x5A5A                        # band value around the integer outputs
-
-
-def _lib():
-    return N.lib(), N.stream()
 
 
 def _bits(v: float) -> int:

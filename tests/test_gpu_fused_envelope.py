@@ -19,9 +19,9 @@ pytestmark = pytest.mark.gpu
 
 from tests import _fused_ref as Q  # noqa: E402
 from tests import _split_ref as R  # noqa: E402
+from tests._envelope import check_units  # noqa: E402
+from tests._gpu import DEV, planes_of  # noqa: E402
 from tests._guards import _guarded, _guards_intact  # noqa: E402
-from tests.test_gpu_kernels import DEV  # noqa: E402
-from tests.test_gpu_split_envelope import planes_of  # noqa: E402
 from videoseal_amd import native as N  # noqa: E402
 from videoseal_amd.engine import pack_cnx_block, pack_conv, rup, split_bf16x3, split_f16x2  # noqa: E402
 
@@ -32,6 +32,9 @@ NANB = 0xFF             # bytes of a NaN in either 16-bit format and in fp32
 PAD = 8                 # extra lanes of res_ld / out_ld
 
 
+_check = functools.partial(check_units, "FUSED-ENVELOPE", 84, Q.FUSED_MARGIN)
+
+
 def envelope(case, got, S, unit, ref, skip=None):
     """prints the case's figures, then asserts max r <= FUSED_MARGIN max(max r_ref, 1) over every element (skip: the pixels of a planted overflow)"""
     r_all, r_ref_all = Q.ratio_units(got, S, unit), Q.ratio_units(ref, S, unit)
@@ -40,9 +43,7 @@ def envelope(case, got, S, unit, ref, skip=None):
     r, r_ref = float(r_all.max()), float(r_ref_all.max())
     if torch.isnan(r_all).any():
         r = NAN
-    ratio = r / max(r_ref, 1.0)
-    print(f"FUSED-ENVELOPE {case:<84s} hip {r:9.3f}  aten-fp32 {r_ref:9.3f}  ratio {ratio:6.3f}")
-    assert ratio <= Q.FUSED_MARGIN, (case, r, r_ref, ratio)
+    _check(case, r, r_ref)
 
 
 # ---------------------------------------------------------------------------------------------------------------- vs_cnx_block

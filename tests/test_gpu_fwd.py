@@ -19,27 +19,11 @@ from tests._util import GOLDEN, assert_decisions, check_sub, load_golden  # noqa
 
 FWD_MARGIN = 2e-5         # train-mode forward: measured logit error 1.3e-6 (gpurun_out/r06a/decisions.jsonl -> profiles/r06a_decision_margins.txt)
 CHAIN_MARGIN = 2e-5       # through the augmentation chain: measured logit error 2.2e-6 (profiles/r06a_decision_margins.txt)
-from tests.test_gpu_e2e import _run_case, make_model  # noqa: E402
-from tests.test_oracle_fwd import FWD_FULL, FWD_TINY, PIXELSEAL, bn_vectors  # noqa: E402
-from tests.test_oracle_golden import CARDS  # noqa: E402
+from tests._cases import CARDS, FWD_FULL, FWD_TINY, PIXELSEAL, bn_vectors  # noqa: E402
+from tests._model import _run_case, hip_forward, make_model  # noqa: E402
 
 import videoseal_amd  # noqa: E402
 from videoseal_amd import augmentation as G  # noqa: E402
-
-
-def hip_forward(model, spec, meta):
-    imgs = synthetic_frames(meta["n"], meta["h"], meta["w"], seed=meta["seed"], kind=meta["kind"])
-    msgs = synthetic_msgs(1 if meta["is_video"] else meta["n"], spec.nbits, seed=meta["seed"])
-    masks = torch.ones(meta["n"], 1, meta["h"], meta["w"])
-    model.augmenter = G.Augmenter(masks={"kind": "none"}, augs=meta["augs"], augs_params=meta["augs_params"], num_augs=meta["num_augs"])
-    model.train()
-    if not meta["bn_train"]:
-        model.embedder.eval()
-        model.detector.eval()
-    model.step_size, model.video_mode, model.lowres_attenuation = meta["step"], meta["video_mode"], meta["lowres"]
-    model.blender.scaling_i = meta["scaling_i"]
-    torch.manual_seed(meta["torch_seed"])
-    return model(imgs.cuda(), masks.cuda(), msgs, is_video=meta["is_video"]), imgs, msgs
 
 
 def _check_fwd(spec, sd, name):

@@ -14,9 +14,10 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
+from tests import _envelope as E  # noqa: E402
 from tests import _fwd_ref as R  # noqa: E402
+from tests._gpu import Eng, _padded, attention_launch, dv, from_nhwc, to_nhwc  # noqa: E402
 from tests._guards import _guarded, _guards_intact  # noqa: E402
-from tests.test_gpu_kernels import Eng, dv, from_nhwc, to_nhwc  # noqa: E402
 from videoseal_amd import native as N  # noqa: E402
 from videoseal_amd import pixel_head as PH  # noqa: E402
 from videoseal_amd.engine import ConvW, pack_conv, pack_patch_conv, rup  # noqa: E402
@@ -26,20 +27,13 @@ DEV = "cuda"
 NAN = float("nan")
 
 
-def _padded(t, ld):
-    """[rows, C] (CPU) -> [rows, ld] with zero pad lanes"""
-    out = torch.zeros(t.shape[0], ld)
-    out[:, : t.shape[1]] = t
-    return out
-
-
 def _pad1(v, ld):
     return dv(torch.cat([v, torch.zeros(ld - v.numel())]))
 
 
 def _rows(got, r64, r32, name="y/row"):
     """one envelope line: groups = slices along the last dim (a row / pixel)"""
-    return (name, R.group_err(got, r64, -1), R.group_err(r32, r64, -1))
+    return (name, E.group_err(got, r64, -1), E.group_err(r32, r64, -1))
 
 
 # ------------------------------------------------------------------------------------------------------------------------ vs_layernorm_act
@@ -227,7 +221,7 @@ def test_grn_scale_fp64_envelope(B, HW, C, ld):
     torch.cuda.synchronize()
     assert _guards_intact(sbuf, -7.0) and _guards_intact(pbuf, -7.0) and _guards_intact(hbuf, NAN)
     assert (scale[:, C:] == 0).all()
-    R.envelope(f"grn_scale B={B} HW={HW} C={C} ld={ld}", [("scale/elem", R.group_err(scale[:, :C], r64, None), R.group_err(r32, r64, None))])
+    R.envelope(f"grn_scale B={B} HW={HW} C={C} ld={ld}", [("scale/elem", E.group_err(scale[:, :C], r64, None), E.group_err(r32, r64, None))])
 
 
 def _grn_apply_lines(L, h, scale, sld, beta, r64s, r32s):
@@ -260,7 +254,7 @@ def test_grn_scale_from_partials_fp64_envelope(B, HW, C):
     assert _guards_intact(sbuf, -7.0) and _guards_intact(pbuf, NAN)
     assert (scale[:, C:] == 0).all()
     R.envelope(f"grn_scale_from_partials B={B} HW={HW} C={C}", [
-        ("scale/elem", R.group_err(scale[:, :C], r64, None), R.group_err(r32, r64, None)),
+        ("scale/elem", E.group_err(scale[:, :C], r64, None), E.group_err(r32, r64, None)),
         _grn_apply_lines(L, h, scale, sld, beta, r64, r32)])
 
 
@@ -280,26 +274,11 @@ def test_grn_scale_from_straddle_partials_fp64_envelope(B, HW, C):
     assert _guards_intact(sbuf, -7.0) and _guards_intact(pbuf, NAN)
     assert (scale[:, C:] == 0).all()
     R.envelope(f"grn_scale_from_straddle_partials B={B} HW={HW} C={C}", [
-        ("scale/elem", R.group_err(scale[:, :C], r64, None), R.group_err(r32, r64, None)),
+        ("scale/elem", E.group_err(scale[:, :C], r64, None), E.group_err(r32, r64, None)),
         _grn_apply_lines(L, h, scale, sld, beta, r64, r32)])
 
 
 # ------------------------------------------------------------------------------------------------------------------------ vs_vit_attention
-def attention_launch(case):
-    """the kernel's output [B, H, W, heads, hd] (CPU) for one (cfg, tables?) case on the hard qkv; which kernel runs is the library's choice
-    (VS_VIT_ATTN, read once per process)"""
-    cfg, rel = case
-    B, H, W, heads, hd, win = cfg
-    qkv, rh, rw = R.attn_inputs(cfg, rel)
-    qd = qkv.to(DEV)
-    rhd, rwd = (rh.to(DEV), rw.to(DEV)) if rel else (None, None)
-    obuf, og = _guarded(torch.full((B, H, W, heads * hd), 9.0, device=DEV), -7.0)
-    N.check(N.lib().vs_vit_attention(N.ptr(qd), B, H, W, heads, hd, win, N.ptr(rhd), N.ptr(rwd), N.ptr(og), N.stream()), "vs_vit_attention")
-    torch.cuda.synchronize()
-    assert _guards_intact(obuf, -7.0)
-    return og.cpu().view(B, H, W, heads, hd).clone()
-
-
 def attention_check(case, kernel, got):
     cfg, rel = case
     qkv, rh, rw = R.attn_inputs(cfg, rel)

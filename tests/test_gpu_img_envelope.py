@@ -12,6 +12,7 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
+from tests import _envelope as E  # noqa: E402
 from tests import _img_ref as R  # noqa: E402
 from tests._guards import _guarded, _guards_intact  # noqa: E402
 from videoseal_amd import native as N  # noqa: E402
@@ -101,7 +102,7 @@ def _resize_pre_lines(x, u8, H, W, oh, ow, aa, sw, rows):
             assert (pad == 0).all()
             got["key-rgb"] = k
     for name, r64, r32 in (("rgb", want64[0], want32[0]), ("key-y", want64[1], want32[1]), ("key-rgb", krgb64, krgb32)):
-        rows.setdefault(name, []).append((R.frame_err(got[name], r64), R.frame_err(r32, r64)))
+        rows.setdefault(name, []).append((E.frame_err(got[name], r64), E.frame_err(r32, r64)))
 
 
 def _emit(case, rows, kinds):
@@ -145,7 +146,7 @@ def test_resize_pre_single_channel_fp64_envelope():
         N.check(L.vs_resize_pre(N.ptr(xin[1]), 2, 1, H, W, oh, ow, 1, N.ptr(rgb[1]), 2.0, -1.0, None, 1, None, N.stream()), "vs_resize_pre")
         (g,) = _done([rgb], [xin])
         assert (g[..., 1:] == 0).all()
-        lines.append((kind, R.frame_err(g[..., 0][:, None], r64 * 2 - 1), R.frame_err(r32 * 2 - 1, r64 * 2 - 1)))
+        lines.append((kind, E.frame_err(g[..., 0][:, None], r64 * 2 - 1), E.frame_err(r32 * 2 - 1, r64 * 2 - 1)))
     R.envelope(f"resize_pre C=1 {H}x{W}->{oh}x{ow} aa=1 rgb", lines)
 
 
@@ -184,7 +185,7 @@ def test_jnd_heatmap_fp64_envelope(H, W, nhwc):
         own, other, amb, y32 = R.jnd_ref(x)
         assert float(amb.float().mean()) <= R.JND_SHARE          # condition on the reference alone
         got = _jnd_launch(x, nhwc)
-        lines.append((kind, R.cand_err(got, own, other, amb), R.cand_err(y32, own, other, amb)))
+        lines.append((kind, E.cand_err(got, own, other, amb), E.cand_err(y32, own, other, amb)))
     R.envelope(f"jnd_heatmap {H}x{W}{' nhwc strides' if nhwc else ''}", lines)
 
 
@@ -230,9 +231,9 @@ def test_embed_tail_fp64_envelope(case):
         kinds.append(kind)
         for variant in (1, 2, 4):
             got, gpw = _tail_launch(imgs, delta, hm, cfg, Cd, S, want_pw, variant)
-            rows.setdefault(f"v{variant} out", []).append((R.cand_err(got, own[0], other[0], amb), R.cand_err(y32[0], own[0], other[0], amb)))
+            rows.setdefault(f"v{variant} out", []).append((E.cand_err(got, own[0], other[0], amb), E.cand_err(y32[0], own[0], other[0], amb)))
             if want_pw:
-                rows.setdefault(f"v{variant} preds_w", []).append((R.cand_err(gpw, own[1], other[1], amb), R.cand_err(y32[1], own[1], other[1], amb)))
+                rows.setdefault(f"v{variant} preds_w", []).append((E.cand_err(gpw, own[1], other[1], amb), E.cand_err(y32[1], own[1], other[1], amb)))
     _emit(f"embed_tail {tag} F={Fn} {H}x{W} S={S} Cd={Cd}", rows, kinds)
 
 
@@ -245,7 +246,7 @@ def test_embed_tail_u8_bytes_are_within_one_level_of_the_float64_tail():
     for kind, imgs in R.tail_frames(Fn, H, W).items():
         imgs = ((imgs * 255).round().to(torch.uint8).float() / 255.0)          # the fp32 value the kernel reads: float(u) / 255.0f
         own, other, amb, y32 = R.tail_ref(imgs, delta, hm, cfg)
-        yard = max(R.cand_err(y32[0], own[0], other[0], amb), R.U32) * float(own[0].abs().max())
+        yard = max(E.cand_err(y32[0], own[0], other[0], amb), E.U32) * float(own[0].abs().max())
         got = _tail_launch(imgs, delta, hm, cfg, Cd, S, False, 0, io_u8=True)[0].permute(0, 3, 1, 2).double()
 
         def ok(ref):
@@ -295,7 +296,7 @@ def test_colour_op_fp64_envelope(colour_inputs, name, op, f):
         r64, r32 = R.color_op(x, op, f, F64), R.color_op(x, op, f, F32)
         got = _color_launch(x, [(op, f)], False)
         assert torch.equal(_color_launch(x, [(op, f)], True), got)
-        lines.append((kind, R.frame_err(got, r64), R.frame_err(r32, r64)))
+        lines.append((kind, E.frame_err(got, r64), E.frame_err(r32, r64)))
     R.envelope(f"aug_color {name} factor {f:g}", lines)
 
 
@@ -304,7 +305,7 @@ def test_colour_chain_fp64_envelope(colour_inputs):
     lines = []
     for kind, x in colour_inputs.items():
         r64, r32 = R.color_chain(x, R.COLOR_CHAIN, F64), R.color_chain(x, R.COLOR_CHAIN, F32)
-        lines.append((kind, R.frame_err(_color_launch(x, R.COLOR_CHAIN, True), r64), R.frame_err(r32, r64)))
+        lines.append((kind, E.frame_err(_color_launch(x, R.COLOR_CHAIN, True), r64), E.frame_err(r32, r64)))
     R.envelope("aug_color_chain contrast>brightness>saturation>hue", lines)
 
 
@@ -341,14 +342,14 @@ def test_plane_resizes_fp64_envelope(case):
         xin, out = _in(xc), _out(2, 3, oh, ow)
         N.check(L.vs_resize_nchw(N.ptr(xin[1]), N.ptr(out[1]), 6, ch, cw, oh, ow, aa, N.stream()), "vs_resize_nchw")
         (g,) = _done([out], [xin])
-        rows.setdefault("resize_nchw", []).append((R.frame_err(g, r64), R.frame_err(r32, r64)))
+        rows.setdefault("resize_nchw", []).append((E.frame_err(g, r64), E.frame_err(r32, r64)))
         for form, tile in (("crc stream", False), ("crc tile", True)):
             g = _crc_launch(x, crop, oh, ow, aa, [], tile)
             if g is None:
                 continue
-            rows.setdefault(form, []).append((R.frame_err(g, r64), R.frame_err(r32, r64)))
+            rows.setdefault(form, []).append((E.frame_err(g, r64), E.frame_err(r32, r64)))
             g = _crc_launch(x, crop, oh, ow, aa, R.CROP_CHAIN, tile)
-            rows.setdefault(form + "+colour", []).append((R.frame_err(g, e64), R.frame_err(e32, e64)))
+            rows.setdefault(form + "+colour", []).append((E.frame_err(g, e64), E.frame_err(e32, e64)))
     _emit(f"planes {H}x{W} crop {crop} -> {oh}x{ow} aa={aa}", rows, kinds)
 
 
@@ -364,7 +365,7 @@ def test_gaussian_blur_fp64_envelope(k):
             xin, tmp, out = _in(x), _out(2, 3, H, W), _out(2, 3, H, W)
             N.check(L.vs_gaussian_blur(N.ptr(xin[1]), N.ptr(tmp[1]), N.ptr(out[1]), 6, H, W, k, R.blur_sigma(k), N.stream()), "vs_gaussian_blur")
             _, g = _done([tmp, out], [xin])
-            lines.append((kind, R.frame_err(g, r64), R.frame_err(r32, r64)))
+            lines.append((kind, E.frame_err(g, r64), E.frame_err(r32, r64)))
         R.envelope(f"gaussian_blur k={k} {H}x{W}", lines)
 
 
@@ -427,7 +428,7 @@ def test_warp_bilinear_fp64_envelope(case):
     for fk, x4 in R.hard_frames(H, W).items():
         x = x4.reshape(6, H, W)
         r64, r32 = R.warp_bilinear(x, kind, co, oh, ow, F64), R.warp_bilinear(x, kind, co, oh, ow, F32)
-        lines.append((fk, R.frame_err(_warp_launch(x, kind, co, oh, ow, 1), r64), R.frame_err(r32, r64)))
+        lines.append((fk, E.frame_err(_warp_launch(x, kind, co, oh, ow, 1), r64), E.frame_err(r32, r64)))
     R.envelope(f"aug_warp bilinear {tag} {H}x{W}", lines)
 
 

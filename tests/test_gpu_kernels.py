@@ -10,24 +10,10 @@ import torch.nn.functional as F
 
 pytestmark = pytest.mark.gpu
 
+from tests._gpu import _KEEP, DEV, Eng, dv, from_nhwc, rel_err, to_nhwc  # noqa: E402
+from tests._guards import GUARD, _guarded, _guards_intact  # noqa: E402
 from videoseal_amd import native as N  # noqa: E402
-from videoseal_amd.engine import Act, ConvW, HipEngine, pack_conv, pack_patch_conv, rup  # noqa: E402
-
-DEV = "cuda"
-
-
-def to_nhwc(x, ld=None):
-    B, Cc, H, W = x.shape
-    ld = ld or rup(Cc, 4)
-    t = torch.zeros(B, H, W, ld)
-    t[..., :Cc] = x.permute(0, 2, 3, 1)
-    return Act(t.to(DEV).contiguous(), B, H, W, Cc, ld)
-
-
-def from_nhwc(a: Act, Cc=None):
-    Cc = Cc or a.C
-    return a.t.view(a.B, a.H, a.W, a.ld)[..., :Cc].permute(0, 3, 1, 2).cpu()
-
+from videoseal_amd.engine import Act, ConvW, pack_conv, pack_patch_conv, rup  # noqa: E402
 
 @pytest.mark.parametrize("cfg", [(15, 2, True), (0x40, 3, True), (15, 4, False), (0x40, 6, False), (15, 8, True)])
 def test_patch_pc_split_k(eng, cfg):
@@ -233,50 +219,10 @@ def test_conv3x3_small_two_phase(eng, cx):
     assert torch.equal(outs[0], outs[1])
 
 
-class Eng(HipEngine):
-    """engine without a model: only the kernel wrappers + workspace."""
-
-    def __init__(self, use_split=True, arith=3):
-        self.arith = arith
-        self.dev = torch.device(DEV)
-        self.lib = N.lib()
-        self._ws = {}
-        self.kernel_timers = None
-        self.use_split = use_split
-        self.autotune = False
-        self.time_all_convs = False
-        self._tile_cache = {}
-        self.msg_table_conv = True
-        self._ws_used = {}
-        self.layer_arith = {}
-        self.planes_chain = self.planes_splitk = self.msg0_planes = True
-        self.planes_chain_ran = False
-        self.grn_fold = self.grn_straddle = True
-        self._calib = None
-
-
 @pytest.fixture(scope="module", params=["split", "h2", "f32"])
 def eng(request):
     """the arithmetic back-ends of vs_conv_gemm: 3 x bf16 split (exact), 2 x f16 split (3 products) and the fp32-input MFMA"""
     return Eng(use_split=(request.param != "f32"), arith=2 if request.param == "h2" else 3)
-
-
-_KEEP = []
-
-
-def dv(t):
-    """device copy that stays referenced until the test module is torn down (the C-ABI only sees raw pointers,
-    so a temporary freed by Python could be recycled by the caching allocator before the kernel runs)."""
-    t = t.to(DEV).contiguous()
-    _KEEP.append(t)
-    if len(_KEEP) > 256:
-        torch.cuda.synchronize()
-        del _KEEP[:128]
-    return t
-
-
-def rel_err(a, b):
-    return ((a - b).abs().max() / (b.abs().max() + 1e-12)).item()
 
 
 CONV_CASES = [
@@ -1167,9 +1113,6 @@ def test_resblock_thin_fused_kernel_32_channels(shape):
 # around a tensor reach the result, and must not write outside the output.  Every operand sits between two guard areas poisoned with signalling
 # patterns: NaN around the inputs (a value read past either end that reaches an accumulator makes the output NaN or different), a sentinel
 # around the output (a store outside the tensor changes it).  The unguarded launch of the same case is the expected value, bit for bit.
-from tests._guards import GUARD, _guarded, _guards_intact  # noqa: E402,F401  (moved to tests/_guards.py; re-exported for the suites that import them from here)
-
-
 REDZONE_CONV = [c for c in CONV_CASES if c[-1] in (10, 11, 12, 15, 0x40, 0x43, 0x44, 0x45, 14)]
 
 

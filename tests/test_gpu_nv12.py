@@ -22,7 +22,7 @@ from oracle.weights import make_state_dict, tiny_spec  # noqa: E402
 from tests import _nv12_ref as R  # noqa: E402
 from tests._guards import GUARD  # noqa: E402
 from tests._util import assert_decisions  # noqa: E402
-from tests.test_gpu_e2e import TOL_IMG, TOL_LOGIT, make_model  # noqa: E402
+from tests._model import TOL_IMG, TOL_LOGIT, make_model  # noqa: E402
 
 from videoseal_amd import native as N  # noqa: E402
 from videoseal_amd import nv12  # noqa: E402
@@ -347,7 +347,7 @@ def test_nv12_graph_replay_matches_eager(tiny):
 def test_model_level_c_api_nv12(which, tiny, tinyc):
     """vs_model_embed / vs_model_detect with io_u8 = 2 on a contiguous clip equal embed_nv12 / detect_nv12: codes equal, logits within 1e-4
     (the bound of the RGB24 twin in tests/test_gpu_e2e.py::test_model_level_c_api); default colour and vs_model_set_nv12_color"""
-    from tests.test_gpu_e2e import cfg_of
+    from tests._model import cfg_of
     from videoseal_amd.capi import CModel
     spec, sd, model = tiny if which == "tiny" else tinyc
     cm = CModel(cfg_of(spec), sd)

@@ -19,7 +19,8 @@ import torch
 
 from tests import _pixel_head_util as U
 from tests._util import load_golden
-from tests.test_gpu_kernels import Eng, _guarded, _guards_intact, from_nhwc, to_nhwc
+from tests._gpu import Eng, from_nhwc, to_nhwc
+from tests._guards import _guarded, _guards_intact
 from videoseal_amd import metrics as M
 from videoseal_amd import native as N
 from videoseal_amd import pixel_head as PH

@@ -16,7 +16,7 @@ from oracle.inputs import synthetic_frames
 from oracle.weights import make_state_dict, tiny_spec
 from tests import _pixel_head_util as U
 from tests._util import DECISION_MARGIN, assert_decisions, load_golden
-from tests.test_gpu_e2e import cfg_of, make_model
+from tests._model import cfg_of, make_model
 from videoseal_amd import native as N
 from videoseal_amd.model import aggregate_bits, build_model
 
@@ -104,7 +104,7 @@ def test_row_interfaces_refuse_pixelwise_models(pw):
 def test_pooled_chain_with_a_factor_one_stage_and_sigmoid():
     """[4, 2, 1] / `pixelwise: False` / sigmoid_output on 64 channels: two gather stages, the 3 x 3 conv path of a factor-1 stage, the mean over
     the pixels, Linear and sigmoid -- all on HIP kernels -- against the reference's PixelDecoder"""
-    from tests.test_gpu_kernels import Eng, to_nhwc
+    from tests._gpu import Eng, to_nhwc
     from videoseal_amd import pixel_head as PH
     sd = U.head_tensors(64, U.POOLED_CHAIN, 16, seed=17)
     x = U.chain_input(3, 5)[:, :64].contiguous()

@@ -11,99 +11,13 @@ Here every case runs its entry point three times:
 and asserts: every band intact; the outputs of `nan` and `zero` bit-identical (no result may depend on what the scratch held: a reducer that
 read an unwritten slot would turn NaN into the output); both equal to `plain`.  The shapes are the smallest that reach each branch of each
 sizing rule; the comment of a case names the branch (figures checked against the size functions on the host)."""
-import zlib
-
 import pytest
 import torch
 
 pytestmark = pytest.mark.gpu
 
-from tests._guards import _guarded, _guards_intact, scratch, scratch_sentinel  # noqa: E402
-
+from tests._gpu import _contract, _lib as _L, r4  # noqa: E402
 from videoseal_amd import native as N  # noqa: E402
-
-NAN = float("nan")
-ISENT = 0x5A5A5A
-
-
-class Alloc:
-    """hands out the operands of one run; `store` keeps the random master tensors so that the three runs of a case see the same values"""
-
-    def __init__(self, mode, store):
-        self.mode, self.store, self.bufs = mode, store, []
-
-    def inp(self, t):
-        t = t.cuda().contiguous()
-        if self.mode == "plain":
-            return t.clone()
-        fill = NAN if t.is_floating_point() else ISENT
-        buf, view = _guarded(t, fill)
-        self.bufs.append((buf, fill))
-        return view
-
-    def rand(self, key, *shape, scale=1.0, shift=0.0, lanes=None, uniform=False):
-        """random input (fixed by `key`), columns [lanes, last dim) zero: the pad lanes of an NHWC row"""
-        if key not in self.store:
-            g = torch.Generator(device="cuda").manual_seed(zlib.crc32(key.encode()))
-            t = (torch.rand if uniform else torch.randn)(*shape, device="cuda", generator=g) * scale + shift
-            if lanes is not None:
-                t[..., lanes:] = 0
-            self.store[key] = t
-        return self.inp(self.store[key])
-
-    def out(self, *shape, dtype=torch.float32, init=3):
-        t = torch.full(shape, init, device="cuda", dtype=dtype)
-        if self.mode == "plain":
-            return t
-        fill = -7.0 if dtype.is_floating_point else ISENT
-        buf, view = _guarded(t, fill)
-        self.bufs.append((buf, fill))
-        return view
-
-    def scratch(self, nelem, dtype=torch.float32):
-        nelem = int(nelem)
-        assert nelem > 0, "the size function answered 0 for a supported shape"
-        if self.mode == "plain":
-            return torch.zeros(nelem, device="cuda", dtype=dtype)
-        if dtype.is_floating_point:
-            fill = NAN if self.mode == "nan" else 0.0
-        else:
-            fill = 0xFF if self.mode == "nan" else 0          # bytes: four 0xFF are a NaN
-        buf, view = scratch(nelem, dtype, fill)
-        self.bufs.append((buf, scratch_sentinel(dtype)))
-        return view
-
-    def intact(self):
-        return [i for i, (b, f) in enumerate(self.bufs) if not _guards_intact(b, f)]
-
-
-def _bits(t):
-    t = t.contiguous()
-    return t.view({4: torch.int32, 8: torch.int64, 1: torch.uint8, 2: torch.int16}[t.element_size()]) if t.is_floating_point() else t
-
-
-def _contract(case, modes=("plain", "nan", "zero")):
-    """run `case(alloc)` once per mode on the same values; see the module docstring for what is asserted ("zero" only matters with a scratch)"""
-    store, outs = {}, {}
-    for mode in modes:
-        a = Alloc(mode, store)
-        res = case(a)
-        torch.cuda.synchronize()
-        assert not a.intact(), f"{mode}: damaged band around operand(s) {a.intact()} (in order of allocation)"
-        outs[mode] = [r.clone() for r in res]
-    for i, (p, n, z) in enumerate(zip(outs["plain"], outs["nan"], outs.get("zero", outs["nan"]))):
-        assert torch.equal(_bits(n), _bits(z)), f"output {i} depends on what the scratch held"
-        assert torch.equal(_bits(n), _bits(p)), f"output {i} differs from the unguarded call"
-        assert not torch.isnan(n.double()).any(), f"output {i} holds NaN"
-
-
-def _L():
-    return N.lib(), N.stream()
-
-
-def r4(c):
-    return (c + 3) // 4 * 4
-
 
 # ====================================================================================================== vs_gemm_wgrad_partial_floats
 # wgrad_splits: matrix cores (N >= 64 and K >= 64): 512 / (tilesN128 * tilesK128); else thin: ceil(1024 / (tilesN64 * tilesK64)); both capped by
@@ -532,7 +446,7 @@ def test_pixel_bce(B, K, HW):
 @pytest.fixture(scope="module")
 def cmodels():
     from oracle.weights import make_state_dict, tiny_spec
-    from tests.test_gpu_e2e import cfg_of
+    from tests._model import cfg_of
     from videoseal_amd.capi import CModel
     out = {}
     for which, spec, seed in (("tiny", tiny_spec(), 3),

@@ -13,7 +13,7 @@ from videoseal.models import Videoseal  # noqa: E402
 from oracle import videoseal_ref as R  # noqa: E402
 from oracle.inputs import synthetic_frames  # noqa: E402
 from oracle.weights import make_state_dict, tiny_spec  # noqa: E402
-from tests.test_gpu_e2e import make_model  # noqa: E402
+from tests._model import make_model  # noqa: E402
 
 
 def embed_video_clip(model: Videoseal, clip: np.ndarray, msgs: torch.Tensor) -> np.ndarray:

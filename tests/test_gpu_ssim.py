@@ -24,8 +24,8 @@ import torch.nn.functional as F
 
 from oracle.weights import make_state_dict, tiny_spec
 from tests._util import load_golden, projection_vector
-from tests.test_gpu_kernels import _guarded, _guards_intact
-from tests.test_oracle_ssim import check_inputs, make_inputs
+from tests._cases import check_inputs, make_inputs
+from tests._guards import _guarded, _guards_intact
 from videoseal_amd import autograd as AG
 from videoseal_amd import metrics as M
 from videoseal_amd import native as N
@@ -229,7 +229,7 @@ def test_metrics_take_the_hip_path():
 
 @pytest.mark.parametrize("string", ["ssim", "msssim", "mse+0.1_ssim"])
 def test_generator_step_with_the_new_terms(string):
-    from tests.test_gpu_e2e import make_model
+    from tests._model import make_model
     from oracle.inputs import synthetic_frames, synthetic_msgs
     from videoseal_amd import augmentation as A
     from videoseal_amd.training import GeneratorStep

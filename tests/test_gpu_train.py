@@ -25,11 +25,10 @@ from oracle import loss as OL  # noqa: E402
 from oracle import videoseal_ref as R  # noqa: E402
 from oracle.inputs import synthetic_frames, synthetic_msgs  # noqa: E402
 from oracle.weights import make_state_dict, spec_from_card, tiny_spec  # noqa: E402
+from tests._cases import CARDS  # noqa: E402
 from tests._util import load_golden, projection_vector  # noqa: E402
-from tests.test_gpu_bwd import _rand  # noqa: E402
-from tests.test_gpu_bwd_unet import _MaskedF, hip_relu_masks  # noqa: E402
-from tests.test_gpu_e2e import make_model  # noqa: E402
-from tests.test_oracle_golden import CARDS  # noqa: E402
+from tests._gpu import _MaskedF, _rand, hip_relu_masks  # noqa: E402
+from tests._model import _setup, make_model  # noqa: E402
 
 from videoseal_amd import augmentation as G  # noqa: E402
 from videoseal_amd import autograd as AG  # noqa: E402
@@ -297,18 +296,6 @@ def test_detector_input_gradient_matches_oracle_autograd(arch):
 
 
 # ------------------------------------------------------------------------------------------------ train.py's inner loop against the reference
-def _setup(spec, sd, meta):
-    model = make_model(spec, sd)
-    model.augmenter = G.Augmenter(masks={"kind": "none"}, augs=meta["augs"], augs_params=meta["augs_params"], num_augs=meta["num_augs"])
-    model.train()
-    if meta["is_video"]:
-        model.step_size = meta["step"]
-    imgs = synthetic_frames(meta["n"], meta["h"], meta["w"], seed=meta["seed"], kind=meta["kind"])
-    msgs = synthetic_msgs(1 if meta["is_video"] else meta["n"], spec.nbits, seed=meta["seed"])
-    masks = torch.ones(meta["n"], 1, meta["h"], meta["w"])
-    return model, imgs, msgs, masks
-
-
 def _summaries(named_grads):
     rows = {}
     for k, g in named_grads:

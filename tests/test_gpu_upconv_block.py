@@ -14,7 +14,7 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from tests._guards import _guarded, _guards_intact  # noqa: E402
-from tests.test_gpu_kernels import Eng, dv, to_nhwc  # noqa: E402
+from tests._gpu import Eng, dv, to_nhwc  # noqa: E402
 from videoseal_amd import native as N  # noqa: E402
 from videoseal_amd.engine import ConvW, pack_conv  # noqa: E402
 

@@ -14,7 +14,7 @@ pytestmark = pytest.mark.gpu
 
 from oracle.inputs import synthetic_frames, synthetic_msgs  # noqa: E402
 from oracle.weights import make_state_dict, tiny_spec  # noqa: E402
-from tests.test_gpu_e2e import make_model  # noqa: E402
+from tests._model import make_model  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -202,7 +202,7 @@ def test_ddp_wrapped_training_step_over_rccl_world1(rccl_world1):
     gradients must equal the un-wrapped step's; the adaptive-weight probes (torch.autograd.grad with retain_graph) must not trip the reducer."""
     from oracle import loss as OL
     from tests._util import load_golden
-    from tests.test_gpu_train import _setup
+    from tests._model import _setup
     from videoseal_amd.dist import convert_sync_batchnorm
     spec = tiny_spec()
     sd = make_state_dict(spec, seed=3)

@@ -1,4 +1,7 @@
 """The red-zone helpers of tests/_guards.py on CPU tensors: a test that relies on a sentinel is only as good as the sentinel check."""
+import pathlib
+import re
+
 import pytest
 import torch
 
@@ -71,3 +74,11 @@ def test_scratch_detects_a_nan_written_outside_a_nan_filled_interior():
     assert _guards_intact(buf, scratch_sentinel(torch.float32))
     buf[GUARD + 6] = NAN                                   # what a reducer's stray NaN store would leave
     assert not _guards_intact(buf, scratch_sentinel(torch.float32))
+
+
+def test_no_module_under_tests_imports_a_test_module():
+    """helpers live in the `_*.py` modules: a test module is never a library, so an import error in one cannot take another down"""
+    here = pathlib.Path(__file__).parent
+    pat = re.compile(r"from tests\.test_|from tests import +test_|import tests\.test_")
+    bad = [(p.name, i + 1) for p in sorted([*here.glob("*.py"), *here.glob("tools/*.py")]) for i, line in enumerate(p.read_text().splitlines()) if pat.search(line)]
+    assert not bad, bad

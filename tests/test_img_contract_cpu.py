@@ -7,6 +7,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from tests import _envelope as E
 from tests import _img_ref as R
 
 F32, F64 = torch.float32, torch.float64
@@ -16,11 +17,11 @@ def _teeth(tag, ref64_by_kind, yard_by_kind, bad_by_kind):
     """prints every figure; True when the defect is outside the envelope on at least one frame kind; the yardstick is inside with ratio 1 by construction"""
     hit = []
     for kind in ref64_by_kind:
-        yard = R.frame_err(yard_by_kind[kind], ref64_by_kind[kind])
-        bad = R.frame_err(bad_by_kind[kind], ref64_by_kind[kind])
+        yard = E.frame_err(yard_by_kind[kind], ref64_by_kind[kind])
+        bad = E.frame_err(bad_by_kind[kind], ref64_by_kind[kind])
         print(f"TEETH {tag:<60s} {kind:<8s} yardstick {yard:.3e}  defect {bad:.3e}")
-        assert not R.outside(yard, yard)
-        if R.outside(bad, yard):
+        assert not E.outside(yard, yard)
+        if E.outside(bad, yard):
             hit.append(kind)
     return hit
 
@@ -38,7 +39,7 @@ def test_resize_restatement_is_atens_formula_and_the_yardstick_is_small(case):
         at = F.interpolate(x.double(), size=(oh, ow), mode="bilinear", align_corners=False, antialias=bool(aa))
         assert (r64 - at).abs().max() < 1e-13, (tag, kind)
         # fp32 coordinates times the local gradient: 2^-24 x (coordinate <= 165) x (gradient <= 1 per pixel) = 1e-5 at most
-        assert R.frame_err(r32, r64) < 2e-5, (tag, kind)
+        assert E.frame_err(r32, r64) < 2e-5, (tag, kind)
 
 
 def test_a_resampler_returns_a_constant_frame():
@@ -83,14 +84,14 @@ def test_jnd_conditions_and_defects(H, W):
     for kind, x in R.jnd_frames(H, W).items():
         own, other, amb, y32 = R.jnd_ref(x)
         share = float(amb.float().mean())
-        yard = R.cand_err(y32, own, other, amb)
+        yard = E.cand_err(y32, own, other, amb)
         print(f"TEETH jnd {H}x{W} {kind:<8s} ambiguous share {share:.4f}  yardstick {yard:.3e}")
         assert share <= R.JND_SHARE, (kind, share)                                   # condition on the float64 reference alone
         assert yard < 2e-6                                                           # no fp32 branch flips outside the band
         for name, kw in (("thr", dict(thr=128.0)), ("gy", dict(gy_sum=True))):
-            bad = R.cand_err(R.jnd(x, F32, **kw)[0], own, other, amb)
+            bad = E.cand_err(R.jnd(x, F32, **kw)[0], own, other, amb)
             print(f"TEETH jnd {H}x{W} {kind:<8s} {name} defect {bad:.3e}")
-            if R.outside(bad, yard):
+            if E.outside(bad, yard):
                 hit[name].append(kind)
     if min(H, W) >= 32:                      # (on 5 x 7 no window of the jump frame need fall between 127 and 128)
         assert "jump" in hit["thr"], hit
@@ -125,19 +126,19 @@ def test_tail_conditions_and_defects(case):
     for kind, imgs in R.tail_frames(Fn, H, W).items():
         own, other, amb, y32 = R.tail_ref(imgs, delta, hm, cfg)
         share = float(amb.float().mean())
-        yard = R.cand_err(y32[0], own[0], other[0], amb)
+        yard = E.cand_err(y32[0], own[0], other[0], amb)
         print(f"TEETH tail {tag:<34s} {kind:<6s} ambiguous share {share:.4f}  yardstick {yard:.3e}")
         assert share <= R.JND_SHARE and yard < 1e-5
         if cfg["mode"] == 2:
             bad = R.tail_ref(imgs, delta, hm, cfg, tail_weight_defect=True)[3]
-            e = R.cand_err(bad[0], own[0], other[0], amb)
+            e = E.cand_err(bad[0], own[0], other[0], amb)
             print(f"TEETH tail {tag:<34s} {kind:<6s} key weight j/step {e:.3e}")
-            assert R.outside(e, yard)
+            assert E.outside(e, yard)
         if cfg["sw"] > 1:
             bad = R.tail_ref(imgs, delta, hm, cfg, no_clamp=True)[3]
-            e = R.cand_err(bad[0], own[0], other[0], amb)
+            e = E.cand_err(bad[0], own[0], other[0], amb)
             print(f"TEETH tail {tag:<34s} {kind:<6s} clamp skipped {e:.3e}")
-            assert R.outside(e, yard)
+            assert E.outside(e, yard)
             assert float(bad[0].min()) < 0 and float(bad[0].max()) > 1          # both clamps act
 
 
@@ -148,11 +149,11 @@ def test_colour_defects_fall_outside_the_envelope():
 
     def err(op, f, inp, **kw):
         r64 = R.color_op(inp, op, f, F64)
-        yard = R.frame_err(R.color_op(inp, op, f, F32), r64)
-        bad = R.frame_err(R.color_op(inp, op, f, F32, **kw), r64)
+        yard = E.frame_err(R.color_op(inp, op, f, F32), r64)
+        bad = E.frame_err(R.color_op(inp, op, f, F32, **kw), r64)
         print(f"TEETH colour op {op} factor {f} {kw}: yardstick {yard:.3e}  defect {bad:.3e}")
         assert yard < 4e-6
-        return R.outside(bad, yard)
+        return E.outside(bad, yard)
     for f in (-0.5, -0.4, -0.1):
         assert err(R.OP_HUE, f, x, c_fmod=True)
     for op in (R.OP_SATURATION, R.OP_CONTRAST):

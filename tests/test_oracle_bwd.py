@@ -13,7 +13,7 @@ import os
 
 from oracle.weights import make_state_dict, spec_from_card, tiny_spec
 from tests._util import load_golden, projection_vector
-from tests.test_oracle_golden import CARDS
+from tests._cases import CARDS
 
 CASES = ["tiny_bwd_img_recipe", "tiny_bwd_img_balanced", "tiny_bwd_vid_recipe", "vs10_bwd_img_recipe"]
 

@@ -12,13 +12,8 @@ from oracle import augment as A
 from oracle import videoseal_ref as R
 from oracle.inputs import synthetic_frames, synthetic_msgs
 from oracle.weights import make_state_dict, spec_from_card, tiny_spec
+from tests._cases import CARDS, FWD_FULL, FWD_TINY, PIXELSEAL, _check_case, bn_vectors
 from tests._util import GOLDEN, check_sub, load_golden
-from tests.test_oracle_golden import CARDS, _check_case
-
-FWD_TINY = ["tiny_fwd_img_train", "tiny_fwd_img_evalbn", "tiny_fwd_img_si", "tiny_fwd_vid_train", "tiny_fwd_vid_lowres", "tiny_fwd_vid_alt"]
-FWD_FULL = ["vs10_fwd_img_train"]
-PIXELSEAL = ["pixelseal_img", "pixelseal_vid"]
-
 
 def oracle_forward(spec, sd, meta):
     imgs = synthetic_frames(meta["n"], meta["h"], meta["w"], seed=meta["seed"], kind=meta["kind"])
@@ -34,15 +29,6 @@ def oracle_forward(spec, sd, meta):
         else:
             out = R.forward_image(sd, spec, imgs, masks, msgs, aug, bn=bn, scaling_i=meta["scaling_i"])
     return out, bn
-
-
-def bn_vectors(sd, bn):
-    merged = dict(sd)
-    merged.update(bn or {})
-    rm = torch.cat([v.flatten() for k, v in merged.items() if k.endswith("running_mean")])
-    rv = torch.cat([v.flatten() for k, v in merged.items() if k.endswith("running_var")])
-    nbt = torch.stack([v for k, v in merged.items() if k.endswith("num_batches_tracked")])
-    return rm, rv, nbt
 
 
 def _check_fwd(spec, sd, name):

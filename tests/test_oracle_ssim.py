@@ -4,22 +4,10 @@ import numpy as np
 import pytest
 import torch
 
-from oracle.inputs import synthetic_frames
+from tests._cases import check_inputs, make_inputs
 from tests._util import load_golden
 from videoseal_amd import autograd as AG
 from videoseal_amd import metrics as M
-
-
-def make_inputs(info):
-    x = synthetic_frames(info["F"], info["H"], info["W"], seed=info["seed"])
-    y = (x + info["amp"] * torch.randn(x.shape, generator=torch.Generator().manual_seed(info["seed"]))).clamp(0, 1)
-    return x, y
-
-
-def check_inputs(g, cname, x, y):
-    """a generator mismatch must read as such, not as a kernel error"""
-    got = np.array([float(x.double().sum()), float(y.double().sum()), float((x.double() * y.double()).sum())])
-    assert np.allclose(got, g[f"{cname}.checksum"], rtol=1e-12, atol=0), f"{cname}: the seeded inputs differ from the fixture's ({got} vs {g[cname + '.checksum']})"
 
 
 @pytest.fixture(scope="module")

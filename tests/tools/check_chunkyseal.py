@@ -7,7 +7,7 @@ import torch
 from oracle import videoseal_ref as R
 from oracle.inputs import synthetic_frames
 from oracle.weights import make_state_dict, spec_from_card
-from tests.test_gpu_e2e import make_model
+from tests._model import make_model
 
 t0 = time.time()
 spec = spec_from_card(os.path.join(os.path.dirname(__file__), "..", "..", "videoseal_amd", "cards", "chunkyseal.yaml"))

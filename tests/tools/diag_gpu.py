@@ -11,7 +11,7 @@ sys.path.insert(0, ROOT)
 from oracle import videoseal_ref as R  # noqa: E402
 from oracle.inputs import synthetic_frames, synthetic_msgs  # noqa: E402
 from oracle.weights import make_state_dict, spec_from_card  # noqa: E402
-from tests.test_gpu_e2e import make_model  # noqa: E402
+from tests._model import make_model  # noqa: E402
 
 spec = spec_from_card(os.path.join(ROOT, "videoseal_amd", "cards", "videoseal_1.0.yaml"))
 sd = make_state_dict(spec, seed=0)

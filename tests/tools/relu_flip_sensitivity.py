@@ -7,7 +7,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspa
 from oracle import videoseal_ref as R
 from oracle.inputs import synthetic_frames, synthetic_msgs
 from oracle.weights import make_state_dict, spec_from_card
-from tests.test_oracle_golden import CARDS
+from tests._cases import CARDS
 torch.set_num_threads(8)
 spec = spec_from_card(os.path.join(CARDS, "videoseal_1.0.yaml")); sd = make_state_dict(spec, seed=0); n=2; seed=52
 S = spec.img_size

@@ -231,7 +231,7 @@ class HipEngine:
     arith = 2          # arithmetic of the split back-end (vs_conv_desc_t::arith); set per instance from VIDEOSEAL_CONV
     planes_chain = True
     planes_gemm = True
-    # (class-level defaults: test harnesses build engines without a model, tests/test_gpu_kernels.py::Eng)
+    # (class-level defaults: test harnesses build engines without a model, tests/_gpu.py::Eng)
     _tr_pass = 0
     _calib = None
     thin_fused = True
