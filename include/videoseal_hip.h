@@ -145,6 +145,32 @@ typedef struct vs_conv_desc {
 #define VS_CONV_PRE 0x80          /* wave-specialised 3x3 kernel (tile codes 15 / 16) only: a_scale is a border-class table [frames][9][N]     */
                                   /*   (frame stride a_scale_ld, 0 = shared): v = act(acc + table[frame][class(y,x)][n] + bias), see vs_msg_pre */
 int vs_conv_gemm(const vs_conv_desc_t* d, void* stream);
+/* The shipped launch rules of a dense layer, host-only (no GPU call, no environment, no state): what the Python engine and the model-level entry
+ * points launch `d` with.  K slices fix the fp32 summation order, so a caller that wants the shipped numerics asks here.  split_k is decided only where
+ * the caller left d->split_k == 0 and d->tile_hint == 0 (sumsq_part forces 1); a given split_k >= 1 or tile hint is kept and ws_slices still computed.
+ * grn_hw / grn_c4: rows per frame and channels of the GRN partials a finish in front of this launch would read (grn_hw == 0: none). */
+typedef struct vs_conv_plan {
+  int32_t routes;     /* VS_ROUTE_* bits: the kernels whose preconditions the shape meets */
+  int32_t split_k;    /* K slices of this launch (>= 1) */
+  int32_t tile_hint;  /* hint to launch with: the caller's own if it gave one, the static tile of a sliced launch if split_k > 1, else 0 */
+  int32_t ws_slices;  /* slices of [M][rup(N, 4)] floats the caller provides in splitk_ws (0 if split_k == 1) */
+  int32_t grn_fold;   /* 1: the GRN finish may ride in this launch (caller sets grn_part / grn_gamma / grn_nchunk = grn_hw / 32), */
+} vs_conv_plan_t;     /* 0: the caller issues vs_grn_scale_from_partials in front of it */
+/* wave-specialised 1x1 GEMM (tile codes 17 / 18 / 26) | 3x3 patch kernel (10 .. 12) | wave-specialised 3x3 patch kernel (15 / 16 / 19 / 21) | thin 3x3 (20) */
+enum { VS_ROUTE_GEMM_PC = 1, VS_ROUTE_PATCH = 2, VS_ROUTE_PATCH_PC = 4, VS_ROUTE_SMALL = 8 };
+int vs_conv_plan(const vs_conv_desc_t* d, int grn_hw, int grn_c4, vs_conv_plan_t* out);
+/* The same for the two GEMMs of one ConvNeXt stage: rows = frames * HW, C channels, h_ld / pw1_cinp = K of pwconv2 / pwconv1 as packed.
+ * flags == 0: the shipped defaults; the VS_CNX_* bits are development switches (NO_SPLIT: the caller runs the fp32 MFMA path). */
+typedef struct vs_cnx_stage_plan {
+  int32_t pl1, pl2;        /* pwconv1 / pwconv2 on operand planes (in_pl) */
+  int32_t sk2;             /* K slices of pwconv2 on planes */
+  int32_t tile1, tile2;    /* tile hints of the planes launches (tile code 24 or 27) */
+  int32_t pw2_narrow;      /* pwconv2 on 128x96 tiles with the whole K (tile code 26, split_k = 1) */
+} vs_cnx_stage_plan_t;
+enum { VS_CNX_NO_PLANES_GEMM = 1, VS_CNX_NO_PW2_SMALL_PC = 2, VS_CNX_NO_PW2_NARROW = 4, VS_CNX_GEMM_BIG = 8, VS_CNX_NO_SPLIT = 16 };
+int vs_cnx_stage_plan(int64_t rows, int HW, int C, int h_ld, int pw1_cinp, int arith, int flags, vs_cnx_stage_plan_t* out);
+int vs_sizeof_conv_plan(void);              /* sizeof(vs_conv_plan_t) */
+int vs_sizeof_cnx_stage_plan(void);         /* sizeof(vs_cnx_stage_plan_t) */
 /* fp32 NHWC rows [rows][ld] -> the operand planes of tile codes 22 / 23: [2][C/16][rows][16] f16, hi = f16(x * a_mul), lo = f16(x * a_mul - hi).
  * C % 16 == 0; `planes` holds 2 * rows * C f16 values. */
 int vs_to_planes(const float* x, int64_t rows, int C, int64_t ld, float a_mul, void* planes, void* stream);

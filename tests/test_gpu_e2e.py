@@ -564,6 +564,33 @@ def test_model_level_c_api_vs10(vs10):
     assert (cm.detect(got) - model.detect(py, is_video=True)["preds"]).abs().max().item() < 1e-4
 
 
+@pytest.mark.parametrize("which", ["tiny", "tinyc", "vs10"])
+def test_model_level_c_api_equals_the_engine_bit_for_bit_without_the_tuner(which, monkeypatch):
+    """With the tuner off both hosts take every K-slice / tile / GRN-fold decision of a dense layer from vs_conv_plan and
+    vs_cnx_stage_plan (csrc/conv_plan.hip): embed and detect are torch.equal (measured equal on these cases before the rules moved into the
+    library as well).  vs10 at 4 frames, step 2, is the case in which both K-slice rules fire (stage-3 GEMMs, bottleneck convs of two key
+    frames).  It runs with VIDEOSEAL_PLANES_SPLITK=0: the K-sliced form of the bottleneck's planes chain (< 200 tiles, engine._planes_split)
+    exists in the Python engine only -- the C host keeps the wave-specialised 3x3 kernel there, measured 6e-8 apart --, and with it off both
+    hosts run these convs by the rule under test."""
+    from videoseal_amd.capi import CModel
+    monkeypatch.setenv("VIDEOSEAL_AUTOTUNE", "0")
+    monkeypatch.setenv("VIDEOSEAL_PLANES_SPLITK", "0")
+    spec, seed, (n, h, w), chunk = {"tiny": (tiny_spec(), 3, (6, 96, 80), 3),
+                                    "tinyc": (tiny_spec(yuv=False, in_ch=3, out_ch=3, dims=[18, 36, 54, 90], stem_stride=2, hidden=32, nbits=16), 4, (6, 96, 80), 3),
+                                    "vs10": (spec_from_card(os.path.join(CARDS, "videoseal_1.0.yaml")), 0, (4, 320, 288), 8)}[which]
+    sd = make_state_dict(spec, seed=seed)
+    model, cm = make_model(spec, sd), CModel(cfg_of(spec), sd)
+    imgs = synthetic_frames(n, h, w, seed=41).cuda()
+    msgs = synthetic_msgs(1, spec.nbits, seed=41)
+    model.chunk_size, model.step_size, model.video_mode = chunk, 2, "repeat"
+    for lowres in (False, True):
+        py = model.embed(imgs, msgs, is_video=True, lowres_attenuation=lowres)["imgs_w"]
+        assert torch.equal(cm.embed(imgs, msgs, step=2, video_mode=0, lowres_attenuation=lowres), py), (which, lowres)
+    assert torch.equal(cm.detect(py), model.detect(py, is_video=True)["preds"])
+    m_img = synthetic_msgs(n, spec.nbits, seed=34)
+    assert torch.equal(cm.embed(imgs, m_img, step=1), model.embed(imgs, m_img, is_video=False)["imgs_w"])
+
+
 def test_streaming_overlap_equals_sequential(tiny):
     """videoseal_amd/streaming.py: detect(chunk i) overlapped with embed(chunk i+1) on two HIP streams returns exactly what the
     sequential 16-frame calls return (fp32 and uint8 clips), chunk after chunk."""

@@ -29,6 +29,7 @@
 #include <algorithm>
 
 #include "conv_common.h"
+#include "conv_plan.h"
 
 namespace {
 
@@ -476,7 +477,7 @@ static int gemm_planes(const vs_conv_desc_t& d, int tile, hipStream_t st) {
 extern "C" int vs_conv_gemm(const vs_conv_desc_t* dp, void* stream) {
   VS_REQUIRE(dp);
   {
-    const int t = (dp->tile_hint & 0xf) + ((dp->tile_hint & VS_CONV_TILE_HI) ? 16 : 0);
+    const int t = vs_tile_code(dp->tile_hint);
     if (t == 22 || t == 23) return conv_planes(*dp, t, (hipStream_t)stream);
     if (t == 24 || t == 25 || t == 27) return gemm_planes(*dp, t, (hipStream_t)stream);
   }
@@ -502,15 +503,14 @@ extern "C" int vs_conv_gemm(const vs_conv_desc_t* dp, void* stream) {
       (d.a_scale && !pre_add && !fits_u32((int64_t)d.B * d.a_scale_ld * 4)))
     return VS_ERR_UNSUPPORTED;   // > 4 GiB operand: the caller chunks the batch
   hipStream_t st = (hipStream_t)stream;
-  int tile = (d.tile_hint & 0xf) + ((d.tile_hint & VS_CONV_TILE_HI) ? 16 : 0);
+  int tile = vs_tile_code(d.tile_hint);
   // ABI v3: the GRN finish folded into the GEMM exists in the wave-specialised 1x1 kernel only; a_scale is not written by anybody in that
   // mode, so every other route must refuse instead of reading it
-  if (d.grn_part && !(tile == 17 || tile == 18 || tile == 26)) return VS_ERR_UNSUPPORTED;
+  if (d.grn_part && !vs_tile_is_gemm_pc(tile)) return VS_ERR_UNSUPPORTED;
   if (d.sumsq_hw && !(tile == 24 || tile == 25 || tile == 27)) return VS_ERR_UNSUPPORTED;                      // (the [M/32][2][N] partials exist in gemm_pl.hip only)
   const bool can_split0 = d.wt_split && (!d.in2 || d.wt2_split) && ((uintptr_t)d.wt_split & 15) == 0;
   // 3x3 / stride 1 / "same" convs on tile-aligned frames go to the patch kernel (input patch staged once per channel chunk)
-  const bool patch_ok = can_split0 && d.KH == 3 && d.KW == 3 && d.SH == 1 && d.SW == 1 && d.PH == 1 && d.PW == 1 && d.Ho == d.H &&
-                        d.Wo == d.W && (!d.a_scale || pre_add) && !(d.tile_hint & VS_CONV_FORCE_F32);
+  const bool patch_ok = can_split0 && vs_conv_same3x3(d) && (!d.a_scale || pre_add) && !(d.tile_hint & VS_CONV_FORCE_F32);
   if (pre_add) VS_REQUIRE(patch_ok && (tile == 15 || tile == 16));
   if (tile >= 10 && tile <= 12) {
     VS_REQUIRE(patch_ok);
@@ -525,18 +525,15 @@ extern "C" int vs_conv_gemm(const vs_conv_desc_t* dp, void* stream) {
     return vs_conv3x3_patch_pc_dispatch(d, tile, st);
   }
   // thin full-resolution layers (16 input channels, <= 32 outputs): persistent kernel with the weights in registers
-  const bool small_ok = patch_ok && d.CinP == 16 && d.N <= 32 && d.n_store <= 32 && (!d.in2 || d.Cin2P == 16) && d.split_k <= 1 &&
-                        !d.sumsq_part;
+  const bool small_ok = patch_ok && vs_conv_small_shape(d);
   if (tile == 20) {
     VS_REQUIRE(small_ok);
     return vs_conv3x3_small_dispatch(d, st);
   }
-  if (tile == 17 || tile == 18 || tile == 26) {   // wave-specialised 1x1 GEMM: dense rows, whole 32-wide K pairs, no second phase
+  if (vs_tile_is_gemm_pc(tile)) {   // wave-specialised 1x1 GEMM: dense rows, whole 32-wide K pairs, no second phase
     if (tile == 26) VS_REQUIRE(d.arith == 2);     // 128 x 96 tiles: 2 x f16 arithmetic only
     VS_REQUIRE(can_split0 && d.wt_blk && ((uintptr_t)d.wt_blk & 15) == 0 && !(d.tile_hint & VS_CONV_FORCE_F32));
-    VS_REQUIRE(d.KH == 1 && d.KW == 1 && d.SH == 1 && d.SW == 1 && d.PH == 0 && d.PW == 0 && d.Ho == d.H && d.Wo == d.W && !d.in2);
-    VS_REQUIRE(d.Cin % 32 == 0 && d.CinP == d.Cin && d.in_sy == (int64_t)d.W * d.in_sx && d.in_sb == (int64_t)d.H * d.in_sy);
-    if (d.a_scale) VS_REQUIRE(d.H * d.W >= 128 || d.H * d.W == 64);   // a 128-row tile touches at most two frames
+    VS_REQUIRE(vs_conv_gemm_pc_shape(d));
     if (d.sumsq_part) VS_REQUIRE(d.split_k <= 1 && !d.res);
     if (d.split_k > 1) VS_REQUIRE(d.splitk_ws && d.splitk_ld >= d.N && d.split_k <= d.CinP / 32);
     return vs_gemm1x1_pc_dispatch(d, tile, st);
@@ -544,7 +541,7 @@ extern "C" int vs_conv_gemm(const vs_conv_desc_t* dp, void* stream) {
   VS_REQUIRE(d.split_k <= 1);
   if (d.sumsq_part) VS_REQUIRE(d.KH == 1 && d.KW == 1 && !d.in2 && !d.res && !patch_ok);
   if (tile == 0 && small_ok && !d.in2) return vs_conv3x3_small_dispatch(d, st);   // (with the fused 1x1 the patch kernel is as fast)
-  if (tile == 0 && patch_ok && d.W % 16 == 0 && d.H % 8 == 0) {
+  if (tile == 0 && patch_ok && vs_conv_patch_frames(d)) {
     const bool blk_ok = d.wt_blk && (!d.in2 || d.wt2_blk) && ((uintptr_t)d.wt_blk & 15) == 0;
     if (blk_ok && pc_vec_ok(d) && d.N >= 128) return vs_conv3x3_patch_pc_dispatch(d, d.N % 192 == 0 ? 16 : 15, st);   // wave-specialised for wide layers
     if (blk_ok && pc_vec_ok(d) && d.N > 32 && d.N <= 64 && d.H % 16 == 0 && d.CinP >= 64) return vs_conv3x3_patch_pc_dispatch(d, 21, st);   // 256 px x 64 ch
@@ -553,11 +550,9 @@ extern "C" int vs_conv_gemm(const vs_conv_desc_t* dp, void* stream) {
   if (tile == 0) {
     // static choice (no tuner: model-level C API, hipGraph capture, VIDEOSEAL_AUTOTUNE=0), following what the tuner measures on
     // the benchmark shapes: deep-K 1x1 GEMMs on the wave-specialised kernel, shallow-K ones on 128x128 generic tiles
-    const bool gemm_ok = can_split0 && d.wt_blk && ((uintptr_t)d.wt_blk & 15) == 0 && !(d.tile_hint & VS_CONV_FORCE_F32) && d.KH == 1 &&
-                         d.KW == 1 && d.SH == 1 && d.SW == 1 && d.PH == 0 && d.PW == 0 && d.Ho == d.H && d.Wo == d.W && !d.in2 &&
-                         d.Cin % 32 == 0 && d.CinP == d.Cin && d.in_sy == (int64_t)d.W * d.in_sx && d.in_sb == (int64_t)d.H * d.in_sy &&
-                         (!d.a_scale || d.H * d.W >= 128 || d.H * d.W == 64) && !(d.sumsq_part && d.res) &&
-                         (!d.a_scale || (int64_t)((d.CinP / 32 + std::max(1, d.split_k) - 1) / std::max(1, d.split_k)) * 32 <= 3072);   // GRN rows of a K slice in LDS
+    const bool gemm_ok = can_split0 && d.wt_blk && ((uintptr_t)d.wt_blk & 15) == 0 && !(d.tile_hint & VS_CONV_FORCE_F32) &&
+                         vs_conv_gemm_pc_shape(d) && !(d.sumsq_part && d.res) &&
+                         (!d.a_scale || (int64_t)((d.CinP / 32 + std::max(1, d.split_k) - 1) / std::max(1, d.split_k)) * 32 <= VS_GRN_SLICE_K);
     if (gemm_ok && d.CinP >= 384 && d.N > 128 && !(d.act == VS_ACT_TANH && d.split_k <= 1)) return vs_gemm1x1_pc_dispatch(d, 18, st);      // (tile 18 has no tanh epilogue)
     if (d.KH == 1 && d.KW == 1 && d.CinP < 384 && d.N >= 256) tile = 1;
     else tile = d.N <= 32 ? 3 : (d.N <= 64 ? 2 : (d.N <= 96 ? 5 : ((d.N % 192 == 0 || (d.N > 128 && d.N <= 192)) ? 4 : 1)));

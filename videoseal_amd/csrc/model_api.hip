@@ -319,12 +319,12 @@ struct Runner {
   bool live() const { return ws && rc == VS_OK; }
   void chk(int code) { if (rc == VS_OK && code != VS_OK) rc = code; }
 
-  // engine.py::conv with tile_hint = 0 (the library's static heuristics) and the shape-only K-split rules
+  // engine.py::conv without the tuner: K slices, the sliced launch's tile and the GRN-finish fold as vs_conv_plan says
   void conv(const Act& x, const CW& w, const Act& out, int stride = 1, int pad = 0, int pad_mode = VS_PAD_ZERO, int act_ = VS_ACT_NONE,
             int out_coff = 0, int n_store = -1, const Act* res = nullptr, const Act* in2 = nullptr, const CW* w2 = nullptr,
             const float* a_scale = nullptr, int64_t a_scale_ld = 0, const float* a_shift = nullptr, const int* geom = nullptr,
             float* sumsq = nullptr, int cin_first = 0, bool pre_table = false, float a_mul_override = 0.f,
-            const float* grn_part = nullptr, const float* grn_gamma = nullptr, int grn_hw = 0, int grn_c4 = 0) {
+            const float* grn_part = nullptr, const float* grn_gamma = nullptr, int grn_hw = 0, int grn_c4 = 0, int tile_hint = 0) {
     vs_conv_desc_t d;
     std::memset(&d, 0, sizeof(d));
     int sh = stride, sw = stride, ph = pad, pw = pad, H = x.H, W = x.W, cin = x.ld;
@@ -342,57 +342,25 @@ struct Runner {
     d.n_store = n_store >= 0 ? n_store : (out_coff == 0 ? out.ld - out_coff : w.N);
     if (res) { d.res = res->p; d.res_ld = res->ld; }
     if (in2) { d.in2 = in2->p; d.in2_ld = in2->ld; d.Cin2 = in2->ld; d.Cin2P = w2->CinP; d.wt2 = w2->wt; d.bias2 = w2->bias; }
-    d.out = out.p; d.out_ld = out.ld; d.out_coff = out_coff; d.tile_hint = 0;
+    d.out = out.p; d.out_ld = out.ld; d.out_coff = out_coff; d.tile_hint = tile_hint;
     d.wt_split = w.split; d.wt_blk = w.blk;
     const float am = a_mul_override > 0.f ? a_mul_override : ((a_scale && !pre_table) ? A_MUL_GRN : A_MUL);
     d.arith = m->arith; d.a_mul = am; d.acc_mul = 1.f / (am * w.w_mul);
     if (in2) { d.wt2_split = w2->split; d.wt2_blk = w2->blk; d.acc_mul2 = 1.f / (am * w2->w_mul); }
-    int split_k = 1;
-    const bool dense_rows = d.in_sy == (int64_t)d.W * d.in_sx && d.in_sb == (int64_t)d.H * d.in_sy;
-    const bool gemm_pc = d.KH == 1 && d.KW == 1 && sh == 1 && sw == 1 && ph == 0 && pw == 0 && !in2 && d.Ho == d.H && d.Wo == d.W &&
-                         d.Cin % 32 == 0 && d.CinP == d.Cin && dense_rows && (!a_scale || d.H * d.W >= 128 || d.H * d.W == 64);
-    const bool patch_pc = d.KH == 3 && d.KW == 3 && sh == 1 && sw == 1 && ph == 1 && pw == 1 && d.Ho == d.H && d.Wo == d.W && !a_scale &&
-                          d.W % 16 == 0 && d.H % 8 == 0;
-    if (pre_table) {                            // border-class table added before bias + activation (engine.py::resblock_msg0)
-      d.tile_hint = (d.N % 192 == 0 ? (VS_CONV_TILE_HI | 0) : 15) | VS_CONV_PRE;
-    } else if (sumsq) {
-      d.sumsq_part = sumsq;
-    } else if (gemm_pc && a_scale && m->arith == 2 && d.N % 96 == 0 && d.H * d.W >= 128 && d.CinP <= 3072 &&      // (K <= 3072: the tile's GRN rows live in LDS)
-               (((int64_t)d.B * d.H * d.W + 127) / 128) * ((d.N + 127) / 128) < 256 && (((int64_t)d.B * d.H * d.W + 127) / 128) * ((d.N + 95) / 96) >= 200) {
-      d.tile_hint = VS_CONV_TILE_HI | 10;                     // engine.py: pwconv2 on 128 x 96 tiles with the whole K per workgroup (tile 26) instead of K slices
-    } else if (gemm_pc) {                                       // engine.py::_split_k_rule
-      const int64_t rows = (int64_t)d.B * d.H * d.W;
-      const int64_t blocks = ((rows + 127) / 128) * ((d.N + 127) / 128);
-      const int pairs = d.CinP / 32;
-      int sk = 1;
-      while (blocks * sk < 256 && pairs % (sk * 2) == 0 && pairs / (sk * 2) >= 4) sk *= 2;
-      if (!a_scale || d.CinP / sk <= 3072) split_k = sk;      // engine.py::conv: the GRN rows of a K SLICE are staged in LDS; longer slices stay unsplit
-    } else if (patch_pc && d.N >= 128 && d.CinP >= 128) {      // engine.py::_split_k_rule_patch
-      const int64_t blocks = (int64_t)d.B * (d.H / 8) * (d.W / 16) * (d.N % 192 == 0 ? (d.N + 191) / 192 : (d.N + 127) / 128);
-      const int spt = d.CinP / 16;
-      const int cands[5] = {2, 3, 4, 6, 8};
-      for (int cand : cands) {
-        if (blocks * split_k >= 192) break;
-        if (spt % cand == 0 && spt / cand >= 2) split_k = cand;
-      }
+    d.sumsq_part = sumsq;
+    if (pre_table) d.tile_hint = (d.N % 192 == 0 ? (VS_CONV_TILE_HI | 0) : 15) | VS_CONV_PRE;   // border-class table added before bias + activation (engine.py::resblock_msg0)
+    vs_conv_plan_t p;
+    chk(vs_conv_plan(&d, grn_part ? grn_hw : 0, grn_c4, &p));
+    d.tile_hint = p.tile_hint;
+    if (p.split_k > 1) {
+      d.splitk_ld = rup(w.N, 4);
+      d.splitk_ws = alloc((int64_t)p.ws_slices * out.rows() * d.splitk_ld);
+      d.split_k = p.split_k;
     }
-    if (split_k > 1) {
-      const int ws_ld = rup(w.N, 4);
-      const int slices = split_k + ((patch_pc && in2) ? 1 : 0);
-      d.splitk_ws = alloc((int64_t)slices * out.rows() * ws_ld);
-      d.splitk_ld = ws_ld;
-      d.split_k = split_k;
-      d.tile_hint = d.KH == 3 ? (d.N % 192 == 0 ? VS_CONV_TILE_HI | 0 : 15) : (VS_CONV_TILE_HI | (d.N % 192 == 0 ? 2 : 1));
-    }
-    if (grn_part) {
-      // engine.py::conv(grn_fold=...): GRN's finish inside the wave-specialised GEMM (ABI v3: explicit tile 17 / 18 / 26, <= 16 partial rows per frame,
-      // K == the partials' channel count) or as the separate launch in front of it; the same scale values either way
-      const int t = (d.tile_hint & 0xf) + ((d.tile_hint & VS_CONV_TILE_HI) ? 16 : 0);
-      if ((t == 17 || t == 18 || t == 26) && grn_hw % 32 == 0 && grn_hw / 32 <= 16 && d.CinP == grn_c4 && a_scale_ld == grn_c4) {
-        d.grn_part = grn_part; d.grn_gamma = grn_gamma; d.grn_nchunk = grn_hw / 32;
-      } else if (live()) {
-        chk(vs_grn_scale_from_partials(grn_part, d.B, grn_hw, grn_c4, grn_gamma, const_cast<float*>(a_scale), a_scale_ld, st));
-      }
+    if (p.grn_fold) {       // (ABI v3) else the finish as the separate launch in front of the GEMM; the same scale values either way
+      d.grn_part = grn_part; d.grn_gamma = grn_gamma; d.grn_nchunk = grn_hw / 32;
+    } else if (grn_part && live()) {
+      chk(vs_grn_scale_from_partials(grn_part, d.B, grn_hw, grn_c4, grn_gamma, const_cast<float*>(a_scale), a_scale_ld, st));
     }
     if (live()) chk(vs_conv_gemm(&d, st));
   }
@@ -421,9 +389,9 @@ struct Runner {
     conv(t, p.c1, out, 1, 1, VS_PAD_ZERO, VS_ACT_RELU, 0, out.ld != rup(p.cout, 4) ? p.cout : -1, nullptr, &x, &p.res);
     return out;
   }
-  // 1x1 GEMM on operand planes (tile code 24, gemm_pl.hip): out = act(in_pl x w + bias) (+ res), optional GRN partials / K split
+  // 1x1 GEMM on operand planes (tile code 24 / 27, gemm_pl.hip): out = act(in_pl x w + bias) (+ res), optional GRN partials / K split
   void gemm_pl(int B, int H, int W, const CW& w, const void* in_pl, const Act& out, int act_, const Act* res, float* sumsq, int split_k,
-               float am = A_MUL, int sumsq_hw = 0) {
+               int tile_hint, float am = A_MUL, int sumsq_hw = 0) {
     vs_conv_desc_t d;
     std::memset(&d, 0, sizeof(d));
     d.B = B; d.H = H; d.W = W; d.Cin = w.CinP; d.KH = d.KW = 1; d.SH = d.SW = 1; d.Ho = H; d.Wo = W;
@@ -440,7 +408,7 @@ struct Runner {
       d.splitk_ld = ws_ld;
       d.split_k = split_k;
     }
-    d.tile_hint = VS_CONV_TILE_HI | 8;
+    d.tile_hint = tile_hint;
     if (live()) chk(vs_conv_gemm(&d, st));
   }
   // one launch of the all-DMA 3x3 kernel on operand planes (tile code 22, conv3x3_pl.hip); out == nullptr: planes only
@@ -655,28 +623,12 @@ struct Runner {
       float* part32 = alloc((int64_t)B * ((HW + 31) / 32) * 4 * Cc);
       float* scale = alloc((int64_t)B * hh.ld + 16);
       float* parts = (HW % 32 != 0 && HW >= 32) ? alloc((((int64_t)B * HW + 31) / 32) * 2 * 4 * Cc) : nullptr;
-      // engine.py::extractor_forward: the GEMMs on operand planes where the 256-row tiles fill the chip (pwconv1), resp. for long K (pwconv2)
+      // engine.py::_extractor_forward: which of the two GEMMs run on operand planes, pwconv2's K slices and its 128 x 96 form
       const int64_t rows = cur.rows();
       const CW& pw1w = m->stages[sti].empty() ? m->stem : m->stages[sti][0].pw1;
-      const bool pl1 = m->arith == 2 && ((rows + 255) / 256) * ((4 * Cc + 191) / 192) >= 200 && pw1w.CinP % 16 == 0 && !m->stages[sti].empty();
-      bool pl2 = false;
-      int sk2 = 1;
-      if (m->arith == 2 && hh.ld >= 2048 && hh.ld % 16 == 0) {
-        const int64_t tiles2 = ((rows + 255) / 256) * ((Cc + 191) / 192);
-        const int steps2 = hh.ld / 16;
-        while (tiles2 * sk2 < 200 && steps2 / (sk2 * 2) >= 24 && steps2 % (sk2 * 2) == 0) sk2 *= 2;
-        pl2 = tiles2 * sk2 >= 128;
-        if (pl2 && rows <= 2048 && HW % 64 == 0 && hh.ld % 32 == 0) {     // engine.py (round 5): small-M layers on the wave-specialised GEMM with the GRN A path
-          int skp = 1;
-          const int64_t blocks = ((rows + 127) / 128) * ((Cc + 127) / 128);
-          const int pairs = (int)(hh.ld / 32);
-          while (blocks * skp < 256 && pairs % (skp * 2) == 0 && pairs / (skp * 2) >= 4) skp *= 2;
-          if (hh.ld / skp <= 3072) pl2 = false;
-        }
-      }
-      else if (m->arith == 2 && hh.ld % 16 == 0 && HW % 64 != 0 && ((rows + 255) / 256) * ((Cc + 191) / 192) >= 200) {
-        pl2 = true; sk2 = 1;      // engine.py (round 6): odd frames pay a pass over h anyway -- make it the planes conversion
-      }
+      vs_cnx_stage_plan_t sp;
+      chk(vs_cnx_stage_plan(rows, HW, Cc, hh.ld, pw1w.CinP, m->arith, 0, &sp));
+      const bool pl1 = sp.pl1 && !m->stages[sti].empty(), pl2 = sp.pl2;
       // engine.py::_extractor_forward: pwconv1 -> GELU -> GRN -> pwconv2 with h on chip (statistics pass, scale, apply pass in place on cur)
       const bool fused = m->arith == 2 && !m->stages[sti].empty() && m->stages[sti][0].fuse && pw1w.CinP == Cc && vs_cnx_block_supported(Cc, rows, HW);
       void* tnpl = (pl1 || fused) ? alloc(rows * pw1w.CinP) : nullptr;
@@ -698,25 +650,25 @@ struct Runner {
           chk(vs_dwconv7_ln(cur.p, B, cur.H, cur.W, Cc, cur.ld, blk.wdw, blk.bdw, blk.lnw, blk.lnb, 1e-6f, tn.p, tn.ld, st));
         }
         if (HW % 32 == 0) {
-          if (pl1) gemm_pl(B, cur.H, cur.W, blk.pw1, tnpl, hh, VS_ACT_GELU, nullptr, part32, 1);
+          if (pl1) gemm_pl(B, cur.H, cur.W, blk.pw1, tnpl, hh, VS_ACT_GELU, nullptr, part32, 1, sp.tile1);
           else conv(tn, blk.pw1, hh, 1, 0, VS_PAD_ZERO, VS_ACT_GELU, 0, -1, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, part32);
           // (the finish is deferred to pwconv2's conv() where that launch can fold it, engine.py)
           if (!(HW % 64 == 0 && !pl2) && live()) chk(vs_grn_scale_from_partials(part32, B, HW, 4 * Cc, blk.gamma, scale, hh.ld, st));
         } else if (pl1 && HW >= 32) {      // engine.py (round 6): straddling 32-row-group partials from the planes GEMM's epilogue
-          gemm_pl(B, cur.H, cur.W, blk.pw1, tnpl, hh, VS_ACT_GELU, nullptr, parts, 1, A_MUL, HW);
+          gemm_pl(B, cur.H, cur.W, blk.pw1, tnpl, hh, VS_ACT_GELU, nullptr, parts, 1, sp.tile1, A_MUL, HW);
           if (live()) chk(vs_grn_scale_from_straddle_partials(parts, B, HW, 4 * Cc, blk.gamma, scale, hh.ld, st));
         } else {
-          if (pl1) gemm_pl(B, cur.H, cur.W, blk.pw1, tnpl, hh, VS_ACT_GELU, nullptr, nullptr, 1);
+          if (pl1) gemm_pl(B, cur.H, cur.W, blk.pw1, tnpl, hh, VS_ACT_GELU, nullptr, nullptr, 1, sp.tile1);
           else conv(tn, blk.pw1, hh, 1, 0, VS_PAD_ZERO, VS_ACT_GELU);
           if (live()) chk(vs_grn_scale(hh.p, B, HW, 4 * Cc, hh.ld, blk.gamma, part, scale, st));
         }
         if (pl2) {
           if (live()) chk(vs_to_planes_affine(hh.p, hh.rows(), hh.ld, hh.ld, A_MUL_GRN, scale, hh.ld, blk.beta, HW, hpl, st));
-          gemm_pl(B, cur.H, cur.W, blk.pw2, hpl, cur, VS_ACT_NONE, &cur, nullptr, sk2, A_MUL_GRN);
+          gemm_pl(B, cur.H, cur.W, blk.pw2, hpl, cur, VS_ACT_NONE, &cur, nullptr, sp.sk2, sp.tile2, A_MUL_GRN);
         } else if (HW % 64 == 0) {
           const bool defer = HW % 32 == 0;
           conv(hh, blk.pw2, cur, 1, 0, VS_PAD_ZERO, VS_ACT_NONE, 0, -1, &cur, nullptr, nullptr, scale, hh.ld, blk.beta, nullptr, nullptr, 0, false, 0.f,
-               defer ? part32 : nullptr, blk.gamma, HW, 4 * Cc);
+               defer ? part32 : nullptr, blk.gamma, HW, 4 * Cc, sp.pw2_narrow ? (VS_CONV_TILE_HI | 10) : 0);
         } else {
           if (live()) chk(vs_grn_apply(hh.p, B, HW, 4 * Cc, hh.ld, scale, hh.ld, blk.beta, st));
           conv(hh, blk.pw2, cur, 1, 0, VS_PAD_ZERO, VS_ACT_NONE, 0, -1, &cur, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, 0, false, A_MUL_GRN);

@@ -282,16 +282,12 @@ class HipEngine:
         self.msg_table_conv = os.environ.get("VIDEOSEAL_MSG_TABLE", "1") != "0"         # first bottleneck block: message channels as a table
         self.planes_chain = os.environ.get("VIDEOSEAL_PLANES", "1") != "0"              # bottleneck chain on pre-split operand planes
         self.msg0_planes = os.environ.get("VIDEOSEAL_MSG0_PLANES", "1") != "0"          # ... including its first block (round 5)
-        # stage-2 pwconv2 on 128 x 96 tiles (tile code 26) with the whole K per workgroup instead of 2 K slices + the epilogue launch.  Neutral while
-        # the wave-specialised GEMM's producers set its K loop's pace (profiles/r05a / r05c); with their lanes all working in both half steps the
-        # kernel alone is 49.9 us against 56.3 + 13 (tools/bench_gemm.py ksweep2) and detect of 32 frames 3.725 -> 3.651 ms (median of five
-        # alternating runs, profiles/r05o_detect_pw2_tile26.json).  VIDEOSEAL_PW2_NARROW=0: the K-slice form
         self.gemm_big = os.environ.get("VIDEOSEAL_GEMM_BIG", "0") == "1"                  # planes GEMMs of >= 3 rounds on 256 x 256 tiles, one wave per SIMD (round 6)
         self.stem_fused = os.environ.get("VIDEOSEAL_STEM_FUSED", "0") == "1"              # stem conv + LayerNorm in one VALU kernel (round 6; measured neutral: opt-in)
         self.down_patch = os.environ.get("VIDEOSEAL_DOWN_PATCH", "1") != "0"              # down-sampler LayerNorm -> patch matrix -> dense GEMM (round 6)
         self.grn_straddle = os.environ.get("VIDEOSEAL_GRN_STRADDLE", "1") != "0"         # GRN statistics from the planes GEMM's epilogue for HW % 32 != 0 (round 6)
         self.grn_fold = os.environ.get("VIDEOSEAL_GRN_FOLD", "1") != "0"                 # GRN finish inside the wave-specialised pwconv2 GEMM (round 6)
-        self.pw2_narrow = os.environ.get("VIDEOSEAL_PW2_NARROW", "1") != "0"
+        self.pw2_narrow = os.environ.get("VIDEOSEAL_PW2_NARROW", "1") != "0"             # stage-2 pwconv2 on 128 x 96 tiles (tile 26; 0: the K-slice form)
         self.pw2_small_pc = os.environ.get("VIDEOSEAL_PW2_SMALL_PC", "1") != "0"        # stage-3 pwconv2 on the wave-specialised GEMM instead of planes (round 5)
         self.planes_gemm = os.environ.get("VIDEOSEAL_PLANES", "1") != "0"               # ConvNeXt 1x1 GEMMs on operand planes
         self.fused_blocks = os.environ.get("VIDEOSEAL_CNX_FUSED", "1") != "0"           # stage 0 / 1 blocks with h kept on chip (convnext_fused.hip)
@@ -562,34 +558,24 @@ class HipEngine:
         if sumsq is not None:       # GRN partial sums of squares from the epilogue ([rows/32][N])
             d.sumsq_part = N.ptr(sumsq)
             d.sumsq_hw = int(sumsq_hw)       # > 0: frames of sumsq_hw rows (not a multiple of 32) -> the straddling [rows/32][2][N] form (tile codes 24 / 25)
-            split_k = 1
-        patch_pc = self._patch_pc_ok(d)
-        if split_k is None:     # static, shape-only rule (never timing-based: a K split changes the summation order)
-            split_k = 1
-            if tile_hint == 0 and self._gemm_pc_ok(d):
-                sk = self._split_k_rule(d)
-                # the GRN rows of a K slice are staged in LDS (<= 3072 elements): the cap applies to the SLICE the rule picks (convnext_base stage 3,
-                # K = 4096, runs as two slices of 2048); a slice beyond it leaves the launch unsplit for vs_conv_gemm's generic dispatch.
-                # model_api.hip mirrors this rule line for line, so the Python engine and the C-ABI host sum K in the same order
-                if not d.a_scale or d.CinP // sk <= 3072:
-                    split_k = sk
-            elif tile_hint == 0 and patch_pc:
-                split_k = self._split_k_rule_patch(d)
-        if split_k > 1:
+        # K slices, the static tile of a sliced launch and the GRN-finish fold: the library's shape-only rules (vs_conv_plan, csrc/conv_plan.hip --
+        # never timing-based: a K split changes the summation order; the model-level C host asks the same function)
+        d.split_k = split_k or 0
+        grn = grn_fold[3:] if grn_fold is not None else (0, 0)
+        p = self._plan(d, *grn)
+        d.split_k, d.tile_hint = (p.split_k if p.split_k > 1 else 0), p.tile_hint
+        if p.split_k > 1:
             ws_ld = rup(w.N, 4)
-            slices = split_k + (1 if ((patch_pc or in_pl is not None) and in2 is not None) else 0)     # + the slice of the 1x1 second phase
-            d.splitk_ws, d.splitk_ld, d.split_k = N.ptr(self.buf(f"splitk.ws@{N.stream()}", slices * out.rows * ws_ld)), ws_ld, split_k
-            if tile_hint == 0 and not self.autotune:
-                d.tile_hint = self._static_split_tile(d)
+            d.splitk_ws, d.splitk_ld = N.ptr(self.buf(f"splitk.ws@{N.stream()}", p.ws_slices * out.rows * ws_ld)), ws_ld
         if tile_hint == 0 and self.autotune:
             d.tile_hint = self._pick_tile(d, w, out)
+            if grn_fold is not None:
+                p = self._plan(d, *grn)       # (the fold test against the tuned tile)
         if grn_fold is not None:
-            # grn_fold = (partials [B][HW/32][K] from pwconv1's epilogue, gamma, B, HW): GRN's finish (||h|| -> scale) either INSIDE this GEMM
-            # (round 6, csrc/gemm1x1_pc.hip: the launch is known to run on the wave-specialised kernel, tile codes 17 / 18 / 26, and a frame has
-            # <= 16 partial rows) or as the separate launch it always was.  Same scale values bit for bit either way
+            # grn_fold = (partials [B][HW/32][K] from pwconv1's epilogue, gamma, B, HW, K): GRN's finish (||h|| -> scale) either INSIDE this GEMM
+            # (round 6, csrc/gemm1x1_pc.hip) or as the separate launch it always was.  Same scale values bit for bit either way
             part, gamma, B_, HW_, C4 = grn_fold
-            pc_tile = (d.tile_hint & 0xf) + (16 if d.tile_hint & N.CONV_TILE_HI else 0)
-            if self.grn_fold and pc_tile in (17, 18, 26) and HW_ % 32 == 0 and HW_ // 32 <= 16 and w.CinP == a_scale_ld == C4:
+            if self.grn_fold and p.grn_fold:
                 d.grn_part, d.grn_gamma, d.grn_nchunk = N.ptr(part), N.ptr(gamma), HW_ // 32
             else:
                 N.check(self.lib.vs_grn_scale_from_partials(N.ptr(part), B_, HW_, C4, N.ptr(gamma), N.ptr(a_scale), a_scale_ld, N.stream()),
@@ -607,51 +593,10 @@ class HipEngine:
             self.kernel_timers.append((prof, ev0, ev1, 2.0 * out.rows * w.N * k_total if flops is None else flops))
         return out
 
-    @staticmethod
-    def _gemm_pc_ok(d: "N.ConvDesc") -> bool:
-        """preconditions of the wave-specialised 1x1 GEMM (tile codes 17 / 18), mirrored from vs_conv_gemm"""
-        return (bool(d.wt_split) and bool(d.wt_blk) and d.KH == 1 and d.KW == 1 and d.SH == 1 and d.SW == 1 and d.PH == 0 and d.PW == 0
-                and not d.in2 and d.Ho == d.H and d.Wo == d.W and d.Cin % 32 == 0 and d.CinP == d.Cin
-                and d.in_sy == d.W * d.in_sx and d.in_sb == d.H * d.in_sy and (not d.a_scale or d.H * d.W >= 128 or d.H * d.W == 64))
-
-    @staticmethod
-    def _patch_pc_ok(d: "N.ConvDesc") -> bool:
-        """preconditions of the wave-specialised 3x3 patch kernel (tile codes 15 / 16), mirrored from vs_conv_gemm"""
-        return (bool(d.wt_split) and bool(d.wt_blk) and d.KH == 3 and d.KW == 3 and d.SH == 1 and d.SW == 1 and d.PH == 1 and d.PW == 1
-                and d.Ho == d.H and d.Wo == d.W and not d.a_scale and d.W % 16 == 0 and d.H % 8 == 0 and (not d.in2 or bool(d.wt2_blk)))
-
-    @staticmethod
-    def _split_k_rule_patch(d: "N.ConvDesc") -> int:
-        """K slices (whole 16-channel chunks) for wide 3x3 layers with too few 128-pixel tiles to fill 256 CUs,
-        e.g. the 4 key frames of a 16-frame streaming chunk: 32 tiles x 2 = 64 workgroups."""
-        if d.N < 128 or d.CinP < 128:
-            return 1
-        blocks = d.B * (d.H // 8) * (d.W // 16) * ((d.N + 191) // 192 if d.N % 192 == 0 else (d.N + 127) // 128)
-        spt = d.CinP // 16
-        sk = 1
-        for cand in (2, 3, 4, 6, 8):
-            if blocks * sk >= 192:
-                break
-            if spt % cand == 0 and spt // cand >= 2:
-                sk = cand
-        return sk
-
-    @staticmethod
-    def _static_split_tile(d: "N.ConvDesc") -> int:
-        if d.KH == 3:
-            return N.CONV_TILE_HI | 0 if d.N % 192 == 0 else 15
-        return N.CONV_TILE_HI | (2 if d.N % 192 == 0 else 1)
-
-    @staticmethod
-    def _split_k_rule(d: "N.ConvDesc") -> int:
-        """K slices for small-M GEMMs: double while 128 x 128 tiles cannot give every CU a workgroup and a slice keeps >= 4 K pairs"""
-        rows = d.B * d.H * d.W
-        blocks = ((rows + 127) // 128) * ((d.N + 127) // 128)
-        pairs = d.CinP // 32
-        sk = 1          # (aiming at 128 / 512 / 1024 workgroups instead of 256 measured slower: detect of 32 frames 4.17 / 3.95 / 4.24 against 3.87 ms, round 4)
-        while blocks * sk < 256 and pairs % (sk * 2) == 0 and pairs // (sk * 2) >= 4:
-            sk *= 2
-        return sk
+    def _plan(self, d: "N.ConvDesc", grn_hw: int = 0, grn_c4: int = 0) -> "N.ConvPlan":
+        p = N.ConvPlan()
+        N.check(self.lib.vs_conv_plan(C.byref(d), grn_hw, grn_c4, C.byref(p)), "vs_conv_plan")
+        return p
 
     def _pick_tile(self, d: "N.ConvDesc", w: ConvW, out: Act) -> int:
         """time the 4-wave tile shapes once per conv signature (on a scratch output) and remember the fastest."""
@@ -664,12 +609,9 @@ class HipEngine:
             return best
         if torch.cuda.is_current_stream_capturing():
             # never time inside a hipGraph capture: static heuristic (same numerics)
-            return self._static_split_tile(d) if d.split_k > 1 else 0
-        patch = (bool(d.wt_split) and d.KH == 3 and d.KW == 3 and d.SH == 1 and d.SW == 1 and d.PH == 1 and d.PW == 1 and
-                 d.Ho == d.H and d.Wo == d.W and not d.a_scale and d.W % 16 == 0 and d.H % 8 == 0)
-        small = (bool(d.wt_split) and d.KH == 3 and d.KW == 3 and d.SH == 1 and d.SW == 1 and d.PH == 1 and d.PW == 1 and d.Ho == d.H
-                 and d.Wo == d.W and not d.a_scale and d.CinP == 16 and d.N <= 32 and d.n_store <= 32 and (not d.in2 or d.Cin2P == 16)
-                 and d.split_k <= 1 and not d.sumsq_part)
+            return d.tile_hint
+        routes = self._plan(d).routes
+        patch, small, gemm_pc = routes & N.ROUTE_PATCH, routes & N.ROUTE_SMALL, routes & N.ROUTE_GEMM_PC
         if patch and d.split_k > 1:
             cands = [15] + ([N.CONV_TILE_HI] if d.N > 128 else [])
         elif patch and small:     # + the persistent thin-layer kernel (tile 20); same K order -> bit-identical
@@ -684,7 +626,7 @@ class HipEngine:
             cands = [N.CONV_TILE_HI | 1] + ([N.CONV_TILE_HI | 2] if d.N > 128 else [])
         else:
             cands = [t for t in (1, 2, 3, 4, 5, 13, 14) if self._tile_ok(t, d.N)]
-            if self._gemm_pc_ok(d) and d.N >= 96:    # same K order as the generic kernel: bit-identical candidates
+            if gemm_pc and d.N >= 96:    # same K order as the generic kernel: bit-identical candidates
                 cands += [N.CONV_TILE_HI | 1] + ([N.CONV_TILE_HI | 2] if d.N > 128 else [])
         real_out, real_coff, real_ld = d.out, d.out_coff, d.out_ld
         scratch = self.buf("autotune.out", out.rows * rup(d.n_store, 4))
@@ -964,9 +906,10 @@ class HipEngine:
                           "switched to the exact 3 x bf16 split and repeated the call")
         return bool(bad)
 
-    def _gemm_planes_ok(self, rows: int, n: int) -> bool:
-        """1x1 GEMM on operand planes (gemm_pl.hip): 2 x f16 arithmetic and enough 256-row x 192-column tiles for the 256 CUs"""
-        return self.planes_gemm and self.use_split and self.arith == 2 and ((rows + 255) // 256) * ((n + 191) // 192) >= 200
+    def _cnx_flags(self) -> int:
+        """the development switches vs_cnx_stage_plan reads (0 = the shipped defaults)"""
+        return ((0 if self.planes_gemm else N.CNX_NO_PLANES_GEMM) | (0 if self.pw2_small_pc else N.CNX_NO_PW2_SMALL_PC) |
+                (0 if self.pw2_narrow else N.CNX_NO_PW2_NARROW) | (N.CNX_GEMM_BIG if self.gemm_big else 0) | (0 if self.use_split else N.CNX_NO_SPLIT))
 
     def _planes_split(self, x: Act) -> int:
         """K slices of the planes conv for few key frames (shape-only rule, never timing: a K split changes the summation order): the smallest
@@ -1223,44 +1166,14 @@ class HipEngine:
             nchunk = (HW + 63) // 64
             part = self.buf(f"st{sti}.gp", nchunk * B * 4 * Cc)
             scale = self.buf(f"st{sti}.gs", B * hh.ld + 16)   # +16: the conv A-transform reads whole 16-float chunks
-            # all-DMA GEMM on operand planes (gemm_pl.hip, tile code 24) where its 256-row tiles give every CU work: pwconv1 reads the
-            # LayerNorm output as f16 planes written by the dwconv kernel itself; pwconv2 only for long K (K >= 2048: the GRN apply then
-            # runs in a separate conversion pass, which costs more than it saves on the shorter layers -- tools/bench_gemm.py planes)
+            # which of the two GEMMs run on operand planes (gemm_pl.hip), pwconv2's K slices there and its 128 x 96 form: the library's shape-only
+            # rules (vs_cnx_stage_plan, csrc/conv_plan.hip); the development switches travel as flags
             pw1w = X["stages"][sti][0]["pw1"]
-            pl1 = self._gemm_planes_ok(cur.rows, 4 * Cc) and pw1w.CinP % 16 == 0
-            pl2, sk2 = False, 1
-            if self.planes_gemm and self.use_split and self.arith == 2 and hh.ld >= 2048 and hh.ld % 16 == 0:
-                tiles2 = ((cur.rows + 255) // 256) * ((Cc + 191) // 192)
-                steps2 = hh.ld // 16
-                while tiles2 * sk2 < 200 and steps2 // (sk2 * 2) >= 24 and steps2 % (sk2 * 2) == 0:
-                    sk2 *= 2
-                pl2 = tiles2 * sk2 >= 128
-                # round 5: small-M layers (VideoSeal stage 3: 2048 rows x K = 3072) go back to the wave-specialised GEMM with the GRN transform on
-                # its A path -- with the producers' lanes all busy it is 50.9 us (4 K slices) against 15.0 (conversion pass over h) + 51.5 us on
-                # planes (tools/bench_gemm.py planes); ChunkySeal's wide layers (thousands of rows, K slices beyond the GRN rows' LDS budget) stay
-                if pl2 and cur.rows <= 2048 and HW % 64 == 0 and hh.ld % 32 == 0 and self.pw2_small_pc:
-                    skp = 1
-                    blocks = ((cur.rows + 127) // 128) * ((Cc + 127) // 128)
-                    pairs = hh.ld // 32
-                    while blocks * skp < 256 and pairs % (skp * 2) == 0 and pairs // (skp * 2) >= 4:
-                        skp *= 2
-                    if hh.ld // skp <= 3072:
-                        pl2 = False
-            elif (self.planes_gemm and self.use_split and self.arith == 2 and hh.ld % 16 == 0 and HW % 64 != 0
-                  and ((cur.rows + 255) // 256) * ((Cc + 191) // 192) >= 200):
-                # round 6 (ChunkySeal stages 0 / 1: 127 x 127 and 63 x 63 frames, K = 1448 / 2896 < 2048 at stage 0): frames that do not align with the
-                # wave-specialised GEMM's 64-row halves pay a full pass over h anyway (vs_grn_apply in place) and then run the slower kernel -- the
-                # planes conversion IS that pass, and the all-DMA GEMM behind it is twice as fast (1.6 -> 0.85 ms per launch at 258 064 x 1448 x 362)
-                pl2, sk2 = True, 1
+            sp = N.CnxStagePlan()
+            N.check(L.vs_cnx_stage_plan(cur.rows, HW, Cc, hh.ld, pw1w.CinP, self.arith, self._cnx_flags(), C.byref(sp)), "vs_cnx_stage_plan")
+            pl1, pl2 = bool(sp.pl1), bool(sp.pl2)
             tnpl = self.buf(f"st{sti}.npl", cur.rows * pw1w.CinP).view(torch.int16) if pl1 else None
             hpl = self.buf(f"st{sti}.hpl", cur.rows * hh.ld).view(torch.int16) if pl2 else None
-            ptile = N.CONV_TILE_HI | 8
-            # round 6: 256 x 256 tiles with one wave per SIMD (tile 27) for the GEMMs with several rounds of 256 x 192 tiles per launch -- those run at the
-            # chip's LDS-DMA stream rate, and the larger tile moves 15 % fewer operand bytes per FLOP (ChunkySeal; VIDEOSEAL_GEMM_BIG=0 keeps tile 24)
-            big1 = self.gemm_big and pl1 and ((cur.rows + 255) // 256) * ((4 * Cc + 255) // 256) >= 3 * 256
-            big2 = self.gemm_big and pl2 and sk2 == 1 and ((cur.rows + 255) // 256) * ((Cc + 255) // 256) >= 3 * 256
-            ptile1 = (N.CONV_TILE_HI | 11) if big1 else ptile
-            ptile2 = (N.CONV_TILE_HI | 11) if big2 else ptile
             fused = (self.fused_blocks and self.arith == 2 and X["stages"][sti] and X["stages"][sti][0].get("fuse") is not None
                      and pw1w.CinP == Cc and bool(L.vs_cnx_block_supported(Cc, cur.rows, HW)))
             if fused and tnpl is None:
@@ -1293,7 +1206,7 @@ class HipEngine:
                     N.check(L.vs_dwconv7_ln(N.ptr(cur.t), B, cur.H, cur.W, Cc, cur.ld, N.ptr(blk["wdw"]), N.ptr(blk["bdw"]), N.ptr(blk["lnw"]),
                                             N.ptr(blk["lnb"]), 1e-6, N.ptr(tn.t), tn.ld, st), "vs_dwconv7_ln")
                     self._note_absmax((sti, bj, "pw1"), tn.t, tn.rows * tn.ld)
-                kw1 = dict(in_pl=tnpl, tile_hint=ptile1) if bpl1 else dict(kwa1)
+                kw1 = dict(in_pl=tnpl, tile_hint=sp.tile1) if bpl1 else dict(kwa1)
                 if self.prof_extractor and sti == 2:      # bench.py --detect-only: the dominant GEMM of an extractor-only workload
                     kw1["prof"] = (f"{'gemm_pl_kernel' if bpl1 else 'gemm1x1_pc_kernel / conv_gemm_kernel'}: ConvNeXt stage-2 pwconv1 "
                                    f"{Cc}->{4 * Cc} @{cur.H}x{cur.W}")
@@ -1323,15 +1236,10 @@ class HipEngine:
                 if bpl2:              # GRN apply + operand split in one pass over h, then the planes GEMM (K split by the shape rule)
                     N.check(L.vs_to_planes_affine(N.ptr(hh.t), hh.rows, hh.ld, hh.ld, A_MUL_GRN, N.ptr(scale), hh.ld, N.ptr(blk["beta"]), HW,
                                                   N.ptr(hpl), st), "vs_to_planes_affine")
-                    self.conv(hh, blk["pw2"], cur, res=cur, in_pl=hpl, tile_hint=ptile2, split_k=sk2, a_mul=A_MUL_GRN)
+                    self.conv(hh, blk["pw2"], cur, res=cur, in_pl=hpl, tile_hint=sp.tile2, split_k=sp.sk2, a_mul=A_MUL_GRN)
                 elif (HW % 64 == 0 or not self.use_split) and not calib:
                     kn = dict(kwa2)
-                    # round 5: where 128-row x 128-column tiles would need K slices to occupy the CUs (stage 2: 64 x 3 tiles -> 2 slices + an
-                    # epilogue launch that adds 25 MB of partial sums), 128 x 96 tiles give 64 x 4 workgroups with the whole K each: one launch
-                    # (tile 26 takes the whole K in one workgroup: its GRN rows must fit the kernel's LDS area, K <= 3072, whole K pairs)
-                    if (self.pw2_narrow and self.use_split and a2 == 2 and ((cur.rows + 127) // 128) * ((Cc + 127) // 128) < 256
-                            and ((cur.rows + 127) // 128) * ((Cc + 95) // 96) >= 200 and Cc % 96 == 0 and HW >= 128
-                            and hh.ld <= 3072 and hh.ld % 32 == 0 and hh.ld == 4 * Cc):
+                    if sp.pw2_narrow and a2 == 2:      # 128 x 96 tiles with the whole K per workgroup (tile 26) instead of K slices
                         kn.update(tile_hint=N.CONV_TILE_HI | 10, split_k=1)
                     self.conv(hh, blk["pw2"], cur, res=cur, a_scale=scale, a_scale_ld=hh.ld, a_shift=blk["beta"], grn_fold=fold, **kn)
                 else:     # odd feature maps (ChunkySeal: 31 x 31): GRN applied in place + plain GEMM measured faster (109 vs 105 frames/s)

@@ -23,7 +23,7 @@ VIDEO_MODES = {"repeat": 0, "alternate": 1, "interpolate": 2}
 
 EXPORTS = [
     "vs_version", "vs_arch", "vs_error_string", "vs_sizeof_conv_desc", "vs_sizeof_tail_desc", "vs_debug_set",
-    "vs_model_create", "vs_model_destroy", "vs_model_workspace_bytes", "vs_model_embed", "vs_model_detect", "vs_model_set_nv12_color", "vs_nv12_default_color", "vs_conv_gemm", "vs_to_planes", "vs_to_planes_affine", "vs_layernorm_act", "vs_layernorm_patch2x2", "vs_stem_conv_ln", "vs_rmsnorm_act", "vs_vit_attention", "vs_dwconv7_ln", "vs_dwconv7_ln_planes", "vs_grn_scale", "vs_grn_scale_from_partials", "vs_grn_scale_from_straddle_partials", "vs_grn_apply",
+    "vs_model_create", "vs_model_destroy", "vs_model_workspace_bytes", "vs_model_embed", "vs_model_detect", "vs_model_set_nv12_color", "vs_nv12_default_color", "vs_conv_gemm", "vs_conv_plan", "vs_cnx_stage_plan", "vs_sizeof_conv_plan", "vs_sizeof_cnx_stage_plan", "vs_to_planes", "vs_to_planes_affine", "vs_layernorm_act", "vs_layernorm_patch2x2", "vs_stem_conv_ln", "vs_rmsnorm_act", "vs_vit_attention", "vs_dwconv7_ln", "vs_dwconv7_ln_planes", "vs_grn_scale", "vs_grn_scale_from_partials", "vs_grn_scale_from_straddle_partials", "vs_grn_apply",
     "vs_upcat2x", "vs_upconv_supported", "vs_upconv_gather_ln", "vs_cat2_scale", "vs_msg_pre", "vs_upconv_fused_supported", "vs_upconv_fused_preferred", "vs_upconv_fused", "vs_im2col3x3", "vs_msg_latent", "vs_broadcast_channels", "vs_outc_tanh", "vs_pool_linear", "vs_resize_pre", "vs_resize_pre_u8",
     "vs_jnd_heatmap", "vs_embed_tail", "vs_aug_color_scratch_floats", "vs_aug_color", "vs_aug_color_chain", "vs_aug_crop_resize_color", "vs_aug_crop_flip", "vs_aug_warp", "vs_resize_nchw",
     "vs_gaussian_blur", "vs_median_filter", "vs_jpeg_workspace_bytes", "vs_jpeg_roundtrip", "vs_h264_proxy_workspace_bytes", "vs_h264_proxy_roundtrip",
@@ -67,6 +67,21 @@ class ConvDesc(C.Structure):
         ("splitk_ws", C.c_void_p), ("splitk_ld", C.c_int64), ("split_k", C.c_int32), ("arith", C.c_int32),
         ("sumsq_part", C.c_void_p), ("in_pl", C.c_void_p), ("in2_pl", C.c_void_p), ("out_pl", C.c_void_p), ("a_mul", C.c_float), ("acc_mul", C.c_float), ("acc_mul2", C.c_float), ("grn_nchunk", C.c_int32), ("grn_part", C.c_void_p), ("grn_gamma", C.c_void_p), ("sumsq_hw", C.c_int32), ("reserved_", C.c_int32),
     ]
+
+
+class ConvPlan(C.Structure):
+    """mirror of vs_conv_plan_t"""
+    _fields_ = [(n, C.c_int32) for n in ("routes", "split_k", "tile_hint", "ws_slices", "grn_fold")]
+
+
+class CnxStagePlan(C.Structure):
+    """mirror of vs_cnx_stage_plan_t"""
+    _fields_ = [(n, C.c_int32) for n in ("pl1", "pl2", "sk2", "tile1", "tile2", "pw2_narrow")]
+
+
+# VS_ROUTE_* bits of ConvPlan.routes, VS_CNX_* flags of vs_cnx_stage_plan
+ROUTE_GEMM_PC, ROUTE_PATCH, ROUTE_PATCH_PC, ROUTE_SMALL = 1, 2, 4, 8
+CNX_NO_PLANES_GEMM, CNX_NO_PW2_SMALL_PC, CNX_NO_PW2_NARROW, CNX_GEMM_BIG, CNX_NO_SPLIT = 1, 2, 4, 8, 16
 
 
 class TailDesc(C.Structure):
@@ -120,6 +135,8 @@ def lib() -> C.CDLL:
     P, I, I64, F = C.c_void_p, C.c_int, C.c_int64, C.c_float
     sig = {
         "vs_conv_gemm": [C.POINTER(ConvDesc), P],
+        "vs_conv_plan": [C.POINTER(ConvDesc), I, I, C.POINTER(ConvPlan)],
+        "vs_cnx_stage_plan": [I64, I, I, I, I, I, I, C.POINTER(CnxStagePlan)],
         "vs_to_planes": [P, I64, I, I64, F, P, P],
         "vs_to_planes_affine": [P, I64, I, I64, F, P, I64, P, I, P, P],
         "vs_layernorm_act": [P, I64, I, I64, P, P, F, I, P, I64, P],
@@ -281,11 +298,13 @@ def lib() -> C.CDLL:
     L.vs_sizeof_conv_desc.restype = C.c_int
     L.vs_sizeof_tail_desc.restype = C.c_int
     L.vs_sizeof_tail_nv12_desc.restype = C.c_int
+    L.vs_sizeof_conv_plan.restype = L.vs_sizeof_cnx_stage_plan.restype = C.c_int
     if L.vs_version() != 3:
         raise NativeError(f"{LIB_PATH} has ABI version {L.vs_version()}, this binding is written for 3: rebuild (make -C videoseal_amd/csrc)")
     if L.vs_sizeof_conv_desc() != C.sizeof(ConvDesc) or L.vs_sizeof_tail_desc() != C.sizeof(TailDesc) or \
-            L.vs_sizeof_tail_nv12_desc() != C.sizeof(TailNv12Desc):
-        raise NativeError("ctypes mirrors of vs_conv_desc_t / vs_tail_desc_t / vs_tail_nv12_desc_t are out of date with the shared library")
+            L.vs_sizeof_tail_nv12_desc() != C.sizeof(TailNv12Desc) or L.vs_sizeof_conv_plan() != C.sizeof(ConvPlan) or \
+            L.vs_sizeof_cnx_stage_plan() != C.sizeof(CnxStagePlan):
+        raise NativeError("ctypes mirrors of vs_conv_desc_t / vs_tail_desc_t / vs_tail_nv12_desc_t / the plan structs are out of date with the shared library")
     _lib = L
     return L
 

@@ -9,7 +9,7 @@ kernels cannot fill 256 CUs (the U-Net bottleneck conv runs at 0.19 of its ceili
     watermarked frames of a group while the tail of the remaining frames is still being issued.
 
 `group=1` is exactly the sequence of per-chunk calls (bit-identical; the round-3 behaviour); larger groups differ from it only by the
-summation order of the dense layers, because whether K is split is a function of the batch shape (engine._split_k_rule*).
+summation order of the dense layers, because whether K is split is a function of the batch shape (the library's vs_conv_plan).
 Stream safety: embedder and extractor use disjoint named workspace buffers, K-split workspaces are per stream, every watermarked
 group is a fresh tensor (recorded on the consuming stream), and the extractor's logits are cloned on the detect stream."""
 from __future__ import annotations
