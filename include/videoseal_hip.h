@@ -46,12 +46,39 @@ extern "C" {
 /* library / device introspection */
 int vs_version(void);                       /* ABI version, currently 3 (round 2: vs_conv_desc_t / vs_model_cfg_t grew the arithmetic and planes fields; round 6: grn_part / grn_gamma / grn_nchunk) */
 const char* vs_arch(void);                  /* "gfx950" */
-/* Development switch for tests / tools.  PROCESS-GLOBAL (one atomic per key: setting it is thread-safe, but a value set by one thread is seen
- * by the resize_pre / embed_tail launches of EVERY thread and stream -- e.g. the streaming overlap stream -- until it is reset; not a per-call
- * option, not for production hosts).  Launch paths never call getenv.  key 0 = resize_pre form (1 = the 32 x 8 tile kernel), 1 = resize_pre
- * strip height in output rows, 2 = embed_tail strip height in rows, 3 = JPEG round-trip form (1 = the one-pixel-per-lane kernels), 4 = Crop -> Resize -> colour form (1 = the 32 x 8 tile kernel), 5 = vs_to_planes_affine form (1 = one row per wave), 6 = output rows per strip of the one-row depthwise kernel (1 / 2), 7 = vs_layernorm_act form (1 = one wave per row), 8 = K-slice epilogue form (1 = the first kernel, one load in flight per thread); value 0 = the
- * library's choice.  The environment default
- * VIDEOSEAL_RESIZE=tile is latched ONCE per process at the first launch: toggling the variable afterwards has no effect, use this call. */
+/* Development switches for tests / tools: kernel forms, strip heights, ablation bits.  PROCESS-GLOBAL (one atomic per key: setting it is
+ * thread-safe, but a value set by one thread is seen by the launches of EVERY thread and stream -- e.g. the streaming overlap stream -- until it
+ * is reset; not a per-call option, not for production hosts).  vs_debug_get(key) is what a launcher reads: the value of vs_debug_set when that
+ * is non-zero, else the key's environment default, else 0 = the library's choice.  The environment defaults of ALL keys are read once per
+ * process, at the first vs_debug_get / vs_debug_set (that is, at the first launch that has a switch): changing a variable afterwards has no
+ * effect, use vs_debug_set; vs_debug_set(key, 0) returns to the environment default.  No launch path reads the environment itself.
+ * vs_debug_key(name) gives the key of a name below, or -1; a key out of range answers VS_ERR_BAD_ARG.  The list is VS_DBG_KEYS of
+ * csrc/vs_common.h (tests/test_host.py checks this comment against it):
+ *    0 RESIZE_FORM       VIDEOSEAL_RESIZE=tile        resize_pre: 1 = the 32 x 8 tile kernel
+ *    1 RESIZE_STRIP      VS_RESIZE_STRIP=<n>          resize_pre strip height in output rows (variable: n >= 2, key: n >= 1)
+ *    2 TAIL_STRIP        VS_TAIL_STRIP=<n>            embed_tail strip height in rows (n >= 4, rounded up to a multiple of 4)
+ *    3 JPEG_FORM         VIDEOSEAL_JPEG=scalar        JPEG round trip: 1 = the one-pixel-per-lane kernels
+ *    4 CROP_RESIZE_FORM  VIDEOSEAL_CROP_RESIZE=tile   Crop -> Resize -> colour: 1 = the 32 x 8 tile kernel
+ *    5 TO_PLANES_FORM    -                            vs_to_planes_affine: 1 = one row per wave
+ *    6 DWCONV_ROWS       VS_DWCONV_ROWS=<n>           output rows per strip of the one-row depthwise kernel (2 = two, else one)
+ *    7 LN_FORM           VIDEOSEAL_LN=wave            vs_layernorm_act: 1 = one wave per row
+ *    8 SPLITK_EPI        VS_SPLITK_EPI=scalar         K-slice epilogue: 1 = the first kernel, one load in flight per thread
+ *    9 UPCONV_FORM       -                            up-conv gather: 1 = per pixel instead of 2 x 2 blocks
+ *   10 TAIL_FORM         VIDEOSEAL_TAIL=v1|sep|keep   embed_tail form, numbered as vs_tail_desc_t::variant (which overrides it per call)
+ *   11 VIT_ATTN          VS_VIT_ATTN=valu             vs_vit_attention: 1 = the vector kernel on the matrix-core shapes too
+ *   12 WGRAD             VS_WGRAD=mfma|fma            vs_gemm_wgrad: 1 / 2 = the fp32 matrix-core / vector kernel everywhere
+ *   13 DWCONV            VS_DWCONV=<n>                depthwise 7 x 7 + LayerNorm: key = 1 + n; n = 0 the one-row kernel, 1.. a tiled one
+ *   14 GEMM_GRID         VS_GEMM_GRID=<n>             workgroups of the wave-specialised 1 x 1 GEMM's persistent grid
+ *   15 GEMM_PL_RASTER    VS_GEMM_PL_RASTER=0          planes GEMMs: 1 = row-major tile order
+ *   16 CNX_PIPE          VS_CNX_PIPE=0                fused ConvNeXt block: 1 = the serial kernel
+ *   17 CNX_ABL           VS_CNX_ABL=<bits>            fused ConvNeXt block: ablation bits (ablation builds only)
+ *   18 UPCONV_ABL        VS_UPCONV_ABL=<bits>         vs_upconv_fused: ablation bits
+ *   19 STEM_FUSED        VIDEOSEAL_STEM_FUSED=1       vs_model_detect: stem conv + LayerNorm in one kernel
+ *   20 ARITH             VIDEOSEAL_CONV=f16x2|bf16x3  default arithmetic (2 / 3) of the model-level entry points
+ * vs_resize_pre_nv12 / vs_embed_tail_nv12 read keys 0 - 2 like their fp32 twins, environment defaults included: VIDEOSEAL_RESIZE=tile,
+ * VS_RESIZE_STRIP and VS_TAIL_STRIP apply to them too. */
+int vs_debug_key(const char* name);
+int vs_debug_get(int key);
 int vs_debug_set(int key, int value);
 const char* vs_error_string(int code);
 int vs_sizeof_conv_desc(void);              /* sizeof(vs_conv_desc_t): lets a binding verify its struct mirror */

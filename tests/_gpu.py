@@ -1,5 +1,5 @@
-"""What the GPU kernel tests share: layouts, the model-less engine, kept-alive device copies, operand builders and the launchers that a test
-and its child process both call (a plain helper module, no pytest in it).  Importing it does not touch the device."""
+"""What the GPU kernel tests share: layouts, the model-less engine, kept-alive device copies, operand builders and the launchers that several
+tests call (a plain helper module, no pytest in it).  Importing it does not touch the device."""
 import zlib
 
 import torch
@@ -104,7 +104,7 @@ def conv_weights(w, b, in_ld):
     return ConvW(wt, dv(b) if b is not None else None, w.shape[0], w.shape[2], w.shape[3], cp)
 
 
-# ---------------------------------------------------------------------------------------------------------------- launchers shared with a child process
+# ---------------------------------------------------------------------------------------------------------------- launchers shared by several tests
 def wgrad_gemm_operands(case):
     rows, n, k, ldn, ldk = case
     return _split_ref.hard_dy(rows, n, 6000 + rows), _split_ref.hard_rows(rows, k, 6001 + rows)
@@ -129,7 +129,7 @@ def wgrad_gemm_launch(case):
 
 def attention_launch(case):
     """the kernel's output [B, H, W, heads, hd] (CPU) for one (cfg, tables?) case on the hard qkv; which kernel runs is the library's choice
-    (VS_VIT_ATTN, read once per process)"""
+    (development switch VIT_ATTN)"""
     cfg, rel = case
     B, H, W, heads, hd, win = cfg
     qkv, rh, rw = _fwd_ref.attn_inputs(cfg, rel)

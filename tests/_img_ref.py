@@ -165,7 +165,7 @@ RESIZE_CASES = [
     ("stream<128> 16-byte loads", 96, 128, 30, 40, 1, {}),
     ("stream<64> 3.9:1 vector loads", 100, 128, 25, 32, 1, {}),
     ("stream<64> 3.9:1 scalar loads", 101, 126, 26, 32, 1, {}),
-    ("staged tile kernel", 93, 118, 29, 37, 1, {0: 1}),
+    ("staged tile kernel", 93, 118, 29, 37, 1, {"RESIZE_FORM": 1}),
     ("unstaged tile path > 4:1", 70, 66, 13, 17, 1, {}),
     ("128 taps", 64, 64, 1, 1, 1, {}),
     ("up-scale aa", 5, 7, 64, 64, 1, {}),
@@ -174,9 +174,9 @@ RESIZE_CASES = [
     ("one input row plain", 1, 9, 4, 33, 0, {}),
     ("up-scale where fp32 coordinates dominate", 93, 118, 130, 165, 1, {}),
     ("plain up", 31, 45, 64, 64, 0, {}),
-    ("strip height 1", 96, 128, 30, 40, 1, {1: 1}),
-    ("strip height 7", 96, 128, 30, 40, 1, {1: 7}),
-    ("strip height 80 (taller than the weight table)", 96, 128, 30, 40, 1, {1: 80}),
+    ("strip height 1", 96, 128, 30, 40, 1, {"RESIZE_STRIP": 1}),
+    ("strip height 7", 96, 128, 30, 40, 1, {"RESIZE_STRIP": 7}),
+    ("strip height 80 (taller than the weight table)", 96, 128, 30, 40, 1, {"RESIZE_STRIP": 80}),
 ]
 RESIZE_IDENTITY = (33, 47)                                  # 33 x 47 -> 33 x 47: must be bit-equal to x * mul + add
 RESIZE_U8_CASES = [(93, 118, 29, 37, 1), (94, 93, 30, 31, 1), (5, 7, 64, 64, 1)]

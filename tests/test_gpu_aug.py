@@ -36,17 +36,13 @@ def test_jpeg_is_bit_exact_with_pillow(hw, quality):
 def test_jpeg_vector_kernels_equal_the_scalar_ones(hw, quality):
     """round 6: frames made of whole 16 x 16 MCUs take the 16-byte-access kernels (4 x 2 pixels per thread in the colour / down-sampling stage,
     4 pixels per thread in the up-sampling / RGB stage, one launch for the blocks of all three components): the same bytes as the one-pixel-per-lane
-    kernels (development switch 3) -- and as Pillow (test above: 64 x 64, 256 x 256 and 768 x 768 run the vector form, the other sizes the scalar one)"""
+    kernels (development switch JPEG_FORM) -- and as Pillow (test above: 64 x 64, 256 x 256 and 768 x 768 run the vector form, the other sizes the scalar one)"""
     x = synthetic_frames(3, hw[0], hw[1], seed=quality).cuda()
     x[0, :, :7, :9] = 1.3
-    L = N.lib()
     got, _ = G.JPEG()(x, None, quality)
-    L.vs_debug_set(3, 1)
-    try:
+    with N.debug("JPEG_FORM", 1):
         ref, _ = G.JPEG()(x, None, quality)
         torch.cuda.synchronize()
-    finally:
-        L.vs_debug_set(3, 0)
     assert torch.equal(got, ref)
     assert torch.equal(got.cpu(), A.jpeg(x.cpu(), quality))
 
@@ -309,8 +305,7 @@ def test_fused_colour_chain_is_bit_identical_to_the_separate_ops(ops):
 def test_fused_crop_resize_colour_is_bit_identical_to_the_separate_launches(H, W, crop, size, aa, form):
     x = synthetic_frames(3, H, W, seed=H + W).cuda()
     ops = [("brightness", 0.5), ("saturation", 1.4), ("contrast", 1.5), ("hue", 0.1)]
-    N.lib().vs_debug_set(4, 1 if form == "tile" else 0)          # development switch 4: the 32 x 8 tile kernel instead of the row-streaming one
-    try:
+    with N.debug("CROP_RESIZE_FORM", 1 if form == "tile" else 0):          # the 32 x 8 tile kernel instead of the row-streaming one
         for use_ops in ([], ops):
             y = G.crop_flip(x, *crop) if crop is not None else x
             ref = G.resize(y, size, aa)
@@ -319,8 +314,6 @@ def test_fused_crop_resize_colour_is_bit_identical_to_the_separate_launches(H, W
             got = G.crop_resize_color(x, crop, size, use_ops, antialias=aa)
             torch.cuda.synchronize()
             assert got.shape == ref.shape and torch.equal(got, ref), float((got - ref).abs().max())
-    finally:
-        N.lib().vs_debug_set(4, 0)
     # a window the LDS cannot hold (down-scaling by 12) takes the separate launches: same answer
     big = synthetic_frames(1, 256, 1300, seed=5).cuda()
     assert torch.equal(G.crop_resize_color(big, None, (20, 100), []), G.resize(big, (20, 100), True))

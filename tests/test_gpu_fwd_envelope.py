@@ -5,10 +5,6 @@ these maps do not reach), the stem and the up-conv gather, the private copies of
 the GRN finish kernels and both attention kernels: worst group of
 max |got - ref| / max |ref| against the formula in float64, at most FWD_FP64_MARGIN times what the same formula costs in float32 on the CPU.
 Every figure is printed as a FWD-ENVELOPE line; profiles/fwd_fp64_envelope.txt is such a run on an MI355X."""
-import os
-import subprocess
-import sys
-
 import pytest
 import torch
 
@@ -22,7 +18,6 @@ from videoseal_amd import native as N  # noqa: E402
 from videoseal_amd import pixel_head as PH  # noqa: E402
 from videoseal_amd.engine import ConvW, pack_conv, pack_patch_conv, rup  # noqa: E402
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DEV = "cuda"
 NAN = float("nan")
 
@@ -41,7 +36,7 @@ def _rows(got, r64, r32, name="y/row"):
 @pytest.mark.parametrize("case", R.LN_CASES, ids=[c[0] for c in R.LN_CASES])
 def test_layernorm_act_fp64_envelope(case, act):
     """every form of vs_layernorm_act (thread-per-row small<4|8|16>, lanes <8|16|32|64, 4> and <64, 12>, wave-per-row by shape and forced through
-    development switch 7) on rows of mean 30 / std 0.5, a constant row, a row with one 4e3 outlier and a row of magnitude 1e-3; input between NaN
+    development switch LN_FORM) on rows of mean 30 / std 0.5, a constant row, a row with one 4e3 outlier and a row of magnitude 1e-3; input between NaN
     bands, output between guard bands, pad lanes of the output zero"""
     tag, rows, C, ld, force_wave = case
     L = N.lib()
@@ -50,12 +45,9 @@ def test_layernorm_act_fp64_envelope(case, act):
     xbuf, xg = _guarded(_padded(x, ld).to(DEV), NAN)
     obuf, og = _guarded(torch.full((rows, ld), 9.0, device=DEV), -7.0)
     wd, bd = _pad1(w, ld), _pad1(b, ld)
-    L.vs_debug_set(7, force_wave)
-    try:
+    with N.debug("LN_FORM", force_wave):
         N.check(L.vs_layernorm_act(N.ptr(xg), rows, C, ld, N.ptr(wd), N.ptr(bd), 1e-6, act, N.ptr(og), ld, N.stream()), "vs_layernorm_act")
         torch.cuda.synchronize()
-    finally:
-        L.vs_debug_set(7, 0)
     assert _guards_intact(obuf, -7.0) and _guards_intact(xbuf, NAN)
     assert (og[:, C:] == 0).all()
     R.envelope(f"layernorm_act {tag} rows={rows} C={C} ld={ld} act={act}", [_rows(og[:, :C], r64, r32)])
@@ -299,17 +291,9 @@ def test_vit_attention_fp64_envelope(case):
     attention_check(case, "mfma" if case in R.ATTN_MFMA_CASES else "valu", attention_launch(case))
 
 
-@pytest.fixture(scope="module")
-def valu_on_mfma_shapes(tmp_path_factory):
-    """VS_VIT_ATTN is read once per process: the vector kernel on the matrix-core shapes runs in ONE fresh child, which opens the GPU once, under
-    its own time limit; its exit status is checked before this process does anything else on the GPU"""
-    path = str(tmp_path_factory.mktemp("attn") / "valu.pt")
-    env = dict(os.environ, VS_VIT_ATTN="valu")
-    p = subprocess.run([sys.executable, "-m", "tests._fwd_attn_child", path], cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
-    assert p.returncode == 0, (p.stdout[-2000:], p.stderr[-2000:])
-    return torch.load(path)
-
-
 @pytest.mark.parametrize("case", R.ATTN_MFMA_CASES, ids=_attn_id)
-def test_vit_attention_vector_kernel_on_the_matrix_core_shapes_fp64_envelope(valu_on_mfma_shapes, case):
-    attention_check(case, "VS_VIT_ATTN=valu", valu_on_mfma_shapes[R.ATTN_MFMA_CASES.index(case)])
+def test_vit_attention_vector_kernel_on_the_matrix_core_shapes_fp64_envelope(case):
+    """the vector kernel on the matrix-core shapes: what VS_VIT_ATTN=valu selects, here through its development switch"""
+    with N.debug("VIT_ATTN", 1):
+        got = attention_launch(case)
+    attention_check(case, "VS_VIT_ATTN=valu", got)

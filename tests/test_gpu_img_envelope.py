@@ -5,6 +5,7 @@ the pointwise / temporal ops, called through the C ABI: per (case, frame kind)  
 at most IMG_FP64_MARGIN times what the same formula costs in float32 on the CPU.  Inputs sit between NaN bands (bytes: 0xFF), outputs are
 pre-filled with a sentinel between -7.0 bands: the bands must be intact and no sentinel may be left.  Every figure is printed as an IMG-ENVELOPE
 line; profiles/img_fp64_envelope.txt is such a run on an MI355X."""
+import contextlib
 import ctypes as C
 
 import pytest
@@ -50,18 +51,13 @@ def _done(outs, ins=()):
     return res
 
 
-class _switch:
-    """development switches {key: value} for the calls inside the block"""
-    def __init__(self, sw):
-        self.sw = sw
-
-    def __enter__(self):
-        for k, v in self.sw.items():
-            N.lib().vs_debug_set(k, v)
-
-    def __exit__(self, *a):
-        for k in self.sw:
-            N.lib().vs_debug_set(k, 0)
+@contextlib.contextmanager
+def _switch(sw):
+    """development switches {name: value} for the calls inside the block"""
+    with contextlib.ExitStack() as stack:
+        for k, v in sw.items():
+            stack.enter_context(N.debug(k, v))
+        yield
 
 
 def _nchw(t):
@@ -316,7 +312,7 @@ def _crc_launch(x, crop, oh, ow, aa, ops, tile):
     i0, j0, ch, cw = crop
     xin, out = _in(x), _out(Fn, 3, oh, ow)
     oa, fa = _ops(ops) if ops else (None, None)
-    with _switch({4: 1} if tile else {}):
+    with _switch({"CROP_RESIZE_FORM": 1} if tile else {}):
         rc = L.vs_aug_crop_resize_color(N.ptr(xin[1]), N.ptr(out[1]), Fn, H, W, i0, j0, ch, cw, oh, ow, aa, len(ops), oa, fa, N.stream())
         if rc == N.ERR_UNSUPPORTED:          # the tile's source window does not fit the LDS: callers take the separate launches
             torch.cuda.synchronize()

@@ -139,13 +139,12 @@ def test_conv3x3_planes_kernel_with_k_slices(cfg):
 def test_k_slice_epilogue_forms_are_bit_identical(kind, cfg):
     """round 6: splitk_epilogue_vec_kernel issues every load of an item -- all K slices, bias, the slice of the second phase, residual -- before the
     first use (one round trip; the first kernel waited behind each of them in turn: 9 - 13 us for a few MB) and adds in the same order: fp32 output and
-    operand planes identical bit for bit to the first form (vs_debug_set key 8 = 1), for compile-time slice counts (2 / 3 / 4 / 6 / 8) and the run-time one."""
+    operand planes identical bit for bit to the first form (development switch SPLITK_EPI = 1), for compile-time slice counts (2 / 3 / 4 / 6 / 8) and the run-time one."""
     eng = Eng(arith=2)
     g = torch.Generator().manual_seed(77)
     res_by_form = []
     for form in (1, 0):
-        N.check(eng.lib.vs_debug_set(8, form), "vs_debug_set")
-        try:
+        with N.debug("SPLITK_EPI", form):
             if kind == "pl":
                 B, C, H, W, Co, two, sk = cfg
                 gg = torch.Generator().manual_seed(31)
@@ -182,8 +181,6 @@ def test_k_slice_epilogue_forms_are_bit_identical(kind, cfg):
                 torch.cuda.synchronize()
                 assert torch.isfinite(out.t).all()
                 res_by_form.append((out.t.clone(),))
-        finally:
-            N.check(eng.lib.vs_debug_set(8, 0), "vs_debug_set")
     for a_, b_ in zip(*res_by_form):
         assert torch.equal(a_, b_)
 
@@ -974,12 +971,9 @@ def test_embed_tail_forms_are_bit_identical(case):
         d.step, d.video_mode, d.total_key = step, vm, nkey
         d.attenuate, d.clamp, d.antialias = att, 1, 1
         d.scaling_i, d.scaling_w, d.io_u8, d.variant = 1.0, 0.2, 0, variant
-        L.vs_debug_set(2, int(strip or 0))              # development switch: strip height of the streaming tail for this call
-        try:
+        with N.debug("TAIL_STRIP", int(strip or 0)):              # development switch: strip height of the streaming tail for this call
             N.check(L.vs_embed_tail(C.byref(d), N.stream()), "vs_embed_tail")
             torch.cuda.synchronize()
-        finally:
-            L.vs_debug_set(2, 0)
         return out, pw
     ref, ref_pw = run(2)
     assert float(ref.min()) >= 0.0                      # every pixel written
@@ -1048,12 +1042,9 @@ def test_resize_pre_forms_are_bit_identical(cfg):
     def run(form, want_rgb=True, want_key=True, y=True):
         rgb = torch.full((B, oh, ow, 4), -9.0, device="cuda") if want_rgb else None
         key = torch.full((nk, oh, ow, 4), -9.0, device="cuda") if want_key else None
-        L.vs_debug_set(0, 1 if form == "tile" else 0)   # development switch: kernel form for this call
-        try:
+        with N.debug("RESIZE_FORM", 1 if form == "tile" else 0):   # development switch: kernel form for this call
             N.check(L.vs_resize_pre(N.ptr(x), B, 3, H, W, oh, ow, aa, N.ptr(rgb), 2.0, -1.0, N.ptr(key), step, ymat if y else None, N.stream()), "vs_resize_pre")
             torch.cuda.synchronize()
-        finally:
-            L.vs_debug_set(0, 0)
         return rgb, key
     r0, k0 = run("tile")
     r1, k1 = run(None)
@@ -1065,11 +1056,8 @@ def test_resize_pre_forms_are_bit_identical(cfg):
         a, b = run("tile", **kw), run(None, **kw)
         assert all((p is None and q is None) or torch.equal(p, q) for p, q in zip(a, b))
     for strip in (2, 6, 512):
-        L.vs_debug_set(1, strip)
-        try:
+        with N.debug("RESIZE_STRIP", strip):
             r2, k2 = run(None)
-        finally:
-            L.vs_debug_set(1, 0)
         assert torch.equal(r2, r0) and torch.equal(k2, k0), strip
 
 
@@ -1246,7 +1234,7 @@ def test_grn_finish_folded_into_the_gemm_equals_the_separate_launch(eng, case):
                                                (1000, 144, 160, 250, True), (31, 48, 48, 31, True)])
 def test_to_planes_affine_forms_are_bit_identical(rows, C, ld, hw, grn):
     """vs_to_planes_affine (GRN apply + f16 operand split of h in front of the planes pwconv2, gemm_pl.hip): the LDS-transposed kernel (round 6:
-    512-byte row pieces in, 1 KiB runs out) against the one-row-per-wave kernel (development switch 5) and against the split computed on the host:
+    512-byte row pieces in, 1 KiB runs out) against the one-row-per-wave kernel (development switch TO_PLANES_FORM) and against the split computed on the host:
     ChunkySeal's stage-2 shape (31 x 31 frames, 5 792 channels = 45.25 channel tiles), ragged row tiles, channel strides above C, fewer than 32 rows"""
     L = N.lib()
     g = torch.Generator().manual_seed(rows + C)
@@ -1258,13 +1246,10 @@ def test_to_planes_affine_forms_are_bit_identical(rows, C, ld, hw, grn):
     outs = []
     for form in (0, 1):
         pl = torch.full((2 * rows * C,), 0x7777, dtype=torch.int16, device=DEV)
-        L.vs_debug_set(5, form)
-        try:
+        with N.debug("TO_PLANES_FORM", form):
             N.check(L.vs_to_planes_affine(N.ptr(xd), rows, C, ld, 1.0, N.ptr(sd) if grn else None, C, N.ptr(hd) if grn else None, hw, N.ptr(pl), N.stream()),
                     "to_planes_affine")
             torch.cuda.synchronize()
-        finally:
-            L.vs_debug_set(5, 0)
         outs.append(pl.cpu())
     assert torch.equal(outs[0], outs[1])
     # planes [2][C / 16][rows][16]: hi = f16(v), lo = f16(v - hi) of v = x * scale[frame] + shift (fp32)
@@ -1327,7 +1312,7 @@ def test_grn_statistics_from_straddling_row_groups(B, H, W, K, Nn):
 @pytest.mark.parametrize("C_,H,W", [(1448, 31, 31), (1030, 9, 5), (96, 6, 7), (2896, 15, 15), (362, 7, 7)])
 def test_dwconv7_ln_two_row_strips_equal_single_rows(C_, H, W):
     """round 6: the one-row depthwise 7x7 + LayerNorm kernel with strips of 4 x 2 output pixels (ChunkySeal's 1448- / 2896-channel maps: 10 instead of
-    17.5 input fetches per output) against single rows (development switch 6): fp32 rows and operand planes agree to fp32 rounding, odd heights (a half strip at the bottom)"""
+    17.5 input fetches per output) against single rows (development switch DWCONV_ROWS): fp32 rows and operand planes agree to fp32 rounding, odd heights (a half strip at the bottom)"""
     L = N.lib()
     g = torch.Generator().manual_seed(C_ + H)
     B = 2
@@ -1340,17 +1325,14 @@ def test_dwconv7_ln_two_row_strips_equal_single_rows(C_, H, W):
     outs = []
     import os
     for rows in (2, 1):
-        L.vs_debug_set(6, rows)
-        try:
+        with N.debug("DWCONV_ROWS", rows):
             o = torch.full((B * H * W * ld,), 3.0, device=DEV)
             pl = torch.full((2 * B * H * W * Cp,), 77, dtype=torch.int16, device=DEV)
-            # VS_DWCONV=0 is process-wide; these shapes take the one-row kernel anyway (tile + LayerNorm buffer beyond the LDS) except the small ones
+            # (the DWCONV switch is left alone: these shapes take the one-row kernel anyway -- tile + LayerNorm buffer beyond the LDS -- except the small ones)
             N.check(L.vs_dwconv7_ln(N.ptr(xa.t), B, H, W, C_, ld, N.ptr(wdw), N.ptr(vecs[0]), N.ptr(vecs[1]), N.ptr(vecs[2]), 1e-6, N.ptr(o), ld, N.stream()), "dw")
             N.check(L.vs_dwconv7_ln_planes(N.ptr(xa.t), B, H, W, C_, ld, N.ptr(wdw), N.ptr(vecs[0]), N.ptr(vecs[1]), N.ptr(vecs[2]), 1e-6, 16.0, Cp, N.ptr(pl),
                                            N.stream()), "dw planes")
             torch.cuda.synchronize()
-        finally:
-            L.vs_debug_set(6, 0)
         outs.append((o.cpu(), pl.cpu()))
     # same depthwise sums (same tap order per output); the LayerNorm behind them spreads a pixel's channels over more or fewer lanes depending on the
     # pixels per workgroup, so the two forms agree to fp32 rounding
@@ -1552,7 +1534,7 @@ def test_planes_gemm_ignores_and_preserves_what_surrounds_its_tensors(case):
                                             (2896, 2912, 33, 2), (20, 20, 77, 1), (100, 128, 50, 0)])
 def test_layernorm_lanes_form_equals_the_wave_per_row_form(C_, ld, rows, act):
     """vs_layernorm_act, round 6: LPP lanes per row with the row in registers (8 lanes for 96 channels ... 64 lanes x 12 float4 for ChunkySeal's 2896)
-    against the one-wave-per-row kernel (development switch 7) and torch: the mean / variance sums run in another order -> fp32 rounding; pad lanes of
+    against the one-wave-per-row kernel (development switch LN_FORM) and torch: the mean / variance sums run in another order -> fp32 rounding; pad lanes of
     the output (ld > C) are written as zeros by both"""
     L = N.lib()
     g = torch.Generator().manual_seed(C_ + rows)
@@ -1563,12 +1545,9 @@ def test_layernorm_lanes_form_equals_the_wave_per_row_form(C_, ld, rows, act):
     outs = []
     for form in (0, 1):
         o = torch.full((rows, ld), 9.0, device=DEV)
-        L.vs_debug_set(7, form)
-        try:
+        with N.debug("LN_FORM", form):
             N.check(L.vs_layernorm_act(N.ptr(xd), rows, C_, ld, N.ptr(wd), N.ptr(bd), 1e-6, act, N.ptr(o), ld, N.stream()), "ln")
             torch.cuda.synchronize()
-        finally:
-            L.vs_debug_set(7, 0)
         outs.append(o.cpu())
     ref = F.layer_norm(x[:, :C_], (C_,), w, b, 1e-6)
     ref = {0: ref, 1: F.relu(ref), 2: F.gelu(ref)}[act]

@@ -77,7 +77,7 @@ def random_clip(shape: str, seed=9) -> torch.Tensor:
 
 
 def call_resize(view, preset, aa, want_rgb, want_y, ymat, y_step=2, form=None, strip=0):
-    """form "tile" keeps the tile kernel, `strip` sets the strip height of the row-streaming one (development switches 0 and 1)"""
+    """form "tile" keeps the tile kernel, `strip` sets the strip height of the row-streaming one (development switches RESIZE_FORM and RESIZE_STRIP)"""
     lib = N.lib()
     F_, R_, W = view.shape
     H = R_ // 3 * 2
@@ -87,15 +87,10 @@ def call_resize(view, preset, aa, want_rgb, want_y, ymat, y_step=2, form=None, s
     nk = (F_ + y_step - 1) // y_step
     key = torch.full((nk, S, S, 4), float("nan"), device="cuda") if want_y else None
     ym = (C.c_float * 3)(*ymat)
-    lib.vs_debug_set(0, 1 if form == "tile" else 0)
-    lib.vs_debug_set(1, int(strip))
-    try:
+    with N.debug("RESIZE_FORM", 1 if form == "tile" else 0), N.debug("RESIZE_STRIP", int(strip)):
         N.check(lib.vs_resize_pre_nv12(view.data_ptr(), F_, H, W, view.stride(1), view.stride(0), dec, S, S, int(aa), N.ptr(rgb), 2.0, -1.0,
                                        N.ptr(key), y_step, ym, None), "vs_resize_pre_nv12")
         torch.cuda.synchronize()
-    finally:
-        lib.vs_debug_set(0, 0)
-        lib.vs_debug_set(1, 0)
     return rgb, key
 
 
@@ -285,23 +280,20 @@ def test_red_zones_and_pitch_padding(shape, full_jnd, tiny):
     dpitch = pitch + 5
     pad = padding_mask(F_, H * 3 // 2, W, dpitch, spare)
     results = []
-    lib = N.lib()
     # (padding poison, tail form, strip height of the row-streaming tail): every combination gives the same bytes, except that the tile form
     # evaluates the full-resolution heat-map tap by tap (compared against the composition in the test above, not bit for bit here)
     for poison, variant, strip in ((0xA5, 0, 0), (0x3C, 0, 0), (0xA5, 0, 4), (0x3C, 0, 20)) + (() if full_jnd else ((0xA5, 1, 0),)):
         eng.tail_variant = variant
-        lib.vs_debug_set(2, strip)
         sbuf, sview = pitched(clip, pitch, spare, poison)
         keep = sbuf.clone()
         dbuf, dview = pitched(torch.zeros_like(clip), dpitch, spare, 0x5A)
-        with torch.cuda.device(eng.dev):
+        with torch.cuda.device(eng.dev), N.debug("TAIL_STRIP", strip):
             rgb, key = eng.resize_pre(sview, (S, S), True, want_rgb=True, want_key=True, key_step=2, tag="t.nv12", color=color)
             res = [rgb.t.clone(), key.t.clone()]
             eng.embed_tail(sview, dview, delta, step=2, video_mode=2, hmap_low=hm, attenuate=True, clamp=True, antialias=True,
                            scaling_i=1.0, scaling_w=0.2, color=color)
         torch.cuda.synchronize()
         eng.tail_variant = 0
-        lib.vs_debug_set(2, 0)
         assert torch.equal(sbuf, keep)                                        # the source is read only
         assert torch.all(dbuf[pad] == 0x5A)                                   # guards, pitch padding and spare rows of the destination
         assert not torch.equal(dview.cpu(), clip)

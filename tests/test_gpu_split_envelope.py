@@ -13,9 +13,6 @@ tests/test_gpu_fused_envelope.py.  Not here and not there: upconv_fused -- its z
 arithmetic-3 envelope of tests/test_gpu_fwd_envelope.py and the bit-identity tests of tests/test_gpu_upconv_block.py -- attention
 (tests/test_gpu_fwd_envelope.py), and range-guard / overflow behaviour of whole networks (tests/test_gpu_e2e.py, test_guards_cpu.py)."""
 import functools
-import os
-import subprocess
-import sys
 
 import pytest
 import torch
@@ -27,8 +24,6 @@ from tests._envelope import check_units  # noqa: E402
 from tests._gpu import DEV, Eng, conv_weights, dv, from_nhwc, planes_of, rows_of, to_nhwc, wgrad_gemm_launch, wgrad_gemm_operands  # noqa: E402
 from videoseal_amd import native as N  # noqa: E402
 from videoseal_amd.engine import A_MUL, Act, ConvW, rup  # noqa: E402
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 _check = functools.partial(check_units, "SPLIT-ENVELOPE", 66, R.SPLIT_MARGIN)
@@ -249,23 +244,12 @@ def test_gemm_wgrad_envelope(case):
     wgrad_gemm_check(case, variant, *wgrad_gemm_launch(case))
 
 
-@pytest.fixture(scope="module")
-def forced_wgrad_kernels(tmp_path_factory):
-    """VS_WGRAD is read once per process: the fp32 MFMA kernel (mfma) and the fp32 FMA kernel on the wide shapes (fma) run in one child each"""
-    got = {}
-    for mode in ("mfma", "fma"):
-        path = str(tmp_path_factory.mktemp("wgrad") / f"{mode}.pt")
-        env = dict(os.environ, VS_WGRAD=mode)
-        p = subprocess.run([sys.executable, "-m", "tests._split_wgrad_child", path], cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
-        assert p.returncode == 0, (mode, p.stdout[-2000:], p.stderr[-2000:])
-        got[mode] = torch.load(path)
-    return got
-
-
 @pytest.mark.parametrize("mode", ["mfma", "fma"])
 @pytest.mark.parametrize("case", R.WGRAD_GEMM_CASES, ids=[f"rows{c[0]}-N{c[1]}-K{c[2]}" for c in R.WGRAD_GEMM_CASES])
-def test_gemm_wgrad_forced_kernels_envelope(forced_wgrad_kernels, case, mode):
-    dw, dw2 = forced_wgrad_kernels[mode][R.WGRAD_GEMM_CASES.index(case)]
+def test_gemm_wgrad_forced_kernels_envelope(case, mode):
+    """the fp32 MFMA kernel (mfma) and the fp32 FMA kernel on the wide shapes (fma): what VS_WGRAD selects, here through its development switch"""
+    with N.debug("WGRAD", {"mfma": 1, "fma": 2}[mode]):
+        dw, dw2 = wgrad_gemm_launch(case)
     wgrad_gemm_check(case, f"VS_WGRAD={mode}", dw, dw2)
 
 

@@ -2,7 +2,7 @@
 
 vs_upconv_gather_ln and phase 3 of vs_upconv_fused produce the four output pixels of a low-resolution cell from 49 shared z loads; every pixel
 still receives its own 36 terms in the per-pixel order, so the outputs must be IDENTICAL (compared as bit patterns: a flipped sign of zero
-counts) to the per-pixel kernels, which the development switch 9 (VS_DBG_UPCONV_FORM = 1) selects.  The shapes walk every border case (1-wide
+counts) to the per-pixel kernels, which the development switch UPCONV_FORM = 1 selects.  The shapes walk every border case (1-wide
 maps, first / last row and column in one cell, odd sizes, more than one workgroup) and every channel-group / lanes-per-pixel pair; the smallest
 real level (32 x 32 x 64) has an edge cell in every wave.  Correctness against torch and fp64 is the business of test_gpu_kernels.py and
 test_gpu_fwd_envelope.py, which run the blocked form by default."""
@@ -20,7 +20,7 @@ from videoseal_amd.engine import ConvW, pack_conv  # noqa: E402
 
 DEV = "cuda"
 NAN = float("nan")
-KEY = 9          # VS_DBG_UPCONV_FORM (csrc/vs_common.h): 1 = per-pixel form, 0 = 2 x 2 blocks
+KEY = "UPCONV_FORM"          # VS_DBG_UPCONV_FORM (csrc/vs_common.h): 1 = per-pixel form, 0 = 2 x 2 blocks
 
 # (B, H, W, Co), wide leading dimensions in every second case
 GATHER_SHAPES = [(1, 1, 1, 16), (2, 1, 4, 16), (2, 2, 3, 16), (1, 3, 2, 32), (2, 4, 4, 64), (1, 5, 7, 32), (1, 8, 8, 128), (1, 32, 32, 64)]
@@ -32,10 +32,6 @@ FUSED_SHAPES = [(1, 1, 1, 16, 16, 16), (2, 3, 5, 16, 16, 16), (1, 8, 8, 32, 32, 
 
 def _bits(t):
     return t.contiguous().view(torch.int32)
-
-
-def _form(L, form):
-    N.check(L.vs_debug_set(KEY, form), "vs_debug_set")
 
 
 def _gather_inputs(shape, wide):
@@ -57,12 +53,9 @@ def _gather_inputs(shape, wide):
 
 def _gather(L, z, z_ld, shape, lw, lb, act, out, out_ld, form):
     B, H, W, Co = shape
-    _form(L, form)
-    try:
+    with N.debug(KEY, form):
         N.check(L.vs_upconv_gather_ln(N.ptr(z), z_ld, B, H, W, Co, N.ptr(lw), N.ptr(lb), 1e-6, act, N.ptr(out), out_ld, N.stream()), "upconv_gather_ln")
         torch.cuda.synchronize()
-    finally:
-        _form(L, 0)
 
 
 @pytest.mark.parametrize("act", ACTS)
@@ -133,13 +126,10 @@ def test_fused_blocked_equals_per_pixel(shape, arith):
     outs = []
     for form in (0, 1):
         obuf, og = _guarded(torch.full((B * 4 * H * W, Co), -3.0, device=DEV), -7.0)
-        _form(L, form)
-        try:
+        with N.debug(KEY, form):
             N.check(L.vs_upconv_fused(N.ptr(xa.t), C1, xa.ld, N.ptr(sa.t), C2, sa.ld, 2 ** -0.5, N.ptr(cw.split), B, H, W, Co, N.ptr(lw), N.ptr(lb),
                                       1e-6, N.ACT_RELU, N.ptr(og), Co, arith, 16.0, 1.0 / (16.0 * cw.w_mul), st), "upconv_fused")
             torch.cuda.synchronize()
-        finally:
-            _form(L, 0)
         assert _guards_intact(obuf, -7.0)
         outs.append(og)
     assert torch.isfinite(outs[1]).all() and bool((outs[1] != -3.0).any())

@@ -82,3 +82,28 @@ def test_no_module_under_tests_imports_a_test_module():
     pat = re.compile(r"from tests\.test_|from tests import +test_|import tests\.test_")
     bad = [(p.name, i + 1) for p in sorted([*here.glob("*.py"), *here.glob("tools/*.py")]) for i, line in enumerate(p.read_text().splitlines()) if pat.search(line)]
     assert not bad, bad
+
+
+def test_only_the_two_switch_tables_read_the_environment_and_the_docs_list_them():
+    """no launcher latches a variable of its own: csrc/api.hip reads the environment for the library (VS_DBG_KEYS, csrc/vs_common.h) and
+    videoseal_amd/switches.py for the Python side; INTEGRATION.md's table lists exactly the names of both"""
+    root = pathlib.Path(__file__).parent.parent
+    pkg = root / "videoseal_amd"
+    c_files = [p for d in (pkg / "csrc", root / "include") for p in d.rglob("*") if p.suffix in (".hip", ".h", ".hpp", ".c", ".cpp")]
+    assert len(c_files) > 20
+    assert [str(p) for p in c_files if p.name != "api.hip" and "getenv" in p.read_text()] == []
+    assert "getenv" in (pkg / "csrc" / "api.hip").read_text()
+    py = [p for p in pkg.rglob("*.py") if p.name != "switches.py"]
+    assert len(py) > 10
+    assert [str(p) for p in py if re.search(r"os\.environ|os\.getenv|\benviron\b|\bgetenv\b", p.read_text())] == []
+    from videoseal_amd import switches
+    rows = re.findall(r'^\s*X\((\w+), (?:"(\w+)"|nullptr), ', (pkg / "csrc" / "vs_common.h").read_text(), re.M)
+    assert len(rows) >= 21
+    names = {env for _, env in rows if env} | set(switches.REGISTRY)
+    assert all(re.fullmatch(r"(VIDEOSEAL|VS)_[A-Z0-9_]+", n) for n in names)
+    doc = (root / "INTEGRATION.md").read_text()
+    table = doc[doc.index("| variable | key (`vs_debug_key` name) |"):doc.index("Other handles:")]
+    cells = [re.split(r"(?<!\\)\|", line)[1:3] for line in table.splitlines()[2:] if line.startswith("|")]
+    listed = {m.group(1) for var, _ in cells for m in [re.match(r" `((?:VIDEOSEAL|VS)_[A-Z0-9_]+)", var)] if m}
+    assert listed == names
+    assert [key.strip() for _, key in cells if key.strip() != "-"] == [f"{k} `{name}`" for k, (name, _) in enumerate(rows)]      # every key, in order

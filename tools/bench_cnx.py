@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """The fused ConvNeXt block kernel (csrc/convnext_fused.hip) alone at the stage-0 / stage-1 shapes of 32 frames, statistics and apply launches;
-VS_CNX_ABL=<bits> removes pieces (1 GELU, 2 pwconv2 MFMAs, 4 pwconv1 MFMAs, 8 output stores).  usage: tools/bench_cnx.py   (GPU box)"""
+--abl walks the ablation bits (development switch CNX_ABL) in one process: (1 GELU, 2 pwconv2 MFMAs, 4 pwconv1 MFMAs, 8 output stores).  usage: tools/bench_cnx.py   (GPU box)"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -38,7 +38,7 @@ for C, HW in ((96, 4096), (192, 1024)):
     aps = lambda: N.check(L.vs_cnx_block(N.ptr(tn), N.ptr(img), C, rows, HW, 2, am1, am2, N.ptr(scale), 4 * C, N.ptr(b2), N.ptr(cur), C, N.ptr(cur), C, None, N.stream()), "a")
     # ablation bits only act in a build with -DVS_CNX_ABLATION (make EXTRA=-DVS_CNX_ABLATION; VIDEOSEAL_LIB=<that build>)
     for abl in ([0] if "--abl" not in sys.argv else [0, 1, 2, 4, 6, 7, 8, 16, 17, 23]):
-        os.environ["VS_CNX_ABL"] = str(abl)
-        ts, ta, tss, tas = timeit(st), timeit(ap), timeit(sts), timeit(aps)
+        with N.debug("CNX_ABL", abl):
+            ts, ta, tss, tas = timeit(st), timeit(ap), timeit(sts), timeit(aps)
         print(f"C={C} rows={rows} abl={abl:2d}: pipelined stats {ts*1e3:6.1f} us ({flop1/ts/1e9:6.0f} TF-eq) apply {ta*1e3:6.1f} us ({2*flop1/ta/1e9:6.0f} TF-eq)"
               f"   serial stats {tss*1e3:6.1f} us apply {tas*1e3:6.1f} us", flush=True)

@@ -74,25 +74,20 @@ def sweep(out_path):
     ym = (C.c_float * 3)(0.299, 0.587, 0.114)
     g = torch.Generator().manual_seed(7)
     res = {}
-    try:
-        for B, want_key in ((8, False), (16, False), (32, True)):
-            clip = torch.randint(0, 256, (B, 1152, 768), generator=g, dtype=torch.uint8).cuda()
-            rgb = torch.empty(B, 256, 256, 4, device="cuda")
-            key = torch.empty((B + 3) // 4, 256, 256, 4, device="cuda") if want_key else None
+    for B, want_key in ((8, False), (16, False), (32, True)):
+        clip = torch.randint(0, 256, (B, 1152, 768), generator=g, dtype=torch.uint8).cuda()
+        rgb = torch.empty(B, 256, 256, 4, device="cuda")
+        key = torch.empty((B + 3) // 4, 256, 256, 4, device="cuda") if want_key else None
 
-            def run():
-                N.check(lib.vs_resize_pre_nv12(clip.data_ptr(), B, 768, 768, 768, 1152 * 768, dec, 256, 256, 1, rgb.data_ptr(), 2.0, -1.0,
-                                               N.ptr(key), 4, ym, None), "vs_resize_pre_nv12")
-            for form, strip in [("tile", 0), ("stream", 0)] + [("stream", s) for s in (8, 12, 16, 24, 32, 48, 64)]:
-                lib.vs_debug_set(0, 1 if form == "tile" else 0)
-                lib.vs_debug_set(1, strip)
+        def run():
+            N.check(lib.vs_resize_pre_nv12(clip.data_ptr(), B, 768, 768, 768, 1152 * 768, dec, 256, 256, 1, rgb.data_ptr(), 2.0, -1.0,
+                                           N.ptr(key), 4, ym, None), "vs_resize_pre_nv12")
+        for form, strip in [("tile", 0), ("stream", 0)] + [("stream", s) for s in (8, 12, 16, 24, 32, 48, 64)]:
+            with N.debug("RESIZE_FORM", 1 if form == "tile" else 0), N.debug("RESIZE_STRIP", strip):
                 limited(lambda: [run() for _ in range(5)], "sweep warm-up")
                 ms = timed_ms(lambda: [run() for _ in range(50)], "sweep")
-                name = form if form == "tile" else ("stream, default strip" if strip == 0 else f"stream, strip {strip}")
-                res.setdefault(f"{B} frames" + (" + key frames" if want_key else ""), {})[name] = round(ms / 50 * 1e3, 1)
-    finally:
-        lib.vs_debug_set(0, 0)
-        lib.vs_debug_set(1, 0)
+            name = form if form == "tile" else ("stream, default strip" if strip == 0 else f"stream, strip {strip}")
+            res.setdefault(f"{B} frames" + (" + key frames" if want_key else ""), {})[name] = round(ms / 50 * 1e3, 1)
     doc = {"tool": "tools/bench_nv12.py --sweep", "when": time.strftime("%Y-%m-%d %H:%M:%S"), "device": torch.cuda.get_device_name(0),
            "what": "us per launch of vs_resize_pre_nv12, 768x768 -> 256x256, antialias, 50 launches per figure", "us_per_launch": res}
     os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)

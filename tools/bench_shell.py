@@ -24,9 +24,8 @@ def timeit(fn, reps=20):
 for aa in (1, 0):
     ms = timeit(lambda: N.check(L.vs_resize_pre(N.ptr(x), B, 3, H, W, S, S, aa, N.ptr(rgb), 2.0, -1.0, None, 1, None, N.stream()), "r"))
     print(f"resize_pre fp32 aa={aa}: {ms*1e3:7.1f} us  {(x.numel()*4 + rgb.numel()*4)/ms/1e6:7.0f} GB/s   (row-streaming separable form)")
-    L.vs_debug_set(0, 1)
-    ms = timeit(lambda: N.check(L.vs_resize_pre(N.ptr(x), B, 3, H, W, S, S, aa, N.ptr(rgb), 2.0, -1.0, None, 1, None, N.stream()), "r"))
-    L.vs_debug_set(0, 0)
+    with N.debug("RESIZE_FORM", 1):
+        ms = timeit(lambda: N.check(L.vs_resize_pre(N.ptr(x), B, 3, H, W, S, S, aa, N.ptr(rgb), 2.0, -1.0, None, 1, None, N.stream()), "r"))
     print(f"resize_pre fp32 aa={aa}: {ms*1e3:7.1f} us  {(x.numel()*4 + rgb.numel()*4)/ms/1e6:7.0f} GB/s   (32 x 8 tile form)")
     ms = timeit(lambda: N.check(L.vs_resize_pre_u8(N.ptr(xu), B, H, W, S, S, aa, N.ptr(rgb), 2.0, -1.0, None, 1, None, N.stream()), "r"))
     print(f"resize_pre u8   aa={aa}: {ms*1e3:7.1f} us  {(xu.numel() + rgb.numel()*4)/ms/1e6:7.0f} GB/s")
@@ -61,8 +60,11 @@ for name, u8, att, low, wpw in [("fp32 full JND + preds_w", 0, 1, 0, 1), ("fp32 
     nbytes = (2 * xu.numel() if u8 else 2 * x.numel() * 4) + (pw.numel() * 4 if wpw else 0)
     print(f"embed_tail {name:24s}: {ms*1e3:7.1f} us  {nbytes/ms/1e6:7.0f} GB/s")
 # the forms of the fp32 tail side by side (vs_tail_desc_t::variant): 1 = 43-tap JND on 16-row tiles, 2 = separable stencils on 16-row tiles,
-# 4 = row-streaming strips (default); VS_TAIL_STRIP=<rows> overrides the strip height of the streaming form
+# 4 = row-streaming strips (default); the development switch TAIL_STRIP (argument strip=<rows>, or VS_TAIL_STRIP in the environment)
+# overrides the strip height of the streaming form
+STRIP = next((int(a[6:]) for a in sys.argv[1:] if a.startswith("strip=")), 0)
 for name, att, low in [("fp32 full JND", 1, 0), ("fp32 lowres JND", 1, 1), ("fp32 no JND", 0, 0)]:
     for variant in (1, 2, 4):
-        ms = timeit(tail(0, att, low, 0, variant=variant))
+        with N.debug("TAIL_STRIP", STRIP):
+            ms = timeit(tail(0, att, low, 0, variant=variant))
         print(f"embed_tail {name:18s} variant {variant}: {ms*1e3:7.1f} us  {2 * x.numel() * 4/ms/1e6:7.0f} GB/s")

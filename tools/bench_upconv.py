@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Upsample groups of the VideoSeal 1.0 U-Net at B = 32 (levels 0..2): fused one-kernel form vs cat2 + 9-tap GEMM + gather, HIP-event
 times; gather + LN and the fused kernel in both forms of the gather -- 2 x 2 blocks (csrc/upconv_gather.h, the default) and per pixel
-(vs_debug_set key 9 = 1) --, alternating in one process.  GPU box only."""
+(development switch UPCONV_FORM = 1) --, alternating in one process.  GPU box only."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -44,11 +44,8 @@ for (H, C1, C2, Co) in ((32, 384, 384, 64), (64, 64, 64, 32), (128, 32, 32, 16))
         best = [1e9, 1e9]
         for _ in range(2):
             for form in (0, 1):
-                L.vs_debug_set(9, form)
-                try:
+                with N.debug("UPCONV_FORM", form):
                     best[form] = min(best[form], timeit(fn))
-                finally:
-                    L.vs_debug_set(9, 0)
         return best
     t = [timeit(f) for f in (cat, gemm)]
     tg = both_forms(gath)

@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Attention of the legacy videoseal_0.0 card's ViT extractor (vs_vit_attention: 16 x 16 tokens, 6 heads of 64; windows of 8 x 8 or global):
-time per call of the kernel the library selects (matrix cores; VS_VIT_ATTN=valu in the environment = the vector kernel) and the detect
+time per call of the matrix-core kernel and of the vector kernel (development switch VIT_ATTN = 1), alternating in one process, and the detect
 step of the card.  usage: tools/bench_vit.py [frames]   (GPU box)"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -33,10 +33,11 @@ def timed(fn, n=20):
 for win in (8, 0):
     T = win * win if win else H * W
     rel = torch.randn(2 * (win or H) - 1, hd, generator=g).cuda() * 0.3
-    us = timed(lambda: N.check(L.vs_vit_attention(N.ptr(qkv), B, H, W, heads, hd, win, N.ptr(rel), N.ptr(rel), N.ptr(out), st), "attn"))
     flop = 4.0 * B * (H * W) * T * D          # q k^T and p v
-    print(f"attention, {B} frames, {'window 8' if win else 'global'} ({T} keys per query): {us:.1f} us = {flop / us * 1e-6:.1f} TFLOP/s "
-          f"[{os.environ.get('VS_VIT_ATTN', 'mfma')}]")
+    for form, name in ((0, "mfma"), (1, "valu")):
+        with N.debug("VIT_ATTN", form):
+            us = timed(lambda: N.check(L.vs_vit_attention(N.ptr(qkv), B, H, W, heads, hd, win, N.ptr(rel), N.ptr(rel), N.ptr(out), st), "attn"))
+        print(f"attention, {B} frames, {'window 8' if win else 'global'} ({T} keys per query): {us:.1f} us = {flop / us * 1e-6:.1f} TFLOP/s [{name}]")
 model = videoseal_amd.build("videoseal_0.0").eval().to("cuda")
 frames = torch.rand(B, 3, 256, 256, device="cuda")
 us = timed(lambda: model.detector(frames), 10)

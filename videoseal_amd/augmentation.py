@@ -18,7 +18,6 @@ from __future__ import annotations
 
 import ctypes as C
 import math
-import os
 import warnings
 from typing import Dict, List, Optional, Tuple
 
@@ -28,8 +27,9 @@ import torch.nn.functional as F
 
 from . import autograd as AG
 from . import native as N
+from . import switches as SW
 
-FUSE = os.environ.get("VIDEOSEAL_AUG_FUSE", "1") != "0"     # Sequential: consecutive Crop / Resize / colour ops in fused passes (round 5)
+FUSE = SW.flag("VIDEOSEAL_AUG_FUSE", True)     # Sequential: consecutive Crop / Resize / colour ops in fused passes (round 5)
 TIMERS = None         # bench.py: a list -> every fused / JPEG launch group appends (name, start event, end event, algorithmic bytes)
 
 
@@ -697,9 +697,7 @@ class VideoCompression(_Aug):
         super().__init__()
         self.codec, self.crf, self.fps = codec, crf, fps
         self.pix_fmt = "yuv420p" if codec != "libx264rgb" else "rgb24"
-        self.backend = os.environ.get("VIDEOSEAL_CODEC", "proxy")
-        if self.backend not in ("proxy", "pyav"):
-            raise ValueError(f"VIDEOSEAL_CODEC={self.backend!r}: expected 'proxy' or 'pyav'")
+        self.backend = SW.choice("VIDEOSEAL_CODEC", "proxy", ("proxy", "pyav"))
 
     def _pyav_roundtrip(self, frames: torch.Tensor, crf: int) -> torch.Tensor:
         try:

@@ -818,8 +818,7 @@ extern "C" int vs_aug_crop_resize_color(const float* src, float* dst, int F, int
     cc.factor[k] = factors[k];
   }
   // the row-streaming form where its windows fit (resize_stream.h); VIDEOSEAL_CROP_RESIZE=tile / vs_debug_set(4, 1) keep the 32 x 8 tile kernel
-  static const bool env_tile = [] { const char* e = getenv("VIDEOSEAL_CROP_RESIZE"); return e && !strcmp(e, "tile"); }();
-  const int OWsel = (env_tile || vs_debug_get(VS_DBG_CROP_RESIZE_FORM) == 1) ? 0 : vs_rs::rs_pick(ch, cw, oh, ow, antialias);
+  const int OWsel = vs_debug_get(VS_DBG_CROP_RESIZE_FORM) == 1 ? 0 : vs_rs::rs_pick(ch, cw, oh, ow, antialias);
   if (OWsel) {
     const int cols = (ow + OWsel - 1) / OWsel;
     int strip = 32;
@@ -913,8 +912,7 @@ extern "C" int vs_jpeg_roundtrip(const float* src, float* dst, int F, int H, int
   unsigned char* Cb = Y + (int64_t)F * Hp * Wp;
   unsigned char* Cr = Cb + (int64_t)F * (Hp / 2) * (Wp / 2);
   // whole-MCU frames with 16-byte-aligned tensors take the vector kernels (same bytes); VIDEOSEAL_JPEG=scalar / vs_debug_set(3, 1) keep the scalar ones
-  static const bool env_scalar = [] { const char* e = getenv("VIDEOSEAL_JPEG"); return e && !strcmp(e, "scalar"); }();
-  const bool vec = !env_scalar && vs_debug_get(VS_DBG_JPEG_FORM) != 1 && H % 16 == 0 && W % 16 == 0 &&
+  const bool vec = vs_debug_get(VS_DBG_JPEG_FORM) != 1 && H % 16 == 0 && W % 16 == 0 &&
                    ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst) | reinterpret_cast<uintptr_t>(workspace)) & 15) == 0 &&
                    ((int64_t)F * Hp * Wp) % 16 == 0;
   if (vec) hipLaunchKernelGGL(jpeg_ycc4_kernel, dim3((W / 4 + 63) / 64, (H / 2 + 3) / 4, F), dim3(256), 0, st, src, H, W, Y, Cb, Cr);

@@ -852,10 +852,11 @@ static inline unsigned blocks_for(int64_t n) { return (unsigned)cdiv64(n, 256); 
 }  // namespace
 
 // ===================================================================================================== C-ABI
-// kernel choice and number of row slices: functions of the shape (and of VS_WGRAD, read once) only -- the summation order never depends on the launch
+// kernel choice and number of row slices: functions of the shape (and of the development switch VS_DBG_WGRAD / VS_WGRAD) only -- the summation order
+// never depends on the launch
 static int wgrad_mode() {
-  static const int mode = [] { const char* e = getenv("VS_WGRAD"); return !e ? 0 : (!strcmp(e, "mfma") ? 1 : (!strcmp(e, "fma") ? 2 : 0)); }();
-  return mode;
+  const int mode = vs_debug_get(VS_DBG_WGRAD);
+  return mode == 1 || mode == 2 ? mode : 0;
 }
 static int64_t wgrad_splits(int64_t rows, int N, int64_t K) {
   int64_t splits, maxs = cdiv64(rows, 256);

@@ -582,7 +582,7 @@ __global__ __launch_bounds__(256) void cnx_pipe_kernel(const CnxArgs a) {
 template <int KS1, int PB>
 int launch_cnx(const CnxArgs& a, bool stats, bool serial, hipStream_t st) {
   const unsigned grid = (unsigned)(a.rows / (128 * PB));
-  static const bool pipe = [] { const char* e = getenv("VS_CNX_PIPE"); return e ? atoi(e) != 0 : true; }();   // (A/B handle: 0 = cnx_block_kernel)
+  const bool pipe = vs_debug_get(VS_DBG_CNX_PIPE) != 1;   // (A/B handle: VS_CNX_PIPE=0 / key value 1 = cnx_block_kernel)
   if (pipe && !serial) {
     if (stats) hipLaunchKernelGGL((cnx_pipe_kernel<KS1, PB, true>), dim3(grid), dim3(256), 0, st, a);
     else hipLaunchKernelGGL((cnx_pipe_kernel<KS1, PB, false>), dim3(grid), dim3(256), 0, st, a);
@@ -617,7 +617,7 @@ extern "C" int vs_cnx_block(const void* tn_planes, const void* wimg, int C, int6
   CnxArgs a{static_cast<const char*>(tn_planes), static_cast<const char*>(wimg), scale, bias2, res, out, part32, rows, scale_ld, res_ld, out_ld, HW,
             acc_mul1, acc_mul2, 0};
 #ifdef VS_CNX_ABLATION
-  { const char* e = getenv("VS_CNX_ABL"); a.abl = e ? atoi(e) : 0; }        // (read per call: tools/bench_cnx.py walks the bits in one process)
+  a.abl = vs_debug_get(VS_DBG_CNX_ABL);        // (tools/bench_cnx.py walks the bits in one process)
 #endif
   // C = 96: the statistics launch takes 64 pixels per wave (weight fragments shared by two pixel blocks, one wave per SIMD: 52 vs 56 us at 32
   // frames), the apply launch 32 (139 + 80 registers: TWO workgroups per CU, whose MFMAs cover each other's GELU / split arithmetic: 103 vs 130 us)

@@ -646,7 +646,7 @@ int launch_g(const vs_conv_desc_t& d, hipStream_t st) {
   // same bound and keep a 64-bit path; this kernel has only the 32-bit one)
   if ((int64_t)BM * std::max<int64_t>(std::max<int64_t>(d.out_ld, d.res ? d.res_ld : 0), sk > 1 ? d.splitk_ld : 0) * 4 >= (1LL << 31)) return VS_ERR_UNSUPPORTED;
   const int ntot = (int)(mt * nt * sk);
-  static const int force_grid = [] { const char* e = getenv("VS_GEMM_GRID"); return e ? atoi(e) : 0; }();      // experiments: 0 = one workgroup per CU
+  const int force_grid = vs_debug_get(VS_DBG_GEMM_GRID);      // experiments: 0 = one workgroup per CU
   const int grid = std::min(ntot, force_grid > 0 ? force_grid : vs_num_cus());
   if (d.arith == 2) {
     if (d.a_scale && pps * 32 <= GRN_KCAP / 2)
@@ -673,8 +673,7 @@ int vs_splitk_epilogue(const vs_conv_desc_t& d, int M, hipStream_t st) {
   if ((d.splitk_ld & 3) || ((uintptr_t)d.splitk_ws & 15)) return VS_ERR_BAD_ARG;
   const int vec = ((d.out_ld & 3) == 0 && (d.out_coff & 3) == 0 && ((uintptr_t)d.out & 15) == 0) ? 1 : 0;
   // every operand in whole 16-byte pieces: the form with all loads of an item in flight at once (VS_SPLITK_EPI=scalar keeps the first form; experiments)
-  static const bool scalar_only = [] { const char* e = getenv("VS_SPLITK_EPI"); return e && e[0] == 's'; }();
-  const bool wide = !scalar_only && vs_debug_get(VS_DBG_SPLITK_EPI) != 1 && (vec || !d.out) && (d.N & 3) == 0 && (d.n_store & 3) == 0 && (!d.bias || ((uintptr_t)d.bias & 15) == 0) &&
+  const bool wide = vs_debug_get(VS_DBG_SPLITK_EPI) != 1 && (vec || !d.out) && (d.N & 3) == 0 && (d.n_store & 3) == 0 && (!d.bias || ((uintptr_t)d.bias & 15) == 0) &&
                     (!d.bias2 || ((uintptr_t)d.bias2 & 15) == 0) && (!d.res || (((uintptr_t)d.res & 15) == 0 && (d.res_ld & 3) == 0));
   if (wide) {
     const dim3 grid((unsigned)cdiv64((int64_t)M * (d.n_store / 4), 256));

@@ -522,6 +522,12 @@ __global__ __launch_bounds__(256, 1) void gemm_pl_big_kernel(const vs_conv_desc_
                                   d.n_store - (n0 + wn * TN * 32));
 }
 
+// XCD-aware grouped tile order for launches of at least `rounds` tiles per CU: tiles per XCD, or 0 = the row-major order (which the development
+// switch VS_DBG_GEMM_PL_RASTER / VS_GEMM_PL_RASTER=0 keeps everywhere)
+static int tiles_per_xcd(int64_t tiles, int rounds) {
+  return (vs_debug_get(VS_DBG_GEMM_PL_RASTER) != 1 && tiles >= (int64_t)rounds * vs_num_cus()) ? (int)((tiles + 7) / 8) : 0;
+}
+
 template <int TN>
 int launch_gpl_big(const vs_conv_desc_t& d, hipStream_t st) {
   constexpr int BN = 64 * TN;
@@ -534,8 +540,7 @@ int launch_gpl_big(const vs_conv_desc_t& d, hipStream_t st) {
   if (mt * nt * sk > 0x7fffffffLL || M > 0x7fffffffLL) return VS_ERR_UNSUPPORTED;
   if ((int64_t)GBM * std::max<int64_t>(std::max<int64_t>(d.out_ld, d.res ? d.res_ld : 0), sk > 1 ? d.splitk_ld : 0) * 4 >= (1LL << 31)) return VS_ERR_UNSUPPORTED;
   if (vs_max_lds_bytes() < BIG_NS * (A_STAGE + 2 * TN * 2048)) return VS_ERR_UNSUPPORTED;
-  static const bool raster = [] { const char* e = getenv("VS_GEMM_PL_RASTER"); return !(e && e[0] == '0'); }();
-  const int per_xcd = (raster && mt * nt >= 2 * vs_num_cus()) ? (int)((mt * nt + 7) / 8) : 0;
+  const int per_xcd = tiles_per_xcd(mt * nt, 2);
   const int64_t grid = per_xcd > 0 ? (int64_t)8 * per_xcd * sk : mt * nt * sk;
   hipLaunchKernelGGL((gemm_pl_big_kernel<TN>), dim3((unsigned)grid), dim3(256), 0, st, d, (int)M, (int)mt, (int)nt, sps, per_xcd);
   int rc = vs_launch_status();
@@ -636,9 +641,7 @@ int launch_gpl(const vs_conv_desc_t& d, hipStream_t st) {
   if (sk > 1 && (int64_t)(sk - 1) * sps >= nsteps) return VS_ERR_BAD_ARG;       // an empty K slice
   if (mt * nt * sk > 0x7fffffffLL || M > 0x7fffffffLL) return VS_ERR_UNSUPPORTED;
   if (TN == 3 && sk == 1 && d.act == VS_ACT_TANH) return VS_ERR_UNSUPPORTED;       // (the TN = 3 register tile is compiled without the tanh epilogue; tile 25 / 27 have it)
-  // XCD-aware grouped tile order for launches of several rounds (VS_GEMM_PL_RASTER=0: the row-major order)
-  static const bool raster = [] { const char* e = getenv("VS_GEMM_PL_RASTER"); return !(e && e[0] == '0'); }();
-  const int per_xcd = (raster && mt * nt >= 4 * vs_num_cus()) ? (int)((mt * nt + 7) / 8) : 0;
+  const int per_xcd = tiles_per_xcd(mt * nt, 4);
   const int64_t grid = per_xcd > 0 ? (int64_t)8 * per_xcd * sk : mt * nt * sk;
   hipLaunchKernelGGL((gemm_pl_kernel<TN>), dim3((unsigned)grid), dim3(512), 0, st, d, (int)M, (int)mt, (int)nt, sps, per_xcd);
   int rc = vs_launch_status();

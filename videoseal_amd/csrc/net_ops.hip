@@ -1187,8 +1187,7 @@ extern "C" int vs_layernorm_act(const float* x, int64_t rows, int C, int64_t ld,
   // lanes-per-row form (round 6): 16-byte aligned rows, the output's pad lanes within reach of the lanes that own the row; the affine parameters
   // must be readable in whole float4 (the engine pads them to ld; vs_layernorm_act's contract says C entries: only C % 4 == 0 takes this form then)
   const int C4 = (C + 3) / 4, O4 = (int)(out_ld / 4);
-  static const bool env_wave = [] { const char* e = getenv("VIDEOSEAL_LN"); return e && !strcmp(e, "wave"); }();      // A/B handle
-  if (!env_wave && vs_debug_get(VS_DBG_LN_FORM) != 1 && ld % 4 == 0 && out_ld % 4 == 0 && C % 4 == 0 && O4 <= 64 * 12 &&
+  if (vs_debug_get(VS_DBG_LN_FORM) != 1 && ld % 4 == 0 && out_ld % 4 == 0 && C % 4 == 0 && O4 <= 64 * 12 &&
       (((uintptr_t)x | (uintptr_t)out | (uintptr_t)w | (uintptr_t)b) & 15) == 0 && rows < (1LL << 31)) {
     const int n4 = O4 > C4 ? O4 : C4;
     hipStream_t st = (hipStream_t)stream;
@@ -1335,7 +1334,7 @@ static int dwconv7_ln_any(const float* x, int B, int H, int W, int C, int64_t ld
   // LDS-tiled kernels where the tile + the [pixel][channel] LayerNorm buffer fit the 160 KB of a CU and the map is large enough to
   // give every CU a tile; every variant produces bit-identical values (same FMA order), so the choice is purely a speed matter.
   // VS_DWCONV=0 forces the one-row kernel, 1 / 2 a tiled configuration (tools/bench_dwconv.py).
-  static const int force = [] { const char* e = getenv("VS_DWCONV"); return e ? atoi(e) : -1; }();
+  const int force = vs_debug_get(VS_DBG_DWCONV) - 1;         // the key holds 1 + configuration: -1 = the rule below
   {
     const int64_t hw = (int64_t)H * W;
     int cfg = 0;
@@ -1367,9 +1366,8 @@ static int dwconv7_ln_any(const float* x, int B, int H, int W, int C, int64_t ld
   // 31 x 31 x 1472, 16 frames 161.6 -> 112.4 us; 15 x 15 x 2912 97.1 -> 86.5; 8 x 8 x 768, 32 frames 22.8 -> 15.1 us.  The conv values are bit-identical
   // to the single-row strips; the LayerNorm behind them sums a pixel's channels over more or fewer lanes depending on the pixels per workgroup
   // (ln_rows_from_lds), so the outputs agree to fp32 rounding, not bit for bit
-  static const int force_rows = [] { const char* e = getenv("VS_DWCONV_ROWS"); return e ? atoi(e) : 0; }();
   const int dbg_rows = vs_debug_get(VS_DBG_DWCONV_ROWS);                    // tests: 1 / 2 rows per strip whatever the shape
-  const bool two = dbg_rows ? dbg_rows == 2 : force_rows ? force_rows == 2 : (NS == 1 && H >= 2 && (int64_t)B * ((H + 1) / 2) * spr >= vs_num_cus());
+  const bool two = dbg_rows ? dbg_rows == 2 : (NS == 1 && H >= 2 && (int64_t)B * ((H + 1) / 2) * spr >= vs_num_cus());
   const int R = two ? 2 : 1;
   const int64_t nstrips = (int64_t)B * ((H + R - 1) / R) * spr;
   const size_t smem = ((size_t)NS * 4 * R * (ld + 4) + 2 * (size_t)C) * sizeof(float);

@@ -1642,9 +1642,7 @@ extern "C" int vs_resize_pre(const float* src, int B, int C, int H, int W, int o
   const float y0 = ymat3 ? ymat3[0] : 0.f, y1 = ymat3 ? ymat3[1] : 0.f, y2 = ymat3 ? ymat3[2] : 0.f;
   // row-streaming separable kernel (default) where its windows fit: 3 planes, <= 8 taps per direction, <= 448 input columns per 128 outputs
   // (scales up to 3.4); VIDEOSEAL_RESIZE=tile keeps the 32 x 8 tile kernel, VS_RESIZE_STRIP=<output rows> overrides the strip height
-  static const bool env_tile = [] { const char* e = getenv("VIDEOSEAL_RESIZE"); return e && !strcmp(e, "tile"); }();       // process-wide default, read once
-  const bool tile_only = env_tile || vs_debug_get(VS_DBG_RESIZE_FORM) == 1;
-  static const int env_strip = [] { const char* e = getenv("VS_RESIZE_STRIP"); return e ? atoi(e) : 0; }();
+  const bool tile_only = vs_debug_get(VS_DBG_RESIZE_FORM) == 1;
   // two tile shapes (resize_stream.h): 128 output columns for scales up to 3.4 (<= 8 taps), 64 columns for scales up to 4 (<= 10 taps, 1024 -> 256)
   const int OWsel = vs_rs::rs_pick(H, W, oh, ow, antialias);
   if (!tile_only && C == 3 && OWsel) {
@@ -1652,7 +1650,6 @@ extern "C" int vs_resize_pre(const float* src, int B, int C, int H, int W, int o
     int strip = 32;
     for (int cand : {64, 48, 32, 24, 16})            // tallest strip that still gives every CU two workgroups (one round at two resident per CU)
       if ((int64_t)cols * ((oh + cand - 1) / cand) * B >= 512) { strip = cand; break; }
-    if (env_strip >= 2) strip = env_strip;
     if (const int v = vs_debug_get(VS_DBG_RESIZE_STRIP); v >= 1) strip = v;       // tests: any strip height, per call
     dim3 gs(cols, (oh + strip - 1) / strip, B);
     const size_t lds = OWsel == 128 ? vs_rs::rs_lds_bytes<128>() : vs_rs::rs_lds_bytes<64>();
@@ -1707,13 +1704,12 @@ extern "C" int vs_embed_tail(const vs_tail_desc_t* d, void* stream) {
   // barriers before the first output row), not HBM traffic, is what the tail pays for (profiles/r03s_shell_keep_form.log)
   // VIDEOSEAL_TAIL: stream (default) = the row-streaming kernel where it applies, sep = separable stencils on 16-row tiles (round 3's default),
   // v1 = 43-tap form, keep = 8-row tiles with the pixels parked in LDS.  d->variant (1 = v1, 2 = sep, 3 = keep, 4 = stream) overrides it per call.
-  static const int env_mode = [] { const char* e = getenv("VIDEOSEAL_TAIL"); return !e ? 3 : (!strcmp(e, "v1") ? 0 : (!strcmp(e, "keep") ? 2 : (!strcmp(e, "sep") ? 1 : 3))); }();
-  const int mode = d->variant >= 1 && d->variant <= 4 ? d->variant - 1 : env_mode;
+  const int form = d->variant >= 1 && d->variant <= 4 ? d->variant : vs_debug_get(VS_DBG_TAIL_FORM);
+  const int mode = form >= 1 && form <= 4 ? form - 1 : 3;
   const bool full_jnd = d->attenuate && !d->hmap_lowres;
   const bool sep = mode > 0 && full_jnd && d->taps43 && standard_jnd_taps(d->taps43);
   if (mode == 3 && !d->io_u8 && (sep || !full_jnd) && d->W >= 2 * d->S_w && d->H >= 2 * d->S_h) {
     // VS_TAIL_STRIP overrides the strip height
-    static const int env_strip = [] { const char* e = getenv("VS_TAIL_STRIP"); return e ? atoi(e) : 0; }();
     const int64_t cols = (d->W + TTW - 1) / TTW;
     // strip height, from tools/bench_tail_sweep.py (profiles/r04zz_tail_sweep.log, 768^2; us for 16 / 32 / 128 frames): without the luminance phase
     // short strips win (32 rows 43 / 104 / 364, 48 rows 44 / 94 / 360, 96 rows 61 / 114 / 354); with it the strip should be tall (4 halo rows + the
@@ -1725,7 +1721,6 @@ extern "C" int vs_embed_tail(const vs_tail_desc_t* d, void* stream) {
     } else if (cols * ((d->H + 47) / 48) * d->F >= 1024) {
       strip = 48;
     }
-    if (env_strip >= 4) strip = (env_strip + 3) / 4 * 4;
     if (const int v = vs_debug_get(VS_DBG_TAIL_STRIP); v >= 4) strip = (v + 3) / 4 * 4;     // tests: every strip height, per call
     dim3 gs((unsigned)cols, (d->H + strip - 1) / strip, d->F);
     const size_t lds_w = (size_t)2 * d->Cd * DW_W * DW_H * sizeof(float);

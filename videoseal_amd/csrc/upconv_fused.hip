@@ -311,7 +311,7 @@ int launch_fused(const float* x, int C1, int64_t ld1, const float* skip, int C2,
   const int tiles_x = (W + UT - 1) / UT, tiles_y = (H + UT - 1) / UT;
   const int64_t nblk = (int64_t)B * tiles_x * tiles_y;
   if (nblk >= (1 << 30)) return VS_ERR_UNSUPPORTED;
-  static const int abl = [] { const char* e = getenv("VS_UPCONV_ABL"); return e ? atoi(e) : 0; }();
+  const int abl = vs_debug_get(VS_DBG_UPCONV_ABL);
   const int form = vs_debug_get(VS_DBG_UPCONV_FORM) == 1 ? 4 : 0;      // abl bit 4: per-pixel phase 3
   hipLaunchKernelGGL(kern, dim3((unsigned)((nblk + 7) / 8 * 8)), dim3(256), smem, st, x, C1, ld1, skip, C2, ld2, s,
                      static_cast<const unsigned short*>(wsplit), H, W, Co, lnw, lnb, eps, act, out, old, tiles_x, tiles_y, (int)nblk, abl | form, a_mul, acc_mul);

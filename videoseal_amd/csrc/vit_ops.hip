@@ -371,7 +371,7 @@ extern "C" int vs_vit_attention(const float* qkv, int frames, int H, int W, int 
   if (Th > 16 || Tw > 16 || Th * Tw > 256) return VS_ERR_UNSUPPORTED;
   hipStream_t st = (hipStream_t)stream;
   // matrix-core kernel for 64 / 128 / 256 tokens per group (VS_VIT_ATTN=valu forces the vector kernel: A/B and the odd shapes' path)
-  static const bool valu = [] { const char* e = getenv("VS_VIT_ATTN"); return e && !strcmp(e, "valu"); }();
+  const bool valu = vs_debug_get(VS_DBG_VIT_ATTN) == 1;
   const int T = Th * Tw;
   if (!valu && (T == 64 || T == 128 || T == 256) && (hd == 16 || hd == 32 || hd == 64)) {
 #define VS_ATT(HD_, NT_) return launch_attn_mfma<HD_, NT_>(qkv, frames, H, W, heads, window, rel_h, rel_w, out, st)

@@ -19,25 +19,50 @@ static inline int vs_launch_status() { return hipGetLastError() == hipSuccess ? 
 
 static inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// Development switches of the launchers: ONE list for the key numbers (VS_DBG_<name>), the names vs_debug_key() answers to and the environment
+// defaults.  A launcher asks vs_debug_get(key) and nothing else: the value vs_debug_set gave the key when that is non-zero, else the key's
+// environment default, else 0 = the library's own choice.  api.hip reads the environment for the whole list once, at the first vs_debug_get /
+// vs_debug_set of the process; no other file of the library reads the environment (not thread-safe against setenv).
+//   X(name, variable or nullptr, words, bias, min, meaning)
+//   words: "word=value,..." -- the variable's text must equal a word ("word*": start with it); nullptr: value = atoi(text) + bias
+//   min:   the smallest value that counts as set; anything below is ignored (VS_DBG_ANY: every non-zero value)
+// Keys 0 - 9 keep their numbers (tests and tools of earlier rounds); new keys go at the end.
+#define VS_DBG_ANY (-0x7fffffff - 1)
+#define VS_DBG_KEYS(X)                                                                                                                              \
+  X(RESIZE_FORM, "VIDEOSEAL_RESIZE", "tile=1", 0, 1, "vs_resize_pre(_nv12): 1 = the 32 x 8 tile kernel")                                            \
+  X(RESIZE_STRIP, "VS_RESIZE_STRIP", nullptr, 0, 2, "vs_resize_pre(_nv12): strip height in output rows (the variable from 2, the key from 1)")      \
+  X(TAIL_STRIP, "VS_TAIL_STRIP", nullptr, 0, 4, "vs_embed_tail(_nv12): strip height in rows, rounded up to 4 (from 4)")                             \
+  X(JPEG_FORM, "VIDEOSEAL_JPEG", "scalar=1", 0, 1, "JPEG round trip: 1 = the one-pixel-per-lane kernels")                                           \
+  X(CROP_RESIZE_FORM, "VIDEOSEAL_CROP_RESIZE", "tile=1", 0, 1, "Crop -> Resize -> colour: 1 = the 32 x 8 tile kernel")                              \
+  X(TO_PLANES_FORM, nullptr, nullptr, 0, 1, "vs_to_planes_affine: 1 = one row per wave")                                                            \
+  X(DWCONV_ROWS, "VS_DWCONV_ROWS", nullptr, 0, VS_DBG_ANY, "one-row depthwise kernel: 2 = two output rows per strip, any other value = one")        \
+  X(LN_FORM, "VIDEOSEAL_LN", "wave=1", 0, 1, "vs_layernorm_act: 1 = one wave per row")                                                              \
+  X(SPLITK_EPI, "VS_SPLITK_EPI", "s*=1", 0, 1, "K-slice epilogue: 1 = the first kernel, one load in flight per thread (VS_SPLITK_EPI=scalar)")      \
+  X(UPCONV_FORM, nullptr, nullptr, 0, 1, "vs_upconv_gather_ln and phase 3 of vs_upconv_fused: 1 = per-pixel gather instead of 2 x 2 blocks")        \
+  X(TAIL_FORM, "VIDEOSEAL_TAIL", "v1=1,sep=2,keep=3", 0, 1, "vs_embed_tail: the numbers of vs_tail_desc_t::variant (which overrides it per call)")  \
+  X(VIT_ATTN, "VS_VIT_ATTN", "valu=1", 0, 1, "vs_vit_attention: 1 = the vector kernel on the matrix-core shapes too")                               \
+  X(WGRAD, "VS_WGRAD", "mfma=1,fma=2", 0, 1, "vs_gemm_wgrad: 1 = the fp32 matrix-core kernel, 2 = the fp32 vector kernel, everywhere")              \
+  X(DWCONV, "VS_DWCONV", nullptr, 1, 1, "depthwise 7 x 7 + LayerNorm: 1 + configuration (1 = the one-row kernel, 2.. = tiled; VS_DWCONV=0 -> 1)")    \
+  X(GEMM_GRID, "VS_GEMM_GRID", nullptr, 0, 1, "wave-specialised 1 x 1 GEMM: workgroups of the persistent grid instead of one per CU")               \
+  X(GEMM_PL_RASTER, "VS_GEMM_PL_RASTER", "0*=1", 0, 1, "planes GEMMs: 1 = row-major tile order instead of the XCD-grouped one (the variable: 0)")    \
+  X(CNX_PIPE, "VS_CNX_PIPE", nullptr, 1, 1, "fused ConvNeXt block: 1 = the serial cnx_block_kernel (VS_CNX_PIPE=0), any other value = the pipeline") \
+  X(CNX_ABL, "VS_CNX_ABL", nullptr, 0, VS_DBG_ANY, "fused ConvNeXt block: ablation bits (builds with VS_CNX_ABLATION only)")                        \
+  X(UPCONV_ABL, "VS_UPCONV_ABL", nullptr, 0, VS_DBG_ANY, "vs_upconv_fused: ablation bits")                                                          \
+  X(STEM_FUSED, "VIDEOSEAL_STEM_FUSED", "1*=1", 0, 1, "vs_model_detect: 1 = stem conv + LayerNorm in one kernel")                                   \
+  X(ARITH, "VIDEOSEAL_CONV", "f16x2=2,bf16x3=3", 0, 2, "default vs_conv_desc_t::arith of the model-level entry points")
+#define VS_DBG_ENUM(name, env, words, bias, min, doc) VS_DBG_##name,
+enum { VS_DBG_KEYS(VS_DBG_ENUM) VS_DBG_COUNT };
+#undef VS_DBG_ENUM
+static_assert(VS_DBG_RESIZE_FORM == 0 && VS_DBG_UPCONV_FORM == 9 && VS_DBG_ARITH == 20 && VS_DBG_COUNT == 21, "development switch keys keep their numbers");
+
 // Default arithmetic of the split conv / GEMM path (vs_conv_desc_t::arith): 3 = "3 x bf16" (exact operand split, 6 products),
 // 2 = "2 x f16" (round-to-nearest split with power-of-two range scaling, 3 products; conv_common.h).  VIDEOSEAL_CONV=f16x2 | bf16x3
 // overrides it for the model-level entry points (the operator level takes it from the descriptor).
 #define VS_DEFAULT_ARITH 2
 static inline int vs_default_arith() {
-  static const int a = [] {
-    const char* e = getenv("VIDEOSEAL_CONV");
-    if (e && !strcmp(e, "f16x2")) return 2;
-    if (e && !strcmp(e, "bf16x3")) return 3;
-    return VS_DEFAULT_ARITH;
-  }();
-  return a;
+  const int a = vs_debug_get(VS_DBG_ARITH);
+  return a == 2 || a == 3 ? a : VS_DEFAULT_ARITH;
 }
-
-// Development switches of the launchers (tests / tools select a kernel form or a strip height PER CALL): set through the exported
-// vs_debug_set(key, value) -- an atomic the launch path reads; nothing on a launch path calls getenv (not thread-safe against setenv, and a
-// test hook in production code).  0 = the library's own choice.
-enum { VS_DBG_RESIZE_FORM = 0 /* 1 = 32 x 8 tile kernel */, VS_DBG_RESIZE_STRIP = 1 /* output rows */, VS_DBG_TAIL_STRIP = 2 /* rows */, VS_DBG_JPEG_FORM = 3 /* 1 = scalar kernels */, VS_DBG_CROP_RESIZE_FORM = 4 /* 1 = 32 x 8 tile kernel */, VS_DBG_TO_PLANES_FORM = 5 /* 1 = one row per wave */, VS_DBG_DWCONV_ROWS = 6 /* rows per strip of the one-row depthwise kernel */, VS_DBG_LN_FORM = 7 /* 1 = wave per row */, VS_DBG_SPLITK_EPI = 8 /* 1 = the first (scalar-load) K-slice epilogue kernel */, VS_DBG_UPCONV_FORM = 9 /* 1 = per-pixel gather in vs_upconv_gather_ln and phase 3 of vs_upconv_fused (0: 2 x 2 blocks, upconv_gather.h) */, VS_DBG_COUNT = 10 };
-int vs_debug_get(int key);     // api.hip
 
 // LDS a workgroup may ask for on the current device (160 KiB on gfx950, 64 KiB on earlier CDNA parts): launchers whose kernels want more than
 // 64 KiB check it and fall back to their small-LDS form instead of failing the launch

@@ -22,6 +22,7 @@ from typing import Dict, List, Optional, Tuple
 import torch
 
 from . import native as N
+from . import switches as SW
 
 
 def rup(x: int, m: int) -> int:
@@ -226,6 +227,36 @@ def padvec(v: torch.Tensor, n: int) -> torch.Tensor:
     return out
 
 
+# HipEngine attributes set from the environment when an engine is constructed: (attribute, variable, default).  True: on unless the variable
+# says 0; False: on only if it says 1; a word: on unless the variable says that word.  What each one does: switches.REGISTRY
+ENGINE_SWITCHES = (
+    ("per_layer_arith", "VIDEOSEAL_LAYER_ARITH", True),
+    ("upconv_lowres", "VIDEOSEAL_UPCONV", "direct"),
+    ("upconv_fused", "VIDEOSEAL_UPCONV", "unfused"),
+    ("msg_table_conv", "VIDEOSEAL_MSG_TABLE", True),
+    ("planes_chain", "VIDEOSEAL_PLANES", True),
+    ("msg0_planes", "VIDEOSEAL_MSG0_PLANES", True),
+    ("gemm_big", "VIDEOSEAL_GEMM_BIG", False),
+    ("stem_fused", "VIDEOSEAL_STEM_FUSED", False),
+    ("down_patch", "VIDEOSEAL_DOWN_PATCH", True),
+    ("grn_straddle", "VIDEOSEAL_GRN_STRADDLE", True),
+    ("grn_fold", "VIDEOSEAL_GRN_FOLD", True),
+    ("pw2_narrow", "VIDEOSEAL_PW2_NARROW", True),
+    ("pw2_small_pc", "VIDEOSEAL_PW2_SMALL_PC", True),
+    ("planes_gemm", "VIDEOSEAL_PLANES", True),
+    ("fused_blocks", "VIDEOSEAL_CNX_FUSED", True),
+    ("thin_fused", "VIDEOSEAL_THIN_FUSED", True),
+    ("planes_splitk", "VIDEOSEAL_PLANES_SPLITK", True),
+    ("check_finite", "VIDEOSEAL_CHECK_FINITE", False),
+    ("autotune", "VIDEOSEAL_AUTOTUNE", True),
+)
+
+
+def engine_switches(env=None) -> Dict[str, bool]:
+    """the attribute values of ENGINE_SWITCHES under `env` (default: the process environment, read now)"""
+    return {attr: SW.flag(name, True, env, off=d) if isinstance(d, str) else SW.flag(name, d, env) for attr, name, d in ENGINE_SWITCHES}
+
+
 class HipEngine:
     """Packed weights + launch sequences for one architecture (ModelCfg) on one device."""
     arith = 2          # arithmetic of the split back-end (vs_conv_desc_t::arith); set per instance from VIDEOSEAL_CONV
@@ -250,7 +281,7 @@ class HipEngine:
         self.time_all_convs = False
         # arithmetic back-end of vs_conv_gemm: "f16x2" (2 x f16 split, 3 products), "bf16x3" (exact 3 x bf16 split, 6 products),
         # "f32" (v_mfma_f32_32x32x2_f32); "split" = the default split back-end
-        conv_mode = os.environ.get("VIDEOSEAL_CONV", "auto")
+        conv_mode = SW.choice("VIDEOSEAL_CONV", "auto")
         if conv_mode not in ("auto", "split", "f32", "bf16x3", "f16x2"):
             raise N.NativeError(f"VIDEOSEAL_CONV={conv_mode!r}: expected auto, f16x2, bf16x3 or f32")
         self.use_split = conv_mode != "f32"
@@ -264,42 +295,16 @@ class HipEngine:
         self.auto_arith = conv_mode in ("auto", "split")
         self.arith_net = {"E": self.arith, "X": self.arith}
         self.verified = {"E": False, "X": False}
-        # per-LAYER arithmetic of the ConvNeXt extractor: when the guard trips, one calibration pass on the exact split records the largest
-        # operand of every dense layer (vs_absmax); only the layers whose operand leaves the f16 range (with a 4 x margin for other data) stay
-        # on 3 x bf16, the rest of the network keeps the fast split -- one GRN outlier channel does not halve the whole extractor.
-        # key (stage, block, 'pw1' | 'pw2') -> 3.  VIDEOSEAL_LAYER_ARITH=0: whole-network switch only.
-        self.per_layer_arith = os.environ.get("VIDEOSEAL_LAYER_ARITH", "1") != "0"
+        # per-LAYER arithmetic of the ConvNeXt extractor (per_layer_arith): key (stage, block, 'pw1' | 'pw2') -> 3
         self.layer_arith: Dict[tuple, int] = {}
         self._calib: Optional[Dict[tuple, int]] = None        # during the calibration pass: key -> slot of _calib_bits
         self._calib_bits: Optional[torch.Tensor] = None
         self._nf_flag = torch.zeros(2, dtype=torch.int32, device=device)
         self._nf_host = torch.zeros(2, dtype=torch.int32).pin_memory() if device.type == "cuda" else None
         self._nf_event = None
-        # Upsample groups as a low-resolution 9-tap GEMM + gather (a quarter of the MACs, no up-sampled concat); 0 = the literal
-        # bilinear x2 -> reflect-pad conv3x3 -> LayerNorm sequence (kept for A/B checks)
-        self.upconv_lowres = os.environ.get("VIDEOSEAL_UPCONV", "lowres") != "direct"
-        self.upconv_fused = os.environ.get("VIDEOSEAL_UPCONV", "lowres") != "unfused"    # thin levels: GEMM + gather in one kernel
-        self.msg_table_conv = os.environ.get("VIDEOSEAL_MSG_TABLE", "1") != "0"         # first bottleneck block: message channels as a table
-        self.planes_chain = os.environ.get("VIDEOSEAL_PLANES", "1") != "0"              # bottleneck chain on pre-split operand planes
-        self.msg0_planes = os.environ.get("VIDEOSEAL_MSG0_PLANES", "1") != "0"          # ... including its first block (round 5)
-        self.gemm_big = os.environ.get("VIDEOSEAL_GEMM_BIG", "0") == "1"                  # planes GEMMs of >= 3 rounds on 256 x 256 tiles, one wave per SIMD (round 6)
-        self.stem_fused = os.environ.get("VIDEOSEAL_STEM_FUSED", "0") == "1"              # stem conv + LayerNorm in one VALU kernel (round 6; measured neutral: opt-in)
-        self.down_patch = os.environ.get("VIDEOSEAL_DOWN_PATCH", "1") != "0"              # down-sampler LayerNorm -> patch matrix -> dense GEMM (round 6)
-        self.grn_straddle = os.environ.get("VIDEOSEAL_GRN_STRADDLE", "1") != "0"         # GRN statistics from the planes GEMM's epilogue for HW % 32 != 0 (round 6)
-        self.grn_fold = os.environ.get("VIDEOSEAL_GRN_FOLD", "1") != "0"                 # GRN finish inside the wave-specialised pwconv2 GEMM (round 6)
-        self.pw2_narrow = os.environ.get("VIDEOSEAL_PW2_NARROW", "1") != "0"             # stage-2 pwconv2 on 128 x 96 tiles (tile 26; 0: the K-slice form)
-        self.pw2_small_pc = os.environ.get("VIDEOSEAL_PW2_SMALL_PC", "1") != "0"        # stage-3 pwconv2 on the wave-specialised GEMM instead of planes (round 5)
-        self.planes_gemm = os.environ.get("VIDEOSEAL_PLANES", "1") != "0"               # ConvNeXt 1x1 GEMMs on operand planes
-        self.fused_blocks = os.environ.get("VIDEOSEAL_CNX_FUSED", "1") != "0"           # stage 0 / 1 blocks with h kept on chip (convnext_fused.hip)
-        self.thin_fused = os.environ.get("VIDEOSEAL_THIN_FUSED", "1") != "0"              # 16-channel ResnetBlocks in one launch (resblock_thin.hip)
-        self.planes_splitk = os.environ.get("VIDEOSEAL_PLANES_SPLITK", "1") != "0"      # planes chain with K slices for 4 - 8 key frames
-        # VIDEOSEAL_CHECK_FINITE=1: synchronise after every network pass and raise if the output is not finite -- the 2 x f16 arithmetic
-        # turns an activation beyond its f16 range (|a| * a_mul >= 65520) into inf / NaN instead of a silently wrong number
-        self.check_finite = os.environ.get("VIDEOSEAL_CHECK_FINITE", "0") == "1"
+        for attr, value in engine_switches().items():
+            setattr(self, attr, value)
         self.bn_sync = None       # callable(sums: float64 [2*ld + 1]) -> None, in-place sum over the ranks (dist.convert_sync_batchnorm)
-        # per-shape tile selection: every candidate walks K in the same order, so the result is bit-identical whatever
-        # tile wins -- only speed changes (measure, don't guess).  VIDEOSEAL_AUTOTUNE=0 keeps the static heuristic.
-        self.autotune = os.environ.get("VIDEOSEAL_AUTOTUNE", "1") != "0"
         self.tail_variant = 0            # vs_tail_desc_t::variant (0 = default: row-streaming kernel where it applies)
         self.shell_timers: Optional[list] = None     # bench.py: (kernel, ev0, ev1, algorithmic bytes) of the HBM-bound shell kernels
         self._tile_cache: Dict[tuple, int] = {}
@@ -307,10 +312,10 @@ class HipEngine:
         # Packaged choices for the benchmark shapes (tools/tune_tiles.py, best of many interleaved rounds on an MI355X): a
         # quick in-process tuning is at the mercy of the box's clock wander, and ranks would otherwise tune independently.
         # Unknown signatures are still tuned on first use.
-        self._tile_cache_path = os.environ.get("VIDEOSEAL_TILE_CACHE")
+        self._tile_cache_path = SW.path("VIDEOSEAL_TILE_CACHE")
         self.tune_rounds = 2
         import json
-        for path in (TUNED_TILES if self.autotune and os.environ.get("VIDEOSEAL_TUNED_TILES", "1") != "0" else None, self._tile_cache_path):
+        for path in (TUNED_TILES if self.autotune and SW.flag("VIDEOSEAL_TUNED_TILES", True) else None, self._tile_cache_path):
             if path and os.path.exists(path):
                 with open(path) as f:
                     self._tile_cache.update({tuple(json.loads(k)): v for k, v in json.load(f).items()})
@@ -920,7 +925,7 @@ class HipEngine:
         if not self.planes_splitk:
             return 0
         spt = x.C // 16
-        force = int(os.environ.get("VIDEOSEAL_PLANES_SK", "0"))        # experiments only (tools/r06_sk.sh): another slice count for launches below 200 tiles
+        force = SW.integer("VIDEOSEAL_PLANES_SK", 0)        # experiments only: another slice count for launches below 200 tiles
         if force > 1 and spt % force == 0:
             return force
         for sk in (2, 3, 4, 6, 8, 12):

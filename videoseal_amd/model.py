@@ -16,20 +16,20 @@ Deliberate differences, each loud rather than silent:
 """
 from __future__ import annotations
 
-import os
 from typing import Dict, Optional, Tuple
 
 import torch
 import torch.nn as nn
 
 from . import native as N
+from . import switches as SW
 from .engine import Act, HipEngine
 from .layout import ModelCfg, build_tree, detector_entries, embedder_entries
 
 _DEFAULT_INTERP = {"mode": "bilinear", "align_corners": False, "antialias": True}
 
 
-_PINNED_RESULTS = os.environ.get("VIDEOSEAL_PINNED_RESULTS", "1") != "0"
+_PINNED_RESULTS = SW.flag("VIDEOSEAL_PINNED_RESULTS", True)
 
 
 def _result_buffer(shape, dtype, device) -> torch.Tensor:
@@ -245,7 +245,7 @@ class Wam(nn.Module):
         self._warned_no_backward = False
         # hipGraph replay of the per-chunk launch sequences (fixed chunk shapes, e.g. streaming callers): the ~300 kernel
         # launches of an embed / detect chunk are captured once per (shape, flags) and replayed with one launch
-        self.use_graphs = os.environ.get("VIDEOSEAL_GRAPHS", "0") == "1"
+        self.use_graphs = SW.flag("VIDEOSEAL_GRAPHS", False)
         self._graphs: Dict[tuple, dict] = {}
         holder = [self]
         embedder._root = detector._root = holder
@@ -308,7 +308,7 @@ class Wam(nn.Module):
         if stale:
             self._eng.invalidate(*stale)
             self._graphs.clear()
-        if self._bn_sync is None and self.embedder.training and os.environ.get("VIDEOSEAL_SYNC_BN", "auto") == "auto":
+        if self._bn_sync is None and self.embedder.training and SW.choice("VIDEOSEAL_SYNC_BN", "auto") == "auto":
             # train.py:438-440 converts every BatchNorm to SyncBatchNorm when it runs distributed; nn.SyncBatchNorm.convert_sync_batchnorm finds
             # no nn.BatchNorm2d children here (the U-Net is one HIP launch sequence), so the same switch is made when a process group with
             # more than one rank exists at the first train-mode forward (VIDEOSEAL_SYNC_BN=0 keeps per-rank statistics)

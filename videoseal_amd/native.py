@@ -6,15 +6,18 @@ point fails, the call raises -- the product path never silently runs on ATen / C
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
 from typing import Optional
 
 import torch
 
+from . import switches as SW
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # VIDEOSEAL_LIB: another build of the same ABI (same-box A/B of two source trees, tools/ab_libs.sh); the default is the in-tree library
-LIB_PATH = os.environ.get("VIDEOSEAL_LIB") or os.path.join(_HERE, "csrc", "libvideoseal_hip.so")
+LIB_PATH = SW.path("VIDEOSEAL_LIB") or os.path.join(_HERE, "csrc", "libvideoseal_hip.so")
 
 ACT_NONE, ACT_RELU, ACT_GELU, ACT_TANH, ACT_SILU = 0, 1, 2, 3, 4
 PAD_ZERO, PAD_REFLECT = 0, 1
@@ -22,7 +25,7 @@ CONV_FORCE_F32, CONV_FORCE_SPLIT, CONV_TILE_HI, CONV_PRE = 0x10, 0x20, 0x40, 0x8
 VIDEO_MODES = {"repeat": 0, "alternate": 1, "interpolate": 2}
 
 EXPORTS = [
-    "vs_version", "vs_arch", "vs_error_string", "vs_sizeof_conv_desc", "vs_sizeof_tail_desc", "vs_debug_set",
+    "vs_version", "vs_arch", "vs_error_string", "vs_sizeof_conv_desc", "vs_sizeof_tail_desc", "vs_debug_set", "vs_debug_key", "vs_debug_get",
     "vs_model_create", "vs_model_destroy", "vs_model_workspace_bytes", "vs_model_embed", "vs_model_detect", "vs_model_set_nv12_color", "vs_nv12_default_color", "vs_conv_gemm", "vs_conv_plan", "vs_cnx_stage_plan", "vs_sizeof_conv_plan", "vs_sizeof_cnx_stage_plan", "vs_to_planes", "vs_to_planes_affine", "vs_layernorm_act", "vs_layernorm_patch2x2", "vs_stem_conv_ln", "vs_rmsnorm_act", "vs_vit_attention", "vs_dwconv7_ln", "vs_dwconv7_ln_planes", "vs_grn_scale", "vs_grn_scale_from_partials", "vs_grn_scale_from_straddle_partials", "vs_grn_apply",
     "vs_upcat2x", "vs_upconv_supported", "vs_upconv_gather_ln", "vs_cat2_scale", "vs_msg_pre", "vs_upconv_fused_supported", "vs_upconv_fused_preferred", "vs_upconv_fused", "vs_im2col3x3", "vs_msg_latent", "vs_broadcast_channels", "vs_outc_tanh", "vs_pool_linear", "vs_resize_pre", "vs_resize_pre_u8",
     "vs_jnd_heatmap", "vs_embed_tail", "vs_aug_color_scratch_floats", "vs_aug_color", "vs_aug_color_chain", "vs_aug_crop_resize_color", "vs_aug_crop_flip", "vs_aug_warp", "vs_resize_nchw",
@@ -315,6 +318,21 @@ ERR_UNSUPPORTED = -2      # VS_ERR_UNSUPPORTED: configuration outside what a ker
 def check(code: int, what: str) -> None:
     if code != 0:
         raise NativeError(f"{what} failed: {lib().vs_error_string(code).decode()} (code {code})")
+
+
+@contextlib.contextmanager
+def debug(name: str, value: int):
+    """Development switch VS_DBG_<name> (csrc/vs_common.h) = value inside the block; 0 again -- the environment default, else the library's
+    choice -- after it.  Process-global: tests and tools only."""
+    L = lib()
+    key = L.vs_debug_key(name.encode())
+    if key < 0:
+        raise NativeError(f"no development switch named {name!r} (VS_DBG_KEYS, csrc/vs_common.h)")
+    check(L.vs_debug_set(key, int(value)), "vs_debug_set")
+    try:
+        yield
+    finally:
+        L.vs_debug_set(key, 0)
 
 
 def ptr(t: Optional[torch.Tensor]) -> Optional[int]:

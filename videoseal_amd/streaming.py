@@ -14,10 +14,11 @@ Stream safety: embedder and extractor use disjoint named workspace buffers, K-sp
 group is a fresh tensor (recorded on the consuming stream), and the extractor's logits are cloned on the detect stream."""
 from __future__ import annotations
 
-import os
 from typing import Callable, Optional, Tuple
 
 import torch
+
+from . import switches as SW
 
 KEY_BATCH = 32      # key frames per U-Net pass at which conv3x3_pl_kernel has one 256-pixel tile x 192 channels per CU (B * 4 * 2 = 256)
 DET_BATCH = 128     # frames per extractor pass.  Round 6: 32 -> 128 (= one default group of 8 x 16 frames): the extractor's stage-2 / 3 GEMMs are one-round
@@ -99,7 +100,7 @@ def embed_detect_chunks(model, frames: torch.Tensor, msgs: torch.Tensor, chunk: 
     # the only overlap it can have is inside the group.  Same U-Net batch, same extractor batches -> the logits are bit-identical to the
     # whole-group hand-over (`fine=False`); VIDEOSEAL_STREAM_FINE=0 restores that
     fine = (group > 1 and db % chunk == 0 and db % step == 0 and not getattr(model, "use_graphs", False)
-            and os.environ.get("VIDEOSEAL_STREAM_FINE", "1") != "0")
+            and SW.flag("VIDEOSEAL_STREAM_FINE", True))
     for a in range(0, F_, span):
         if fine:
             def piece(first, wp):             # on the embed stream's timeline, right behind the tail launches of wp

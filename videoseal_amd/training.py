@@ -11,15 +11,15 @@ exponent range for the gradients); everything else is csrc/bwd_ops.hip.  No CPU 
 Pinned against the reference's own `loss.backward()` (tests/golden/make_golden_bwd.py -> tests/test_gpu_bwd.py)."""
 from __future__ import annotations
 
-import os
 from typing import Dict, List, Optional, Tuple
 
 import torch
 
 from . import native as N
+from . import switches as SW
 from .engine import A_MUL_GRN, Act, ConvW, HipEngine, pack_conv, pack_conv_bwd, rup
 
-DIRECT_WGRAD = os.environ.get("VIDEOSEAL_DIRECT_WGRAD", "1") != "0"       # 0: 3x3 weight gradients through the explicit patch matrix (A/B)
+DIRECT_WGRAD = SW.flag("VIDEOSEAL_DIRECT_WGRAD", True)       # 0: 3x3 weight gradients through the explicit patch matrix (A/B)
 BWD_ARITH = 3          # 3 x bf16: exact operand split, fp32 exponent range (vs_conv_desc_t::arith)
 
 
