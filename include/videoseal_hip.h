@@ -636,6 +636,54 @@ int vs_resize_pre_nv12(const unsigned char* src, int B, int H, int W, int64_t pi
 int vs_embed_tail_nv12(const vs_tail_nv12_desc_t* d, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * 4:2:0 surfaces: NV12 and the three formats decoders deliver beside it, each plane at its own address, pitch and frame stride.
+ * Layout.  H and W even.  (planar, depth, msb_aligned) names the format; every other combination answers VS_ERR_UNSUPPORTED:
+ *     nv12       (0,  8, 0)  uint8   plane[0] = Y [H][W], plane[1] = [H/2][W]: samples 2j, 2j+1 of row i are Cb, Cr of block (i, j)
+ *     i420       (1,  8, 0)  uint8   plane[0] = Y [H][W], plane[1] = Cb [H/2][W/2], plane[2] = Cr [H/2][W/2]
+ *     p010       (0, 10, 1)  uint16  as nv12; sample code = word >> 6 (the low 6 bits are ignored on input and zero on output)
+ *     yuv420p10  (1, 10, 0)  uint16  as i420; sample code = min(word, 1023)
+ *   16-bit words are little-endian.  Consecutive samples of a row are adjacent; rows of plane i lie pitch[i] BYTES apart (any value >= the
+ *   row's bytes, odd ones included, no alignment asked), frames frame_stride[i] bytes apart.  plane[2] of an interleaved format is ignored.
+ *   AVFrame: plane[i] = data[i], pitch[i] = linesize[i].
+ * Colour.  As for NV12, with Kr/Kb = 0.2627/0.0593 (BT.2020) beside BT.601 and BT.709.  Depth 8 codes as there; depth 10 limited range:
+ *   Y -> 64 + 876 Y, C -> 512 + 896 C; full range: Y -> 1023 Y, C -> 512 + 1023 C.  The affines passed in are in code units of the
+ *   surface's depth (HOST arrays of 12 floats, built and inverted in float64: videoseal_amd/yuv420.py::color_affine); the kernels know no presets.
+ * Chroma.  Up: every pixel of a 2 x 2 block uses the block's (Cb, Cr).  Down: the mean of the block's four per-pixel values, then one rounding.
+ * Range and rounding.  After decoding every RGB channel is clamped to [0, 1] before anything else uses it.  Output codes are
+ *   floor(clamp(v, 0, 2^depth - 1) + 0.5), v in code units (p010 stores code << 6); there is no intermediate rounding to RGB24.
+ *
+ * vs_resize_pre_yuv420 / vs_embed_tail_yuv420: vs_resize_pre_nv12 / vs_embed_tail_nv12 on such surfaces -- the same conversion, filter, JND
+ *   and blend expressions in the same order, so two layouts that hold the same codes give the same bits (an nv12 surface: the bits of the
+ *   NV12 entry points).  The descriptor is vs_tail_nv12_desc_t with two surfaces (same format) in place of imgs / out and the pitches:
+ *   clamp must be 1, io_u8 is ignored, variant 0 / 1 / 4 as there, preds_w != NULL and attenuate = 2 answer VS_ERR_UNSUPPORTED.  Bytes of a
+ *   destination plane between a row's end and its pitch are never written.  Development switches: keys 0 - 2, as the NV12 entry points.
+ */
+typedef struct vs_yuv420_surface {
+  void* plane[3];
+  int64_t pitch[3], frame_stride[3];        /* bytes */
+  int32_t planar, depth, msb_aligned, reserved_;
+} vs_yuv420_surface_t;
+typedef struct vs_tail_yuv420_desc {
+  vs_yuv420_surface_t src, dst;
+  float* preds_w;
+  const float* delta; const float* hmap_lowres; const float* taps43;   /* taps43: HOST pointer */
+  int32_t F, H, W, S_h, S_w, Cd;
+  int32_t step, video_mode, total_key;
+  int32_t attenuate, clamp, antialias;
+  float scaling_i, scaling_w;
+  int32_t io_u8;
+  int32_t variant;
+  float yuv2rgb12[12], rgb2yuv12[12];
+} vs_tail_yuv420_desc_t;
+int vs_sizeof_yuv420_surface(void);         /* sizeof(vs_yuv420_surface_t) */
+int vs_sizeof_tail_yuv420_desc(void);       /* sizeof(vs_tail_yuv420_desc_t) */
+int vs_resize_pre_yuv420(const vs_yuv420_surface_t* src, int B, int H, int W, const float* yuv2rgb12, int oh, int ow, int antialias,
+                         float* dst_rgb, float mul, float add, float* dst_y, int y_step, const float* ymat3, void* stream);
+int vs_embed_tail_yuv420(const vs_tail_yuv420_desc_t* d, void* stream);
+/* BT.709 limited range at depth 8 or 10, written to two HOST arrays of 12 floats; needs no GPU.  Depth 8: the floats of vs_nv12_default_color */
+int vs_yuv420_default_color(int depth, float* yuv2rgb12, float* rgb2yuv12);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * Model-level entry points (the granularity a non-Python host would bind): an opaque model built from the card numbers
  * (utils/cfg.py:88-154, embedder.py:243-262, extractor.py:189-208) and the reference state_dict (cfg.py:147-150:
  * checkpoint['model'], HOST fp32 tensors by their reference names, loaded like strict=False: unknown names are ignored,
@@ -678,6 +726,14 @@ int vs_model_detect(vs_model_t* m, const void* imgs, int frames, int H, int W, i
 int vs_model_set_nv12_color(vs_model_t* m, const float* yuv2rgb12, const float* rgb2yuv12);
 /* the pair a fresh model holds (BT.709 limited range), written to two HOST arrays of 12 floats; needs no GPU */
 int vs_nv12_default_color(float* yuv2rgb12, float* rgb2yuv12);
+/* vs_model_embed / vs_model_detect on 4:2:0 surfaces (vs_yuv420_surface_t, any pitches): `in` and `out` hold the same format, H and W even.
+ * yuv2rgb12 / rgb2yuv12: HOST arrays of 12 floats in code units of the surface's depth, or NULL (both, for embed) = BT.709 limited range at
+ * that depth (vs_yuv420_default_color); the model's stored NV12 pair is not consulted.  There is no preds_w. */
+int vs_model_embed_yuv420(vs_model_t* m, const vs_yuv420_surface_t* in, const vs_yuv420_surface_t* out, const float* yuv2rgb12,
+                          const float* rgb2yuv12, const int32_t* msgs, int n_msgs, int frames, int H, int W, int step, int video_mode,
+                          int lowres_attenuation, int antialias, void* ws, int64_t ws_bytes, void* stream);
+int vs_model_detect_yuv420(vs_model_t* m, const vs_yuv420_surface_t* in, const float* yuv2rgb12, int frames, int H, int W, int antialias,
+                           float* logits, void* ws, int64_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Augmentations (videoseal/augmentation/valuemetric.py, geometric.py, utils/image.py).  Frames are NCHW fp32 [F][3][H][W]

@@ -43,6 +43,10 @@ def _bind(L):
     L.vs_model_detect.restype = I
     L.vs_model_set_nv12_color.argtypes = [P, P, P]
     L.vs_model_set_nv12_color.restype = I
+    L.vs_model_embed_yuv420.argtypes = [P, C.POINTER(N.Yuv420Surface), C.POINTER(N.Yuv420Surface), P, P, P, I, I, I, I, I, I, I, I, P, I64, P]
+    L.vs_model_embed_yuv420.restype = I
+    L.vs_model_detect_yuv420.argtypes = [P, C.POINTER(N.Yuv420Surface), P, I, I, I, I, P, P, I64, P]
+    L.vs_model_detect_yuv420.restype = I
     L._model_api_bound = True
 
 
@@ -135,4 +139,41 @@ class CModel:
         ws = self._workspace(F_, H, W, 1)
         N.check(self._L.vs_model_detect(self._h, N.ptr(x), F_, H, W, int(antialias), int(u8), N.ptr(logits), N.ptr(ws), ws.numel(), N.stream()),
                 "vs_model_detect")
+        return logits
+
+    @staticmethod
+    def _yuv420_color(fmt: str, color):
+        """(yuv2rgb12, rgb2yuv12) host arrays for `color` = (matrix, full_range), or (None, None) = the library's default at that depth"""
+        if color is None:
+            return None, None
+        from .yuv420 import color_affine, fmt_info
+        fwd, inv = color_affine(color[0], bool(color[1]), fmt_info(fmt)[1])
+        return (C.c_float * 12)(*[float(v) for v in inv.reshape(-1)]), (C.c_float * 12)(*[float(v) for v in fwd.reshape(-1)])
+
+    def embed_yuv420(self, planes, fmt: str, msgs: torch.Tensor, *, out_planes=None, color=None, step: int = 1, video_mode: int = 0,
+                     lowres_attenuation: bool = False, antialias: bool = True):
+        """vs_model_embed_yuv420 on device-resident planes (any pitches); `out_planes`: where the watermarked clip goes (default: a new
+        packed clip).  `color` = (matrix, full_range) or None = NULL affines.  Returns the output planes."""
+        from .yuv420 import Clip420, check_clip
+        F_, H, W = check_clip(planes, fmt)
+        src = Clip420(planes, fmt)
+        dst = Clip420(out_planes, fmt) if out_planes is not None else src.empty_like()
+        m = msgs.to(device=src.device, dtype=torch.int32).contiguous()
+        ws = self._workspace(F_, H, W, step)
+        dec, enc = self._yuv420_color(fmt, color)
+        sin, sout = N.yuv420_surface(src.planes, fmt), N.yuv420_surface(dst.planes, fmt)
+        N.check(self._L.vs_model_embed_yuv420(self._h, C.byref(sin), C.byref(sout), dec, enc, N.ptr(m), m.shape[0], F_, H, W, step, video_mode,
+                                              int(lowres_attenuation), int(antialias), N.ptr(ws), ws.numel(), N.stream()), "vs_model_embed_yuv420")
+        return dst.planes
+
+    def detect_yuv420(self, planes, fmt: str, *, color=None, antialias: bool = True) -> torch.Tensor:
+        from .yuv420 import Clip420, check_clip
+        F_, H, W = check_clip(planes, fmt)
+        src = Clip420(planes, fmt)
+        logits = torch.empty(F_, self.cfg.nbits + 1, device=src.device)
+        ws = self._workspace(F_, H, W, 1)
+        dec, _ = self._yuv420_color(fmt, color)
+        sin = N.yuv420_surface(src.planes, fmt)
+        N.check(self._L.vs_model_detect_yuv420(self._h, C.byref(sin), dec, F_, H, W, int(antialias), N.ptr(logits), N.ptr(ws), ws.numel(),
+                                               N.stream()), "vs_model_detect_yuv420")
         return logits

@@ -3,9 +3,7 @@
 //   vs_jnd_heatmap   : JND heat-map at the processing resolution (low-res attenuation)
 //   vs_embed_tail    : delta up-resize x JND(img) -> blend -> clamp, one pass over the frame
 // These are the HBM-bound kernels (7.08 MB read + 7.08 MB written per 768x768 frame in the tail).
-#include "vs_common.h"
-#include "resize_taps.h"
-#include "resize_stream.h"
+#include "shell_common.h"
 
 namespace {
 
@@ -32,11 +30,6 @@ template <> struct Px<unsigned char> {
   static __device__ __forceinline__ void st(unsigned char* img, int64_t, int c, int64_t pix, float v) { img[pix * 3 + c] = (unsigned char)(v * 255.0f); }
 };
 
-// ---------------------------------------------------------------------------------------------------
-constexpr int TTW = 256, TTH = 16, TLW = TTW + 4;   // embed tail tile: 256 columns (one per thread) x 16 rows
-constexpr int DW_W = 136, DW_H = 12;      // its delta source window in LDS (covers up-resizes by >= 2x; a 3x one needs ~90 x 9)
-constexpr int RS_WW = 113, RS_WH = 32;   // LDS window of resize_pre (odd row pitch); covers down-scales up to ~3.3x
-constexpr int MAXT = 8;   // taps held in registers by the resize kernels (triangle filter support 2*scale + 1 <= 8 for scale <= 3.5)
 
 template <typename T>
 __global__ __launch_bounds__(256) void resize_pre_kernel(const T* __restrict__ src, int B, int C, int H, int W, int oh, int ow,
@@ -182,28 +175,6 @@ __global__ __launch_bounds__(256) void resize_pre_kernel(const T* __restrict__ s
 //   3. vertical pass: every output row whose tap window is complete is combined from the ring and stored (NHWC rgb / Y key frames).
 // The expressions and their order are those of the tile kernel (r += wx * pixel over the taps, then acc += wy * r): bit-identical outputs.
 // An input row is fetched once per 128-column tile (+ the strip's first window): ~1.15 x the frame.
-// The row-streaming form lives in resize_stream.h (shared with aug.hip's Crop -> Resize -> colour kernel); this is its `resize_pre` epilogue:
-// NHWC(4) rgb * mul + add and / or the key frames' Y (or rgb) mapped to [-1, 1].
-struct ResizePreEpi {
-  float* dst_rgb; float* dst_key; float mul, add; int key_step, key_mode; float y0c, y1c, y2c; int oh, ow;
-  __device__ __forceinline__ void operator()(const int b, const int oy, const int ox, const float (&acc)[3]) const {
-    const int64_t opix = ((int64_t)oy * ow + ox);
-    if (dst_rgb) {
-      f32x4 v = {acc[0] * mul + add, acc[1] * mul + add, acc[2] * mul + add, 0.f};
-      *reinterpret_cast<f32x4*>(dst_rgb + ((int64_t)b * oh * ow + opix) * 4) = v;
-    }
-    if (dst_key && (b % key_step) == 0) {
-      f32x4 v;
-      if (key_mode == 0) {
-        const float y = y0c * acc[0] + y1c * acc[1] + y2c * acc[2];
-        v = f32x4{y * 2.f - 1.f, 0.f, 0.f, 0.f};
-      } else {
-        v = f32x4{acc[0] * 2.f - 1.f, acc[1] * 2.f - 1.f, acc[2] * 2.f - 1.f, 0.f};
-      }
-      *reinterpret_cast<f32x4*>(dst_key + ((int64_t)(b / key_step) * oh * ow + opix) * 4) = v;
-    }
-  }
-};
 template <int OW>
 __global__ __launch_bounds__(256) void resize_pre_stream_kernel(const float* __restrict__ src, int B, int H, int W, int oh, int ow, int antialias,
                                                                 ResizePreEpi epi, int strip) {
@@ -211,51 +182,6 @@ __global__ __launch_bounds__(256) void resize_pre_stream_kernel(const float* __r
   vs_rs::resize_stream_body<OW>(rs_smem, src, H, W, 0, 0, H, W, oh, ow, antialias, strip, epi);
 }
 
-// ---- JND (jnd.py:63-108) on a luminance tile held in LDS --------------------------------------------------
-struct JndTaps { float lum[25]; float sx[9]; float sy[9]; };
-
-// luminance of 255 * rgb (jnd.py:86-89) and the blend (blender.py:61-68, wam.py:103-113 / jnd.py:110-114) evaluated the way ATen does: separate
-// multiplications and additions, no fused multiply-add.  Every kernel of the tail calls these two functions, so its forms agree bit for bit
-// (hipcc's contraction of `a * b + c * d` picks either product for the fma depending on the surrounding code).
-__device__ __forceinline__ float lum255(const float r, const float g, const float b) {
-#pragma clang fp contract(off)
-  return 0.299f * (255.f * r) + 0.587f * (255.f * g) + 0.114f * (255.f * b);
-}
-__device__ __forceinline__ float blend_px(const float si, const float sw, const float p, const float dw, const float hm, const bool fwd_order) {
-#pragma clang fp contract(off)
-  float v = si * p + sw * dw;
-  if (fwd_order) v = p + hm * (v - p);
-  return v;
-}
-
-__device__ __forceinline__ float jnd_at(const float* L, int stride, int x, int y, const JndTaps& k) {
-  // L points at tile origin, (x,y) is the centre inside the tile with a 2-pixel halo available
-  float la = 0.f;
-#pragma unroll
-  for (int i = 0; i < 5; ++i)
-#pragma unroll
-    for (int j = 0; j < 5; ++j) la += k.lum[i * 5 + j] * L[(y + i - 2) * stride + (x + j - 2)];
-  la = la / 32.f;
-  la = la <= 127.f ? 17.f * (1.f - sqrtf(la / 127.f + 1e-5f)) : 3.f / 128.f * (la - 127.f) + 3.f;
-  float gx = 0.f, gy = 0.f;
-#pragma unroll
-  for (int i = 0; i < 3; ++i)
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-      const float v = L[(y + i - 1) * stride + (x + j - 1)];
-      gx += k.sx[i * 3 + j] * v;
-      gy += k.sy[i * 3 + j] * v;
-    }
-  float cm = sqrtf(__builtin_fmaf(gx, gx, gy * gy));
-  // cm^2.4 through the hardware log2/exp2 (1 ulp each): relative error <= ~1e-6 on a term that enters the frame scaled by
-  // 1/255 * delta * scaling_w, i.e. < 1e-8 absolute -- ocml's powf costs ~10x the instructions
-  cm = 16.f * (cm > 0.f ? __builtin_amdgcn_exp2f(2.4f * __builtin_amdgcn_logf(cm)) : 0.f) / (cm * cm + 676.f);
-  cm = 0.117f * cm;
-  const float h = la + cm - 0.3f * fminf(la, cm);
-  return fmaxf(h, 0.f) / 255.f;
-}
-
-constexpr int TW = 32, TH = 8, HALO = 2, LW = TW + 2 * HALO, LH = TH + 2 * HALO;
 
 // luminance of 255*img (jnd.py:86-89), zero outside the image (conv zero padding)
 __device__ __forceinline__ void load_lum_tile(float* L, const float* img, int64_t sc, int64_t sy, int64_t sx, int H, int W,
@@ -297,65 +223,8 @@ __global__ __launch_bounds__(256) void jnd_heatmap_kernel(const float* __restric
   if (x < W && y < H) hmap[((int64_t)b * H + y) * W + x] = jnd_at(L, LW, lx + HALO, ly + HALO, k);
 }
 
-// delta taps of one output pixel from the staged source window: d[c] = sum_jy wy * sum_jx wx * Dw[c][..] (Dw = hm*(wa*key_a+wb*key_b))
-template <int NT, int DWH = DW_H>
-__device__ __forceinline__ void tail_taps(float (&d)[3], const float* Dw, const int Cd, const int base, const int xn, const int yn,
-                                          const float* wxp, const float* wyp) {
-  int ox[NT], oy[NT];
-  float wx[NT], wy[NT];
-#pragma unroll
-  for (int j = 0; j < NT; ++j) {       // clamped offsets + zero weights past the real tap count: no branches, all reads in flight
-    ox[j] = j < xn ? j : xn - 1;
-    oy[j] = (j < yn ? j : yn - 1) * DW_W;
-    wx[j] = wxp[j];
-    wy[j] = wyp[j];
-  }
-  for (int c = 0; c < Cd; ++c) {
-    const float* p = Dw + c * (DW_W * DWH) + base;
-    float v[NT][NT];
-#pragma unroll
-    for (int jy = 0; jy < NT; ++jy)
-#pragma unroll
-      for (int jx = 0; jx < NT; ++jx) v[jy][jx] = p[oy[jy] + ox[jx]];
-    // explicit fma chains: `r += wx * v` with r starting at 0 leaves hipcc an `a * b + c * d` to contract, and it fuses EITHER product depending on
-    // the surrounding code -- two kernels calling this function disagreed in the last bit (round 4)
-    float dc = 0.f;
-#pragma unroll
-    for (int jy = 0; jy < NT; ++jy) {
-      float r = 0.f;
-#pragma unroll
-      for (int jx = 0; jx < NT; ++jx) r = __builtin_fmaf(wx[jx], v[jy][jx], r);
-      dc = __builtin_fmaf(wy[jy], r, dc);
-    }
-    d[c] = dc;
-  }
-}
 
-// STANDARD JND kernels (jnd.py:24-41: Sobel pair + the 5 x 5 luminance mask = box5 + box3 - 2 centre) evaluated separably inside
-// embed_tail_kernel<T, true>: for a group of RG output rows the RG + 4 luminance rows are read once (5 LDS reads per row: x-2 .. x+2), giving per
-// row H5 = box5 row sum, H3, S = L[x+1] - L[x-1] and T = L[x-1] + 2 L[x] + L[x+1]; the vertical combinations run over registers -- 10 LDS reads
-// per pixel instead of 43.  The luminance mask jumps at la = 127 (jnd.py:66-68): a pixel whose separable sum lands within 0.02 of the jump is
-// re-evaluated with the 25-tap order of jnd_at, so the branch taken is the one the generic path / the low-resolution heat-map kernel take.
-// Measured (32 x 768^2, fp32, full JND, no preds_w): 43-tap form 227 us, this form 215 us -- the LDS taps were not the limit; what the JND costs
-// over the plain tail (137 us) is the separate luminance phase (1.27 x frame read + LDS fill + barrier before the first output row).  A
-// column-register form that reads the frame once and keeps the 16 centre pixels in registers needed 195 VGPRs (two waves per SIMD) and
-// ran at 391 us: profiles/r03h_shell_*.log, r03i_shell_separable.log.
-__device__ __forceinline__ float jnd_finish(float la_sum, float gx, float gy) {
-  float la = la_sum / 32.f;
-  la = la <= 127.f ? 17.f * (1.f - sqrtf(la / 127.f + 1e-5f)) : 3.f / 128.f * (la - 127.f) + 3.f;
-  float cm = sqrtf(__builtin_fmaf(gx, gx, gy * gy));
-  cm = 16.f * (cm > 0.f ? __builtin_amdgcn_exp2f(2.4f * __builtin_amdgcn_logf(cm)) : 0.f) / (cm * cm + 676.f);
-  cm = 0.117f * cm;
-  const float h = la + cm - 0.3f * fminf(la, cm);
-  return fmaxf(h, 0.f) / 255.f;
-}
 
-// ---------------------------------------------------------------------------------------------------
-struct TailArgs {
-  const void* imgs; void* out; float* preds_w; const float* delta; const float* hmap_lowres;
-  int F, H, W, Sh, Sw, Cd, step, video_mode, total_key, attenuate, clamp, antialias;
-  float scaling_i, scaling_w;
-};
 
 // Workgroup = 256 consecutive columns x TTH rows of one frame: every wave touches 256 contiguous bytes (fp32) per row and
 // plane -- 32-pixel-wide tiles (128-byte pieces at a 3 KB stride) ran at ~1.3 TB/s, a quarter of what a plain copy reaches.
@@ -587,36 +456,7 @@ __global__ __launch_bounds__(256) void embed_tail_kernel(TailArgs a, JndTaps k) 
 //     one group ahead of its first use; ONE barrier per group covers ring, window and row taps (three-slot ring / two-slot window: a writer
 //     is always at least one barrier behind the last reader of the slot it overwrites).
 // Needs an up-scale by >= 2 in both directions (<= 3 taps per direction, window <= 136 x 12); everything else takes the tile kernel.
-constexpr int SG = 4, RING = 3 * SG, SUBR = 16;
 
-__device__ __forceinline__ float jnd_at_ring(const float* Lr, const int cslot, const int lxh, const JndTaps& k) {
-  // jnd_at() on the ring: rows cslot - 2 .. cslot + 2 (mod RING), columns lxh - 2 .. lxh + 2; same summation order
-  float la = 0.f;
-#pragma unroll
-  for (int i = 0; i < 5; ++i) {
-    const float* row = Lr + ((cslot + i + RING - 2) % RING) * TLW + lxh;
-#pragma unroll
-    for (int j = 0; j < 5; ++j) la += k.lum[i * 5 + j] * row[j - 2];
-  }
-  la = la / 32.f;
-  la = la <= 127.f ? 17.f * (1.f - sqrtf(la / 127.f + 1e-5f)) : 3.f / 128.f * (la - 127.f) + 3.f;
-  float gx = 0.f, gy = 0.f;
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-    const float* row = Lr + ((cslot + i + RING - 1) % RING) * TLW + lxh;
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-      const float v = row[j - 1];
-      gx += k.sx[i * 3 + j] * v;
-      gy += k.sy[i * 3 + j] * v;
-    }
-  }
-  float cm = sqrtf(__builtin_fmaf(gx, gx, gy * gy));
-  cm = 16.f * (cm > 0.f ? __builtin_amdgcn_exp2f(2.4f * __builtin_amdgcn_logf(cm)) : 0.f) / (cm * cm + 676.f);
-  cm = 0.117f * cm;
-  const float h = la + cm - 0.3f * fminf(la, cm);
-  return fmaxf(h, 0.f) / 255.f;
-}
 
 // (No waves-per-SIMD hint and no wrapper around the body: `__launch_bounds__(256, 3 | 4)` as well as a __forceinline__ body called from two
 // __global__ wrappers made hipcc spill 16-40 bytes per lane; a scratch reload waits for every older global load -- the row prefetch -- and the
@@ -846,49 +686,6 @@ __global__ __launch_bounds__(256) void embed_tail_stream_kernel(TailArgs a, JndT
 // VGPRs and three waves per SIMD either way, measured 175 -> 245-260 us at 32 x 768^2, profiles/r04_tail_forms.md)
 
 
-// ---------------------------------------------------------------------------------------------------
-// NV12 frames (uint8 [F][3H/2][W] at a row pitch and a frame stride in bytes: H luma rows, then H/2 rows of interleaved CbCr, one pair per
-// 2 x 2 pixel block).  The colour affines come from the host (videoseal_amd/nv12.py: built and inverted in float64, handed over as 12 floats,
-// row-major 3 x 4): dec maps (Y, Cb, Cr, 1) in code units to RGB, which is clamped to [0, 1] before anything else uses it; enc maps
-// (R, G, B, 1) back to code units.  Output codes are floor(clamp(v, 0, 255) + 0.5); the chroma of a block is the mean of its four per-pixel
-// values, rounded once.  Frame bytes move as 16-byte pieces wherever a piece lies inside the row and its address is aligned; every other
-// piece (unaligned base or pitch, right edge) goes byte by byte, guarded -- padding bytes are neither used nor written.
-struct Nv12Mat { float m[12]; };
-struct Nv12Geo { int64_t sp, sfs, dp, dfs; Nv12Mat dec, enc; };
-
-__device__ __forceinline__ uint4 nv12_ld16(const unsigned char* __restrict__ row, const int col, const int W) {
-  const unsigned char* p = row + col;
-  if (col >= 0 && col + 16 <= W && (reinterpret_cast<uintptr_t>(p) & 15) == 0) return *reinterpret_cast<const uint4*>(p);
-  unsigned w[4] = {0u, 0u, 0u, 0u};
-#pragma unroll
-  for (int q = 0; q < 16; ++q) {
-    const int c = col + q;
-    if (c >= 0 && c < W) w[q >> 2] |= (unsigned)p[q] << (8 * (q & 3));
-  }
-  return uint4{w[0], w[1], w[2], w[3]};
-}
-__device__ __forceinline__ void nv12_st16(unsigned char* __restrict__ row, const int col, const int W, const unsigned char* __restrict__ lds16) {
-  unsigned char* p = row + col;
-  if (col + 16 <= W && (reinterpret_cast<uintptr_t>(p) & 15) == 0) {
-    *reinterpret_cast<uint4*>(p) = *reinterpret_cast<const uint4*>(lds16);
-    return;
-  }
-  for (int q = 0; q < 16; ++q)
-    if (col + q < W) p[q] = lds16[q];
-}
-__device__ __forceinline__ unsigned nv12_byte(const uint4& v, const int q) {       // q: compile-time constant after unrolling
-  const unsigned w = q < 4 ? v.x : (q < 8 ? v.y : (q < 12 ? v.z : v.w));
-  return (w >> (8 * (q & 3))) & 0xffu;
-}
-// (explicit fma chains: every NV12 kernel evaluates the same expression, see tail_taps)
-__device__ __forceinline__ float nv12_aff(const Nv12Mat& k, const int r, const float a, const float b, const float c) {
-  return __builtin_fmaf(k.m[4 * r], a, __builtin_fmaf(k.m[4 * r + 1], b, __builtin_fmaf(k.m[4 * r + 2], c, k.m[4 * r + 3])));
-}
-__device__ __forceinline__ void nv12_rgb(const Nv12Mat& k, const float y, const float cb, const float cr, float (&rgb)[3]) {
-#pragma unroll
-  for (int c = 0; c < 3; ++c) rgb[c] = fminf(fmaxf(nv12_aff(k, c, y, cb, cr), 0.f), 1.f);
-}
-__device__ __forceinline__ unsigned char nv12_code(const float v) { return (unsigned char)(int)floorf(fminf(fmaxf(v, 0.f), 255.f) + 0.5f); }
 
 // resize_pre_kernel on NV12 frames: conversion and clamp per source pixel in front of the filter, then the same taps in the same order.
 // Staging: a task is one 16-byte column piece x one row PAIR (two luma pieces and the chroma piece they share); the window of at most
@@ -1615,22 +1412,6 @@ __global__ __launch_bounds__(256) void embed_tail_nv12_stream_kernel(TailArgs a,
   store_group(niter - 1);
 }
 
-// ---------------------------------------------------------------------------------------------------
-// the taps of jnd.py:24-41 (what every released card carries in its state dict)
-bool standard_jnd_taps(const float* t) {
-  static const float lum[25] = {1, 1, 1, 1, 1, 1, 2, 2, 2, 1, 1, 2, 0, 2, 1, 1, 2, 2, 2, 1, 1, 1, 1, 1, 1};
-  static const float sx[9] = {-1, 0, 1, -2, 0, 2, -1, 0, 1}, sy[9] = {1, 2, 1, 0, 0, 0, -1, -2, -1};
-  for (int i = 0; i < 25; ++i) if (t[i] != lum[i]) return false;
-  for (int i = 0; i < 9; ++i) if (t[25 + i] != sx[i] || t[34 + i] != sy[i]) return false;
-  return true;
-}
-
-JndTaps taps_from(const float* t43) {
-  JndTaps k;
-  for (int i = 0; i < 25; ++i) k.lum[i] = t43[i];
-  for (int i = 0; i < 9; ++i) { k.sx[i] = t43[25 + i]; k.sy[i] = t43[34 + i]; }
-  return k;
-}
 
 }  // namespace
 

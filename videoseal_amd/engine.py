@@ -1393,6 +1393,57 @@ class HipEngine:
             self._nv12_arrays[color] = ((C.c_float * 12)(*[float(v) for v in inv.reshape(-1)]), (C.c_float * 12)(*[float(v) for v in fwd.reshape(-1)]))
         return self._nv12_arrays[color]
 
+    def yuv420_arrays(self, color, depth: int):
+        """nv12_arrays for `yuv420.color_affine(matrix, full_range, depth)`: code units of a surface's depth"""
+        key = (color[0], bool(color[1]), int(depth))
+        if key not in self._nv12_arrays:
+            from .yuv420 import color_affine
+            fwd, inv = color_affine(*key)
+            self._nv12_arrays[key] = ((C.c_float * 12)(*[float(v) for v in inv.reshape(-1)]), (C.c_float * 12)(*[float(v) for v in fwd.reshape(-1)]))
+        return self._nv12_arrays[key]
+
+    def _resize_pre_yuv420(self, clip, S, antialias, *, want_rgb, mul, add, want_key, key_step, tag):
+        """resize_pre on a 4:2:0 clip (yuv420.Clip420: device-resident planes at any pitch, its format and colour choice)"""
+        from .yuv420 import fmt_info
+        B, H, W = clip.shape
+        rgb = self.new_act(tag + ".rgb", B, S[0], S[1], 3, 4) if want_rgb else None
+        nk = (B + key_step - 1) // key_step
+        key = self.new_act(tag + ".key", nk, S[0], S[1], self.cfg.in_ch, 4) if want_key else None
+        depth = fmt_info(clip.fmt)[1]
+        surf = N.yuv420_surface(clip.planes, clip.fmt)
+        ev = self._shell_t0()
+        N.check(self.lib.vs_resize_pre_yuv420(C.byref(surf), B, H, W, self.yuv420_arrays(clip.color, depth)[0], S[0], S[1], 1 if antialias else 0,
+                                              N.ptr(rgb.t) if rgb else None, mul, add, N.ptr(key.t) if key else None, key_step,
+                                              self.ymat if self.cfg.yuv else None, N.stream()), "vs_resize_pre_yuv420")
+        # algorithmic HBM bytes: 1.5 samples per pixel once + the low-resolution outputs
+        self._shell_t1(ev, f"resize_pre_yuv_kernel<{clip.fmt}>",
+                       B * H * W * 3 // 2 * clip.planes[0].element_size() + 16 * S[0] * S[1] * ((B if rgb else 0) + (nk if key else 0)))
+        return rgb, key
+
+    def _embed_tail_yuv420(self, clip, out, delta, *, step, video_mode, hmap_low, attenuate, clamp, antialias, scaling_i, scaling_w, preds_w=None):
+        """embed_tail on 4:2:0 clips: `clip` and `out` are yuv420.Clip420 of one format and size, each plane with its own pitch"""
+        from .yuv420 import Clip420, fmt_info
+        if not isinstance(out, Clip420) or out.fmt != clip.fmt or out.shape != clip.shape:
+            raise ValueError("4:2:0 frames need an output clip of the same format and size")
+        if preds_w is not None or int(attenuate) == 2:
+            raise NotImplementedError("the 4:2:0 tail has no preds_w and no training order of operations")
+        F_, H, W = clip.shape
+        d = N.TailYuv420Desc()
+        d.src, d.dst = N.yuv420_surface(clip.planes, clip.fmt), N.yuv420_surface(out.planes, out.fmt)
+        d.preds_w = None
+        d.delta, d.hmap_lowres = N.ptr(delta), N.ptr(hmap_low)
+        d.taps43 = C.cast(self.taps43, C.c_void_p)
+        d.F, d.H, d.W, d.S_h, d.S_w, d.Cd = F_, H, W, delta.shape[-2], delta.shape[-1], delta.shape[1]
+        d.step, d.video_mode, d.total_key = step, video_mode, delta.shape[0]
+        d.attenuate, d.clamp, d.antialias = int(attenuate), int(clamp), int(antialias)
+        d.scaling_i, d.scaling_w = float(scaling_i), float(scaling_w)
+        d.variant = 1 if int(self.tail_variant) in (1, 2, 3) else 0           # (the tile variants of the fp32 tail -> the tile kernel)
+        d.yuv2rgb12, d.rgb2yuv12 = self.yuv420_arrays(clip.color, fmt_info(clip.fmt)[1])
+        ev = self._shell_t0()
+        N.check(self.lib.vs_embed_tail_yuv420(C.byref(d), N.stream()), "vs_embed_tail_yuv420")
+        # algorithmic HBM bytes: 1.5 samples per pixel each way + the low-resolution watermark
+        self._shell_t1(ev, f"embed_tail_yuv_kernel<{clip.fmt}>", 2 * (F_ * H * W * 3 // 2) * clip.planes[0].element_size() + delta.numel() * 4)
+
     @staticmethod
     def _nv12_geometry(t: torch.Tensor):
         """(F, H, W, pitch, frame stride) of an NV12 clip uint8 [F, 3H/2, W]; pitch and strides come from the tensor's strides"""
@@ -1407,6 +1458,8 @@ class HipEngine:
                    want_key: bool = False, key_step: int = 1, tag="rs", color=None) -> Tuple[Optional[Act], Optional[Act]]:
         """imgs on device, fp32 NCHW [B,3,H,W], uint8 RGB24 [B,H,W,3] or uint8 NV12 [B,3H/2,W] (any pitch / frame stride, colour choice
         `color` = (matrix, full_range), default self.nv12_color) -> (rgb Act [B,S,S,4] or None, key Act [ceil(B/step),S,S,4] or None)."""
+        if not torch.is_tensor(imgs):         # a 4:2:0 clip (yuv420.Clip420) carries its own format and colour choice
+            return self._resize_pre_yuv420(imgs, S, antialias, want_rgb=want_rgb, mul=mul, add=add, want_key=want_key, key_step=key_step, tag=tag)
         nv12 = imgs.dtype == torch.uint8 and imgs.dim() == 3
         u8 = imgs.dtype == torch.uint8 and not nv12
         if nv12:
@@ -1493,6 +1546,9 @@ class HipEngine:
     def embed_tail(self, imgs, out, delta, *, step, video_mode, hmap_low, attenuate, clamp, antialias, scaling_i, scaling_w,
                    preds_w=None, color=None):
         """`color` = (matrix, full_range) of NV12 clips (default self.nv12_color); unused by the other frame formats"""
+        if not torch.is_tensor(imgs):         # a 4:2:0 clip (yuv420.Clip420)
+            return self._embed_tail_yuv420(imgs, out, delta, step=step, video_mode=video_mode, hmap_low=hmap_low, attenuate=attenuate, clamp=clamp,
+                                           antialias=antialias, scaling_i=scaling_i, scaling_w=scaling_w, preds_w=preds_w)
         if imgs.dtype == torch.uint8 and imgs.dim() == 3:
             return self._embed_tail_nv12(imgs, out, delta, step=step, video_mode=video_mode, hmap_low=hmap_low, attenuate=attenuate, clamp=clamp,
                                          antialias=antialias, scaling_i=scaling_i, scaling_w=scaling_w, preds_w=preds_w, color=color)

@@ -46,6 +46,15 @@ def _result_buffer(shape, dtype, device) -> torch.Tensor:
     return torch.empty(tuple(shape), dtype=dtype, device=device)
 
 
+def _raw_frames(x) -> bool:
+    """frames that travel in their own format: uint8 tensors (RGB24, NV12) and 4:2:0 clips (yuv420.Clip420); everything else is fp32 NCHW"""
+    return not torch.is_tensor(x) or x.dtype == torch.uint8
+
+
+def _empty_like(x):
+    return torch.empty_like(x) if torch.is_tensor(x) else x.empty_like()
+
+
 def _to_caller(t, device):
     """device tensor -> the caller's device (no-grad result paths)"""
     if not torch.is_tensor(t) or t.device == torch.device(device):
@@ -393,7 +402,7 @@ class Wam(nn.Module):
             return {"preds": eng.extractor_forward(rgb)}
         if self.use_graphs and not torch.cuda.is_current_stream_capturing():
             def key():           # the arithmetic is part of the key: network-wide split AND the layers the calibration pinned to the exact split
-                return ("det", fr.dtype, tuple(fr.shape), eng.nv12_color if fr.dim() == 3 else None, tuple(S), antialias, id(eng), eng.arith_net["X"], tuple(sorted(eng.layer_arith.items())))
+                return ("det", fr.dtype, tuple(fr.shape), eng.nv12_color if fr.dim() == 3 else getattr(fr, "graph_key", None), tuple(S), antialias, id(eng), eng.arith_net["X"], tuple(sorted(eng.layer_arith.items())))
             out = self._graphed(key(), {"fr": fr}, run, rekey=key)["preds"].clone()
             eng.note_guard()           # the captured vs_check_finite has run: deliver its flag like an eager steady-state pass does
             return out
@@ -406,12 +415,12 @@ class Wam(nn.Module):
                       fwd_order: bool = False, tail_span: int = 0) -> None:
         bn_train = self.embedder.training
         if self.use_graphs and not bn_train and not torch.cuda.is_current_stream_capturing():
-            key = ("emb", fr.dtype, tuple(fr.shape), eng.nv12_color if fr.dim() == 3 else None, tuple(msgs_i32.shape), step, video_mode, antialias, lowres, preds_w is not None, self.img_size,
+            key = ("emb", fr.dtype, tuple(fr.shape), eng.nv12_color if fr.dim() == 3 else getattr(fr, "graph_key", None), tuple(msgs_i32.shape), step, video_mode, antialias, lowres, preds_w is not None, self.img_size,
                    self.clamp, float(self.blender.scaling_i), float(self.blender.scaling_w), self.attenuation is not None, fwd_order, tail_span, id(eng), eng.arith_net["E"])
             ent = self._graphs.get(key)
             if ent is None:
                 sin = {"fr": fr.clone(), "msgs": msgs_i32.clone()}
-                sout = torch.empty_like(sin["fr"])
+                sout = _empty_like(sin["fr"])
                 spw = torch.empty_like(preds_w) if preds_w is not None else None
                 for _ in range(2):
                     self._embed_frames_eager(eng, sin["fr"], sin["msgs"], sout, step=step, video_mode=video_mode, antialias=antialias,
@@ -484,11 +493,16 @@ class Wam(nn.Module):
         the result comes back on imgs.device."""
         on_dev = imgs.device == eng.dev
         if on_dev:
-            src = imgs if imgs.dtype == torch.uint8 else N.f32c(imgs)
-            out = torch.empty_like(src) if want_out else None
+            src = imgs if _raw_frames(imgs) else N.f32c(imgs)
+            out = _empty_like(src) if want_out else None
         else:
             src = imgs
-            out = _result_buffer(imgs.shape, imgs.dtype if imgs.dtype == torch.uint8 else torch.float32, imgs.device) if want_out else None
+            if not want_out:
+                out = None
+            elif torch.is_tensor(imgs):
+                out = _result_buffer(imgs.shape, imgs.dtype if imgs.dtype == torch.uint8 else torch.float32, imgs.device)
+            else:
+                out = imgs.empty_like()
         for attempt in range(2):
             for a in range(0, imgs.shape[0], span):
                 b = min(imgs.shape[0], a + span)
@@ -496,8 +510,8 @@ class Wam(nn.Module):
                     fn(src[a:b], out[a:b] if want_out else None, a, b)
                 else:
                     ch = src[a:b].to(eng.dev)
-                    ch = ch.contiguous() if ch.dtype == torch.uint8 else N.f32c(ch)
-                    oc = torch.empty_like(ch) if want_out else None
+                    ch = ch.contiguous() if _raw_frames(ch) else N.f32c(ch)
+                    oc = _empty_like(ch) if want_out else None
                     fn(ch, oc, a, b)
                     if want_out:
                         out[a:b].copy_(oc, non_blocking=True)
@@ -809,6 +823,45 @@ class Videoseal(Wam):
         conversion fused into the resize kernel."""
         self._nv12_clip(clip, "detect_nv12", matrix, full_range)
         self._per_frame_rows_only("detect_nv12")
+        if clip.shape[0] == 0:
+            return {"preds": torch.zeros((0, self.embedder.cfg.nbits + 1), device=clip.device)}
+        return {"preds": self._detect_clip(clip, interpolation)}
+
+    # ---- 4:2:0 clips as planes (videoseal_amd/yuv420.py): nv12, i420, p010, yuv420p10, every plane at its own pitch
+    def _yuv420_clip(self, planes, fmt: str, what: str, matrix: str, full_range: bool):
+        from .yuv420 import MATRICES, Clip420, check_clip
+        check_clip(planes, fmt, what)
+        if matrix not in MATRICES:
+            raise ValueError(f"{what}: matrix must be one of {sorted(MATRICES)}, got {matrix!r}")
+        return Clip420(planes, fmt, (matrix, bool(full_range)))
+
+    @torch.no_grad()
+    def embed_yuv420(self, planes, fmt: str, msgs: torch.Tensor = None, interpolation: dict = None, lowres_attenuation: bool = True,
+                     matrix: str = "bt709", full_range: bool = False) -> dict:
+        """planes: the plane tensors of a 4:2:0 clip of format `fmt` ("nv12", "i420", "p010", "yuv420p10": yuv420.py; H, W even, last stride 1,
+        any row pitch and frame stride per plane) -> {'planes_w': plane views, 'imgs_w': the packed contiguous buffer [F, 3HW/2] they view,
+        'msgs'}.  Means: yuv420.to_rgb -> embed(..., is_video=True) -> yuv420.from_rgb with both conversions fused into the resize and tail
+        kernels: no RGB or fp32 frame is written, and a 10-bit clip keeps its 10 bits.  `matrix` is "bt601", "bt709" or "bt2020",
+        `full_range` selects full-range codes.  Needs clamp=True."""
+        clip = self._yuv420_clip(planes, fmt, "embed_yuv420", matrix, full_range)
+        if not self.clamp:
+            raise NotImplementedError("4:2:0 output needs clamp=True (codes are undefined outside [0, 1])")
+        if msgs is None:
+            msgs = self.get_random_msg()
+        else:
+            assert msgs.shape[0] == 1, "Message should be unique"
+        if clip.shape[0] == 0 or clip.numel() == 0:
+            out = clip.clone()
+        else:
+            out = self._embed_clip(clip, msgs, interpolation, lowres_attenuation)
+        return {"planes_w": out.planes, "imgs_w": out.buf, "msgs": msgs[0:1].repeat(len(clip), 1)}
+
+    @torch.no_grad()
+    def detect_yuv420(self, planes, fmt: str, interpolation: dict = None, matrix: str = "bt709", full_range: bool = False) -> dict:
+        """planes, fmt as in embed_yuv420 -> {'preds': [F, 1+nbits]}: detect(yuv420.to_rgb(planes, fmt), is_video=True) with the conversion
+        fused into the resize kernel."""
+        clip = self._yuv420_clip(planes, fmt, "detect_yuv420", matrix, full_range)
+        self._per_frame_rows_only("detect_yuv420")
         if clip.shape[0] == 0:
             return {"preds": torch.zeros((0, self.embedder.cfg.nbits + 1), device=clip.device)}
         return {"preds": self._detect_clip(clip, interpolation)}

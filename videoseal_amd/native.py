@@ -45,6 +45,8 @@ EXPORTS = [
     "vs_disc_input", "vs_disc_input_bwd", "vs_groupnorm_partial_doubles", "vs_groupnorm_lrelu", "vs_groupnorm_lrelu_bwd", "vs_conv4x4_wgrad_supported",
     "vs_conv4x4_wgrad_partial_floats", "vs_conv4x4_wgrad", "vs_conv4x4_n1", "vs_conv4x4_n1_bwd", "vs_conv4x4_n1_bias_grad", "vs_disc_loss",
     "vs_sizeof_tail_nv12_desc", "vs_resize_pre_nv12", "vs_embed_tail_nv12",
+    "vs_sizeof_yuv420_surface", "vs_sizeof_tail_yuv420_desc", "vs_resize_pre_yuv420", "vs_embed_tail_yuv420", "vs_yuv420_default_color",
+    "vs_model_embed_yuv420", "vs_model_detect_yuv420",
 ]
 
 
@@ -105,6 +107,34 @@ class TailNv12Desc(C.Structure):
         ("src_pitch", C.c_int64), ("src_frame_stride", C.c_int64), ("dst_pitch", C.c_int64), ("dst_frame_stride", C.c_int64),
         ("yuv2rgb12", C.c_float * 12), ("rgb2yuv12", C.c_float * 12),
     ]
+
+
+class Yuv420Surface(C.Structure):
+    """mirror of vs_yuv420_surface_t: plane addresses, row pitches and frame strides in bytes, the format triple"""
+    _fields_ = [
+        ("plane", C.c_void_p * 3), ("pitch", C.c_int64 * 3), ("frame_stride", C.c_int64 * 3),
+        ("planar", C.c_int32), ("depth", C.c_int32), ("msb_aligned", C.c_int32), ("reserved_", C.c_int32),
+    ]
+
+
+class TailYuv420Desc(C.Structure):
+    """mirror of vs_tail_yuv420_desc_t: two surfaces, then TailDesc's members from preds_w on and the two colour affines"""
+    _fields_ = [("src", Yuv420Surface), ("dst", Yuv420Surface)] + TailDesc._fields_[2:] + [
+        ("yuv2rgb12", C.c_float * 12), ("rgb2yuv12", C.c_float * 12),
+    ]
+
+
+def yuv420_surface(planes, fmt: str) -> Yuv420Surface:
+    """the surface of device-resident planes (videoseal_amd/yuv420.py): addresses and strides of the tensors, nothing is copied"""
+    from .yuv420 import fmt_info
+    planar, depth, msb = fmt_info(fmt)
+    s = Yuv420Surface()
+    for i, p in enumerate(planes):
+        s.plane[i] = ptr(p)
+        s.pitch[i] = p.stride(1) * p.element_size()
+        s.frame_stride[i] = p.stride(0) * p.element_size()
+    s.planar, s.depth, s.msb_aligned = int(planar), depth, int(msb)
+    return s
 
 
 class ResblockThinDesc(C.Structure):
@@ -173,6 +203,9 @@ def lib() -> C.CDLL:
         "vs_nv12_default_color": [P, P],
         "vs_resize_pre_nv12": [P, I, I, I, I64, I64, P, I, I, I, P, F, F, P, I, P, P],
         "vs_embed_tail_nv12": [C.POINTER(TailNv12Desc), P],
+        "vs_resize_pre_yuv420": [C.POINTER(Yuv420Surface), I, I, I, P, I, I, I, P, F, F, P, I, P, P],
+        "vs_embed_tail_yuv420": [C.POINTER(TailYuv420Desc), P],
+        "vs_yuv420_default_color": [I, P, P],
         "vs_aug_color": [P, P, I, I, I, I, F, P, P],
         "vs_aug_crop_flip": [P, P, I, I, I, I, I, I, I, I, P],
         "vs_aug_color_chain": [P, P, I, I, I, I, C.POINTER(C.c_int), C.POINTER(C.c_float), P, P],
@@ -301,13 +334,15 @@ def lib() -> C.CDLL:
     L.vs_sizeof_conv_desc.restype = C.c_int
     L.vs_sizeof_tail_desc.restype = C.c_int
     L.vs_sizeof_tail_nv12_desc.restype = C.c_int
+    L.vs_sizeof_yuv420_surface.restype = L.vs_sizeof_tail_yuv420_desc.restype = C.c_int
     L.vs_sizeof_conv_plan.restype = L.vs_sizeof_cnx_stage_plan.restype = C.c_int
     if L.vs_version() != 3:
         raise NativeError(f"{LIB_PATH} has ABI version {L.vs_version()}, this binding is written for 3: rebuild (make -C videoseal_amd/csrc)")
     if L.vs_sizeof_conv_desc() != C.sizeof(ConvDesc) or L.vs_sizeof_tail_desc() != C.sizeof(TailDesc) or \
             L.vs_sizeof_tail_nv12_desc() != C.sizeof(TailNv12Desc) or L.vs_sizeof_conv_plan() != C.sizeof(ConvPlan) or \
-            L.vs_sizeof_cnx_stage_plan() != C.sizeof(CnxStagePlan):
-        raise NativeError("ctypes mirrors of vs_conv_desc_t / vs_tail_desc_t / vs_tail_nv12_desc_t / the plan structs are out of date with the shared library")
+            L.vs_sizeof_cnx_stage_plan() != C.sizeof(CnxStagePlan) or L.vs_sizeof_yuv420_surface() != C.sizeof(Yuv420Surface) or \
+            L.vs_sizeof_tail_yuv420_desc() != C.sizeof(TailYuv420Desc):
+        raise NativeError("ctypes mirrors of vs_conv_desc_t / vs_tail_desc_t / vs_tail_nv12_desc_t / vs_tail_yuv420_desc_t / the plan structs are out of date with the shared library")
     _lib = L
     return L
 
