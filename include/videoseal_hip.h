@@ -607,6 +607,9 @@ int vs_embed_tail(const vs_tail_desc_t* d, void* stream);
  * Range and rounding.  After NV12 -> RGB every channel is clamped to [0, 1] before anything else uses it.  Output codes are
  *   floor(clamp(v, 0, 255) + 0.5), v in code units; there is no intermediate rounding to RGB24.
  *
+ * Both entry points are the 4:2:0 entry points below on the two planes of the buffer (Y at `base`, CbCr at base + H * pitch, one pitch and
+ *   one frame stride for both: format nv12) -- the same kernels, the same bits.  They ask for frame_stride >= pitch * (3H/2 - 1) + W, which
+ *   keeps the chroma rows of a frame clear of the next frame's luma rows; the per-plane rule of a surface would not.
  * vs_resize_pre_nv12: vs_resize_pre on such frames (conversion and clamp per source pixel in front of the filter); dst_rgb / dst_y / ymat3
  *   as there.
  * vs_embed_tail_nv12: vs_embed_tail on the converted, clamped pixel (key-frame expansion in all three video modes, Cd 1 and 3, attenuate 0 /
@@ -652,11 +655,12 @@ int vs_embed_tail_nv12(const vs_tail_nv12_desc_t* d, void* stream);
  * Range and rounding.  After decoding every RGB channel is clamped to [0, 1] before anything else uses it.  Output codes are
  *   floor(clamp(v, 0, 2^depth - 1) + 0.5), v in code units (p010 stores code << 6); there is no intermediate rounding to RGB24.
  *
- * vs_resize_pre_yuv420 / vs_embed_tail_yuv420: vs_resize_pre_nv12 / vs_embed_tail_nv12 on such surfaces -- the same conversion, filter, JND
- *   and blend expressions in the same order, so two layouts that hold the same codes give the same bits (an nv12 surface: the bits of the
- *   NV12 entry points).  The descriptor is vs_tail_nv12_desc_t with two surfaces (same format) in place of imgs / out and the pitches:
- *   clamp must be 1, io_u8 is ignored, variant 0 / 1 / 4 as there, preds_w != NULL and attenuate = 2 answer VS_ERR_UNSUPPORTED.  Bytes of a
- *   destination plane between a row's end and its pitch are never written.  Development switches: keys 0 - 2, as the NV12 entry points.
+ * vs_resize_pre_yuv420 / vs_embed_tail_yuv420: vs_resize_pre / vs_embed_tail on such surfaces, as described for the NV12 entry points (which
+ *   run these kernels) -- one kernel family for all four formats, the same conversion, filter, JND and blend expressions in the same order,
+ *   so two layouts that hold the same codes give the same bits.  The descriptor is vs_tail_nv12_desc_t with two surfaces (same format) in
+ *   place of imgs / out and the pitches: clamp must be 1, io_u8 is ignored, variant 0 / 1 / 4 as there, preds_w != NULL and attenuate = 2
+ *   answer VS_ERR_UNSUPPORTED.  Bytes of a destination plane between a row's end and its pitch are never written.  Development switches:
+ *   keys 0 - 2 (VIDEOSEAL_RESIZE=tile, VS_RESIZE_STRIP, VS_TAIL_STRIP), with the meaning they have for vs_resize_pre / vs_embed_tail.
  */
 typedef struct vs_yuv420_surface {
   void* plane[3];
@@ -696,7 +700,8 @@ int vs_yuv420_default_color(int depth, float* yuv2rgb12, float* rgb2yuv12);
  *                     one message for the clip) or ceil(frames/step) (image mode: step = 1); preds_w optional.
  *   vs_model_detect = Wam.detect / Videoseal.detect (wam.py:206-234): resize -> ConvNeXt-V2 -> logits [frames][1+nbits].
  * io_u8 = 1: imgs / imgs_w are uint8 RGB24 [frames][H][W][3] (inference_streaming.py:26,31), conversions fused.
- * io_u8 = 2: imgs / imgs_w are uint8 NV12 [frames][3H/2][W] (see vs_resize_pre_nv12), contiguous (pitch = W), H and W even, conversions fused;
+ * io_u8 = 2: imgs / imgs_w are uint8 NV12 [frames][3H/2][W] (see vs_resize_pre_nv12), contiguous (pitch = W), H and W even, conversions fused
+ *            (vs_model_embed_yuv420 / vs_model_detect_yuv420 on the nv12 surfaces of the two buffers, with the model's stored colour);
  *            BT.709 limited range unless vs_model_set_nv12_color has stored another pair of affines (the one mutation of a model: call it
  *            before the model is shared between threads).  preds_w is not available with NV12 frames (VS_ERR_UNSUPPORTED).
  * Chunking over long clips, frame aggregation (videoseal.py:390-428) and message generation stay with the caller. */

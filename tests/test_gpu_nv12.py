@@ -26,6 +26,7 @@ from tests._model import TOL_IMG, TOL_LOGIT, make_model  # noqa: E402
 
 from videoseal_amd import native as N  # noqa: E402
 from videoseal_amd import nv12  # noqa: E402
+from videoseal_amd.yuv420 import Clip420  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -288,10 +289,11 @@ def test_red_zones_and_pitch_padding(shape, full_jnd, tiny):
         keep = sbuf.clone()
         dbuf, dview = pitched(torch.zeros_like(clip), dpitch, spare, 0x5A)
         with torch.cuda.device(eng.dev), N.debug("TAIL_STRIP", strip):
-            rgb, key = eng.resize_pre(sview, (S, S), True, want_rgb=True, want_key=True, key_step=2, tag="t.nv12", color=color)
+            src, dst = (Clip420(nv12.planes(v), "nv12", color) for v in (sview, dview))      # the planes are views of the pitched buffers
+            rgb, key = eng.resize_pre(src, (S, S), True, want_rgb=True, want_key=True, key_step=2, tag="t.nv12")
             res = [rgb.t.clone(), key.t.clone()]
-            eng.embed_tail(sview, dview, delta, step=2, video_mode=2, hmap_low=hm, attenuate=True, clamp=True, antialias=True,
-                           scaling_i=1.0, scaling_w=0.2, color=color)
+            eng.embed_tail(src, dst, delta, step=2, video_mode=2, hmap_low=hm, attenuate=True, clamp=True, antialias=True,
+                           scaling_i=1.0, scaling_w=0.2)
         torch.cuda.synchronize()
         eng.tail_variant = 0
         assert torch.equal(sbuf, keep)                                        # the source is read only
@@ -301,6 +303,80 @@ def test_red_zones_and_pitch_padding(shape, full_jnd, tiny):
     for other in results[1:]:
         for a, b in zip(results[0], other):
             assert torch.equal(a, b)
+
+
+def call_tail(sview, dview, delta, hm, eng, preset, variant, frame_strides=None):
+    """vs_embed_tail_nv12 on two single-buffer views; returns the entry point's code.  variant 1 = the tile kernel, 4 = the row-streaming one"""
+    F_, R_, W = sview.shape
+    fwd, inv = nv12.color_affine(*preset)
+    d = N.TailNv12Desc()
+    d.imgs, d.out, d.preds_w = sview.data_ptr(), dview.data_ptr(), None
+    d.delta, d.hmap_lowres = N.ptr(delta), N.ptr(hm)
+    d.taps43 = C.cast(eng.taps43, C.c_void_p)
+    d.F, d.H, d.W, d.S_h, d.S_w, d.Cd = F_, R_ // 3 * 2, W, delta.shape[-2], delta.shape[-1], delta.shape[1]
+    d.step, d.video_mode, d.total_key = 2, 2, delta.shape[0]
+    d.attenuate, d.clamp, d.antialias = 1, 1, 1
+    d.scaling_i, d.scaling_w = 1.0, 0.2
+    d.variant = variant
+    d.src_pitch, d.dst_pitch = sview.stride(1), dview.stride(1)
+    d.src_frame_stride, d.dst_frame_stride = frame_strides or (sview.stride(0), dview.stride(0))
+    d.yuv2rgb12 = (C.c_float * 12)(*[float(v) for v in inv.reshape(-1)])
+    d.rgb2yuv12 = (C.c_float * 12)(*[float(v) for v in fwd.reshape(-1)])
+    with torch.cuda.device(eng.dev):
+        rc = N.lib().vs_embed_tail_nv12(C.byref(d), N.stream())
+        torch.cuda.synchronize()
+    return rc
+
+
+def test_misaligned_chroma_plane_and_unequal_pitches(tiny):
+    """The single-buffer entry points place the chroma plane at base + H * pitch.  2 x 74 x 88 with source pitch 91 and destination pitch 93:
+    H * pitch is 14 resp. 2 past a multiple of 16, so neither chroma plane starts on a 16-byte boundary, and the two buffers disagree on
+    every row's alignment.  vs_resize_pre_nv12 (tile and row-streaming form) against float64 interpolation (2e-6, the bound of section 1),
+    vs_embed_tail_nv12 (both forms, full-resolution and low-resolution heat-map) against the fp32 tail on the decoded clip (0.5 +
+    255 * TOL_IMG, the bound of section 2); no padding or spare byte of either buffer changes."""
+    spec, sd, model = tiny
+    eng = model._engine()
+    F_, H, W, spitch, dpitch, spare = 2, 74, 88, 91, 93, 2
+    assert (H * spitch) % 16 == 14 and (H * dpitch) % 16 == 2
+    preset = R.PRESETS[2]
+    x = synthetic_frames(F_, H, W, seed=70, kind="noise")
+    clip = torch.from_numpy(R.encode(x.numpy(), *preset))
+    sbuf, sview = pitched(clip, spitch, spare)
+    keep = sbuf.clone()
+    # resize
+    ymat = [float(np.float32(v)) for v in (0.299, 0.587, 0.114)]
+    ref = F.interpolate(torch.from_numpy(R.decode(clip.numpy(), *preset)), size=(S, S), mode="bilinear", align_corners=False, antialias=True)
+    ref_rgb = (ref * 2.0 - 1.0).permute(0, 2, 3, 1)
+    ref_y = ((ymat[0] * ref[:, 0] + ymat[1] * ref[:, 1] + ymat[2] * ref[:, 2]) * 2.0 - 1.0)[::2]
+    got = [call_resize(sview, preset, True, True, True, ymat, form=form) for form in ("tile", None)]
+    for rgb, key in got:
+        e_rgb, e_y = (rgb[..., :3].cpu().double() - ref_rgb).abs().max().item(), (key[..., 0].cpu().double() - ref_y).abs().max().item()
+        print(f"resize_pre_nv12 pitch 91: max |delta| rgb {e_rgb:.2e}, y {e_y:.2e}")
+        assert e_rgb < 2e-6 and e_y < 2e-6
+    assert got[0][0].equal(got[1][0]) and got[0][1].equal(got[1][1])
+    # tail: the watermark at 32 x 32, so that the row-streaming form applies (an up-scale by >= 2 in both directions)
+    g = torch.Generator().manual_seed(71)
+    delta = torch.tanh(torch.randn(1, 1, 32, 32, generator=g)).cuda()
+    pad = padding_mask(F_, H * 3 // 2, W, dpitch, spare)
+    rgb = nv12.nv12_to_rgb(clip, *preset).cuda()
+    for hm in (None, torch.rand(F_ * 32 * 32, generator=g).cuda()):
+        w = torch.empty_like(rgb)
+        with torch.cuda.device(eng.dev):
+            eng.embed_tail(rgb, w, delta, step=2, video_mode=2, hmap_low=hm, attenuate=True, clamp=True, antialias=True, scaling_i=1.0, scaling_w=0.2)
+        v = R.encode_values(w.cpu().double().numpy(), *preset)
+        outs = []
+        for variant in (1, 4):
+            dbuf, dview = pitched(torch.zeros_like(clip), dpitch, spare, 0x5A)
+            assert call_tail(sview, dview, delta, hm, eng, preset, variant) == 0
+            err = np.abs(dview.cpu().numpy().astype(np.float64) - v).max()
+            print(f"embed_tail_nv12 pitch 91 -> 93, variant {variant}, {'full' if hm is None else 'low-resolution'} heat-map: max |code - v| = {err:.4f}")
+            assert err <= 0.5 + 255 * TOL_IMG
+            assert torch.all(dbuf[pad] == 0x5A)
+            assert not torch.equal(dview.cpu(), clip)
+            outs.append(dview.clone())
+        if hm is not None:                            # without the full-resolution heat-map both forms evaluate the same expressions
+            assert torch.equal(outs[0], outs[1])
+    assert torch.equal(sbuf, keep)                    # the source is read only
 
 
 # ---------------------------------------------------------------------------------------------------- 7. graphs
@@ -383,6 +459,30 @@ def test_errors_empty_and_host_clips(tiny):
     host = model.embed_nv12(ok.cpu(), msgs)["imgs_w"]
     assert not host.is_cuda and torch.equal(host, dev.cpu())
     assert torch.equal(model.detect_nv12(ok.cpu())["preds"], model.detect_nv12(ok)["preds"].cpu())
+
+
+def test_frame_stride_must_hold_the_whole_buffer(tiny):
+    """a frame of a single-buffer clip is pitch * (3H/2 - 1) + W bytes.  frame_stride = pitch * H holds the luma plane and the chroma plane
+    each on its own (the rule of the plane entry points) but lets the chroma rows of a frame overlap the luma rows of the next: both entry
+    points answer VS_ERR_BAD_ARG (-1), for the source and for the destination, before any launch"""
+    spec, sd, model = tiny
+    eng = model._engine()
+    F_, H, W, pitch = 2, 8, 16, 16
+    whole, planes_only = pitch * (H * 3 // 2), pitch * H
+    src = torch.zeros(F_, H * 3 // 2, W, dtype=torch.uint8, device="cuda")
+    dst = torch.zeros_like(src)
+    dec = (C.c_float * 12)(*[float(v) for v in nv12.color_affine()[1].reshape(-1)])
+    rgb = torch.zeros(F_, 4, 4, 4, device="cuda")
+
+    def resize(frame_stride):
+        return N.lib().vs_resize_pre_nv12(src.data_ptr(), F_, H, W, pitch, frame_stride, dec, 4, 4, 1, N.ptr(rgb), 1.0, 0.0, None, 1, None, None)
+    delta = torch.zeros(1, 1, 4, 4, device="cuda")
+    hm = torch.ones(F_ * 16, device="cuda")
+    assert resize(planes_only) == -1
+    assert call_tail(src, dst, delta, hm, eng, nv12.DEFAULT_COLOR, 0, frame_strides=(planes_only, whole)) == -1
+    assert call_tail(src, dst, delta, hm, eng, nv12.DEFAULT_COLOR, 0, frame_strides=(whole, planes_only)) == -1
+    assert resize(whole) == 0 and call_tail(src, dst, delta, hm, eng, nv12.DEFAULT_COLOR, 0, frame_strides=(whole, whole)) == 0
+    torch.cuda.synchronize()
 
 
 def test_pixelwise_detector_is_refused(tiny, monkeypatch):

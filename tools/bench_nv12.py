@@ -66,7 +66,7 @@ def timed_ms(fn, what):
 
 def sweep(out_path):
     """us per launch of vs_resize_pre_nv12 at 768^2 -> 256^2 for the tile form and the row-streaming form at every strip height, for the launch
-    shapes of the scenario (8-frame detect chunks, 16 frames, the 32-frame embed launch with key frames): what the strip rule in shell.hip follows"""
+    shapes of the scenario (8-frame detect chunks, 16 frames, the 32-frame embed launch with key frames): what the strip rule in yuv420.hip follows"""
     from videoseal_amd import native as N
     lib = N.lib()
     _, inv = nv12.color_affine()
@@ -170,7 +170,7 @@ def main():
     a, c = res["a_nv12"], res["c_rgb24"]
     gap = a["median_ms"] - c["median_ms"]
     holds = gap <= c["spread_ms"]
-    pairs = [("resize_pre_nv12_kernel", "resize_pre_kernel<u8>"), ("embed_tail_nv12_kernel", "embed_tail_kernel<u8>")]
+    pairs = [("resize_pre_yuv_kernel<nv12>", "resize_pre_kernel<u8>"), ("embed_tail_yuv_kernel<nv12>", "embed_tail_kernel<u8>")]
     kernel_gaps = {n: round(shell[n]["us"] - shell[u]["us"], 1) for n, u in pairs if n in shell and u in shell}
     doc = {
         "tool": "tools/bench_nv12.py", "when": time.strftime("%Y-%m-%d %H:%M:%S"), "device": torch.cuda.get_device_name(0),

@@ -6,7 +6,8 @@ Scenario (that of tools/bench_nv12.py): VideoSeal 1.0, 32 x 768^2 frames residen
 detect of the clip), for each format:
   (a) embed_yuv420 + detect_yuv420 on the surfaces;
   (b) the same surfaces through torch: yuv420.to_rgb -> embed + detect (fp32) -> yuv420.from_rgb;
-  (c) embed_nv12 + detect_nv12 on the same frames: an unchanged code path, the yardstick.
+  (c) embed_nv12 + detect_nv12 on the same frames: the same kernels on the interleaved 8-bit layout (`<nv12>` among the shell kernels),
+      the yardstick -- tools/bench_nv12.py holds it to the RGB24 route.
 What to look for: (a, i420) moves NV12's bytes and should sit within the spread of (c) over its own repeats; the 10-bit formats move twice
 the surface bytes and should cost about the shell kernels' share more.  The json states both, with the shell kernels' time and fraction of
 8 TB/s over their algorithmic bytes (1.5 samples per pixel each way + the low-resolution tensors).

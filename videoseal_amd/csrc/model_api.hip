@@ -693,14 +693,12 @@ struct Runner {
     if (live()) chk(vs_pool_linear(hl.p, B, hl.H * hl.W, hl.C, hl.ld, m->lin_w, m->lin_b, c.nbits + 1, logits, st));
   }
   // model.py::_embed_frames_eager
-  // io: 0 = fp32 NCHW, 2 = NV12 (contiguous: pitch = W), 3 = the 4:2:0 surface `ysrc`, any other value = RGB24
+  // io: 0 = fp32 NCHW, 3 = the 4:2:0 surface `ysrc` (io_u8 = 2 arrives here as a contiguous nv12 surface), any other value = RGB24
   void resize(const void* imgs, int io, int F, int H, int W, int S, int antialias, float* rgb, float mul, float add, float* key, int step,
               const float* ymat) {
     if (!live()) return;
     const bool u8 = io != 0;
     if (io == 3) chk(vs_resize_pre_yuv420(ysrc, F, H, W, ydec, S, S, antialias, rgb, mul, add, key, step, ymat, st));
-    else if (io == 2) chk(vs_resize_pre_nv12(static_cast<const unsigned char*>(imgs), F, H, W, W, (int64_t)W * (H / 2 * 3), m->yuv2rgb12, S, S, antialias,
-                                        rgb, mul, add, key, step, ymat, st));
     else if (u8) chk(vs_resize_pre_u8(static_cast<const unsigned char*>(imgs), F, H, W, S, S, antialias, rgb, mul, add, key, step, ymat, st));
     else chk(vs_resize_pre(static_cast<const float*>(imgs), F, 3, H, W, S, S, antialias, rgb, mul, add, key, step, ymat, st));
   }
@@ -730,21 +728,6 @@ struct Runner {
       std::memcpy(n.yuv2rgb12, ydec, sizeof(n.yuv2rgb12));
       std::memcpy(n.rgb2yuv12, yenc, sizeof(n.rgb2yuv12));
       if (live()) chk(vs_embed_tail_yuv420(&n, st));
-      return;
-    }
-    if (io == 2) {
-      vs_tail_nv12_desc_t n;
-      std::memset(&n, 0, sizeof(n));
-      n.imgs = imgs; n.out = out; n.preds_w = preds_w; n.delta = delta; n.hmap_lowres = hmap; n.taps43 = m->taps43;
-      n.F = F; n.H = H; n.W = W; n.S_h = Sh; n.S_w = Sw; n.Cd = c.out_ch;
-      n.step = step; n.video_mode = video_mode; n.total_key = nk;
-      n.attenuate = att ? 1 : 0; n.clamp = c.clamp; n.antialias = antialias;
-      n.scaling_i = c.scaling_i; n.scaling_w = c.scaling_w;
-      n.src_pitch = n.dst_pitch = W;
-      n.src_frame_stride = n.dst_frame_stride = (int64_t)W * (H / 2 * 3);
-      std::memcpy(n.yuv2rgb12, m->yuv2rgb12, sizeof(n.yuv2rgb12));
-      std::memcpy(n.rgb2yuv12, m->rgb2yuv12, sizeof(n.rgb2yuv12));
-      if (live()) chk(vs_embed_tail_nv12(&n, st));
       return;
     }
     const bool u8 = io != 0;
@@ -883,7 +866,7 @@ extern "C" int vs_model_create(const vs_model_cfg_t* cfg, const vs_tensor_t* ten
   return VS_OK;
 }
 
-// BT.709 limited range, the expressions of videoseal_amd/nv12.py::color_affine (depth 10: yuv420.py::color_affine) in the same order: the
+// BT.709 limited range, the expressions of videoseal_amd/yuv420.py::color_affine (nv12.py's is its depth 8) in the same order: the
 // forward affine in double, its inverse by cofactors in double (no contraction into fused multiply-adds: numpy has none), both rounded to
 // fp32 once -- the same 24 floats, bit for bit
 static void yuv420_default_color(int depth, float* yuv2rgb12, float* rgb2yuv12) {
@@ -947,6 +930,9 @@ extern "C" int64_t vs_model_workspace_bytes(const vs_model_t* m, int frames, int
   return std::max(e.used, dt.used) + 256;
 }
 
+// io_u8 = 2: uint8 NV12 [frames][3H/2][W], contiguous (pitch W), as a surface of the 4:2:0 path
+static vs_yuv420_surface_t nv12_contiguous(const void* frames, int H, int W) { return vs_nv12_surface(frames, H, W, (int64_t)W * (H / 2 * 3)); }
+
 extern "C" int vs_model_embed(vs_model_t* m, const void* imgs, const int32_t* msgs, int n_msgs, int frames, int H, int W, int step,
                               int video_mode, int lowres_attenuation, int antialias, int io_u8, void* imgs_w, float* preds_w, void* ws,
                               int64_t ws_bytes, void* stream) {
@@ -956,9 +942,14 @@ extern "C" int vs_model_embed(vs_model_t* m, const void* imgs, const int32_t* ms
   VS_REQUIRE(video_mode >= 0 && video_mode <= 2);
   Runner r{m, static_cast<char*>(ws), ws_bytes, 0, stream};
   if (io_u8) VS_REQUIRE(m->c.clamp);
-  if (io_u8 == 2) {
+  vs_yuv420_surface_t in, out;
+  if (io_u8 == 2) {       // the 4:2:0 path on two contiguous nv12 surfaces, with the model's stored colour
     VS_REQUIRE(!(H & 1) && !(W & 1));
     if (preds_w) return VS_ERR_UNSUPPORTED;
+    in = nv12_contiguous(imgs, H, W);
+    out = nv12_contiguous(imgs_w, H, W);
+    r.ysrc = &in; r.ydst = &out; r.ydec = m->yuv2rgb12; r.yenc = m->rgb2yuv12;
+    io_u8 = 3;
   }
   r.embed(imgs, io_u8, msgs, n_msgs, frames, H, W, step, video_mode, lowres_attenuation, antialias, imgs_w, preds_w);
   return r.rc;
@@ -968,7 +959,13 @@ extern "C" int vs_model_detect(vs_model_t* m, const void* imgs, int frames, int 
                                int64_t ws_bytes, void* stream) {
   VS_REQUIRE(m && imgs && logits && ws && frames > 0 && H > 0 && W > 0 && ((uintptr_t)ws & 255) == 0);
   Runner r{m, static_cast<char*>(ws), ws_bytes, 0, stream};
-  if (io_u8 == 2) VS_REQUIRE(!(H & 1) && !(W & 1));
+  vs_yuv420_surface_t in;
+  if (io_u8 == 2) {
+    VS_REQUIRE(!(H & 1) && !(W & 1));
+    in = nv12_contiguous(imgs, H, W);
+    r.ysrc = &in; r.ydec = m->yuv2rgb12;
+    io_u8 = 3;
+  }
   r.detect(imgs, io_u8, frames, H, W, antialias, logits);
   return r.rc;
 }

@@ -11,8 +11,9 @@
 // 1024 -> 256, BASELINE configs[4]); (3) the source may be a crop window (i0, j0, H x W) of a larger frame (srcH x srcW) -- the crop is an index
 // offset, the cropped clip is never written; (4) the vertical tap weights of the strip's rows are tabulated ONCE per workgroup in LDS (a weight is a
 // triangle and an IEEE division: evaluated per thread and output row they were ~a third of the kernel's instructions); (5) the store is a functor.
-// (shell.hip::resize_pre_nv12_stream_kernel restates the passes below behind an NV12 loader, and nv12_rs_pick restates rs_pick with a wider
-// column margin: a change to the body or to rs_pick belongs there as well -- tests/test_gpu_nv12.py holds that form to the tile kernel bit for bit.)
+// (yuv420.hip::resize_pre_yuv_stream_kernel restates the passes below behind a 4:2:0 loader, and yuv_rs_pick restates rs_pick with a wider
+// column margin: a change to the body or to rs_pick belongs there as well -- tests/test_gpu_nv12.py and tests/test_gpu_yuv420.py hold that
+// form to the tile kernel bit for bit.)
 #pragma once
 #include <hip/hip_runtime.h>
 #include "resize_taps.h"

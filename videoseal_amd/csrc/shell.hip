@@ -685,734 +685,6 @@ __global__ __launch_bounds__(256) void embed_tail_stream_kernel(TailArgs a, JndT
 // (no waves-per-SIMD hint on the JND form: with `__launch_bounds__(256, 3)` or `(256, 4)` hipcc schedules the same body 40 % slower -- 132
 // VGPRs and three waves per SIMD either way, measured 175 -> 245-260 us at 32 x 768^2, profiles/r04_tail_forms.md)
 
-
-
-// resize_pre_kernel on NV12 frames: conversion and clamp per source pixel in front of the filter, then the same taps in the same order.
-// Staging: a task is one 16-byte column piece x one row PAIR (two luma pieces and the chroma piece they share); the window of at most
-// RS_WW x RS_WH pixels spans <= 8 pieces x 17 pairs, one task per thread.
-__global__ __launch_bounds__(256) void resize_pre_nv12_kernel(const unsigned char* __restrict__ src, int B, int H, int W, int64_t pitch,
-                                                              int64_t fstride, Nv12Mat dec, int oh, int ow, int antialias,
-                                                              float* __restrict__ dst_rgb, float mul, float add, float* __restrict__ dst_key,
-                                                              int key_step, int key_mode, float y0, float y1, float y2) {
-  __shared__ float Lw[3 * RS_WH * RS_WW];
-  const int ox0 = blockIdx.x * 32, oy0 = blockIdx.y * 8;
-  const int b = blockIdx.z;
-  const unsigned char* base = src + (int64_t)b * fstride;
-  const unsigned char* cbase = base + (int64_t)H * pitch;
-  int x_lo, y_lo, x_hi, y_hi, n_;
-  tap_range(ox0, W, ow, antialias, x_lo, n_);
-  tap_range(min(ox0 + 31, ow - 1), W, ow, antialias, x_hi, n_);
-  const int ww = x_hi + n_ - x_lo;
-  tap_range(oy0, H, oh, antialias, y_lo, n_);
-  tap_range(min(oy0 + 7, oh - 1), H, oh, antialias, y_hi, n_);
-  const int wh = y_hi + n_ - y_lo;
-  const bool staged = ww <= RS_WW && wh <= RS_WH;          // block-uniform
-  if (staged) {
-    const int pc0 = x_lo >> 4, npc = ((x_lo + ww - 1) >> 4) - pc0 + 1;
-    const int rp0 = y_lo >> 1, nrp = ((y_lo + wh - 1) >> 1) - rp0 + 1;
-    const int t = threadIdx.x;
-    if (t < npc * nrp) {
-      const int ri = t / npc, pi = t - ri * npc;
-      const int col = (pc0 + pi) * 16, row = (rp0 + ri) * 2;            // row + 1 < H: H is even
-      const uint4 ya = nv12_ld16(base + (int64_t)row * pitch, col, W);
-      const uint4 yb = nv12_ld16(base + (int64_t)(row + 1) * pitch, col, W);
-      const uint4 cc = nv12_ld16(cbase + (int64_t)(rp0 + ri) * pitch, col, W);
-#pragma unroll
-      for (int q = 0; q < 16; ++q) {
-        const int xx = col + q - x_lo;
-        if (xx >= 0 && xx < ww) {
-          const float cb = (float)nv12_byte(cc, q & ~1), cr = (float)nv12_byte(cc, q | 1);
-#pragma unroll
-          for (int h = 0; h < 2; ++h) {
-            const int yy = row + h - y_lo;
-            if (yy >= 0 && yy < wh) {
-              float rgb[3];
-              nv12_rgb(dec, (float)nv12_byte(h ? yb : ya, q), cb, cr, rgb);
-#pragma unroll
-              for (int c = 0; c < 3; ++c) Lw[(c * RS_WH + yy) * RS_WW + xx] = rgb[c];
-            }
-          }
-        }
-      }
-    }
-    __syncthreads();
-  }
-  const int ox = ox0 + (threadIdx.x & 31);
-  const int oy = oy0 + (threadIdx.x >> 5);
-  if (ox >= ow || oy >= oh) return;
-  const Taps ty = make_taps(oy, H, oh, antialias), tx = make_taps(ox, W, ow, antialias);
-  float acc[3] = {0.f, 0.f, 0.f};
-  if (staged && tx.n <= MAXT) {
-    float wxs[MAXT];
-#pragma unroll
-    for (int jx = 0; jx < MAXT; ++jx) wxs[jx] = jx < tx.n ? tap_w(tx, jx) : 0.f;
-    const float* Lp = Lw + (ty.lo - y_lo) * RS_WW + (tx.lo - x_lo);
-    for (int jy = 0; jy < ty.n; ++jy) {
-      const float wy = tap_w(ty, jy);
-      float r[3] = {0.f, 0.f, 0.f};
-#pragma unroll
-      for (int jx = 0; jx < MAXT; ++jx)
-        if (jx < tx.n) {
-#pragma unroll
-          for (int c = 0; c < 3; ++c) r[c] = __builtin_fmaf(wxs[jx], Lp[(c * RS_WH + jy) * RS_WW + jx], r[c]);
-        }
-#pragma unroll
-      for (int c = 0; c < 3; ++c) acc[c] = __builtin_fmaf(wy, r[c], acc[c]);
-    }
-  } else if (tx.n > LONG_TAPS || ty.n > LONG_TAPS) {        // long filters: compensated sums, as resize_pre_kernel
-    CompSum a3[3];
-    for (int jy = 0; jy < ty.n; ++jy) {
-      const float wy = tap_w(ty, jy);
-      const int yy = ty.lo + jy;
-      const unsigned char* yr = base + (int64_t)yy * pitch;
-      const unsigned char* cr_ = cbase + (int64_t)(yy >> 1) * pitch;
-      CompSum r3[3];
-      for (int jx = 0; jx < tx.n; ++jx) {
-        const float wx = tap_w(tx, jx);
-        const int xx = tx.lo + jx;
-        float rgb[3];
-        nv12_rgb(dec, (float)yr[xx], (float)cr_[xx & ~1], (float)cr_[xx | 1], rgb);
-#pragma unroll
-        for (int c = 0; c < 3; ++c) r3[c].add(wx, rgb[c]);
-      }
-#pragma unroll
-      for (int c = 0; c < 3; ++c) a3[c].add(wy, r3[c].value());
-    }
-#pragma unroll
-    for (int c = 0; c < 3; ++c) acc[c] = a3[c].value();
-  } else {
-    for (int jy = 0; jy < ty.n; ++jy) {
-      const float wy = tap_w(ty, jy);
-      const int yy = ty.lo + jy;
-      const unsigned char* yr = base + (int64_t)yy * pitch;
-      const unsigned char* cr_ = cbase + (int64_t)(yy >> 1) * pitch;
-      float r[3] = {0.f, 0.f, 0.f};
-      for (int jx = 0; jx < tx.n; ++jx) {
-        const float wx = tap_w(tx, jx);
-        const int xx = tx.lo + jx;
-        float rgb[3];
-        nv12_rgb(dec, (float)yr[xx], (float)cr_[xx & ~1], (float)cr_[xx | 1], rgb);
-#pragma unroll
-        for (int c = 0; c < 3; ++c) r[c] = __builtin_fmaf(wx, rgb[c], r[c]);
-      }
-#pragma unroll
-      for (int c = 0; c < 3; ++c) acc[c] = __builtin_fmaf(wy, r[c], acc[c]);
-    }
-  }
-  const int64_t opix = ((int64_t)oy * ow + ox);
-  if (dst_rgb) {
-    f32x4 v = {acc[0] * mul + add, acc[1] * mul + add, acc[2] * mul + add, 0.f};
-    *reinterpret_cast<f32x4*>(dst_rgb + ((int64_t)b * oh * ow + opix) * 4) = v;
-  }
-  if (dst_key && (b % key_step) == 0) {
-    f32x4 v;
-    if (key_mode == 0) {
-      const float y = y0 * acc[0] + y1 * acc[1] + y2 * acc[2];
-      v = f32x4{y * 2.f - 1.f, 0.f, 0.f, 0.f};
-    } else {
-      v = f32x4{acc[0] * 2.f - 1.f, acc[1] * 2.f - 1.f, acc[2] * 2.f - 1.f, 0.f};
-    }
-    *reinterpret_cast<f32x4*>(dst_key + ((int64_t)(b / key_step) * oh * ow + opix) * 4) = v;
-  }
-}
-
-// Row-streaming form of resize_pre on NV12 frames: vs_rs::resize_stream_body (resize_stream.h) with another loader.  A workgroup owns OW
-// output columns x a strip of output rows and walks the input rows eight at a time, groups starting on an EVEN row: a group is four row
-// pairs, a load task is one 16-byte column piece x one pair (two luma pieces and the chroma piece they share, <= 28 pieces x 4 pairs = 112
-// of the 256 threads, three loads each, requested one group ahead) -- every luma row and every chroma row is fetched once per column tile
-// (+ the first window of a strip).  The thread that holds a task converts its 32 pixels straight from registers into the [8][3][INW] fp32
-// window; the horizontal and vertical passes, their expressions and their order are resize_stream_body's and the tile kernel's: the same bits.
-inline int nv12_rs_pick(int H, int W, int oh, int ow, int antialias) {          // vs_rs::rs_pick with a 16-column-aligned window start
-  const float sx = (float)W / (float)ow, sy = (float)H / (float)oh;
-  const float supx = antialias ? (sx >= 1.f ? sx : 1.f) : 1.f, supy = antialias ? (sy >= 1.f ? sy : 1.f) : 1.f;
-  auto fits = [&](int OW, int INW, int MT, int RING) {
-    return 2.f * supx + 2.f <= (float)MT && 2.f * supy + 2.f <= (float)MT && (float)OW * sx + 2.f * supx + 4.f + 16.f <= (float)INW &&
-           2.f * supy + 2.f + (float)vs_rs::RS_GI <= (float)RING;
-  };
-  if (fits(128, vs_rs::RsGeo<128>::INW, vs_rs::RsGeo<128>::MT, vs_rs::RsGeo<128>::RING)) return 128;
-  if (fits(64, vs_rs::RsGeo<64>::INW, vs_rs::RsGeo<64>::MT, vs_rs::RsGeo<64>::RING)) return 64;
-  return 0;
-}
-template <int OW>
-__global__ __launch_bounds__(256) void resize_pre_nv12_stream_kernel(const unsigned char* __restrict__ src, int H, int W, int64_t pitch,
-                                                                     int64_t fstride, Nv12Mat dec, int oh, int ow, int antialias,
-                                                                     ResizePreEpi epi, int strip) {
-  using namespace vs_rs;
-  extern __shared__ __attribute__((aligned(16))) float rs_smem[];
-  constexpr int INW = RsGeo<OW>::INW, MT = RsGeo<OW>::MT, RING = RsGeo<OW>::RING, NPART = 256 / OW, RPP = RS_GI / NPART;
-  float* In = rs_smem;                                   // [RS_GI][3][INW]
-  float* Hr = rs_smem + RS_GI * 3 * INW;                 // [RING][3][OW]
-  float* Wy = Hr + RING * 3 * OW;                        // [RS_WTAB_ROWS][MT] vertical weights | first row | tap count
-  int* WyLo = reinterpret_cast<int*>(Wy + RS_WTAB_ROWS * MT);
-  int* WyN = WyLo + RS_WTAB_ROWS;
-  const int ox0 = blockIdx.x * OW, oy0 = blockIdx.y * strip, b = blockIdx.z;
-  const int oy_end = min(oh, oy0 + strip);
-  const unsigned char* base = src + (int64_t)b * fstride;
-  const unsigned char* cbase = base + (int64_t)H * pitch;
-  const int tid = threadIdx.x;
-  const int oxl = tid & (OW - 1), part = tid / OW;
-  const int ox = min(ox0 + oxl, ow - 1);
-  const bool ox_ok = ox0 + oxl < ow;
-  const bool wtab = strip <= RS_WTAB_ROWS;               // block-uniform
-  if (wtab && tid < oy_end - oy0) {
-    const Taps t = make_taps(oy0 + tid, H, oh, antialias);
-    WyLo[tid] = t.lo;
-    WyN[tid] = t.n;
-    for (int q = 0; q < MT; ++q) Wy[tid * MT + q] = q < t.n ? tap_w(t, q) : 0.f;
-  }
-  int x_lo, x_hi, n_;
-  tap_range(ox0, W, ow, antialias, x_lo, n_);
-  tap_range(min(ox0 + OW - 1, ow - 1), W, ow, antialias, x_hi, n_);
-  const int xa = x_lo & ~15;                             // LDS column 0 <-> frame column xa
-  const int ww = min(x_hi + n_ - xa, INW);               // (<= INW: nv12_rs_pick)
-  const int npc = (ww + 15) >> 4;
-  int y_lo, y_hi;
-  tap_range(oy0, H, oh, antialias, y_lo, n_);
-  tap_range(oy_end - 1, H, oh, antialias, y_hi, n_);
-  const int y_end = y_hi + n_;
-  const Taps tx = make_taps(ox, W, ow, antialias);
-  float wxs[MT];
-#pragma unroll
-  for (int jx = 0; jx < MT; ++jx) wxs[jx] = jx < tx.n ? tap_w(tx, jx) : 0.f;
-  const int xoff = tx.lo - xa;
-
-  const bool loader = tid < 4 * npc;
-  const int ri = tid / npc, pi = tid - ri * npc;          // row pair of the group, column piece
-  uint4 pv[3];
-  auto load_group = [&](const int r0) __attribute__((always_inline)) {
-    const int row = r0 + 2 * ri;
-    pv[0] = pv[1] = pv[2] = uint4{0u, 0u, 0u, 0u};
-    if (loader && row < y_end) {                          // (row + 1 < H: H is even)
-      pv[0] = nv12_ld16(base + (int64_t)row * pitch, xa + 16 * pi, W);
-      pv[1] = nv12_ld16(base + (int64_t)(row + 1) * pitch, xa + 16 * pi, W);
-      pv[2] = nv12_ld16(cbase + (int64_t)(row >> 1) * pitch, xa + 16 * pi, W);
-    }
-  };
-  int oy_next = oy0 + part;
-  const int ye0 = y_lo & ~1;
-  load_group(ye0);
-  for (int r0 = ye0; r0 < y_end; r0 += RS_GI) {
-    if (loader) {       // whole pieces, four pixels per LDS store (INW is a multiple of 16: a piece that starts inside the window row ends inside it;
-                        // columns past ww and rows past y_end receive values nobody reads)
-#pragma unroll
-      for (int k4 = 0; k4 < 4; ++k4) {
-        float px[2][3][4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const int q = 4 * k4 + e;
-          const float cb = (float)nv12_byte(pv[2], q & ~1), cr = (float)nv12_byte(pv[2], q | 1);
-#pragma unroll
-          for (int h = 0; h < 2; ++h) {
-            float rgb[3];
-            nv12_rgb(dec, (float)nv12_byte(pv[h], q), cb, cr, rgb);
-#pragma unroll
-            for (int c = 0; c < 3; ++c) px[h][c][e] = rgb[c];
-          }
-        }
-#pragma unroll
-        for (int h = 0; h < 2; ++h)
-#pragma unroll
-          for (int c = 0; c < 3; ++c)
-            *reinterpret_cast<f32x4*>(In + ((2 * ri + h) * 3 + c) * INW + 16 * pi + 4 * k4) = f32x4{px[h][c][0], px[h][c][1], px[h][c][2], px[h][c][3]};
-      }
-    }
-    if (r0 + RS_GI < y_end) load_group(r0 + RS_GI);       // in flight during the two passes below
-    __syncthreads();
-#pragma unroll
-    for (int q = 0; q < RPP; ++q) {
-      const int rl = part * RPP + q;
-      const int row = r0 + rl;
-      if (row < y_end) {
-        float r[3] = {0.f, 0.f, 0.f};
-        const float* Lp = In + rl * 3 * INW + xoff;
-#pragma unroll
-        for (int jx = 0; jx < MT; ++jx)
-          if (jx < tx.n) {
-#pragma unroll
-            for (int c = 0; c < 3; ++c) r[c] = __builtin_fmaf(wxs[jx], Lp[c * INW + jx], r[c]);
-          }
-#pragma unroll
-        for (int c = 0; c < 3; ++c) Hr[((row & (RING - 1)) * 3 + c) * OW + oxl] = r[c];
-      }
-    }
-    __syncthreads();
-    const int done = min(r0 + RS_GI, y_end);
-    while (oy_next < oy_end) {
-      float acc[3] = {0.f, 0.f, 0.f};
-      if (wtab) {
-        const int tl = WyLo[oy_next - oy0], tn = WyN[oy_next - oy0];
-        if (tl + tn > done) break;
-        const float* wyp = Wy + (oy_next - oy0) * MT;
-        for (int jy = 0; jy < tn; ++jy) {
-          const float wy = wyp[jy];
-          const float* hp = Hr + (((tl + jy) & (RING - 1)) * 3) * OW + oxl;
-#pragma unroll
-          for (int c = 0; c < 3; ++c) acc[c] = __builtin_fmaf(wy, hp[c * OW], acc[c]);
-        }
-      } else {
-        const Taps ty = make_taps(oy_next, H, oh, antialias);
-        if (ty.lo + ty.n > done) break;
-        for (int jy = 0; jy < ty.n; ++jy) {
-          const float wy = tap_w(ty, jy);
-          const float* hp = Hr + (((ty.lo + jy) & (RING - 1)) * 3) * OW + oxl;
-#pragma unroll
-          for (int c = 0; c < 3; ++c) acc[c] = __builtin_fmaf(wy, hp[c * OW], acc[c]);
-        }
-      }
-      if (ox_ok) epi(b, oy_next, ox, acc);
-      oy_next += NPART;
-    }
-  }
-}
-
-// embed_tail_kernel on NV12 frames.  Workgroup = 256 columns x 16 rows of one frame (a tile starts on an even row: a chroma row belongs to
-// one tile).  The tile's bytes + a 2-pixel halo (20 luma rows, 10 chroma rows, columns x0 - 16 .. x0 + 271: 18 pieces per row) are staged
-// in LDS once; luminance and blend both read the pixel from there.  The arithmetic between decode and encode is embed_tail_kernel's (43-tap
-// JND, the same taps, key-frame expansion and blend); a thread owns one column and walks the rows in pairs, the horizontal half of the
-// 2 x 2 chroma sum comes from the neighbouring lane.  The watermarked tile is collected in LDS and leaves as one 16-byte luma piece per
-// thread and one chroma piece per thread of the first two waves.
-constexpr int NVW = TTW + 32, NVR = TTH + 2 * HALO, NVC = NVR / 2;       // staged window: 288 byte columns, 20 luma rows, 10 chroma rows
-__global__ __launch_bounds__(256) void embed_tail_nv12_kernel(TailArgs a, JndTaps k, Nv12Geo g) {
-  __shared__ __attribute__((aligned(16))) unsigned char YC[(NVR + NVC) * NVW];
-  __shared__ __attribute__((aligned(16))) unsigned char Yo[TTH * TTW];
-  __shared__ __attribute__((aligned(16))) unsigned char Co[(TTH / 2) * TTW];
-  __shared__ float L[TLW * NVR];
-  __shared__ float Dw[3 * DW_W * DW_H];
-  __shared__ int ty_lo[TTH], ty_n[TTH];
-  __shared__ float ty_w[TTH][4];
-  __shared__ int s_xhi, s_nmax, s_xlo;
-  const int x0 = blockIdx.x * TTW, y0 = blockIdx.y * TTH, f = blockIdx.z;
-  const unsigned char* img = static_cast<const unsigned char*>(a.imgs) + (int64_t)f * g.sfs;
-  unsigned char* outf = static_cast<unsigned char*>(a.out) + (int64_t)f * g.dfs;
-  const bool full_jnd = a.attenuate && !a.hmap_lowres;
-  if (threadIdx.x == 0) { s_xhi = 0; s_nmax = 0; }
-  {     // frame bytes -> LDS: (NVR + NVC) rows x 18 pieces, all loads of a thread issued before its stores
-    constexpr int NPC = NVW / 16, NTASK = (NVR + NVC) * NPC, NIT = (NTASK + 255) / 256;
-    uint4 v[NIT];
-#pragma unroll
-    for (int i = 0; i < NIT; ++i) {
-      const int t = threadIdx.x + 256 * i;
-      v[i] = uint4{0u, 0u, 0u, 0u};
-      if (t < NTASK) {
-        const int r = t / NPC, p = t - r * NPC;
-        int gy, lim;
-        bool need;
-        if (r < NVR) { gy = y0 - HALO + r; lim = a.H; need = full_jnd || (r >= HALO && r < HALO + TTH); }
-        else { gy = y0 / 2 - 1 + (r - NVR); lim = a.H / 2; need = full_jnd || (r - NVR >= 1 && r - NVR <= TTH / 2); }
-        if (need && gy >= 0 && gy < lim) v[i] = nv12_ld16(img + (int64_t)(r < NVR ? gy : a.H + gy) * g.sp, x0 - 16 + 16 * p, a.W);
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < NIT; ++i) {
-      const int t = threadIdx.x + 256 * i;
-      if (t < NTASK) *reinterpret_cast<uint4*>(YC + 16 * t) = v[i];
-    }
-  }
-  __syncthreads();
-  // decoded, clamped pixel at tile row rr (0 .. NVR - 1 <-> frame row y0 - 2 + rr) and window column wc (<-> frame column x0 - 16 + wc)
-  auto pixel = [&](const int rr, const int wc, float (&rgb)[3]) __attribute__((always_inline)) {
-    const unsigned char* cr_ = YC + (NVR + (rr >> 1)) * NVW;
-    nv12_rgb(g.dec, (float)YC[rr * NVW + wc], (float)cr_[wc & ~1], (float)cr_[wc | 1], rgb);
-  };
-  if (full_jnd) {       // luminance of the tile + halo, zero outside the frame (conv zero padding)
-    auto lum_column = [&](const int lxx) __attribute__((always_inline)) {
-      const int gx = x0 + lxx - HALO;
-#pragma unroll 4
-      for (int rr = 0; rr < NVR; ++rr) {
-        const int gy = y0 + rr - HALO;
-        float v = 0.f;
-        if (gx >= 0 && gx < a.W && gy >= 0 && gy < a.H) {
-          float rgb[3];
-          pixel(rr, lxx + 16 - HALO, rgb);
-          v = lum255(rgb[0], rgb[1], rgb[2]);
-        }
-        L[rr * TLW + lxx] = v;
-      }
-    };
-    lum_column(threadIdx.x + HALO);
-    if (threadIdx.x < 2 * HALO) lum_column(threadIdx.x < HALO ? threadIdx.x : TTW + threadIdx.x);
-  }
-  const int lx = threadIdx.x;
-  const int x = x0 + lx;
-  const bool xin = x < a.W;
-  const Taps tx = make_taps(xin ? x : a.W - 1, a.Sw, a.W, a.antialias);
-  float wxs[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) wxs[j] = j < tx.n ? tap_w(tx, j) : 0.f;
-  if (xin) { atomicMax(&s_xhi, tx.lo + tx.n); atomicMax(&s_nmax, tx.n); }
-  if (threadIdx.x == 0) s_xlo = tx.lo;
-  if (threadIdx.x < TTH) {
-    const int yy = y0 + threadIdx.x;
-    const Taps tp = make_taps(yy < a.H ? yy : a.H - 1, a.Sh, a.H, a.antialias);
-    ty_lo[threadIdx.x] = tp.lo;
-    ty_n[threadIdx.x] = tp.n;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) ty_w[threadIdx.x][j] = j < tp.n ? tap_w(tp, j) : 0.f;
-    if (yy < a.H) atomicMax(&s_nmax, tp.n);
-  }
-  __syncthreads();
-
-  // key-frame expansion (videoseal.py:80-118): value = wa*key[ka] + wb*key[kb]   (same as embed_tail_kernel)
-  int ka = 0, kb = 0;
-  float wa = 1.f, wb = 0.f;
-  if (a.video_mode == VS_VIDEO_REPEAT) {
-    ka = f / a.step;
-  } else if (a.video_mode == VS_VIDEO_ALTERNATE) {
-    ka = f / a.step;
-    wa = (f % a.step) == 0 ? 1.f : 0.f;
-  } else {
-    const int ninter = ((a.F - 1) / a.step) * a.step;
-    if (f < ninter) {
-      ka = f / a.step; kb = ka + 1;
-      const int j = f % a.step;
-      const float lin = a.step > 1 ? (float)j / (float)(a.step - 1) : 0.f;
-      wa = 1.f - lin; wb = 1.f - wa;
-    } else {
-      ka = a.total_key - 1;
-    }
-  }
-  if (ka >= a.total_key) ka = a.total_key - 1;
-  if (kb >= a.total_key) kb = a.total_key - 1;
-  const int splane = a.Sh * a.Sw;
-  const float* dka = a.delta + (int64_t)ka * a.Cd * splane;
-  const float* dkb = a.delta + (int64_t)kb * a.Cd * splane;
-  const float* hml = a.hmap_lowres ? a.hmap_lowres + (int64_t)f * splane : nullptr;
-
-  const int lasty = min(TTH, a.H - y0) - 1;              // odd: H and y0 are even
-  const int wx0 = s_xlo, wy0 = ty_lo[0];
-  const int dww = s_xhi - wx0, dwh = ty_lo[lasty] + ty_n[lasty] - wy0;
-  const int blk_n = s_nmax;
-  const bool staged = blk_n <= 4 && dww <= DW_W && dwh <= DW_H;
-  if (staged) {
-    for (int i = threadIdx.x; i < dwh * dww; i += 256) {
-      const int yy = i / dww, xx = i - yy * dww;
-      const int sp = (wy0 + yy) * a.Sw + wx0 + xx;
-      const float hm = hml ? hml[sp] : 1.f;
-      for (int c = 0; c < a.Cd; ++c) {
-        float v = wa * dka[c * splane + sp];
-        if (wb != 0.f) v = __builtin_fmaf(wb, dkb[c * splane + sp], v);
-        Dw[c * (DW_W * DW_H) + yy * DW_W + xx] = hm * v;
-      }
-    }
-  }
-  __syncthreads();      // L, Dw
-
-  auto tap = [&](const int sp, const float wx, float (&r)[3]) __attribute__((always_inline)) {
-    const float hm = hml ? hml[sp] : 1.f;
-    for (int c = 0; c < a.Cd; ++c) {
-      float v = wa * dka[c * splane + sp];
-      if (wb != 0.f) v += wb * dkb[c * splane + sp];
-      r[c] += wx * (hm * v);
-    }
-  };
-  for (int ly0 = 0; ly0 <= lasty; ly0 += 2) {             // every lane runs every pair: the chroma sum crosses lanes
-    float cbs = 0.f, crs = 0.f;
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-      const int ly = ly0 + q;
-      const int y = y0 + ly;
-      if (xin) {
-        float px[3];
-        pixel(ly + HALO, lx + 16, px);
-        float d[3] = {0.f, 0.f, 0.f};
-        const int ylo = ty_lo[ly], yn = ty_n[ly];
-        if (staged) {
-          const int basep = (ylo - wy0) * DW_W + (tx.lo - wx0);
-          if (blk_n <= 3) tail_taps<3, DW_H>(d, Dw, a.Cd, basep, tx.n, yn, wxs, ty_w[ly]);
-          else tail_taps<4, DW_H>(d, Dw, a.Cd, basep, tx.n, yn, wxs, ty_w[ly]);
-        } else {
-          const Taps ty = make_taps(y, a.Sh, a.H, a.antialias);
-          for (int jy = 0; jy < ty.n; ++jy) {
-            const float wy = tap_w(ty, jy);
-            float r[3] = {0.f, 0.f, 0.f};
-            for (int jx = 0; jx < tx.n; ++jx) tap((ty.lo + jy) * a.Sw + tx.lo + jx, tap_w(tx, jx), r);
-            for (int c = 0; c < a.Cd; ++c) d[c] += wy * r[c];
-          }
-        }
-        float hm = 1.f;
-        if (full_jnd) {
-          hm = jnd_at(L, TLW, lx + HALO, ly + HALO, k);
-          for (int c = 0; c < a.Cd; ++c) d[c] = hm * d[c];
-        }
-        float v[3];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-          const float t = blend_px(a.scaling_i, a.scaling_w, px[c], d[a.Cd == 1 ? 0 : c], hm, false);
-          v[c] = t <= 0.f ? 0.f : (t >= 1.f ? 1.f : t);
-        }
-        Yo[ly * TTW + lx] = nv12_code(nv12_aff(g.enc, 0, v[0], v[1], v[2]));
-        cbs += nv12_aff(g.enc, 1, v[0], v[1], v[2]);
-        crs += nv12_aff(g.enc, 2, v[0], v[1], v[2]);
-      }
-    }
-    cbs += __shfl_xor(cbs, 1);
-    crs += __shfl_xor(crs, 1);
-    if (xin) Co[(ly0 >> 1) * TTW + lx] = nv12_code(0.25f * ((lx & 1) ? crs : cbs));
-  }
-  __syncthreads();      // Yo, Co
-  {
-    const int r = threadIdx.x >> 4, col = x0 + 16 * (threadIdx.x & 15);
-    if (y0 + r < a.H && col < a.W) nv12_st16(outf + (int64_t)(y0 + r) * g.dp, col, a.W, Yo + 16 * threadIdx.x);
-    if (r < TTH / 2 && y0 / 2 + r < a.H / 2 && col < a.W)
-      nv12_st16(outf + (int64_t)(a.H + y0 / 2 + r) * g.dp, col, a.W, Co + 16 * threadIdx.x);
-  }
-}
-
-// Row-streaming form of the NV12 tail: embed_tail_stream_kernel's structure (256 columns x a strip of rows walked in groups of SG = 4, luminance
-// ring, accumulators of the separable JND stencils, double-buffered watermark window, ONE barrier per group) with the frame bytes staged through
-// LDS as 16-byte pieces.  A group's 4 luma rows + 2 chroma rows x 18 pieces (columns x0 - 16 .. x0 + 271) are 108 loads, one per thread of the
-// first 108, requested two groups ahead of their use: loaded during group it - 1, written to the byte stage before the barrier of group it, read
-// by every thread (own column, halo columns) at the top of group it + 1.  Strips start on a multiple of four rows, so the two row pairs of a
-// group are whole 2 x 2 blocks: the horizontal half of the chroma sum comes from the neighbouring lane.  The group's codes (4 x 256 luma bytes,
-// 2 x 256 chroma bytes) are collected in LDS and leave after the next barrier as 96 16-byte pieces.
-constexpr int NSW = TTW + 32, NSR = SG + SG / 2, NSP = NSW / 16;
-template <bool JND, int CD>
-__global__ __launch_bounds__(256) void embed_tail_nv12_stream_kernel(TailArgs a, JndTaps k, Nv12Geo g, const int strip) {
-  extern __shared__ float dyn_smem[];
-  float* Lr = dyn_smem;                                        // [RING][TLW] luminance ring (JND only)
-  float* DwB = dyn_smem + (JND ? RING * TLW : 0);              // [2][Cd][DW_H][DW_W] watermark source windows
-  __shared__ __attribute__((aligned(16))) unsigned char Bst[2][NSR * NSW];     // incoming bytes: rows 0-3 luma, 4-5 chroma
-  __shared__ __attribute__((aligned(16))) unsigned char Ost[2][NSR * TTW];     // outgoing codes, same row order
-  __shared__ int ty_lo[2][SUBR], ty_n[2][SUBR], s_wy0[2];
-  __shared__ float ty_w[2][SUBR][4];
-  __shared__ int s_xhi, s_xlo;
-  constexpr int dwsz = CD * DW_W * DW_H;
-  const int x0 = blockIdx.x * TTW, y0 = blockIdx.y * strip, f = blockIdx.z;
-  const int ys_end = min(a.H, y0 + strip);
-  const unsigned char* img = static_cast<const unsigned char*>(a.imgs) + (int64_t)f * g.sfs;
-  unsigned char* outf = static_cast<unsigned char*>(a.out) + (int64_t)f * g.dfs;
-  const int lx = threadIdx.x;
-  const int x = x0 + lx;
-  const bool xin = x < a.W;
-  const int cx = xin ? x : a.W - 1;
-  if (threadIdx.x == 0) s_xhi = 0;
-  __syncthreads();
-  const Taps tx = make_taps(cx, a.Sw, a.W, a.antialias);
-  float wxs[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) wxs[j] = j < tx.n ? tap_w(tx, j) : 0.f;
-  if (xin) atomicMax(&s_xhi, tx.lo + tx.n);
-  if (threadIdx.x == 0) s_xlo = tx.lo;
-  // halo columns of the luminance ring: threads 0 .. 3 carry one extra column each (x0 - 2, x0 - 1, x0 + 256, x0 + 257)
-  const bool hal = JND && lx < 2 * HALO;
-  const int hgx = lx < HALO ? x0 - HALO + lx : x0 + TTW + (lx - HALO);
-  const int hl = lx < HALO ? lx : TTW + lx;
-  const bool hin = hal && hgx >= 0 && hgx < a.W;
-
-  // one 16-byte piece per loader thread and group: group gi brings rows y0 + 4 gi + 2 .. + 5 and the two chroma rows under them
-  const bool ldr = lx < NSR * NSP;
-  const int lrow = lx / NSP, lpc = lx - lrow * NSP;
-  auto load_piece = [&](const int gi) __attribute__((always_inline)) -> uint4 {
-    const int r0 = y0 + SG * gi + HALO;                        // even
-    uint4 v = uint4{0u, 0u, 0u, 0u};
-    if (ldr) {
-      const int gy = lrow < SG ? r0 + lrow : (r0 >> 1) + (lrow - SG);
-      const int lim = lrow < SG ? a.H : a.H / 2;
-      if (gy >= 0 && gy < lim) v = nv12_ld16(img + (int64_t)(lrow < SG ? gy : a.H + gy) * g.sp, x0 - 16 + 16 * lpc, a.W);
-    }
-    return v;
-  };
-  auto pixel = [&](const int slot, const int q, const int wc, float (&rgb)[3]) __attribute__((always_inline)) {
-    const unsigned char* B = Bst[slot];
-    const unsigned char* cr_ = B + (SG + (q >> 1)) * NSW;
-    nv12_rgb(g.dec, (float)B[q * NSW + wc], (float)cr_[wc & ~1], (float)cr_[wc | 1], rgb);
-  };
-  uint4 pv = load_piece(-1);
-  if (ldr) *reinterpret_cast<uint4*>(Bst[0] + 16 * lx) = pv;
-
-  // key-frame expansion (videoseal.py:80-118): value = wa*key[ka] + wb*key[kb]   (same as the tile kernel)
-  int ka = 0, kb = 0;
-  float wa = 1.f, wb = 0.f;
-  if (a.video_mode == VS_VIDEO_REPEAT) {
-    ka = f / a.step;
-  } else if (a.video_mode == VS_VIDEO_ALTERNATE) {
-    ka = f / a.step;
-    wa = (f % a.step) == 0 ? 1.f : 0.f;
-  } else {
-    const int ninter = ((a.F - 1) / a.step) * a.step;
-    if (f < ninter) {
-      ka = f / a.step; kb = ka + 1;
-      const int j = f % a.step;
-      const float lin = a.step > 1 ? (float)j / (float)(a.step - 1) : 0.f;
-      wa = 1.f - lin; wb = 1.f - wa;
-    } else {
-      ka = a.total_key - 1;
-    }
-  }
-  if (ka >= a.total_key) ka = a.total_key - 1;
-  if (kb >= a.total_key) kb = a.total_key - 1;
-  const int splane = a.Sh * a.Sw;
-  const float* dka = a.delta + (int64_t)ka * CD * splane;
-  const float* dkb = a.delta + (int64_t)kb * CD * splane;
-  const float* hml = a.hmap_lowres ? a.hmap_lowres + (int64_t)f * splane : nullptr;
-  __syncthreads();                                             // s_xlo / s_xhi, byte stage of group -1
-  const int wx0 = s_xlo, dww = s_xhi - s_xlo;
-
-  auto stage = [&](const int sub, const int b) __attribute__((always_inline)) {      // source window + row taps of output rows [16 sub, 16 sub + 16)
-    const int sy0 = y0 + SUBR * sub;
-    const int lasty = min(SUBR, ys_end - sy0) - 1;
-    int wy0, n0, wyl, nl;
-    tap_range(sy0, a.Sh, a.H, a.antialias, wy0, n0);
-    tap_range(sy0 + lasty, a.Sh, a.H, a.antialias, wyl, nl);
-    const int dwh = wyl + nl - wy0;
-    if (threadIdx.x < SUBR) {
-      const int yy = sy0 + threadIdx.x;
-      const Taps tp = make_taps(yy < a.H ? yy : a.H - 1, a.Sh, a.H, a.antialias);
-      ty_lo[b][threadIdx.x] = tp.lo;
-      ty_n[b][threadIdx.x] = tp.n;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) ty_w[b][threadIdx.x][j] = j < tp.n ? tap_w(tp, j) : 0.f;
-      if (threadIdx.x == 0) s_wy0[b] = wy0;
-    }
-    float* Dw = DwB + b * dwsz;
-    const int nel = dwh * dww;
-    for (int i0 = 0; i0 < nel; i0 += 4 * 256) {
-      int sp[4], lo[4];
-      float hmv[4], da[4][CD], db[4][CD];
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int i = min(i0 + q * 256 + (int)threadIdx.x, nel - 1);
-        const int yy = i / dww, xx = i - yy * dww;
-        sp[q] = (wy0 + yy) * a.Sw + wx0 + xx;
-        lo[q] = yy * DW_W + xx;
-      }
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        hmv[q] = hml ? hml[sp[q]] : 1.f;
-#pragma unroll
-        for (int c = 0; c < CD; ++c) {
-          da[q][c] = dka[c * splane + sp[q]];
-          db[q][c] = wb != 0.f ? dkb[c * splane + sp[q]] : 0.f;
-        }
-      }
-#pragma unroll
-      for (int q = 0; q < 4; ++q)
-        if (i0 + q * 256 + (int)threadIdx.x < nel) {
-#pragma unroll
-          for (int c = 0; c < CD; ++c) {
-            float v = wa * da[q][c];
-            if (wb != 0.f) v = __builtin_fmaf(wb, db[q][c], v);
-            Dw[c * (DW_W * DW_H) + lo[q]] = hmv[q] * v;
-          }
-        }
-    }
-  };
-  auto store_group = [&](const int gi) __attribute__((always_inline)) {         // codes of output rows y0 + 4 gi .. + 3 -> the frame
-    if (lx < NSR * (TTW / 16)) {
-      const int orow = lx >> 4, col = x0 + 16 * (lx & 15);
-      const int yb = y0 + SG * gi;
-      const int y = orow < SG ? yb + orow : yb + 2 * (orow - SG);               // (the first luma row of a chroma row's block)
-      if (y < ys_end && col < a.W)
-        nv12_st16(outf + (int64_t)(orow < SG ? y : a.H + (y >> 1)) * g.dp, col, a.W, Ost[gi & 1] + 16 * lx);
-    }
-  };
-
-  const int nrows = ys_end - y0;
-  const int niter = (nrows + SG - 1) / SG;
-  float acc_la[2 * SG], acc_gx[2 * SG], acc_gy[2 * SG];
-#pragma unroll
-  for (int i = 0; i < 2 * SG; ++i) { acc_la[i] = 0.f; acc_gx[i] = 0.f; acc_gy[i] = 0.f; }
-  float hist[2][3] = {{0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}};
-  pv = load_piece(0);
-  stage(0, 0);
-  for (int it = -1; it < niter; ++it) {
-    const int r0 = y0 + SG * it + HALO;                       // first incoming row of this group; its output rows are r0 - 2 .. r0 + 1
-    const int slot0 = ((it + 1) % 3) * SG;
-    const int bs = (it + 1) & 1;
-    float cu[SG][3];
-#pragma unroll
-    for (int q = 0; q < SG; ++q) pixel(bs, q, lx + 16, cu[q]);
-    if (JND) {
-#pragma unroll
-      for (int q = 0; q < SG; ++q) {
-        const int gy = r0 + q;
-        const bool rok = gy >= 0 && gy < a.H;
-        Lr[(slot0 + q) * TLW + lx + HALO] = (rok && xin) ? lum255(cu[q][0], cu[q][1], cu[q][2]) : 0.f;
-        if (hal) {
-          float hp[3];
-          pixel(bs, q, hl + 16 - HALO, hp);
-          Lr[(slot0 + q) * TLW + hl] = (rok && hin) ? lum255(hp[0], hp[1], hp[2]) : 0.f;
-        }
-      }
-    }
-    if (it + 1 < niter) {
-      if (ldr) *reinterpret_cast<uint4*>(Bst[bs ^ 1] + 16 * lx) = pv;       // group it + 1, read after the barrier below
-      if (it + 2 < niter) pv = load_piece(it + 2);                          // in flight for a whole group
-      if (((it + 1) & 3) == 0 && it + 1 > 0) stage((it + 1) >> 2, ((it + 1) >> 2) & 1);
-    }
-    __syncthreads();
-    if (it >= 1) store_group(it - 1);
-    const int sb = (it >> 2) & 1;
-    const float* Dw = DwB + sb * dwsz;
-    unsigned char* Og = Ost[it & 1];
-    float cbs = 0.f, crs = 0.f;
-#pragma unroll
-    for (int j = 0; j < SG; ++j) {
-      if (JND) {
-        const float* row = Lr + (slot0 + j) * TLW + lx + HALO;
-        const float m2 = row[-2], m1 = row[-1], c0 = row[0], p1 = row[1], p2 = row[2];
-        const float h3 = m1 + c0 + p1;
-        const float h5 = h3 + m2 + p2;
-        const float sd = p1 - m1;
-        const float tt = m1 + 2.f * c0 + p1;
-#pragma unroll
-        for (int i = j; i <= j + 4; ++i) {
-          const int dy = 2 + j - i;                            // incoming row - output row
-          if (dy >= -2 && dy <= 2) acc_la[i] += h5;
-          if (dy >= -1 && dy <= 1) acc_la[i] += h3;
-          if (dy == 0) acc_la[i] -= 2.f * c0;
-          if (dy == -1 || dy == 1) acc_gx[i] += sd;
-          if (dy == 0) acc_gx[i] += 2.f * sd;
-          if (dy == -1) acc_gy[i] += tt;
-          if (dy == 1) acc_gy[i] -= tt;
-        }
-      }
-      const int y = r0 - HALO + j;                             // the output row this incoming row completes
-      const bool live = it >= 0 && y < ys_end && xin;
-      if (live) {
-        float hm = 1.f;
-        if (JND) {
-          if (fabsf(acc_la[j] * (1.f / 32.f) - 127.f) < 0.02f) hm = jnd_at_ring(Lr, (slot0 + j + RING - HALO) % RING, lx + HALO, k);
-          else hm = jnd_finish(acc_la[j], acc_gx[j], acc_gy[j]);
-        }
-        const int ly = (SG * it + j) & (SUBR - 1);
-        float d[3] = {0.f, 0.f, 0.f};
-        const int basep = (ty_lo[sb][ly] - s_wy0[sb]) * DW_W + (tx.lo - wx0);
-        tail_taps<3, DW_H>(d, Dw, CD, basep, tx.n, ty_n[sb][ly], wxs, ty_w[sb][ly]);
-        if (JND)
-#pragma unroll
-          for (int c = 0; c < CD; ++c) d[c] = hm * d[c];
-        float v[3];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-          const float p = j < 2 ? hist[j][c] : cu[j - 2][c];
-          const float t = blend_px(a.scaling_i, a.scaling_w, p, d[CD == 1 ? 0 : c], hm, false);
-          v[c] = t <= 0.f ? 0.f : (t >= 1.f ? 1.f : t);
-        }
-        Og[j * TTW + lx] = nv12_code(nv12_aff(g.enc, 0, v[0], v[1], v[2]));
-        cbs += nv12_aff(g.enc, 1, v[0], v[1], v[2]);
-        crs += nv12_aff(g.enc, 2, v[0], v[1], v[2]);
-      }
-      if (j & 1) {                                             // a row pair is complete: every lane takes part in the exchange
-        cbs += __shfl_xor(cbs, 1);
-        crs += __shfl_xor(crs, 1);
-        if (live) Og[(SG + (j >> 1)) * TTW + lx] = nv12_code(0.25f * ((lx & 1) ? crs : cbs));
-        cbs = 0.f; crs = 0.f;
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < SG; ++i) {
-      acc_la[i] = acc_la[i + SG]; acc_gx[i] = acc_gx[i + SG]; acc_gy[i] = acc_gy[i + SG];
-      acc_la[i + SG] = 0.f; acc_gx[i + SG] = 0.f; acc_gy[i + SG] = 0.f;
-    }
-#pragma unroll
-    for (int c = 0; c < 3; ++c) { hist[0][c] = cu[2][c]; hist[1][c] = cu[3][c]; }
-  }
-  __syncthreads();
-  store_group(niter - 1);
-}
-
-
 }  // namespace
 
 extern "C" int vs_resize_pre(const float* src, int B, int C, int H, int W, int oh, int ow, int antialias, float* dst_rgb,
@@ -1489,20 +761,9 @@ extern "C" int vs_embed_tail(const vs_tail_desc_t* d, void* stream) {
   const int mode = form >= 1 && form <= 4 ? form - 1 : 3;
   const bool full_jnd = d->attenuate && !d->hmap_lowres;
   const bool sep = mode > 0 && full_jnd && d->taps43 && standard_jnd_taps(d->taps43);
-  if (mode == 3 && !d->io_u8 && (sep || !full_jnd) && d->W >= 2 * d->S_w && d->H >= 2 * d->S_h) {
-    // VS_TAIL_STRIP overrides the strip height
+  if (mode == 3 && !d->io_u8 && tail_can_stream(full_jnd, d->taps43, d->H, d->W, d->S_h, d->S_w)) {
     const int64_t cols = (d->W + TTW - 1) / TTW;
-    // strip height, from tools/bench_tail_sweep.py (profiles/r04zz_tail_sweep.log, 768^2; us for 16 / 32 / 128 frames): without the luminance phase
-    // short strips win (32 rows 43 / 104 / 364, 48 rows 44 / 94 / 360, 96 rows 61 / 114 / 354); with it the strip should be tall (4 halo rows + the
-    // pipeline fill per strip) as long as the launch still has three workgroups per CU: 96 rows 115 / 155 / 503, 48 rows 76 / 151 / 510, 32 rows 87 / 152 / 521
-    int strip = 32;
-    if (full_jnd) {
-      for (int cand : {96, 48})
-        if (cols * ((d->H + cand - 1) / cand) * d->F >= 768) { strip = cand; break; }
-    } else if (cols * ((d->H + 47) / 48) * d->F >= 1024) {
-      strip = 48;
-    }
-    if (const int v = vs_debug_get(VS_DBG_TAIL_STRIP); v >= 4) strip = (v + 3) / 4 * 4;     // tests: every strip height, per call
+    const int strip = tail_strip(full_jnd, d->F, d->H, d->W);
     dim3 gs((unsigned)cols, (d->H + strip - 1) / strip, d->F);
     const size_t lds_w = (size_t)2 * d->Cd * DW_W * DW_H * sizeof(float);
     const size_t lds_j = lds_w + RING * TLW * sizeof(float);
@@ -1521,87 +782,5 @@ extern "C" int vs_embed_tail(const vs_tail_desc_t* d, void* stream) {
     else if (sep) hipLaunchKernelGGL((embed_tail_kernel<float, true, 16, false>), grid, dim3(256), 0, (hipStream_t)stream, a, k);
     else hipLaunchKernelGGL((embed_tail_kernel<float, false, 16, false>), grid, dim3(256), 0, (hipStream_t)stream, a, k);
   }
-  return vs_launch_status();
-}
-
-extern "C" int vs_sizeof_tail_nv12_desc(void) { return (int)sizeof(vs_tail_nv12_desc_t); }
-
-extern "C" int vs_resize_pre_nv12(const unsigned char* src, int B, int H, int W, int64_t pitch, int64_t frame_stride, const float* yuv2rgb12,
-                                  int oh, int ow, int antialias, float* dst_rgb, float mul, float add, float* dst_y, int y_step,
-                                  const float* ymat3, void* stream) {
-  VS_REQUIRE(src && yuv2rgb12 && B > 0 && H > 0 && W > 0 && oh > 0 && ow > 0 && (dst_rgb || dst_y));
-  VS_REQUIRE(!(H & 1) && !(W & 1) && pitch >= W && (B == 1 || frame_stride >= pitch * (H / 2 * 3 - 1) + W));
-  VS_REQUIRE(!dst_y || y_step >= 1);
-  const int key_mode = ymat3 ? 0 : 1;
-  const float y0 = ymat3 ? ymat3[0] : 0.f, y1 = ymat3 ? ymat3[1] : 0.f, y2 = ymat3 ? ymat3[2] : 0.f;
-  Nv12Mat dec;
-  for (int i = 0; i < 12; ++i) dec.m[i] = yuv2rgb12[i];
-  // row-streaming form where its windows fit (the development switches of vs_resize_pre apply: form, strip height), the tile form elsewhere
-  const int OWsel = nv12_rs_pick(H, W, oh, ow, antialias);
-  if (vs_debug_get(VS_DBG_RESIZE_FORM) != 1 && OWsel) {
-    const int cols = (ow + OWsel - 1) / OWsel;
-    // tallest strip that still launches ~512 workgroups (two per CU), down to 8 rows for the 8-frame launches of detect: the fastest height of
-    // every batch size in `tools/bench_nv12.py --sweep` (profiles/nv12_resize_strip_sweep.json)
-    int strip = 8;
-    for (int cand : {64, 48, 32, 24, 16, 12})
-      if ((int64_t)cols * ((oh + cand - 1) / cand) * B >= 512) { strip = cand; break; }
-    if (const int v = vs_debug_get(VS_DBG_RESIZE_STRIP); v >= 1) strip = v;
-    dim3 gs(cols, (oh + strip - 1) / strip, B);
-    const size_t lds = OWsel == 128 ? vs_rs::rs_lds_bytes<128>() : vs_rs::rs_lds_bytes<64>();
-    const ResizePreEpi epi{dst_rgb, dst_y, mul, add, y_step < 1 ? 1 : y_step, key_mode, y0, y1, y2, oh, ow};
-    if ((int64_t)lds <= vs_max_lds_bytes()) {
-      if (OWsel == 128) hipLaunchKernelGGL(resize_pre_nv12_stream_kernel<128>, gs, dim3(256), lds, (hipStream_t)stream, src, H, W, pitch, frame_stride, dec, oh, ow, antialias, epi, strip);
-      else hipLaunchKernelGGL(resize_pre_nv12_stream_kernel<64>, gs, dim3(256), lds, (hipStream_t)stream, src, H, W, pitch, frame_stride, dec, oh, ow, antialias, epi, strip);
-      return vs_launch_status();
-    }
-  }
-  dim3 grid((ow + 31) / 32, (oh + 7) / 8, B);
-  hipLaunchKernelGGL(resize_pre_nv12_kernel, grid, dim3(256), 0, (hipStream_t)stream, src, B, H, W, pitch, frame_stride, dec, oh, ow,
-                     antialias, dst_rgb, mul, add, dst_y, y_step < 1 ? 1 : y_step, key_mode, y0, y1, y2);
-  return vs_launch_status();
-}
-
-extern "C" int vs_embed_tail_nv12(const vs_tail_nv12_desc_t* d, void* stream) {
-  VS_REQUIRE(d && d->imgs && d->out && d->delta && d->F > 0 && d->H > 0 && d->W > 0 && d->S_h > 0 && d->S_w > 0);
-  VS_REQUIRE((d->Cd == 1 || d->Cd == 3) && d->step >= 1 && d->total_key >= 1);
-  VS_REQUIRE(d->video_mode >= 0 && d->video_mode <= 2);
-  VS_REQUIRE(!(d->H & 1) && !(d->W & 1) && d->clamp);        // codes are only defined for values in [0, 1]
-  const int64_t rows = d->H / 2 * 3;
-  VS_REQUIRE(d->src_pitch >= d->W && d->dst_pitch >= d->W);
-  VS_REQUIRE(d->F == 1 || (d->src_frame_stride >= d->src_pitch * (rows - 1) + d->W && d->dst_frame_stride >= d->dst_pitch * (rows - 1) + d->W));
-  if (d->preds_w || d->attenuate == 2 || (d->variant != 0 && d->variant != 1 && d->variant != 4)) return VS_ERR_UNSUPPORTED;
-  VS_REQUIRE(!(d->attenuate && !d->hmap_lowres) || d->taps43);
-  TailArgs a{d->imgs, d->out, nullptr, d->delta, d->attenuate ? d->hmap_lowres : nullptr, d->F, d->H, d->W, d->S_h, d->S_w,
-             d->Cd, d->step, d->video_mode, d->total_key, d->attenuate, d->clamp, d->antialias, d->scaling_i, d->scaling_w};
-  JndTaps k{};
-  if (d->taps43) k = taps_from(d->taps43);
-  Nv12Geo g{d->src_pitch, d->src_frame_stride, d->dst_pitch, d->dst_frame_stride, {}, {}};
-  for (int i = 0; i < 12; ++i) { g.dec.m[i] = d->yuv2rgb12[i]; g.enc.m[i] = d->rgb2yuv12[i]; }
-  // row-streaming form (default) where vs_embed_tail's applies: an up-scale of the watermark by >= 2 in both directions and, for the
-  // full-resolution heat-map, the standard JND taps; the 16-row tile form elsewhere and with variant = 1
-  const bool full_jnd = d->attenuate && !d->hmap_lowres;
-  const bool can_stream = (!full_jnd || standard_jnd_taps(d->taps43)) && d->W >= 2 * d->S_w && d->H >= 2 * d->S_h;
-  if (d->variant == 4 && !can_stream) return VS_ERR_UNSUPPORTED;
-  if (d->variant != 1 && can_stream) {
-    const int64_t cols = (d->W + TTW - 1) / TTW;
-    int strip = 32;                                   // strip heights of vs_embed_tail (profiles/r04zz_tail_sweep.log)
-    if (full_jnd) {
-      for (int cand : {96, 48})
-        if (cols * ((d->H + cand - 1) / cand) * d->F >= 768) { strip = cand; break; }
-    } else if (cols * ((d->H + 47) / 48) * d->F >= 1024) {
-      strip = 48;
-    }
-    if (const int v = vs_debug_get(VS_DBG_TAIL_STRIP); v >= 4) strip = (v + 3) / 4 * 4;     // tests: every strip height, per call
-    dim3 gs((unsigned)cols, (d->H + strip - 1) / strip, d->F);
-    const size_t lds_w = (size_t)2 * d->Cd * DW_W * DW_H * sizeof(float);
-    const size_t lds_j = lds_w + RING * TLW * sizeof(float);
-    if (full_jnd && d->Cd == 1) hipLaunchKernelGGL((embed_tail_nv12_stream_kernel<true, 1>), gs, dim3(256), lds_j, (hipStream_t)stream, a, k, g, strip);
-    else if (full_jnd) hipLaunchKernelGGL((embed_tail_nv12_stream_kernel<true, 3>), gs, dim3(256), lds_j, (hipStream_t)stream, a, k, g, strip);
-    else if (d->Cd == 1) hipLaunchKernelGGL((embed_tail_nv12_stream_kernel<false, 1>), gs, dim3(256), lds_w, (hipStream_t)stream, a, k, g, strip);
-    else hipLaunchKernelGGL((embed_tail_nv12_stream_kernel<false, 3>), gs, dim3(256), lds_w, (hipStream_t)stream, a, k, g, strip);
-    return vs_launch_status();
-  }
-  dim3 grid((d->W + TTW - 1) / TTW, (d->H + TTH - 1) / TTH, d->F);
-  hipLaunchKernelGGL(embed_tail_nv12_kernel, grid, dim3(256), 0, (hipStream_t)stream, a, k, g);
   return vs_launch_status();
 }

@@ -1,5 +1,6 @@
 // What the shell kernels of shell.hip and yuv420.hip share: tile geometry, the resize_pre epilogue, the JND and blend expressions (every kernel
-// calls the SAME functions, so its forms agree bit for bit), the tail arguments and the byte-surface access of the NV12 kernels.
+// calls the SAME functions, so its forms agree bit for bit), the tail arguments, the launch rule of the row-streaming tail and the colour
+// affines of the 4:2:0 kernels.
 #pragma once
 #include "vs_common.h"
 #include "resize_taps.h"
@@ -176,40 +177,12 @@ __device__ __forceinline__ float jnd_at_ring(const float* Lr, const int cslot, c
 }
 
 // ---------------------------------------------------------------------------------------------------
-// NV12 frames (uint8 [F][3H/2][W] at a row pitch and a frame stride in bytes: H luma rows, then H/2 rows of interleaved CbCr, one pair per
-// 2 x 2 pixel block).  The colour affines come from the host (videoseal_amd/nv12.py: built and inverted in float64, handed over as 12 floats,
-// row-major 3 x 4): dec maps (Y, Cb, Cr, 1) in code units to RGB, which is clamped to [0, 1] before anything else uses it; enc maps
-// (R, G, B, 1) back to code units.  Output codes are floor(clamp(v, 0, 255) + 0.5); the chroma of a block is the mean of its four per-pixel
-// values, rounded once.  Frame bytes move as 16-byte pieces wherever a piece lies inside the row and its address is aligned; every other
-// piece (unaligned base or pitch, right edge) goes byte by byte, guarded -- padding bytes are neither used nor written.
+// The colour affines of the 4:2:0 kernels (yuv420.hip).  They come from the host (videoseal_amd/yuv420.py: built and inverted in float64,
+// handed over as 12 floats, row-major 3 x 4) in code units of the surface's depth: dec maps (Y, Cb, Cr, 1) to RGB, which is clamped to [0, 1]
+// before anything else uses it; enc maps (R, G, B, 1) back to code units.
 struct Nv12Mat { float m[12]; };
-struct Nv12Geo { int64_t sp, sfs, dp, dfs; Nv12Mat dec, enc; };
 
-__device__ __forceinline__ uint4 nv12_ld16(const unsigned char* __restrict__ row, const int col, const int W) {
-  const unsigned char* p = row + col;
-  if (col >= 0 && col + 16 <= W && (reinterpret_cast<uintptr_t>(p) & 15) == 0) return *reinterpret_cast<const uint4*>(p);
-  unsigned w[4] = {0u, 0u, 0u, 0u};
-#pragma unroll
-  for (int q = 0; q < 16; ++q) {
-    const int c = col + q;
-    if (c >= 0 && c < W) w[q >> 2] |= (unsigned)p[q] << (8 * (q & 3));
-  }
-  return uint4{w[0], w[1], w[2], w[3]};
-}
-__device__ __forceinline__ void nv12_st16(unsigned char* __restrict__ row, const int col, const int W, const unsigned char* __restrict__ lds16) {
-  unsigned char* p = row + col;
-  if (col + 16 <= W && (reinterpret_cast<uintptr_t>(p) & 15) == 0) {
-    *reinterpret_cast<uint4*>(p) = *reinterpret_cast<const uint4*>(lds16);
-    return;
-  }
-  for (int q = 0; q < 16; ++q)
-    if (col + q < W) p[q] = lds16[q];
-}
-__device__ __forceinline__ unsigned nv12_byte(const uint4& v, const int q) {       // q: compile-time constant after unrolling
-  const unsigned w = q < 4 ? v.x : (q < 8 ? v.y : (q < 12 ? v.z : v.w));
-  return (w >> (8 * (q & 3))) & 0xffu;
-}
-// (explicit fma chains: every NV12 kernel evaluates the same expression, see tail_taps)
+// (explicit fma chains: every 4:2:0 kernel evaluates the same expression, see tail_taps)
 __device__ __forceinline__ float nv12_aff(const Nv12Mat& k, const int r, const float a, const float b, const float c) {
   return __builtin_fmaf(k.m[4 * r], a, __builtin_fmaf(k.m[4 * r + 1], b, __builtin_fmaf(k.m[4 * r + 2], c, k.m[4 * r + 3])));
 }
@@ -217,7 +190,6 @@ __device__ __forceinline__ void nv12_rgb(const Nv12Mat& k, const float y, const 
 #pragma unroll
   for (int c = 0; c < 3; ++c) rgb[c] = fminf(fmaxf(nv12_aff(k, c, y, cb, cr), 0.f), 1.f);
 }
-__device__ __forceinline__ unsigned char nv12_code(const float v) { return (unsigned char)(int)floorf(fminf(fmaxf(v, 0.f), 255.f) + 0.5f); }
 
 // ---------------------------------------------------------------------------------------------------
 // the taps of jnd.py:24-41 (what every released card carries in its state dict)
@@ -227,6 +199,27 @@ inline bool standard_jnd_taps(const float* t) {
   for (int i = 0; i < 25; ++i) if (t[i] != lum[i]) return false;
   for (int i = 0; i < 9; ++i) if (t[25 + i] != sx[i] || t[34 + i] != sy[i]) return false;
   return true;
+}
+
+// The launch rule of the row-streaming tail, one copy for vs_embed_tail (fp32) and the 4:2:0 tails.  The form applies to an up-scale of the
+// watermark by >= 2 in both directions and, for the full-resolution heat-map, the standard JND taps.
+inline bool tail_can_stream(bool full_jnd, const float* taps43, int H, int W, int Sh, int Sw) {
+  return (!full_jnd || (taps43 && standard_jnd_taps(taps43))) && W >= 2 * Sw && H >= 2 * Sh;
+}
+// strip height, from tools/bench_tail_sweep.py (profiles/r04zz_tail_sweep.log, 768^2; us for 16 / 32 / 128 frames): without the luminance phase
+// short strips win (32 rows 43 / 104 / 364, 48 rows 44 / 94 / 360, 96 rows 61 / 114 / 354); with it the strip should be tall (4 halo rows + the
+// pipeline fill per strip) as long as the launch still has three workgroups per CU: 96 rows 115 / 155 / 503, 48 rows 76 / 151 / 510, 32 rows 87 / 152 / 521
+inline int tail_strip(bool full_jnd, int F, int H, int W) {
+  const int64_t cols = (W + TTW - 1) / TTW;
+  int strip = 32;
+  if (full_jnd) {
+    for (int cand : {96, 48})
+      if (cols * ((H + cand - 1) / cand) * F >= 768) { strip = cand; break; }
+  } else if (cols * ((H + 47) / 48) * F >= 1024) {
+    strip = 48;
+  }
+  if (const int v = vs_debug_get(VS_DBG_TAIL_STRIP); v >= 4) strip = (v + 3) / 4 * 4;     // VS_TAIL_STRIP; tests: every strip height, per call
+  return strip;
 }
 
 inline JndTaps taps_from(const float* t43) {

@@ -19,6 +19,18 @@ static inline int vs_launch_status() { return hipGetLastError() == hipSuccess ? 
 
 static inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// an NV12 clip in one buffer (uint8 [F][3H/2][W]: the chroma rows under the luma rows, one pitch, one frame stride) as a two-plane surface
+static inline vs_yuv420_surface_t vs_nv12_surface(const void* base, int H, int64_t pitch, int64_t frame_stride) {
+  vs_yuv420_surface_t s{};
+  unsigned char* p = static_cast<unsigned char*>(const_cast<void*>(base));
+  s.plane[0] = p;
+  s.plane[1] = p + (int64_t)H * pitch;
+  s.pitch[0] = s.pitch[1] = pitch;
+  s.frame_stride[0] = s.frame_stride[1] = frame_stride;
+  s.depth = 8;
+  return s;
+}
+
 // Development switches of the launchers: ONE list for the key numbers (VS_DBG_<name>), the names vs_debug_key() answers to and the environment
 // defaults.  A launcher asks vs_debug_get(key) and nothing else: the value vs_debug_set gave the key when that is non-zero, else the key's
 // environment default, else 0 = the library's own choice.  api.hip reads the environment for the whole list once, at the first vs_debug_get /

@@ -1,4 +1,5 @@
-// 4:2:0 frames as a decoder delivers them, on the kernels of shell.hip's NV12 section: one body per kernel, a surface trait per format.
+// 4:2:0 frames as a decoder delivers them: vs_resize_pre and vs_embed_tail (shell.hip) with the colour conversion fused in, each way.  Four
+// kernels (resize and tail, each as a tile form and a row-streaming form), one body per kernel, a surface trait per format.
 //   nv12       uint8   Y plane + interleaved CbCr plane           i420       uint8   Y, U, V planes
 //   p010       uint16  as nv12, code = word >> 6                  yuv420p10  uint16  as i420, code = min(word, 1023)
 // Every plane has its own row pitch and frame stride in bytes (any value, odd ones included).  The colour affines come from the host in code
@@ -7,7 +8,9 @@
 // The trait supplies "load 16 bytes of this row of this plane" (8 or 16 samples; a planar chroma piece serves twice as many luma columns),
 // "sample q as a float code" and "store 16 bytes"; a piece moves as one 16-byte access where it lies inside the row and its address is
 // aligned, sample by sample, guarded, elsewhere -- padding bytes are neither used nor written.  Conversion, filter taps, JND and blend are the
-// expressions of the NV12 kernels in their order (shell_common.h), so layouts that hold the same codes give the same bits.
+// same expressions in the same order for every trait (shell_common.h), so layouts that hold the same codes give the same bits.
+// The single-buffer NV12 entry points (vs_resize_pre_nv12, vs_embed_tail_nv12: uint8 [F][3H/2][W], chroma rows under the luma rows at the
+// same pitch) are shims at the end of this file: they check their arguments and run the nv12 trait on a two-plane surface.
 #include "shell_common.h"
 
 #include <type_traits>
@@ -138,7 +141,7 @@ struct Surf {
   };
   // the pieces of SPP luma columns x one row pair for the row-streaming resize: two luma pieces and ONE chroma piece.  Planar: the lanes of a
   // pair hold neighbouring chunks; the even lane loads the U piece that serves both, the odd lane the V piece, and each hands the other the
-  // half it needs when the chunk is converted (one 16-byte load of U and one of V per 2 SPP luma columns, three loads per thread as for NV12)
+  // half it needs when the chunk is converted (one 16-byte load of U and one of V per 2 SPP luma columns, three loads per thread as for an interleaved surface)
   struct SChunk {
     uint4 y[2];
     uint4 c;
@@ -172,8 +175,10 @@ using SurfI420 = Surf<true, 8, false>;
 using SurfP010 = Surf<false, 10, true>;
 using SurfP10 = Surf<true, 10, false>;
 
-// resize_pre_nv12_kernel on a surface.  Staging: a task is one chunk of CW columns x one row pair; the window of at most RS_WW x RS_WH pixels
-// spans <= 15 chunks x 17 pairs, tasks taken in turn by the 256 threads.
+// Tile form of the resize: resize_pre_kernel (shell.hip) on 4:2:0 frames -- conversion and clamp per source pixel in front of the filter, then
+// the same taps in the same order.  A workgroup owns 32 x 8 output pixels.  Staging: a task is one chunk of CW columns x one row PAIR (the luma
+// pieces of both rows and the chroma they share), converted from registers into the fp32 window in LDS; the window of at most RS_WW x RS_WH
+// pixels spans <= 15 chunks x 17 pairs, tasks taken in turn by the 256 threads.  A window that does not fit is filtered straight from the frame.
 template <class SF>
 __global__ __launch_bounds__(256) void resize_pre_yuv_kernel(YuvSurf s, int B, int H, int W, Nv12Mat dec, int oh, int ow, int antialias,
                                                              float* __restrict__ dst_rgb, float mul, float add, float* __restrict__ dst_key,
@@ -305,10 +310,15 @@ __global__ __launch_bounds__(256) void resize_pre_yuv_kernel(YuvSurf s, int B, i
   }
 }
 
-// Row-streaming form: resize_pre_nv12_stream_kernel on a surface.  The window starts on a multiple of `align` = max(16, Surf::CW) columns
-// (luma and chroma pieces stay 16-byte aligned); a load task is one piece of SPP columns x one row pair of the group's four (Surf::SChunk),
-// <= 56 pieces x 4 pairs; planar surfaces take an even number of pieces per row, so that the lanes of a pair share a chroma piece.
-inline int yuv_rs_pick(int H, int W, int oh, int ow, int antialias, int align) {          // nv12_rs_pick with the window start's alignment
+// Row-streaming form of the resize: vs_rs::resize_stream_body (resize_stream.h) with another loader.  A workgroup owns OW output columns x a
+// strip of output rows and walks the input rows eight at a time, groups starting on an EVEN row: a group is four row pairs.  The window starts
+// on a multiple of `align` = max(16, Surf::CW) columns (luma and chroma pieces stay 16-byte aligned); a load task is one piece of SPP columns
+// x one row pair of the group's four (Surf::SChunk: two luma pieces and one chroma piece, requested one group ahead), <= 56 pieces x 4 pairs;
+// planar surfaces take an even number of pieces per row, so that the lanes of a pair share a chroma piece.  Every luma row and every chroma
+// row is fetched once per column tile (+ the first window of a strip).  The thread that holds a task converts its pixels straight from
+// registers into the [8][3][INW] fp32 window; the horizontal and vertical passes, their expressions and their order are resize_stream_body's
+// and the tile kernel's: the same bits.
+inline int yuv_rs_pick(int H, int W, int oh, int ow, int antialias, int align) {          // vs_rs::rs_pick with an `align`-column-aligned window start
   const float sx = (float)W / (float)ow, sy = (float)H / (float)oh;
   const float supx = antialias ? (sx >= 1.f ? sx : 1.f) : 1.f, supy = antialias ? (sy >= 1.f ? sy : 1.f) : 1.f;
   auto fits = [&](int OW, int INW, int MT, int RING) {
@@ -452,9 +462,12 @@ __global__ __launch_bounds__(256) void resize_pre_yuv_stream_kernel(YuvSurf s, i
   }
 }
 
-// embed_tail_nv12_kernel on a surface.  Workgroup = 256 columns x 16 rows of one frame, tiles start on even rows.  The tile's samples + halo
-// (20 luma rows of NVW columns from x0 - SPP, 10 chroma rows) are staged in LDS as stored words, piece by piece; the watermarked tile is
-// collected in LDS as output words and leaves as 16-byte pieces (16 luma rows, 8 chroma rows of 256 samples: pairs, or U then V).
+// Tile form of the tail: embed_tail_kernel (shell.hip) on 4:2:0 frames.  Workgroup = 256 columns x 16 rows of one frame (a tile starts on an
+// even row: a chroma row belongs to one tile).  The tile's samples + a 2-pixel halo (20 luma rows of NVW columns from x0 - SPP, 10 chroma
+// rows) are staged in LDS once as stored words, piece by piece; luminance and blend both read the pixel from there.  The arithmetic between
+// decode and encode is embed_tail_kernel's (43-tap JND, the same taps, key-frame expansion and blend); a thread owns one column and walks the
+// rows in pairs, the horizontal half of the 2 x 2 chroma sum comes from the neighbouring lane.  The watermarked tile is collected in LDS as
+// output words and leaves as 16-byte pieces (16 luma rows, 8 chroma rows of 256 samples: pairs, or U then V).
 constexpr int NVR = TTH + 2 * HALO, NVC = NVR / 2;
 template <class SF>
 __global__ __launch_bounds__(256) void embed_tail_yuv_kernel(TailArgs a, JndTaps k, YuvGeo g) {
@@ -658,9 +671,13 @@ __global__ __launch_bounds__(256) void embed_tail_yuv_kernel(TailArgs a, JndTaps
   }
 }
 
-// Row-streaming form: embed_tail_nv12_stream_kernel on a surface.  A group's 4 luma rows (NPY pieces each) and 2 chroma rows (NPC pieces each)
-// are <= 208 loads, one per thread, requested two groups ahead of their use; the group's words (4 x 256 luma, 2 x 256 chroma) leave after
-// the next barrier as <= 192 pieces, one per thread.
+// Row-streaming form of the tail: embed_tail_stream_kernel's structure (shell.hip: 256 columns x a strip of rows walked in groups of SG = 4,
+// luminance ring, accumulators of the separable JND stencils, double-buffered watermark window, ONE barrier per group) with the frame's words
+// staged through LDS as 16-byte pieces.  A group's 4 luma rows (NPY pieces each) and 2 chroma rows (NPC pieces each) are <= 208 loads, one per
+// thread, requested two groups ahead of their use: loaded during group it - 1, written to the word stage before the barrier of group it, read
+// by every thread (own column, halo columns) at the top of group it + 1.  Strips start on a multiple of four rows, so the two row pairs of a
+// group are whole 2 x 2 blocks: the horizontal half of the chroma sum comes from the neighbouring lane.  The group's words (4 x 256 luma,
+// 2 x 256 chroma) are collected in LDS and leave after the next barrier as <= 192 pieces, one per thread.
 template <class SF, bool JND, int CD>
 __global__ __launch_bounds__(256) void embed_tail_yuv_stream_kernel(TailArgs a, JndTaps k, YuvGeo g, const int strip) {
   using S = typename SF::S;
@@ -953,7 +970,9 @@ int launch_resize(const YuvSurf& s, int B, int H, int W, const Nv12Mat& dec, int
   const int OWsel = yuv_rs_pick(H, W, oh, ow, antialias, SF::CW > 16 ? SF::CW : 16);
   if (vs_debug_get(VS_DBG_RESIZE_FORM) != 1 && OWsel) {
     const int cols = (ow + OWsel - 1) / OWsel;
-    int strip = 8;                                    // strip heights of vs_resize_pre_nv12 (profiles/nv12_resize_strip_sweep.json)
+    // tallest strip that still launches ~512 workgroups (two per CU), down to 8 rows for the 8-frame launches of detect: the fastest height of
+    // every batch size in `tools/bench_nv12.py --sweep` (profiles/nv12_resize_strip_sweep.json)
+    int strip = 8;
     for (int cand : {64, 48, 32, 24, 16, 12})
       if ((int64_t)cols * ((oh + cand - 1) / cand) * B >= 512) { strip = cand; break; }
     if (const int v = vs_debug_get(VS_DBG_RESIZE_STRIP); v >= 1) strip = v;
@@ -975,16 +994,8 @@ int launch_resize(const YuvSurf& s, int B, int H, int W, const Nv12Mat& dec, int
 template <class SF>
 int launch_tail(const TailArgs& a, const JndTaps& k, const YuvGeo& g, bool stream_form, bool full_jnd, hipStream_t st) {
   if (stream_form) {
-    const int64_t cols = (a.W + TTW - 1) / TTW;
-    int strip = 32;                                   // strip heights of vs_embed_tail (profiles/r04zz_tail_sweep.log)
-    if (full_jnd) {
-      for (int cand : {96, 48})
-        if (cols * ((a.H + cand - 1) / cand) * a.F >= 768) { strip = cand; break; }
-    } else if (cols * ((a.H + 47) / 48) * a.F >= 1024) {
-      strip = 48;
-    }
-    if (const int v = vs_debug_get(VS_DBG_TAIL_STRIP); v >= 4) strip = (v + 3) / 4 * 4;     // tests: every strip height, per call
-    dim3 gs((unsigned)cols, (a.H + strip - 1) / strip, a.F);
+    const int strip = tail_strip(full_jnd, a.F, a.H, a.W);
+    dim3 gs((a.W + TTW - 1) / TTW, (a.H + strip - 1) / strip, a.F);
     const size_t lds_w = (size_t)2 * a.Cd * DW_W * DW_H * sizeof(float);
     const size_t lds_j = lds_w + RING * TLW * sizeof(float);
     if (full_jnd && a.Cd == 1) hipLaunchKernelGGL((embed_tail_yuv_stream_kernel<SF, true, 1>), gs, dim3(256), lds_j, st, a, k, g, strip);
@@ -1042,9 +1053,9 @@ extern "C" int vs_embed_tail_yuv420(const vs_tail_yuv420_desc_t* d, void* stream
   if (d->taps43) k = taps_from(d->taps43);
   YuvGeo g{dev_surface(d->src), dev_surface(d->dst), {}, {}};
   for (int i = 0; i < 12; ++i) { g.dec.m[i] = d->yuv2rgb12[i]; g.enc.m[i] = d->rgb2yuv12[i]; }
-  // the forms of vs_embed_tail_nv12 and their rule
+  // row-streaming form (default) where vs_embed_tail's applies, the 16-row tile form elsewhere and with variant = 1
   const bool full_jnd = d->attenuate && !d->hmap_lowres;
-  const bool can_stream = (!full_jnd || standard_jnd_taps(d->taps43)) && d->W >= 2 * d->S_w && d->H >= 2 * d->S_h;
+  const bool can_stream = tail_can_stream(full_jnd, d->taps43, d->H, d->W, d->S_h, d->S_w);
   if (d->variant == 4 && !can_stream) return VS_ERR_UNSUPPORTED;
   const bool sf = d->variant != 1 && can_stream;
   hipStream_t st = (hipStream_t)stream;
@@ -1054,4 +1065,36 @@ extern "C" int vs_embed_tail_yuv420(const vs_tail_yuv420_desc_t* d, void* stream
     case 2: return launch_tail<SurfP010>(a, k, g, sf, full_jnd, st);
     default: return launch_tail<SurfP10>(a, k, g, sf, full_jnd, st);
   }
+}
+
+// ---- NV12 clips in one buffer: uint8 [F][3H/2][W], the chroma rows under the luma rows at the same pitch.  The entry points check what a
+// single buffer asks beyond its two planes (a frame is pitch * (3H/2 - 1) + W bytes: the planes of consecutive frames must not interleave)
+// and hand the two-plane surface (vs_nv12_surface) to the entry points above.
+
+extern "C" int vs_sizeof_tail_nv12_desc(void) { return (int)sizeof(vs_tail_nv12_desc_t); }
+
+extern "C" int vs_resize_pre_nv12(const unsigned char* src, int B, int H, int W, int64_t pitch, int64_t frame_stride, const float* yuv2rgb12,
+                                  int oh, int ow, int antialias, float* dst_rgb, float mul, float add, float* dst_y, int y_step,
+                                  const float* ymat3, void* stream) {
+  VS_REQUIRE(src && yuv2rgb12 && B > 0 && H > 0 && W > 0 && oh > 0 && ow > 0 && (dst_rgb || dst_y));
+  VS_REQUIRE(!(H & 1) && !(W & 1) && pitch >= W && (B == 1 || frame_stride >= pitch * (H / 2 * 3 - 1) + W));
+  const vs_yuv420_surface_t s = vs_nv12_surface(src, H, pitch, frame_stride);
+  return vs_resize_pre_yuv420(&s, B, H, W, yuv2rgb12, oh, ow, antialias, dst_rgb, mul, add, dst_y, y_step, ymat3, stream);
+}
+
+extern "C" int vs_embed_tail_nv12(const vs_tail_nv12_desc_t* d, void* stream) {
+  VS_REQUIRE(d && d->imgs && d->out && d->H > 0 && d->W > 0 && !(d->H & 1) && !(d->W & 1));
+  const int64_t rows = d->H / 2 * 3;
+  VS_REQUIRE(d->src_pitch >= d->W && d->dst_pitch >= d->W);
+  VS_REQUIRE(d->F == 1 || (d->src_frame_stride >= d->src_pitch * (rows - 1) + d->W && d->dst_frame_stride >= d->dst_pitch * (rows - 1) + d->W));
+  vs_tail_yuv420_desc_t y{};
+  y.src = vs_nv12_surface(d->imgs, d->H, d->src_pitch, d->src_frame_stride);
+  y.dst = vs_nv12_surface(d->out, d->H, d->dst_pitch, d->dst_frame_stride);
+  y.preds_w = d->preds_w; y.delta = d->delta; y.hmap_lowres = d->hmap_lowres; y.taps43 = d->taps43;
+  y.F = d->F; y.H = d->H; y.W = d->W; y.S_h = d->S_h; y.S_w = d->S_w; y.Cd = d->Cd;
+  y.step = d->step; y.video_mode = d->video_mode; y.total_key = d->total_key;
+  y.attenuate = d->attenuate; y.clamp = d->clamp; y.antialias = d->antialias;
+  y.scaling_i = d->scaling_i; y.scaling_w = d->scaling_w; y.variant = d->variant;
+  for (int i = 0; i < 12; ++i) { y.yuv2rgb12[i] = d->yuv2rgb12[i]; y.rgb2yuv12[i] = d->rgb2yuv12[i]; }
+  return vs_embed_tail_yuv420(&y, stream);       // (every remaining check, in the order this entry point has always applied them)
 }

@@ -328,9 +328,7 @@ class HipEngine:
         self.Et = None         # embedder weights with BatchNorm NOT folded (batch-statistics forward under model.train())
         self.X = None
         self.ymat = self.taps43 = None
-        # NV12 clips (uint8 [F, 3H/2, W]): the colour choice in force and the (yuv2rgb12, rgb2yuv12) float arrays per (matrix, full_range)
-        self.nv12_color = ("bt709", False)
-        self._nv12_arrays = {}
+        self._yuv420_arrays = {}         # 4:2:0 clips: the (yuv2rgb12, rgb2yuv12) float arrays per (matrix, full_range, depth)
         self._pack_misc()
 
     def _fetch(self, k: str) -> torch.Tensor:
@@ -1383,24 +1381,15 @@ class HipEngine:
         return self._pixel_decoder(n3, V)
 
     # ------------------------------------------------------------------ shell
-    def nv12_arrays(self, color=None):
-        """(yuv2rgb12, rgb2yuv12) as host arrays of 12 floats for `color` = (matrix, full_range) (default: self.nv12_color); built in
-        float64 by nv12.color_affine, rounded to fp32 once"""
-        color = tuple(color or self.nv12_color)
-        if color not in self._nv12_arrays:
-            from .nv12 import color_affine
-            fwd, inv = color_affine(*color)
-            self._nv12_arrays[color] = ((C.c_float * 12)(*[float(v) for v in inv.reshape(-1)]), (C.c_float * 12)(*[float(v) for v in fwd.reshape(-1)]))
-        return self._nv12_arrays[color]
-
     def yuv420_arrays(self, color, depth: int):
-        """nv12_arrays for `yuv420.color_affine(matrix, full_range, depth)`: code units of a surface's depth"""
+        """(yuv2rgb12, rgb2yuv12) as host arrays of 12 floats for `color` = (matrix, full_range) in code units of a surface's depth; built
+        in float64 by yuv420.color_affine, rounded to fp32 once"""
         key = (color[0], bool(color[1]), int(depth))
-        if key not in self._nv12_arrays:
+        if key not in self._yuv420_arrays:
             from .yuv420 import color_affine
             fwd, inv = color_affine(*key)
-            self._nv12_arrays[key] = ((C.c_float * 12)(*[float(v) for v in inv.reshape(-1)]), (C.c_float * 12)(*[float(v) for v in fwd.reshape(-1)]))
-        return self._nv12_arrays[key]
+            self._yuv420_arrays[key] = ((C.c_float * 12)(*[float(v) for v in inv.reshape(-1)]), (C.c_float * 12)(*[float(v) for v in fwd.reshape(-1)]))
+        return self._yuv420_arrays[key]
 
     def _resize_pre_yuv420(self, clip, S, antialias, *, want_rgb, mul, add, want_key, key_step, tag):
         """resize_pre on a 4:2:0 clip (yuv420.Clip420: device-resident planes at any pitch, its format and colour choice)"""
@@ -1444,27 +1433,14 @@ class HipEngine:
         # algorithmic HBM bytes: 1.5 samples per pixel each way + the low-resolution watermark
         self._shell_t1(ev, f"embed_tail_yuv_kernel<{clip.fmt}>", 2 * (F_ * H * W * 3 // 2) * clip.planes[0].element_size() + delta.numel() * 4)
 
-    @staticmethod
-    def _nv12_geometry(t: torch.Tensor):
-        """(F, H, W, pitch, frame stride) of an NV12 clip uint8 [F, 3H/2, W]; pitch and strides come from the tensor's strides"""
-        F_, R, W = t.shape
-        if R % 3 or W % 2:
-            raise ValueError("NV12 frames need even H and W (uint8 [F, 3H/2, W])")
-        if t.stride(2) != 1 or t.stride(1) < W or (F_ > 1 and t.stride(0) < t.stride(1) * (R - 1) + W):
-            raise ValueError("NV12 frames: the last dimension must have stride 1, rows and frames must not overlap")
-        return F_, R // 3 * 2, W, t.stride(1), t.stride(0)
-
     def resize_pre(self, imgs: torch.Tensor, S: Tuple[int, int], antialias: bool, *, want_rgb: bool, mul=1.0, add=0.0,
-                   want_key: bool = False, key_step: int = 1, tag="rs", color=None) -> Tuple[Optional[Act], Optional[Act]]:
-        """imgs on device, fp32 NCHW [B,3,H,W], uint8 RGB24 [B,H,W,3] or uint8 NV12 [B,3H/2,W] (any pitch / frame stride, colour choice
-        `color` = (matrix, full_range), default self.nv12_color) -> (rgb Act [B,S,S,4] or None, key Act [ceil(B/step),S,S,4] or None)."""
+                   want_key: bool = False, key_step: int = 1, tag="rs") -> Tuple[Optional[Act], Optional[Act]]:
+        """imgs on device, fp32 NCHW [B,3,H,W], uint8 RGB24 [B,H,W,3] or a 4:2:0 clip (yuv420.Clip420)
+        -> (rgb Act [B,S,S,4] or None, key Act [ceil(B/step),S,S,4] or None)."""
         if not torch.is_tensor(imgs):         # a 4:2:0 clip (yuv420.Clip420) carries its own format and colour choice
             return self._resize_pre_yuv420(imgs, S, antialias, want_rgb=want_rgb, mul=mul, add=add, want_key=want_key, key_step=key_step, tag=tag)
-        nv12 = imgs.dtype == torch.uint8 and imgs.dim() == 3
-        u8 = imgs.dtype == torch.uint8 and not nv12
-        if nv12:
-            B, H, W, pitch, fstride = self._nv12_geometry(imgs)
-        elif u8:
+        u8 = imgs.dtype == torch.uint8
+        if u8:
             B, H, W, Cc = imgs.shape
             if Cc != 3:
                 raise ValueError("uint8 frames must be RGB24 [F, H, W, 3]")
@@ -1475,13 +1451,6 @@ class HipEngine:
         key = self.new_act(tag + ".key", nk, S[0], S[1], self.cfg.in_ch, 4) if want_key else None
         ymat = self.ymat if self.cfg.yuv else None
         ev = self._shell_t0()
-        if nv12:
-            N.check(self.lib.vs_resize_pre_nv12(N.ptr(imgs), B, H, W, pitch, fstride, self.nv12_arrays(color)[0], S[0], S[1], 1 if antialias else 0,
-                                                N.ptr(rgb.t) if rgb else None, mul, add, N.ptr(key.t) if key else None, key_step, ymat,
-                                                N.stream()), "vs_resize_pre_nv12")
-            # algorithmic HBM bytes: 1.5 bytes per pixel once + the low-resolution outputs
-            self._shell_t1(ev, "resize_pre_nv12_kernel", B * H * W * 3 // 2 + 16 * S[0] * S[1] * ((B if rgb else 0) + (nk if key else 0)))
-            return rgb, key
         if u8:
             N.check(self.lib.vs_resize_pre_u8(N.ptr(imgs), B, H, W, S[0], S[1], 1 if antialias else 0, N.ptr(rgb.t) if rgb else None,
                                               mul, add, N.ptr(key.t) if key else None, key_step, ymat, N.stream()), "vs_resize_pre_u8")
@@ -1506,30 +1475,6 @@ class HipEngine:
             ev1.record()
             self.shell_timers.append((name, ev0, ev1, nbytes))
 
-    def _embed_tail_nv12(self, imgs, out, delta, *, step, video_mode, hmap_low, attenuate, clamp, antialias, scaling_i, scaling_w, preds_w=None, color=None):
-        """embed_tail on NV12 clips: uint8 [F, 3H/2, W] in and out, each with its own pitch / frame stride"""
-        if out.dtype != torch.uint8 or out.shape != imgs.shape:
-            raise ValueError("NV12 frames need a uint8 output of the same shape")
-        if preds_w is not None or int(attenuate) == 2:
-            raise NotImplementedError("the NV12 tail has no preds_w and no training order of operations")
-        F_, H, W, sp, sfs = self._nv12_geometry(imgs)
-        _, _, _, dp, dfs = self._nv12_geometry(out)
-        d = N.TailNv12Desc()
-        d.imgs, d.out, d.preds_w = N.ptr(imgs), N.ptr(out), None
-        d.delta, d.hmap_lowres = N.ptr(delta), N.ptr(hmap_low)
-        d.taps43 = C.cast(self.taps43, C.c_void_p)
-        d.F, d.H, d.W, d.S_h, d.S_w, d.Cd = F_, H, W, delta.shape[-2], delta.shape[-1], delta.shape[1]
-        d.step, d.video_mode, d.total_key = step, video_mode, delta.shape[0]
-        d.attenuate, d.clamp, d.antialias = int(attenuate), int(clamp), int(antialias)
-        d.scaling_i, d.scaling_w = float(scaling_i), float(scaling_w)
-        d.src_pitch, d.src_frame_stride, d.dst_pitch, d.dst_frame_stride = sp, sfs, dp, dfs
-        d.variant = 1 if int(self.tail_variant) in (1, 2, 3) else 0           # (the tile variants of the fp32 tail -> the NV12 tile kernel)
-        d.yuv2rgb12, d.rgb2yuv12 = self.nv12_arrays(color)
-        ev = self._shell_t0()
-        N.check(self.lib.vs_embed_tail_nv12(C.byref(d), N.stream()), "vs_embed_tail_nv12")
-        # algorithmic HBM bytes: 1.5 bytes per pixel each way + the low-resolution watermark
-        self._shell_t1(ev, "embed_tail_nv12_kernel", 2 * (F_ * H * W * 3 // 2) + delta.numel() * 4)
-
     def jnd_lowres(self, rgb: Act) -> torch.Tensor:
         h = self.buf("jnd.low", rgb.B * rgb.H * rgb.W)
         N.check(self.lib.vs_jnd_heatmap(N.ptr(rgb.t), rgb.B, rgb.H, rgb.W, rgb.H * rgb.W * rgb.ld, 1, rgb.W * rgb.ld, rgb.ld,
@@ -1544,14 +1489,10 @@ class HipEngine:
         return h
 
     def embed_tail(self, imgs, out, delta, *, step, video_mode, hmap_low, attenuate, clamp, antialias, scaling_i, scaling_w,
-                   preds_w=None, color=None):
-        """`color` = (matrix, full_range) of NV12 clips (default self.nv12_color); unused by the other frame formats"""
+                   preds_w=None):
         if not torch.is_tensor(imgs):         # a 4:2:0 clip (yuv420.Clip420)
             return self._embed_tail_yuv420(imgs, out, delta, step=step, video_mode=video_mode, hmap_low=hmap_low, attenuate=attenuate, clamp=clamp,
                                            antialias=antialias, scaling_i=scaling_i, scaling_w=scaling_w, preds_w=preds_w)
-        if imgs.dtype == torch.uint8 and imgs.dim() == 3:
-            return self._embed_tail_nv12(imgs, out, delta, step=step, video_mode=video_mode, hmap_low=hmap_low, attenuate=attenuate, clamp=clamp,
-                                         antialias=antialias, scaling_i=scaling_i, scaling_w=scaling_w, preds_w=preds_w, color=color)
         d = N.TailDesc()
         u8 = imgs.dtype == torch.uint8          # RGB24 [F,H,W,3] in and out
         if u8:

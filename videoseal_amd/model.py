@@ -47,7 +47,7 @@ def _result_buffer(shape, dtype, device) -> torch.Tensor:
 
 
 def _raw_frames(x) -> bool:
-    """frames that travel in their own format: uint8 tensors (RGB24, NV12) and 4:2:0 clips (yuv420.Clip420); everything else is fp32 NCHW"""
+    """frames that travel in their own format: uint8 tensors (RGB24) and 4:2:0 clips (yuv420.Clip420, NV12 clips among them); everything else is fp32 NCHW"""
     return not torch.is_tensor(x) or x.dtype == torch.uint8
 
 
@@ -402,7 +402,7 @@ class Wam(nn.Module):
             return {"preds": eng.extractor_forward(rgb)}
         if self.use_graphs and not torch.cuda.is_current_stream_capturing():
             def key():           # the arithmetic is part of the key: network-wide split AND the layers the calibration pinned to the exact split
-                return ("det", fr.dtype, tuple(fr.shape), eng.nv12_color if fr.dim() == 3 else getattr(fr, "graph_key", None), tuple(S), antialias, id(eng), eng.arith_net["X"], tuple(sorted(eng.layer_arith.items())))
+                return ("det", fr.dtype, tuple(fr.shape), getattr(fr, "graph_key", None), tuple(S), antialias, id(eng), eng.arith_net["X"], tuple(sorted(eng.layer_arith.items())))
             out = self._graphed(key(), {"fr": fr}, run, rekey=key)["preds"].clone()
             eng.note_guard()           # the captured vs_check_finite has run: deliver its flag like an eager steady-state pass does
             return out
@@ -415,7 +415,7 @@ class Wam(nn.Module):
                       fwd_order: bool = False, tail_span: int = 0) -> None:
         bn_train = self.embedder.training
         if self.use_graphs and not bn_train and not torch.cuda.is_current_stream_capturing():
-            key = ("emb", fr.dtype, tuple(fr.shape), eng.nv12_color if fr.dim() == 3 else getattr(fr, "graph_key", None), tuple(msgs_i32.shape), step, video_mode, antialias, lowres, preds_w is not None, self.img_size,
+            key = ("emb", fr.dtype, tuple(fr.shape), getattr(fr, "graph_key", None), tuple(msgs_i32.shape), step, video_mode, antialias, lowres, preds_w is not None, self.img_size,
                    self.clamp, float(self.blender.scaling_i), float(self.blender.scaling_w), self.attenuation is not None, fwd_order, tail_span, id(eng), eng.arith_net["E"])
             ent = self._graphs.get(key)
             if ent is None:
@@ -787,14 +787,18 @@ class Videoseal(Wam):
         return {"preds": self._detect_clip(clip.contiguous(), interpolation)}
 
     # ---- uint8 NV12 clips (videoseal_amd/nv12.py): what a hardware decoder hands over, 1.5 bytes per pixel each way
-    def _nv12_clip(self, clip: torch.Tensor, what: str, matrix: str, full_range: bool) -> HipEngine:
-        from .nv12 import MATRICES, check_clip
-        check_clip(clip, what)
+    def _nv12_clip(self, clip: torch.Tensor, what: str, matrix: str, full_range: bool):
+        """the clip as a yuv420.Clip420 of format "nv12": its two planes are strided views of the caller's buffer"""
+        from .nv12 import MATRICES, planes
+        from .yuv420 import Clip420
+        y, uv = planes(clip, what)
         if matrix not in MATRICES:
             raise ValueError(f"{what}: matrix must be one of {sorted(MATRICES)}, got {matrix!r}")
-        eng = self._engine()
-        eng.nv12_color = (matrix, bool(full_range))
-        return eng
+        F_, R, W = clip.shape
+        if clip.stride(1) < W or (F_ > 1 and clip.stride(0) < clip.stride(1) * (R - 1) + W):
+            raise ValueError(f"{what}: rows and frames must not overlap")
+        self._engine()
+        return Clip420((y, uv), "nv12", (matrix, bool(full_range)))
 
     @torch.no_grad()
     def embed_nv12(self, clip: torch.Tensor, msgs: torch.Tensor = None, interpolation: dict = None, lowres_attenuation: bool = True,
@@ -805,7 +809,7 @@ class Videoseal(Wam):
         embed(..., is_video=True) -> RGB -> NV12 (nv12.rgb_to_nv12: mean of the block's four chroma values, codes =
         floor(clamp(v, 0, 255) + 0.5)), with both conversions fused into the resize and tail kernels: no RGB or fp32 frame is written.
         `matrix` is "bt601" or "bt709", `full_range` selects 0..255 codes instead of 16..235 / 16..240.  Needs clamp=True."""
-        eng = self._nv12_clip(clip, "embed_nv12", matrix, full_range)
+        planes = self._nv12_clip(clip, "embed_nv12", matrix, full_range)
         if not self.clamp:
             raise NotImplementedError("NV12 output needs clamp=True (codes are undefined outside [0, 1])")
         if msgs is None:
@@ -814,18 +818,18 @@ class Videoseal(Wam):
             assert msgs.shape[0] == 1, "Message should be unique"
         if clip.shape[0] == 0 or clip.numel() == 0:
             return {"imgs_w": clip.clone().contiguous(), "msgs": msgs[0:1].repeat(len(clip), 1)}
-        out = self._embed_clip(clip, msgs, interpolation, lowres_attenuation)
-        return {"imgs_w": out, "msgs": msgs[0:1].repeat(len(clip), 1)}
+        out = self._embed_clip(planes, msgs, interpolation, lowres_attenuation)          # a packed buffer [F, 3HW/2]: Y, then UV
+        return {"imgs_w": out.buf.view(clip.shape), "msgs": msgs[0:1].repeat(len(clip), 1)}
 
     @torch.no_grad()
     def detect_nv12(self, clip: torch.Tensor, interpolation: dict = None, matrix: str = "bt709", full_range: bool = False) -> dict:
         """clip uint8 [F, 3H/2, W] (see embed_nv12) -> {'preds': [F, 1+nbits]}: detect(nv12.nv12_to_rgb(clip), is_video=True) with the
         conversion fused into the resize kernel."""
-        self._nv12_clip(clip, "detect_nv12", matrix, full_range)
+        planes = self._nv12_clip(clip, "detect_nv12", matrix, full_range)
         self._per_frame_rows_only("detect_nv12")
         if clip.shape[0] == 0:
             return {"preds": torch.zeros((0, self.embedder.cfg.nbits + 1), device=clip.device)}
-        return {"preds": self._detect_clip(clip, interpolation)}
+        return {"preds": self._detect_clip(planes, interpolation)}
 
     # ---- 4:2:0 clips as planes (videoseal_amd/yuv420.py): nv12, i420, p010, yuv420p10, every plane at its own pitch
     def _yuv420_clip(self, planes, fmt: str, what: str, matrix: str, full_range: bool):

@@ -12,9 +12,9 @@ U, then V -- or Y, then UV: the byte order of ffmpeg's `rawvideo`), `pack` is it
 
 Colour.  `matrix` is "bt601" (Kr, Kb = 0.299, 0.114), "bt709" (0.2126, 0.0722) or "bt2020" (0.2627, 0.0593), Kg = 1 - Kr - Kb:
     Y = Kr R + Kg G + Kb B,   Cb = (B - Y) / (2 (1 - Kb)),   Cr = (R - Y) / (2 (1 - Kr))
-Codes at depth 8: limited range Y -> 16 + 219 Y, C -> 128 + 224 C; full range Y -> 255 Y, C -> 128 + 255 C (the bits of nv12.color_affine).
+Codes at depth 8: limited range Y -> 16 + 219 Y, C -> 128 + 224 C; full range Y -> 255 Y, C -> 128 + 255 C.
 Codes at depth 10: limited range Y -> 64 + 876 Y, C -> 512 + 896 C; full range Y -> 1023 Y, C -> 512 + 1023 C.
-`color_affine` builds the forward 3 x 4 affine (RGB in [0, 1] -> code units) in float64 and inverts it in float64, in nv12.color_affine's order.
+`color_affine` builds the forward 3 x 4 affine (RGB in [0, 1] -> code units) in float64 and inverts it in float64.
 
 Chroma.  Up: every pixel of a 2 x 2 block uses that block's (Cb, Cr).  Down: the mean of the four per-pixel chroma values, then one rounding.
 Range and rounding.  After decoding every RGB channel is clamped to [0, 1]; output codes are floor(clamp(v, 0, 2^depth - 1) + 0.5), v in code
@@ -64,8 +64,8 @@ def color_affine(matrix: str = "bt709", full_range: bool = False, depth: int = 8
     fwd[0, :3], fwd[0, 3] = ys * y, y0
     fwd[1, :3], fwd[1, 3] = cs * cb, c0
     fwd[2, :3], fwd[2, 3] = cs * cr, c0
-    # inverse by cofactors, every product and sum in float64 and in this order (nv12.color_affine; csrc/model_api.hip states the same
-    # expressions for vs_yuv420_default_color, and tests/test_yuv420_cpu.py holds them to the same bits)
+    # inverse by cofactors, every product and sum in float64 and in this order: csrc/model_api.hip states the same expressions for
+    # vs_yuv420_default_color, and tests/test_yuv420_cpu.py and tests/test_nv12_cpu.py hold them to the same bits
     a = [[float(fwd[i, j]) for j in range(3)] for i in range(3)]
     cof = [[a[(i + 1) % 3][(j + 1) % 3] * a[(i + 2) % 3][(j + 2) % 3] - a[(i + 1) % 3][(j + 2) % 3] * a[(i + 2) % 3][(j + 1) % 3]
             for j in range(3)] for i in range(3)]
@@ -153,7 +153,7 @@ def to_rgb(planes: Sequence[torch.Tensor], fmt: str, matrix: str = "bt709", full
     fwd, inv = color_affine(matrix, full_range, depth)
     dev = planes[0].device
     m = torch.tensor(inv, dtype=dtype, device=dev)
-    # the affine as A^-1 (code - offset): the offsets are subtracted exactly, so no large constant is cancelled in fp32 (nv12.nv12_to_rgb)
+    # the affine as A^-1 (code - offset): the offsets are subtracted exactly, so no large constant is cancelled in fp32
     y = _codes(planes[0], depth, msb).to(dtype) - float(fwd[0, 3])
     if planar:
         c = torch.stack([_codes(planes[1], depth, msb), _codes(planes[2], depth, msb)], dim=-1).to(dtype)
