@@ -165,6 +165,10 @@ typedef struct vs_conv_desc {
   int32_t sumsq_hw;         /* ABI v3, tile codes 24 / 25 with sumsq_part only: rows per frame when that is NOT a multiple of 32 (>= 32): sumsq_part */
   int32_t reserved_;        /*   is then [ceil(M/32)][2][N] -- per 32-row group the sums of its rows in the frame of its first row | in the next      */
                             /*   frame (vs_grn_scale_from_straddle_partials); 0 = the [M/32][N] form                                               */
+  int64_t bias_fs;          /* appended, vs_version() stays 3: frame strides of bias / bias2 in floats (frames = Ho*Wo rows): row m reads bias[(m / (Ho*Wo)) * bias_fs + n].    */
+  int64_t bias2_fs;         /*   0 = one shared vector (the v3 behaviour); else a multiple of 4 and >= N.  The epilogue order is unchanged.  bias_fs:     */
+                            /*   the generic kernel (tiles 1 - 5, 13, 14; no phase 2), 17 / 18 / 26 (without K slices: Ho*Wo % 128 == 0) and K-sliced launches */
+                            /*   of tiles 22 / 23; bias2_fs: tiles 15 / 16 / 19 / 21 / 22 / 23, with or without K slices.  Every other kernel: VS_ERR_UNSUPPORTED  */
 } vs_conv_desc_t;
 #define VS_CONV_FORCE_F32 0x10
 #define VS_CONV_FORCE_SPLIT 0x20
@@ -391,6 +395,12 @@ typedef struct vs_resblock_thin_desc {
   int32_t Cout;                             /* mid = output channels: 16 (or 0) / 32; weights then [P][Cout][9 * K], K = 16 / 32  */
   float a_mul, acc_mul0, acc_mul1, acc_mulr;
   float* out; int64_t out_ld;
+  /* appended (vs_version() stays 3), Cout = 16 only: the U-Net's last layer (`outc`, 1x1 16 -> out_ch <= 4, + tanh: vs_outc_tanh) in the block's epilogue.  delta != NULL
+   * selects it: the block's output is NOT stored (out / out_ld ignored) and delta [B][out_ch][H][W] gets the same bits as vs_resblock_thin +
+   * vs_outc_tanh (same accumulation order).  Cout = 32 or out_ch > 4 answers VS_ERR_UNSUPPORTED.  delta == NULL: the other four stay 0 / NULL. */
+  const float *outc_w, *outc_b;             /* [out_ch][16], [out_ch]                                             */
+  int32_t out_ch, use_tanh;
+  float* delta;
 } vs_resblock_thin_desc_t;
 int vs_resblock_thin_supported(int cin_ld, int cmid, int cout);
 int vs_resblock_thin(const vs_resblock_thin_desc_t* d, void* stream);
@@ -532,8 +542,11 @@ int vs_broadcast_channels(const float* lat, int Bm, int hidden, float* dst, int 
  * and columns miss taps).  P[bm][tap*N + n] = sum_c W[n][tap][msg c] * latent[bm][c] comes from one small vs_conv_gemm; vs_msg_pre
  * reduces it to table[bm][cy*3 + cx][n] = sum_{valid ky, kx} P[bm][(ky*3+kx)*N + n]  (cy / cx: 0 first, 1 interior, 2 last row / column).
  * The 3x3 conv over the latent channels alone then adds table[frame][class(y, x)][n] before bias + activation (VS_CONV_PRE with
- * a_scale = table, a_scale_ld = 9*N, or 0 when one message serves every frame): K shrinks from 9*(lat+msg) to 9*lat. */
+ * a_scale = table, a_scale_ld = 9*N, or 0 when one message serves every frame): K shrinks from 9*(lat+msg) to 9*lat.
+ * vs_msg_pre_rows: the same with P_ld floats between the rows of P (>= 9*N) -- the small GEMM may carry further rows per message (the per-frame
+ * bias vectors of the block's 1x1 res_conv and of the first Upsample GEMM, vs_conv_desc_t::bias2_fs / bias_fs). */
 int vs_msg_pre(const float* P, int Bm, int N, float* table, void* stream);
+int vs_msg_pre_rows(const float* P, int64_t P_ld, int Bm, int N, float* table, void* stream);
 
 /* 1x1 conv C -> Cout (Cout <= 4) + bias + optional tanh, NHWC in, planar [B][Cout][HW] out.  unet.py:166,194-196. */
 int vs_outc_tanh(const float* x, int64_t rows_per_frame, int B, int C, int64_t ld, const float* w, const float* bias,

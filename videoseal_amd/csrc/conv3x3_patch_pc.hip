@@ -306,13 +306,14 @@ __global__ __launch_bounds__(512, 2) void conv3x3_patch_pc_kernel(const vs_conv_
   // v = act(acc (+ table) + bias1) + bias2 on every float4 group (the activation sits between the two K phases)
   auto finish_phase1 = [&](const bool with_b2) __attribute__((always_inline)) {
     const float* tb = (d.tile_hint & VS_CONV_PRE) ? d.a_scale + (int64_t)fb * d.a_scale_ld : nullptr;
+    const int b2off = __builtin_amdgcn_readfirstlane(fb * (int)d.bias2_fs);      // bias2_fs: one vector per frame, 0 = shared (B * bias2_fs < 2^31: launcher)
 #pragma unroll
     for (int j = 0; j < TN; ++j)
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         const int n = cbase[j] + 8 * q;
         const f32x4 b1 = ld4(d.bias, n, d.N);
-        const f32x4 b2 = with_b2 ? ld4(d.bias2, n, d.N) : f32x4{0.f, 0.f, 0.f, 0.f};
+        const f32x4 b2 = with_b2 ? ld4(d.bias2 ? d.bias2 + b2off : nullptr, n, d.N) : f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int i = 0; i < TM; ++i) {
           f32x4 v = grp(i, j, q) + b1;

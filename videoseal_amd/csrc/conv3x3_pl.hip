@@ -411,6 +411,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_pl_kernel(const vs_conv_desc_t
   const bool full = n0 + BN <= d.N;
   if (sk == 1) {   // v = act(acc (+ border-class table) + bias1) (+ bias2: the activation sits between the two K phases)
     const float* tb = (d.tile_hint & VS_CONV_PRE) ? d.a_scale + (int64_t)fb * d.a_scale_ld : nullptr;
+    const int64_t b2off = (int64_t)fb * d.bias2_fs;                  // bias2_fs: one vector per frame, 0 = shared
     if (full && d.bias && (n2 == 0 || d.bias2)) {
       // three passes over the register tile -- + bias1 (+ table), activation, + bias2 -- with the switch on d.act around the whole second
       // pass: a switch per element made the section ~100 tiny basic blocks (hipcc's wait-count bookkeeping gives up across them)
@@ -450,7 +451,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_pl_kernel(const vs_conv_desc_t
       for (int j = 0; j < TN; ++j) {
         f32x4 b2[4];
 #pragma unroll
-        for (int q = 0; q < 4; ++q) b2[q] = n2 > 0 ? *reinterpret_cast<const f32x4*>(d.bias2 + cbase[j] + 8 * q) : f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int q = 0; q < 4; ++q) b2[q] = n2 > 0 ? *reinterpret_cast<const f32x4*>(d.bias2 + b2off + cbase[j] + 8 * q) : f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int q = 0; q < 4; ++q)
 #pragma unroll
@@ -463,7 +464,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_pl_kernel(const vs_conv_desc_t
       for (int q = 0; q < 4; ++q) {
         const int n = cbase[j] + 8 * q;
         const f32x4 b1 = ld4(d.bias, n, d.N);
-        const f32x4 b2 = n2 > 0 ? ld4(d.bias2, n, d.N) : f32x4{0.f, 0.f, 0.f, 0.f};
+        const f32x4 b2 = n2 > 0 ? ld4(d.bias2 ? d.bias2 + b2off : nullptr, n, d.N) : f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int i = 0; i < TM; ++i) {
           f32x4 v = grp(i, j, q) + b1;

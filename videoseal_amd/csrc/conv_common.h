@@ -237,6 +237,37 @@ __device__ __forceinline__ void write_sumsq(const f32x16 (&acc)[TM][TN], float* 
     }
 }
 
+// Per-frame bias (vs_conv_desc_t::bias_fs != 0): acc[row][col] += bias[(row / HW) * fs + col] on a register tile in the C layout above, in front of
+// apply_act_all with a zero b1 -- the same `acc + bias` per element as the shared vector.  A wave whose rows lie in one frame (every shipped
+// shape) adds one value per column; a wave that straddles frames looks every row's frame up.  Rows >= M take the last frame (never stored).
+template <int TM, int TN>
+__device__ __forceinline__ void add_frame_bias(f32x16 (&acc)[TM][TN], const float* bias, const int64_t fs, const int HW, const int64_t mrow0,
+                                               const int M, const int (&col)[TN], const int g, const int N) {
+  const int last = M - 1;
+  const int m_lo = (int)min(mrow0, (int64_t)last), m_hi = (int)min(mrow0 + TM * 32 - 1, (int64_t)last);
+  const int f_lo = m_lo / HW, f_hi = m_hi / HW;              // wave-uniform
+  if (f_lo == f_hi) {
+#pragma unroll
+    for (int j = 0; j < TN; ++j) {
+      const float b = col[j] < N ? bias[(int64_t)f_lo * fs + col[j]] : 0.f;
+#pragma unroll
+      for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) acc[i][j][e] += b;
+    }
+    return;
+  }
+#pragma unroll
+  for (int i = 0; i < TM; ++i)
+#pragma unroll
+    for (int e = 0; e < 16; ++e) {
+      const int m = (int)min(mrow0 + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * g, (int64_t)last);
+      const float* bf = bias + (int64_t)(m / HW) * fs;
+#pragma unroll
+      for (int j = 0; j < TN; ++j) acc[i][j][e] += col[j] < N ? bf[col[j]] : 0.f;
+    }
+}
+
 // The same statistics for frames whose row count HW is NOT a multiple of 32 (ChunkySeal: 31 x 31 = 961): a 32-row group may then straddle two
 // frames (never three: HW >= 32), so every group writes TWO sums -- slot 0: its rows inside the frame f0 its first row lies in, slot 1: its rows in
 // frame f0 + 1.  part is [ceil(M / 32)][2][N]; vs_grn_scale_from_straddle_partials adds, per frame, the slots that belong to it in ascending

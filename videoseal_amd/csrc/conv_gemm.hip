@@ -35,9 +35,14 @@ namespace {
 
 using namespace vsconv;
 
-// NPL: 0 = f32 MFMA, 3 = "3 x bf16", 2 = "2 x f16" (conv_common.h, Arith<NP>)
-template <int WM, int WN, int TM, int TN, int NPL>
+// NPLF & 7 = NPL: 0 = f32 MFMA, 3 = "3 x bf16", 2 = "2 x f16" (conv_common.h, Arith<NP>); NPLF & FRAME_BIAS: the instantiations that take one bias
+// vector per frame (vs_conv_desc_t::bias_fs; 1x1 GEMMs whose spatially constant input channels arrive as a vector) -- their own instantiations, so
+// that the others compile to what they always were (one more template parameter would rename them for tools and the codegen ratchet)
+constexpr int FRAME_BIAS = 8;
+template <int WM, int WN, int TM, int TN, int NPLF>
 __global__ __launch_bounds__(NT, (TM * TN > 4 ? 1 : 2)) void conv_gemm_kernel(const vs_conv_desc_t d, const int M, const int mtiles) {
+  constexpr int NPL = NPLF & 7;
+  constexpr bool FB = (NPLF & FRAME_BIAS) != 0;
   constexpr bool SPLIT = NPL != 0;
   using AR = Arith<SPLIT ? NPL : 3>;
   constexpr int BM = WM * TM * 32;
@@ -262,7 +267,7 @@ __global__ __launch_bounds__(NT, (TM * TN > 4 ? 1 : 2)) void conv_gemm_kernel(co
   for (int j = 0; j < TN; ++j) {
     col[j] = n0 + (wn * TN + j) * 32 + r;
     const bool ok = col[j] < d.N;
-    bias1[j] = (ok && d.bias) ? d.bias[col[j]] : 0.f;
+    bias1[j] = (!FB && ok && d.bias) ? d.bias[col[j]] : 0.f;     // (FB: one vector per frame, added by add_frame_bias below)
     bias2[j] = (ok && d.bias2) ? d.bias2[col[j]] : 0.f;
   }
 
@@ -356,6 +361,8 @@ __global__ __launch_bounds__(NT, (TM * TN > 4 ? 1 : 2)) void conv_gemm_kernel(co
     float zero[TN];
 #pragma unroll
     for (int j = 0; j < TN; ++j) zero[j] = 0.f;
+    // one bias vector per frame (the launcher admits it without a second phase only): bias1 is zero then
+    if constexpr (FB) add_frame_bias<TM, TN>(acc, d.bias, d.bias_fs, d.Ho * d.Wo, m0 + (int64_t)wm * TM * 32, M, col, g, d.N);
     apply_act_all<TM, TN>(acc, bias1, zero, d.act);
   }
   if (d.sumsq_part) write_sumsq<TM, TN>(acc, d.sumsq_part, d.N, m0 + (int64_t)wm * TM * 32, M, col, g);
@@ -476,10 +483,17 @@ static int gemm_planes(const vs_conv_desc_t& d, int tile, hipStream_t st) {
 
 extern "C" int vs_conv_gemm(const vs_conv_desc_t* dp, void* stream) {
   VS_REQUIRE(dp);
+  // Per-frame bias vectors (bias_fs / bias2_fs).  A kernel that does not index its bias by frame must refuse instead of reading frame 0's vector for every row
+  const bool fs1 = dp->bias_fs != 0, fs2 = dp->bias2_fs != 0, fs_any = fs1 || fs2;
+  if (fs1) VS_REQUIRE(dp->bias && dp->bias_fs >= dp->N && dp->bias_fs % 4 == 0);
+  if (fs2) VS_REQUIRE(dp->bias2 && dp->bias2_fs >= dp->N && dp->bias2_fs % 4 == 0 && (int64_t)dp->B * dp->bias2_fs < (1LL << 31));
   {
     const int t = vs_tile_code(dp->tile_hint);
-    if (t == 22 || t == 23) return conv_planes(*dp, t, (hipStream_t)stream);
-    if (t == 24 || t == 25 || t == 27) return gemm_planes(*dp, t, (hipStream_t)stream);
+    if (t == 22 || t == 23) {
+      if (fs1 && dp->split_k <= 1) return VS_ERR_UNSUPPORTED;         // (the kernel's own epilogue takes bias2 per frame; the K-slice epilogue both)
+      return conv_planes(*dp, t, (hipStream_t)stream);
+    }
+    if (t == 24 || t == 25 || t == 27) return fs_any ? VS_ERR_UNSUPPORTED : gemm_planes(*dp, t, (hipStream_t)stream);
   }
   VS_REQUIRE(dp->in && dp->wt && dp->out);
   const vs_conv_desc_t& d = *dp;
@@ -514,6 +528,7 @@ extern "C" int vs_conv_gemm(const vs_conv_desc_t* dp, void* stream) {
   if (pre_add) VS_REQUIRE(patch_ok && (tile == 15 || tile == 16));
   if (tile >= 10 && tile <= 12) {
     VS_REQUIRE(patch_ok);
+    if (fs_any) return VS_ERR_UNSUPPORTED;
     return vs_conv3x3_patch_dispatch(d, tile, st);
   }
   VS_REQUIRE(d.arith == 0 || d.arith == 2 || d.arith == 3);
@@ -521,13 +536,14 @@ extern "C" int vs_conv_gemm(const vs_conv_desc_t* dp, void* stream) {
   if (tile == 15 || tile == 16 || tile == 19 || tile == 21) {   // wave-specialised patch kernel
     VS_REQUIRE(patch_ok && d.wt_blk && (!d.in2 || d.wt2_blk) && ((uintptr_t)d.wt_blk & 15) == 0);
     if (d.split_k > 1) VS_REQUIRE(d.splitk_ws && d.splitk_ld >= d.N && d.split_k <= d.CinP / 16 && !d.sumsq_part);
-    if (!pc_vec_ok(d)) return VS_ERR_UNSUPPORTED;
+    if (!pc_vec_ok(d) || fs1) return VS_ERR_UNSUPPORTED;             // (bias2 per frame: the kernel's own epilogue and the K-slice epilogue)
     return vs_conv3x3_patch_pc_dispatch(d, tile, st);
   }
   // thin full-resolution layers (16 input channels, <= 32 outputs): persistent kernel with the weights in registers
   const bool small_ok = patch_ok && vs_conv_small_shape(d);
   if (tile == 20) {
     VS_REQUIRE(small_ok);
+    if (fs_any) return VS_ERR_UNSUPPORTED;
     return vs_conv3x3_small_dispatch(d, st);
   }
   if (vs_tile_is_gemm_pc(tile)) {   // wave-specialised 1x1 GEMM: dense rows, whole 32-wide K pairs, no second phase
@@ -536,10 +552,13 @@ extern "C" int vs_conv_gemm(const vs_conv_desc_t* dp, void* stream) {
     VS_REQUIRE(vs_conv_gemm_pc_shape(d));
     if (d.sumsq_part) VS_REQUIRE(d.split_k <= 1 && !d.res);
     if (d.split_k > 1) VS_REQUIRE(d.splitk_ws && d.splitk_ld >= d.N && d.split_k <= d.CinP / 32);
+    if (fs2) return VS_ERR_UNSUPPORTED;                  // (no second phase here; bias_fs: launch_g)
     return vs_gemm1x1_pc_dispatch(d, tile, st);
   }
   VS_REQUIRE(d.split_k <= 1);
   if (d.sumsq_part) VS_REQUIRE(d.KH == 1 && d.KW == 1 && !d.in2 && !d.res && !patch_ok);
+  // what is left: the 3x3 kernels chosen unasked (none takes a per-frame vector: the caller names tile 15 / 16 for bias2) and the generic kernel (bias_fs without a second phase)
+  if (fs2 || (fs1 && d.in2) || (fs_any && tile == 0 && patch_ok && (vs_conv_patch_frames(d) || (small_ok && !d.in2)))) return VS_ERR_UNSUPPORTED;
   if (tile == 0 && small_ok && !d.in2) return vs_conv3x3_small_dispatch(d, st);   // (with the fused 1x1 the patch kernel is as fast)
   if (tile == 0 && patch_ok && vs_conv_patch_frames(d)) {
     const bool blk_ok = d.wt_blk && (!d.in2 || d.wt2_blk) && ((uintptr_t)d.wt_blk & 15) == 0;
@@ -551,7 +570,7 @@ extern "C" int vs_conv_gemm(const vs_conv_desc_t* dp, void* stream) {
     // static choice (no tuner: model-level C API, hipGraph capture, VIDEOSEAL_AUTOTUNE=0), following what the tuner measures on
     // the benchmark shapes: deep-K 1x1 GEMMs on the wave-specialised kernel, shallow-K ones on 128x128 generic tiles
     const bool gemm_ok = can_split0 && d.wt_blk && ((uintptr_t)d.wt_blk & 15) == 0 && !(d.tile_hint & VS_CONV_FORCE_F32) &&
-                         vs_conv_gemm_pc_shape(d) && !(d.sumsq_part && d.res) &&
+                         vs_conv_gemm_pc_shape(d) && !(d.sumsq_part && d.res) && (!fs1 || (d.H * d.W) % 128 == 0) &&
                          (!d.a_scale || (int64_t)((d.CinP / 32 + std::max(1, d.split_k) - 1) / std::max(1, d.split_k)) * 32 <= VS_GRN_SLICE_K);
     if (gemm_ok && d.CinP >= 384 && d.N > 128 && !(d.act == VS_ACT_TANH && d.split_k <= 1)) return vs_gemm1x1_pc_dispatch(d, 18, st);      // (tile 18 has no tanh epilogue)
     if (d.KH == 1 && d.KW == 1 && d.CinP < 384 && d.N >= 256) tile = 1;
@@ -570,6 +589,10 @@ extern "C" int vs_conv_gemm(const vs_conv_desc_t* dp, void* stream) {
   if (tile >= 6 && tile <= 9) return VS_ERR_UNSUPPORTED;   // (codes of a retired generic producer/consumer kernel)
   const bool can_split = d.wt_split && (!d.in2 || d.wt2_split) && ((uintptr_t)d.wt_split & 15) == 0;
   if (d.tile_hint & VS_CONV_FORCE_SPLIT) VS_REQUIRE(can_split);
+  if (fs1) {
+    if (can_split && !(d.tile_hint & VS_CONV_FORCE_F32)) return d.arith == 2 ? dispatch<2 | FRAME_BIAS>(d, tile, st) : dispatch<3 | FRAME_BIAS>(d, tile, st);
+    return dispatch<FRAME_BIAS>(d, tile, st);
+  }
   if (can_split && !(d.tile_hint & VS_CONV_FORCE_F32)) return d.arith == 2 ? dispatch<2>(d, tile, st) : dispatch<3>(d, tile, st);
   return dispatch<0>(d, tile, st);
 }

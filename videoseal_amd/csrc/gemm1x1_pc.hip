@@ -474,9 +474,11 @@ __device__ __forceinline__ void gemm1x1_pc_tile(const vs_conv_desc_t& d, const i
   const bool sk = d.split_k > 1;
   if (!sk) {
     float bias1[TN], zero[TN];
+    // bias_fs: one bias vector per frame; the launcher admits only frames of whole 128-row tiles, so a workgroup's rows share one (uniform) vector
+    const float* const bp = d.bias_fs ? d.bias + (int64_t)(m0 / (d.H * d.W)) * d.bias_fs : d.bias;
 #pragma unroll
     for (int j = 0; j < TN; ++j) {
-      bias1[j] = (col[j] < d.N && d.bias) ? d.bias[col[j]] : 0.f;
+      bias1[j] = (col[j] < d.N && d.bias) ? bp[col[j]] : 0.f;
       zero[j] = 0.f;
     }
     const int abl = VS_KERNEL_ABL(d);       // ablations (tools/bench_gemm.py ksweep): 64 no activation, 32 no output stores
@@ -514,6 +516,9 @@ __global__ __launch_bounds__(256) void splitk_epilogue_kernel(const vs_conv_desc
   const int n4 = (int)(idx % ncol4) * 4;
   float v[4] = {0.f, 0.f, 0.f, 0.f};
   const bool full = n4 + 4 <= d.N;
+  const int64_t fr = (d.bias_fs | d.bias2_fs) ? m / ((int64_t)d.Ho * d.Wo) : 0;       // per-frame bias vectors (frame strides, 0 = shared)
+  const float* const bias = d.bias ? d.bias + fr * d.bias_fs : nullptr;
+  const float* const bias2 = d.bias2 ? d.bias2 + fr * d.bias2_fs : nullptr;
   if (full) {            // splitk_ld % 4 == 0 and the workspace is 16-byte aligned (checked by the launcher)
     for (int k = 0; k < d.split_k; ++k) {
       const f32x4 t = *reinterpret_cast<const f32x4*>(d.splitk_ws + ((int64_t)k * M + m) * d.splitk_ld + n4);
@@ -529,11 +534,11 @@ __global__ __launch_bounds__(256) void splitk_epilogue_kernel(const vs_conv_desc
   for (int c = 0; c < 4; ++c) {
     const int n = n4 + c;
     if (n >= d.N) { v[c] = 0.f; continue; }
-    float t = v[c] + (d.bias ? d.bias[n] : 0.f);
+    float t = v[c] + (bias ? bias[n] : 0.f);
     if (d.act == VS_ACT_RELU) t = vs_relu(t);
     else if (d.act == VS_ACT_GELU) t = vs_gelu(t);
     else if (d.act == VS_ACT_TANH) t = tanhf(t);
-    if (d.in2 || d.in2_pl) t += d.splitk_ws[((int64_t)d.split_k * M + m) * d.splitk_ld + n] + (d.bias2 ? d.bias2[n] : 0.f);
+    if (d.in2 || d.in2_pl) t += d.splitk_ws[((int64_t)d.split_k * M + m) * d.splitk_ld + n] + (bias2 ? bias2[n] : 0.f);
     if (d.res) t += d.res[m * d.res_ld + n];
     v[c] = t;
   }
@@ -577,24 +582,27 @@ __global__ __launch_bounds__(256) void splitk_epilogue_vec_kernel(const vs_conv_
   const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
   f32x4 bv = z4, b2v = z4, p2 = z4, rv = z4;
   f32x4 v = z4;
+  const int64_t fr = (d.bias_fs | d.bias2_fs) ? m / ((int64_t)d.Ho * d.Wo) : 0;       // per-frame bias vectors (frame strides, 0 = shared)
+  const float* const bias = d.bias ? d.bias + fr * d.bias_fs : nullptr;
+  const float* const bias2 = d.bias2 ? d.bias2 + fr * d.bias2_fs : nullptr;
   if constexpr (SK > 0) {
     f32x4 t[SK];
 #pragma unroll
     for (int k = 0; k < SK; ++k) t[k] = *reinterpret_cast<const f32x4*>(w0 + k * sstride);
-    if (d.bias) bv = *reinterpret_cast<const f32x4*>(d.bias + n4);
+    if (bias) bv = *reinterpret_cast<const f32x4*>(bias + n4);
     if (two) {
       p2 = *reinterpret_cast<const f32x4*>(w0 + SK * sstride);
-      if (d.bias2) b2v = *reinterpret_cast<const f32x4*>(d.bias2 + n4);
+      if (bias2) b2v = *reinterpret_cast<const f32x4*>(bias2 + n4);
     }
     if (d.res) rv = *reinterpret_cast<const f32x4*>(d.res + m * d.res_ld + n4);
 #pragma unroll
     for (int k = 0; k < SK; ++k) v += t[k];
   } else {
     const int sk = d.split_k;
-    if (d.bias) bv = *reinterpret_cast<const f32x4*>(d.bias + n4);
+    if (bias) bv = *reinterpret_cast<const f32x4*>(bias + n4);
     if (two) {
       p2 = *reinterpret_cast<const f32x4*>(w0 + sk * sstride);
-      if (d.bias2) b2v = *reinterpret_cast<const f32x4*>(d.bias2 + n4);
+      if (bias2) b2v = *reinterpret_cast<const f32x4*>(bias2 + n4);
     }
     if (d.res) rv = *reinterpret_cast<const f32x4*>(d.res + m * d.res_ld + n4);
     int k = 0;
@@ -642,6 +650,7 @@ int launch_g(const vs_conv_desc_t& d, hipStream_t st) {
   if (d.grn_part && (!d.a_scale || !d.grn_gamma || d.grn_nchunk < 1 || d.grn_nchunk > 16 || d.grn_nchunk * 32 != d.H * d.W)) return VS_ERR_BAD_ARG;
   if (mt * nt * sk > 0x7fffffffLL || M > 0x7fffffffLL) return VS_ERR_UNSUPPORTED;
   if (TN * WN >= 6 && sk == 1 && d.act == VS_ACT_TANH) return VS_ERR_UNSUPPORTED;      // (the 128 x 192 register tile is compiled without the tanh epilogue)
+  if (d.bias_fs && sk == 1 && (d.H * d.W) % BM) return VS_ERR_UNSUPPORTED;             // (per-frame bias: one vector per 128-row tile; K slices: any frame size)
   // store_tile_full / store_tile_guarded address a tile with 32-bit byte offsets from its first element (conv_gemm.hip / gemm_pl.hip check the
   // same bound and keep a 64-bit path; this kernel has only the 32-bit one)
   if ((int64_t)BM * std::max<int64_t>(std::max<int64_t>(d.out_ld, d.res ? d.res_ld : 0), sk > 1 ? d.splitk_ld : 0) * 4 >= (1LL << 31)) return VS_ERR_UNSUPPORTED;

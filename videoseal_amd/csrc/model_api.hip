@@ -50,6 +50,12 @@ struct vs_model {
   std::vector<RB> down_rb, bottleneck;
   CW b0_lat, b0_msg;             // first bottleneck block with the message channels as a border-class table (engine.py::resblock_msg0)
   bool b0_table = false;
+  // engine.py::_msg_vectors_pack: the pointwise consumers of the message channels take them as one vector per message -- b0_msg carries the
+  // rows of res_conv's message columns (+ res_conv.bias) at msgv_off_res and of the first Upsample GEMM's message-skip columns (x connect_scale)
+  // at msgv_off_up; b0_res_lat / up0_xl are those layers without the message columns
+  CW b0_res_lat, up0_xl;
+  bool msgv = false;
+  int msgv_off_res = 0, msgv_off_up = 0;
   std::vector<Up> ups;
   float *outc_w = nullptr, *outc_b = nullptr, *table = nullptr;
   // extractor
@@ -230,7 +236,7 @@ struct Packer {
     if (keep_wt) *keep_wt = std::move(wt);
   }
   // engine.py::_pack_embedder (Upsample groups): [Co,Cin,3,3] -> rows (tap, channel) of a 1x1 GEMM on the low-resolution [x | skip] map
-  void upconv9(CW& cw, const std::string& wkey, int cin, int cout) {
+  void upconv9(CW& cw, const std::string& wkey, int cin, int cout, std::vector<float>* keep_wt = nullptr) {
     const HostT& w = get(wkey);
     if (!w.p) return;
     const int cinp = rup(cin, 16);
@@ -240,6 +246,7 @@ struct Packer {
       for (int c = 0; c < cin; ++c)
         for (int t = 0; t < 9; ++t) wt[((size_t)t * cout + o) * cinp + c] = w.p[((size_t)o * cin + c) * 9 + t];
     finish(cw, wt, {}, false);
+    if (keep_wt) *keep_wt = std::move(wt);
   }
   // engine.py::pack_patch_conv: kw pixels of a row are one run of kw*pix_ld floats -> KH x 1 conv with Cin' = kw*pix_ld
   void patch_conv(CW& cw, const std::string& wkey, int cin, int k, int pix_ld, const std::string& bias_key, CW* as_gemm = nullptr) {
@@ -269,7 +276,9 @@ struct Packer {
   }
   // engine.py::resblock_msg0: c0 of the first bottleneck block split into its latent columns (3x3, K = 9*nlat) and the per-tap
   // message columns (rows (tap, n), K = hidden) from the BN-folded packed weight [N][9][cinp]
-  void msg_table_convs(CW& lat, CW& msg, const std::vector<float>& wt, const std::vector<float>& bias, int n, int cinp, int nlat, int hidden) {
+  // extra / extra_bias: further rows [rows][hidden] of the message GEMM behind the 9 n tap rows (engine.py::_msg_vectors_pack)
+  void msg_table_convs(CW& lat, CW& msg, const std::vector<float>& wt, const std::vector<float>& bias, int n, int cinp, int nlat, int hidden,
+                       const std::vector<float>* extra = nullptr, const std::vector<float>* extra_bias = nullptr) {
     std::vector<float> wl((size_t)n * 9 * nlat), wm((size_t)9 * n * hidden);
     for (int o = 0; o < n; ++o)
       for (int t = 0; t < 9; ++t) {
@@ -280,9 +289,18 @@ struct Packer {
     lat.N = n; lat.KH = 3; lat.KW = 3; lat.CinP = nlat;
     finish(lat, wl, bias, true);
     msg.N = 9 * n; msg.KH = 1; msg.KW = 1; msg.CinP = hidden;
+    if (extra) {
+      wm.insert(wm.end(), extra->begin(), extra->end());
+      msg.N += (int)(extra->size() / hidden);
+      std::vector<float> mb((size_t)9 * n, 0.f);
+      mb.insert(mb.end(), extra_bias->begin(), extra_bias->end());
+      finish(msg, wm, mb, true);
+      return;
+    }
     finish(msg, wm, {}, false);
   }
-  void resblock(RB& rb, const std::string& p, int cin, std::vector<float>* keep_c0 = nullptr, std::vector<float>* keep_b0 = nullptr) {   // engine.py::_pack_resblock
+  void resblock(RB& rb, const std::string& p, int cin, std::vector<float>* keep_c0 = nullptr, std::vector<float>* keep_b0 = nullptr,
+                std::vector<float>* keep_res = nullptr) {   // engine.py::_pack_resblock
     const HostT& w0 = get(p + ".double_conv.0.weight");
     if (!w0.p) return;
     const int cout = (int)(w0.n / ((int64_t)cin * 9));
@@ -293,7 +311,7 @@ struct Packer {
     conv(rb.c0, p + ".double_conv.0.weight", cin, 3, 3, rup(cin, 4), &s0, &b0, "", nullptr, keep_c0);
     if (keep_b0) *keep_b0 = b0;
     conv(rb.c1, p + ".double_conv.3.weight", cout, 3, 3, rup(cout, 4), &s1, &b1, "");
-    conv(rb.res, p + ".res_conv.weight", cin, 1, 1, rup(cin, 4), nullptr, nullptr, p + ".res_conv.bias");
+    conv(rb.res, p + ".res_conv.weight", cin, 1, 1, rup(cin, 4), nullptr, nullptr, p + ".res_conv.bias", nullptr, keep_res);
   }
 };
 
@@ -324,6 +342,14 @@ struct Runner {
   bool live() const { return ws && rc == VS_OK; }
   void chk(int code) { if (rc == VS_OK && code != VS_OK) rc = code; }
 
+  // engine.py::conv(bias_frames= / bias2_frames=): one bias vector per frame for the NEXT conv / conv_pl call (taken and cleared by it)
+  const float* fb_bias = nullptr; int64_t fb_bias_fs = 0;
+  const float* fb_bias2 = nullptr; int64_t fb_bias2_fs = 0;
+  void frame_bias(vs_conv_desc_t& d) {
+    if (fb_bias) { d.bias = fb_bias; d.bias_fs = fb_bias_fs; }
+    if (fb_bias2) { d.bias2 = fb_bias2; d.bias2_fs = fb_bias2_fs; }
+    fb_bias = fb_bias2 = nullptr; fb_bias_fs = fb_bias2_fs = 0;
+  }
   // engine.py::conv without the tuner: K slices, the sliced launch's tile and the GRN-finish fold as vs_conv_plan says
   void conv(const Act& x, const CW& w, const Act& out, int stride = 1, int pad = 0, int pad_mode = VS_PAD_ZERO, int act_ = VS_ACT_NONE,
             int out_coff = 0, int n_store = -1, const Act* res = nullptr, const Act* in2 = nullptr, const CW* w2 = nullptr,
@@ -353,6 +379,7 @@ struct Runner {
     d.arith = m->arith; d.a_mul = am; d.acc_mul = 1.f / (am * w.w_mul);
     if (in2) { d.wt2_split = w2->split; d.wt2_blk = w2->blk; d.acc_mul2 = 1.f / (am * w2->w_mul); }
     d.sumsq_part = sumsq;
+    frame_bias(d);
     if (pre_table) d.tile_hint = (d.N % 192 == 0 ? (VS_CONV_TILE_HI | 0) : 15) | VS_CONV_PRE;   // border-class table added before bias + activation (engine.py::resblock_msg0)
     vs_conv_plan_t p;
     chk(vs_conv_plan(&d, grn_part ? grn_hw : 0, grn_c4, &p));
@@ -372,11 +399,15 @@ struct Runner {
   void layernorm(const Act& x, const float* w, const float* b, const Act& out, int act_ = VS_ACT_NONE) {
     if (live()) chk(vs_layernorm_act(x.p, x.rows(), x.C, x.ld, w, b, 1e-6f, act_, out.p, out.ld, st));
   }
-  Act resblock(const Act& x, const RB& p, const Act* out_in = nullptr) {                      // engine.py::resblock
+  bool thin_ok(const Act& x, const RB& p, const Act* out_in) const {                          // engine.py::_thin_ok
     const int tk = p.cout == 16 ? 16 : 32;
-    if ((p.cout == 16 || (p.cout == 32 && m->arith == 2)) && x.ld <= tk && p.c0.CinP == tk && p.c1.CinP == tk && p.res.CinP == tk &&
-        (!out_in || out_in->ld == p.cout) && vs_resblock_thin_supported(x.ld, p.cout, p.cout)) {   // engine.py::resblock_thin: t stays on chip
-      Act out = out_in ? *out_in : act(x.B, x.H, x.W, p.cout);
+    return (p.cout == 16 || (p.cout == 32 && m->arith == 2)) && x.ld <= tk && p.c0.CinP == tk && p.c1.CinP == tk && p.res.CinP == tk &&
+           (!out_in || out_in->ld == p.cout) && vs_resblock_thin_supported(x.ld, p.cout, p.cout);
+  }
+  // delta != nullptr (engine.py::resblock_thin with outc): outc + tanh in the block's epilogue, the block's output is not stored
+  Act resblock(const Act& x, const RB& p, const Act* out_in = nullptr, float* delta = nullptr) {  // engine.py::resblock
+    if (thin_ok(x, p, out_in)) {                                                                   // engine.py::resblock_thin: t stays on chip
+      Act out = delta ? Act{nullptr, x.B, x.H, x.W, p.cout, p.cout} : (out_in ? *out_in : act(x.B, x.H, x.W, p.cout));
       vs_resblock_thin_desc_t d;
       std::memset(&d, 0, sizeof(d));
       d.x = x.p; d.x_ld = x.ld; d.B = x.B; d.H = x.H; d.W = x.W; d.Cin = x.ld;
@@ -384,10 +415,15 @@ struct Runner {
       d.b0 = p.c0.bias; d.b1 = p.c1.bias; d.br = p.res.bias;
       d.arith = m->arith; d.Cout = p.cout; d.a_mul = A_MUL;
       d.acc_mul0 = 1.f / (A_MUL * p.c0.w_mul); d.acc_mul1 = 1.f / (A_MUL * p.c1.w_mul); d.acc_mulr = 1.f / (A_MUL * p.res.w_mul);
-      d.out = out.p; d.out_ld = out.ld;
+      if (delta) {
+        d.outc_w = m->outc_w; d.outc_b = m->outc_b; d.out_ch = m->c.out_ch; d.use_tanh = m->c.last_tanh ? 1 : 0; d.delta = delta;
+      } else {
+        d.out = out.p; d.out_ld = out.ld;
+      }
       if (live()) chk(vs_resblock_thin(&d, st));
       return out;
     }
+    if (delta) { rc = VS_ERR_UNSUPPORTED; return Act{}; }              // (callers ask thin_ok first)
     Act t = act(x.B, x.H, x.W, p.cout);
     conv(x, p.c0, t, 1, 1, VS_PAD_ZERO, VS_ACT_RELU);
     Act out = out_in ? *out_in : act(x.B, x.H, x.W, p.cout);
@@ -429,6 +465,7 @@ struct Runner {
       d.in2_pl = in2_pl; d.Cin2 = d.Cin2P = w2->CinP; d.wt2 = w2->wt; d.bias2 = w2->bias; d.wt2_split = w2->split; d.wt2_blk = w2->blk;
       d.acc_mul2 = 1.f / (A_MUL * w2->w_mul);
     }
+    frame_bias(d);
     d.n_store = w.N;
     if (out) { d.out = out->p; d.out_ld = out->ld; d.n_store = out->ld != rup(w.N, 4) ? w.N : out->ld; }
     d.tile_hint = VS_CONV_TILE_HI | 6;
@@ -458,6 +495,10 @@ struct Runner {
     }
     return out;
   }
+  bool msg_vectors_ok(int B, int H, int W) const {        // engine.py::_msg_vectors_ok (the weight-only part: vs_model_create)
+    const int N = m->bottleneck.empty() ? 0 : m->bottleneck[0].cout;
+    return m->msgv && m->b0_table && N > 0 && W % 16 == 0 && H % 8 == 0 && (int64_t)B * (H / 8) * (W / 16) >= 128;
+  }
   bool planes_ok(const Act& x, int j0) const {            // engine.py::_planes_ok
     if (m->arith != 2 || x.ld != x.C || x.C % 192 || x.H % 16 || x.W % 16 || (int64_t)x.B * (x.H / 16) * (x.W / 16) * (x.C / 192) < 200) return false;
     for (size_t j = j0; j < m->bottleneck.size(); ++j) {
@@ -471,6 +512,9 @@ struct Runner {
     const vs_model_cfg_t& c = m->c;
     const int B = x.B, nlev = (int)m->zc.size() - 1;
     std::vector<Act> hid;
+    bool msgv = false;
+    const float* up0_bias = nullptr;
+    int64_t up0_fs = 0;
     hid.push_back(resblock(x, m->inc));
     for (int i = 0; i < nlev; ++i) {
       const Act src = hid.back();
@@ -478,7 +522,8 @@ struct Runner {
       Act dwn = act(B, Ho, Wo, m->zc[i + 1]);
       conv(src, m->down_conv[i], dwn, 2, 1);
       if (i == nlev - 1) {
-        Act h3 = act(B, Ho, Wo, m->bott);
+        msgv = msg_vectors_ok(B, Ho, Wo);         // engine.py::_msg_vectors_ok: the message channels never become a tensor, h3 = the latent alone
+        Act h3 = act(B, Ho, Wo, msgv ? m->zc.back() : m->bott);
         resblock(dwn, m->down_rb[i], &h3);
         hid.push_back(h3);
       } else {
@@ -488,7 +533,7 @@ struct Runner {
     Act h3 = hid.back();
     float* lat = alloc((int64_t)n_msgs * c.hidden);
     if (live()) chk(vs_msg_latent(m->table, msgs, n_msgs, c.nbits, c.hidden, lat, st));
-    if (live()) chk(vs_broadcast_channels(lat, n_msgs, c.hidden, h3.p, B, h3.H * h3.W, h3.ld, m->zc.back(), st));
+    if (!msgv && live()) chk(vs_broadcast_channels(lat, n_msgs, c.hidden, h3.p, B, h3.H * h3.W, h3.ld, m->zc.back(), st));
     Act cur = h3;
     // Upsample group k on the low-resolution map: its [x | skip] concat buffer is allocated before x's producer runs, so that the
     // producer (last bottleneck block / previous up block) writes columns [0, C) itself (engine.py::embedder_forward)
@@ -508,13 +553,44 @@ struct Runner {
       Act view{};
       const bool direct = j == c.num_blocks - 1 && lowres_cat(0, cur, view);
       const RB& rb = m->bottleneck[j];
+      if (j == 0 && msgv) {                                                      // engine.py::resblock_msg0_vec
+        const int nx = m->b0_msg.N, N = rb.cout, nlat = m->zc.back();
+        Act P = act(n_msgs, 1, 1, nx);
+        conv(Act{lat, n_msgs, 1, 1, c.hidden, c.hidden}, m->b0_msg, P);
+        float* table = alloc((int64_t)n_msgs * 9 * N);
+        if (live()) chk(vs_msg_pre_rows(P.p, nx, n_msgs, N, table, st));
+        const int64_t fs = n_msgs == 1 ? 0 : nx;
+        up0_bias = P.p + m->msgv_off_up; up0_fs = fs;
+        if (!planes_ok(Act{nullptr, B, h3.H, h3.W, N, N}, 1)) {                  // per-conv path: both convs on the wave-specialised kernel, named by tile
+          const int tile = N % 192 == 0 ? (VS_CONV_TILE_HI | 0) : 15;
+          Act t = act(B, h3.H, h3.W, N);
+          conv(h3, m->b0_lat, t, 1, 1, VS_PAD_ZERO, VS_ACT_RELU, 0, -1, nullptr, nullptr, nullptr, table, n_msgs == 1 ? 0 : 9 * (int64_t)N, nullptr,
+               nullptr, nullptr, nlat, true);
+          Act out = act(B, h3.H, h3.W, N);
+          fb_bias2 = P.p + m->msgv_off_res; fb_bias2_fs = fs;
+          conv(t, rb.c1, out, 1, 1, VS_PAD_ZERO, VS_ACT_RELU, 0, -1, nullptr, &h3, &m->b0_res_lat, nullptr, 0, nullptr, nullptr, nullptr, 0, false, 0.f,
+               nullptr, nullptr, 0, 0, tile);
+          cur = out;
+          continue;
+        }
+        void* latpl = alloc(h3.rows() * nlat);
+        void* tpl = alloc(h3.rows() * N);
+        void* xpl = alloc(h3.rows() * N);
+        if (live()) chk(vs_to_planes(h3.p, h3.rows(), nlat, h3.ld, A_MUL, latpl, st));
+        conv_pl(B, h3.H, h3.W, m->b0_lat, latpl, tpl, nullptr, nullptr, nullptr, table, n_msgs == 1 ? 0 : 9 * (int64_t)N);
+        fb_bias2 = P.p + m->msgv_off_res; fb_bias2_fs = fs;                      // res_conv's message part (+ its bias), one vector per frame
+        conv_pl(B, h3.H, h3.W, rb.c1, tpl, xpl, nullptr, &m->b0_res_lat, latpl);
+        cur = Act{nullptr, B, h3.H, h3.W, N, N};
+        cur_pl = xpl;
+        continue;
+      }
       if (j == 0 && !direct && m->b0_table && h3.ld == h3.C && rb.c0.CinP == h3.C && h3.W % 16 == 0 && h3.H % 8 == 0 &&
           (int64_t)B * (h3.H / 8) * (h3.W / 16) >= 128) {                        // engine.py::resblock_msg0
-        const int N9 = m->b0_msg.N, N = rb.cout;
+        const int N9 = m->b0_msg.N, N = rb.cout;             // (N9 > 9 N: the rows of the per-frame vectors, unused on this path)
         Act P = act(n_msgs, 1, 1, N9);
         conv(Act{lat, n_msgs, 1, 1, c.hidden, c.hidden}, m->b0_msg, P);
         float* table = alloc((int64_t)n_msgs * 9 * N);
-        if (live()) chk(vs_msg_pre(P.p, n_msgs, N, table, st));
+        if (live()) chk(vs_msg_pre_rows(P.p, N9, n_msgs, N, table, st));
         const Act nxt{nullptr, B, h3.H, h3.W, N, N};
         if (c.num_blocks > 1 && N == h3.C && m->zc.back() % 16 == 0 && planes_ok(nxt, 1)) {
           // engine.py::resblock_msg0(planes_out=True), round 5: the block on the all-DMA planes kernel, output handed to the chain as planes
@@ -565,7 +641,12 @@ struct Runner {
         Act lc = direct ? Act{cur.p, B, cur.H, cur.W, cur.C + skip.C, cur.ld} : act(B, cur.H, cur.W, cur.C + skip.C);
         if (live()) chk(vs_cat2_scale(direct ? nullptr : cur.p, cur.C, cur.ld, skip.p, skip.C, skip.ld, 0.70710678118654752440f, lc.rows(), lc.p, lc.ld, st));
         Act z = act(B, lc.H, lc.W, 9 * co);
-        conv(lc, up.gemm, z);
+        if (k == 0 && up0_bias) {               // [x | latent skip]: the message-skip columns arrive as one bias vector per frame
+          fb_bias = up0_bias; fb_bias_fs = up0_fs;
+          conv(lc, m->up0_xl, z);
+        } else {
+          conv(lc, up.gemm, z);
+        }
         ln = act(B, 2 * lc.H, 2 * lc.W, co);
         if (live()) chk(vs_upconv_gather_ln(z.p, z.ld, B, lc.H, lc.W, co, up.lnw, up.lnb, 1e-6f, VS_ACT_RELU, ln.p, ln.ld, st));
       } else {
@@ -578,6 +659,13 @@ struct Runner {
       }
       Act view{};
       const bool direct = lowres_cat(k + 1, Act{nullptr, B, ln.H, ln.W, up.rb.cout, 0}, view);
+      if (k == nlev - 1 && !direct && up.rb.cout == 16 && c.out_ch <= 4 && m->zc[0] == 16 && thin_ok(ln, up.rb, nullptr)) {
+        // engine.py: outc + tanh in the last block's epilogue (its 16-channel output was written to be read once); same bits as the two launches
+        float* delta = alloc((int64_t)B * c.out_ch * ln.H * ln.W);
+        resblock(ln, up.rb, nullptr, delta);
+        Sh = ln.H; Sw = ln.W;
+        return delta;
+      }
       cur = resblock(ln, up.rb, direct ? &view : nullptr);
     }
     float* delta = alloc((int64_t)B * c.out_ch * cur.H * cur.W);
@@ -781,15 +869,12 @@ extern "C" int vs_model_create(const vs_model_cfg_t* cfg, const vs_tensor_t* ten
     P.conv(m->down_conv[i], p + ".down.weight", m->zc[i], 3, 3, rup(m->zc[i], 4), nullptr, nullptr, p + ".down.bias");
     P.resblock(m->down_rb[i], p + ".conv", m->zc[i + 1]);
   }
+  std::vector<float> w0, b0, wres0, wup0;             // packed host weights of the layers that read the message channels
+  const int nlat = m->zc.back(), hidden = cfg->hidden;
   for (int j = 0; j < cfg->num_blocks; ++j) {
-    std::vector<float> w0, b0;
-    const int nlat = m->zc.back(), hidden = cfg->hidden;
     const bool table = j == 0 && nlat % 16 == 0 && hidden % 32 == 0 && m->bott % 16 == 0;
-    P.resblock(m->bottleneck[j], u + ".bottleneck.model." + std::to_string(j), m->bott, table ? &w0 : nullptr, table ? &b0 : nullptr);
-    if (table && !w0.empty() && m->bottleneck[0].cout >= 128) {
-      P.msg_table_convs(m->b0_lat, m->b0_msg, w0, b0, m->bottleneck[0].cout, m->bottleneck[0].c0.CinP, nlat, hidden);
-      m->b0_table = true;
-    }
+    P.resblock(m->bottleneck[j], u + ".bottleneck.model." + std::to_string(j), m->bott, table ? &w0 : nullptr, table ? &b0 : nullptr,
+               table ? &wres0 : nullptr);
   }
   std::vector<int> zz(m->zc.begin(), m->zc.end() - 1);
   zz.push_back(m->bott);
@@ -798,11 +883,43 @@ extern "C" int vs_model_create(const vs_model_cfg_t* cfg, const vs_tensor_t* ten
     const int cin = 2 * zz[i + 1], cout = zz[i];
     const std::string p = u + ".ups." + std::to_string(k);
     m->ups[k].lowres = vs_upconv_supported(cout) != 0;
-    if (m->ups[k].lowres) P.upconv9(m->ups[k].gemm, p + ".up.upsample_block.2.weight", cin, cout);
+    if (m->ups[k].lowres) P.upconv9(m->ups[k].gemm, p + ".up.upsample_block.2.weight", cin, cout, k == 0 ? &wup0 : nullptr);
     else P.conv(m->ups[k].conv, p + ".up.upsample_block.2.weight", cin, 3, 3, rup(cin, 4), nullptr, nullptr, "");
     m->ups[k].lnw = P.vec(p + ".up.upsample_block.3.weight");
     m->ups[k].lnb = P.vec(p + ".up.upsample_block.3.bias");
     P.resblock(m->ups[k].rb, p + ".conv", cout);
+  }
+  if (!w0.empty() && m->bottleneck[0].cout >= 128) {
+    const RB& rb0 = m->bottleneck[0];
+    const int n = rb0.cout;
+    const HostT& bres = P.get(u + ".bottleneck.model.0.res_conv.bias");
+    const CW* gm = nlev > 0 && m->ups[0].lowres ? &m->ups[0].gemm : nullptr;
+    // engine.py::_msg_vectors_ok, the part that depends on the weights alone
+    if (cfg->num_blocks > 1 && gm && !wres0.empty() && !wup0.empty() && bres.p && bres.n == n && n == m->bott && n % 192 == 0 && rb0.res.CinP == m->bott &&
+        gm->CinP == n + m->bott && (n + nlat) % 32 == 0 && gm->N % 4 == 0) {
+      const int cx = gm->CinP - nlat - hidden, nu = gm->N;
+      std::vector<float> extra((size_t)(n + nu) * hidden), eb((size_t)n + nu, 0.f), wrl((size_t)n * nlat), wxl((size_t)nu * (cx + nlat));
+      for (int o = 0; o < n; ++o) {
+        const float* src = &wres0[(size_t)o * rb0.res.CinP];
+        std::copy(src, src + nlat, &wrl[(size_t)o * nlat]);
+        std::copy(src + nlat, src + nlat + hidden, &extra[(size_t)o * hidden]);
+        eb[o] = bres.p[o];
+      }
+      for (int o = 0; o < nu; ++o) {
+        const float* src = &wup0[(size_t)o * gm->CinP];
+        std::copy(src, src + cx + nlat, &wxl[(size_t)o * (cx + nlat)]);
+        for (int c = 0; c < hidden; ++c) extra[(size_t)(n + o) * hidden + c] = src[cx + nlat + c] * 0.70710678118654752440f;
+      }
+      P.msg_table_convs(m->b0_lat, m->b0_msg, w0, b0, n, rb0.c0.CinP, nlat, hidden, &extra, &eb);
+      m->b0_res_lat.N = n; m->b0_res_lat.KH = m->b0_res_lat.KW = 1; m->b0_res_lat.CinP = nlat;
+      P.finish(m->b0_res_lat, wrl, {}, false);
+      m->up0_xl.N = nu; m->up0_xl.KH = m->up0_xl.KW = 1; m->up0_xl.CinP = cx + nlat;
+      P.finish(m->up0_xl, wxl, {}, false);
+      m->msgv = true; m->msgv_off_res = 9 * n; m->msgv_off_up = 10 * n;
+    } else {
+      P.msg_table_convs(m->b0_lat, m->b0_msg, w0, b0, n, rb0.c0.CinP, nlat, hidden);
+    }
+    m->b0_table = true;
   }
   m->outc_w = P.vec(u + ".outc.weight");
   m->outc_b = P.vec(u + ".outc.bias");

@@ -54,15 +54,26 @@ struct RbArgs {
   float a_mul, acc_mul0, acc_mul1, acc_mulr;
   float* out; int64_t out_ld;
 };
+struct OutcArgs { const float *w, *b; int out_ch, use_tanh; float* delta; };      // OUTC form: [out_ch][16], [out_ch], planar [B][out_ch][H][W]
 
 __device__ __forceinline__ bf16x8 zero_frag() {
   const u32x4 z = {0u, 0u, 0u, 0u};
   return __builtin_bit_cast(bf16x8, z);
 }
 
-template <int NP, int NBUF, int OCC>
-__global__ __launch_bounds__(256, OCC) void resblock_thin_kernel(const RbArgs d, const int tiles_x, const int tiles_y, const int ntiles_total,
-                                                                 const int tiles_per_wg) {
+// OUTC: the U-Net's last layer (`outc`: 1x1, 16 -> out_ch <= 4, + tanh; outc_tanh_kernel of net_ops.hip) in the block's epilogue.  The block's own
+// output is not stored (134 MB written to be read once, 32 x 256^2): after v = relu(..) + res a pixel's 16 channels sit in lanes n, n + 16, n + 32,
+// n + 48 (four each).  An output channel's sum is handed from lane group to lane group (three cross-lane moves), each group adding its four
+// channels, which is exactly the order of outc_tanh_kernel (channels ascending, fused multiply-add from 0, then bias, then tanhf) -> the same bits
+// as the two launches.  The last group stores: 16 consecutive pixels of one plane of delta = 64 contiguous bytes per row group and output channel.
+// Tile, buffers and barriers are those of the plain form.
+// FORM = workgroups per CU the kernel is built for (+ OUTC_FORM for the epilogue above: one more template parameter would rename the plain
+// instantiations, which tools and the codegen ratchet know by name)
+constexpr int OUTC_FORM = 16;
+template <int NP, int NBUF, int FORM>
+__global__ __launch_bounds__(256, FORM & 15) void resblock_thin_kernel(const RbArgs d, const int tiles_x, const int tiles_y, const int ntiles_total,
+                                                                       const int tiles_per_wg, const OutcArgs oc) {
+  constexpr bool OUTC = (FORM & OUTC_FORM) != 0;
   using AR = Arith<NP>;
   using A16 = Arith16<NP>;
   constexpr int XP_BYTES = NP * X_PX * ROWB16;                         // one patch buffer
@@ -104,6 +115,16 @@ __global__ __launch_bounds__(256, OCC) void resblock_thin_kernel(const RbArgs d,
     b0v[e] = d.b0 ? d.b0[4 * kb + e] : 0.f;
     b1v[e] = d.b1 ? d.b1[4 * kb + e] : 0.f;
     brv[e] = d.br ? d.br[4 * kb + e] : 0.f;
+  }
+  // OUTC: this lane's four input channels 4 kb + e of every output channel o of `outc` ([out_ch][16])
+  float ow[OUTC ? 4 : 1][4], ob[OUTC ? 4 : 1];
+  if constexpr (OUTC) {
+#pragma unroll
+    for (int o = 0; o < 4; ++o) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) ow[o][e] = o < oc.out_ch ? oc.w[o * 16 + 4 * kb + e] : 0.f;
+      ob[o] = o < oc.out_ch ? oc.b[o] : 0.f;
+    }
   }
 
   // ---- patch items of this thread (positions relative to the tile origin are constant)
@@ -247,7 +268,33 @@ __global__ __launch_bounds__(256, OCC) void resblock_thin_kernel(const RbArgs d,
         for (int q = 0; q < AR::NPROD; ++q) accr = A16::mfma(wrf[AR::PB[q]], xf[AR::PA[q]], accr);
       }
       const int y = y0 + wave * G1_PER_WAVE + gi, x = x0 + n;
-      if (y < d.H && x < d.W) {
+      if constexpr (OUTC) {
+        f32x4 v;                                  // every lane computes and takes part in the gather (pixels outside the image: values unused)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const float a = NP == 2 ? acc[e] * am1 : acc[e];
+          const float r = NP == 2 ? accr[e] * amr : accr[e];
+          v[e] = vs_relu(a + b1v[e]) + (r + brv[e]);
+        }
+        const bool st = kb == 3 && y < d.H && x < d.W;
+#pragma unroll
+        for (int o = 0; o < 4; ++o) {
+          if (o >= oc.out_ch) break;                 // (uniform)
+          // the sum walks the lane groups: group s continues the chain of group s - 1 with its channels 4 s .. 4 s + 3; lanes of other groups
+          // compute values nobody uses.  Three cross-lane moves per output channel, the result ends in group 3.
+          float a = 0.f;
+#pragma unroll
+          for (int s = 0; s < 4; ++s) {
+            float t = s == 0 ? 0.f : __shfl_up(a, 16, 64);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) t = __builtin_fmaf(v[e], ow[o][e], t);
+            a = kb == s ? t : a;
+          }
+          a += ob[o];
+          if (oc.use_tanh) a = tanhf(a);
+          if (st) oc.delta[(((int64_t)fb * oc.out_ch + o) * d.H + y) * d.W + x] = a;
+        }
+      } else if (y < d.H && x < d.W) {
         f32x4 v;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
@@ -504,14 +551,24 @@ extern "C" int vs_resblock_thin_supported(int cin_ld, int cmid, int cout) {
 }
 
 extern "C" int vs_resblock_thin(const vs_resblock_thin_desc_t* d, void* stream) {
-  VS_REQUIRE(d && d->x && d->out && d->w0_split && d->w1_split && d->wr_split && d->B > 0 && d->H > 0 && d->W > 0);
+  VS_REQUIRE(d && d->x && d->w0_split && d->w1_split && d->wr_split && d->B > 0 && d->H > 0 && d->W > 0);
   const int C = d->Cout == 32 ? 32 : 16;
   VS_REQUIRE(d->Cout == 0 || d->Cout == 16 || d->Cout == 32);
-  VS_REQUIRE(vs_resblock_thin_supported(d->Cin, C, C) && d->x_ld >= d->Cin && (d->x_ld & 3) == 0 && d->out_ld >= C && (d->out_ld & 3) == 0);
+  // outc epilogue (delta set): the block's own output is not stored, `out` is ignored.  16 channels only.
+  const bool outc = d->delta != nullptr;
+  if (outc) {
+    VS_REQUIRE(d->outc_w && d->outc_b && d->out_ch >= 1 && ((uintptr_t)d->delta & 3) == 0);
+    if (C != 16 || d->out_ch > 4) return VS_ERR_UNSUPPORTED;
+  } else {
+    VS_REQUIRE(d->out && !d->outc_w && !d->outc_b && d->out_ch == 0 && d->out_ld >= C && (d->out_ld & 3) == 0 && ((uintptr_t)d->out & 15) == 0);
+  }
+  VS_REQUIRE(vs_resblock_thin_supported(d->Cin, C, C) && d->x_ld >= d->Cin && (d->x_ld & 3) == 0);
   VS_REQUIRE(d->arith == 2 || (d->arith == 3 && C == 16));
-  VS_REQUIRE((((uintptr_t)d->x | (uintptr_t)d->out | (uintptr_t)d->w0_split | (uintptr_t)d->w1_split | (uintptr_t)d->wr_split) & 15) == 0);
+  VS_REQUIRE((((uintptr_t)d->x | (uintptr_t)d->w0_split | (uintptr_t)d->w1_split | (uintptr_t)d->wr_split) & 15) == 0);
   RbArgs a{d->x, (int64_t)d->H * d->W * d->x_ld, (int64_t)d->W * d->x_ld, d->x_ld, d->B, d->H, d->W, d->Cin,
-           d->w0_split, d->w1_split, d->wr_split, d->b0, d->b1, d->br, d->a_mul, d->acc_mul0, d->acc_mul1, d->acc_mulr, d->out, d->out_ld};
+           d->w0_split, d->w1_split, d->wr_split, d->b0, d->b1, d->br, d->a_mul, d->acc_mul0, d->acc_mul1, d->acc_mulr,
+           outc ? nullptr : d->out, d->out_ld};
+  const OutcArgs oc{d->outc_w, d->outc_b, d->out_ch, d->use_tanh ? 1 : 0, d->delta};
   const int tiles_x = (d->W + TW - 1) / TW, tiles_y = (d->H + TH - 1) / TH;
   const int64_t nt = (int64_t)d->B * tiles_x * tiles_y;
   if (nt > 0x7fffffffLL) return VS_ERR_UNSUPPORTED;
@@ -522,7 +579,9 @@ extern "C" int vs_resblock_thin(const vs_resblock_thin_desc_t* d, void* stream) 
   const int tpw = per < 1 ? 1 : per;
   const unsigned grid = (unsigned)((nt + tpw - 1) / tpw);
   if (C == 32) hipLaunchKernelGGL(resblock_thin32_kernel, dim3(grid), dim3(NT32), 0, (hipStream_t)stream, a, tiles_x, tiles_y, (int)nt, tpw);
-  else if (d->arith == 2) hipLaunchKernelGGL((resblock_thin_kernel<2, 2, 2>), dim3(grid), dim3(256), 0, (hipStream_t)stream, a, tiles_x, tiles_y, (int)nt, tpw);
-  else hipLaunchKernelGGL((resblock_thin_kernel<3, 1, 2>), dim3(grid), dim3(256), 0, (hipStream_t)stream, a, tiles_x, tiles_y, (int)nt, tpw);
+  else if (outc && d->arith == 2) hipLaunchKernelGGL((resblock_thin_kernel<2, 2, 2 | OUTC_FORM>), dim3(grid), dim3(256), 0, (hipStream_t)stream, a, tiles_x, tiles_y, (int)nt, tpw, oc);
+  else if (outc) hipLaunchKernelGGL((resblock_thin_kernel<3, 1, 2 | OUTC_FORM>), dim3(grid), dim3(256), 0, (hipStream_t)stream, a, tiles_x, tiles_y, (int)nt, tpw, oc);
+  else if (d->arith == 2) hipLaunchKernelGGL((resblock_thin_kernel<2, 2, 2>), dim3(grid), dim3(256), 0, (hipStream_t)stream, a, tiles_x, tiles_y, (int)nt, tpw, oc);
+  else hipLaunchKernelGGL((resblock_thin_kernel<3, 1, 2>), dim3(grid), dim3(256), 0, (hipStream_t)stream, a, tiles_x, tiles_y, (int)nt, tpw, oc);
   return vs_launch_status();
 }

@@ -266,6 +266,8 @@ class HipEngine:
     _tr_pass = 0
     _calib = None
     thin_fused = True
+    outc_fused = True
+    msg_vectors = True
     tail_variant = 0
     prof_extractor = False
 
@@ -304,7 +306,9 @@ class HipEngine:
         self._nf_event = None
         for attr, value in engine_switches().items():
             setattr(self, attr, value)
-        self.bn_sync = None       # callable(sums: float64 [2*ld + 1]) -> None, in-place sum over the ranks (dist.convert_sync_batchnorm)
+        self.outc_fused = SW.flag("VIDEOSEAL_OUTC_FUSED", True)
+        self.msg_vectors = SW.flag("VIDEOSEAL_MSG_VECTORS", True)
+        self.bn_sync = None      # callable(sums: float64 [2*ld + 1]) -> None, in-place sum over the ranks (dist.convert_sync_batchnorm)
         self.tail_variant = 0            # vs_tail_desc_t::variant (0 = default: row-streaming kernel where it applies)
         self.shell_timers: Optional[list] = None     # bench.py: (kernel, ev0, ev1, algorithmic bytes) of the HBM-bound shell kernels
         self._tile_cache: Dict[tuple, int] = {}
@@ -516,8 +520,11 @@ class HipEngine:
              split_k: Optional[int] = None, sumsq: Optional[torch.Tensor] = None, cin: Optional[int] = None, flops: Optional[float] = None,
              grn_fold: Optional[tuple] = None, sumsq_hw: int = 0,
              arith: Optional[int] = None, in_pl: Optional[torch.Tensor] = None, in2_pl: Optional[torch.Tensor] = None,
-             out_pl: Optional[torch.Tensor] = None, a_mul: Optional[float] = None):
-        """cin: read only the first `cin` channels of every pixel (pixel stride stays x.ld)"""
+             out_pl: Optional[torch.Tensor] = None, a_mul: Optional[float] = None,
+             bias_frames: Optional[tuple] = None, bias2_frames: Optional[tuple] = None):
+        """cin: read only the first `cin` channels of every pixel (pixel stride stays x.ld)
+        bias_frames / bias2_frames = (tensor, frame stride in floats): one bias vector per frame instead of w.bias / w2.bias (stride 0: one shared
+        vector) -- the contribution of spatially constant input channels to a pointwise conv (vs_conv_desc_t::bias_fs / bias2_fs)"""
         d = N.ConvDesc()
         if geom is None:
             sh = sw = stride
@@ -541,6 +548,10 @@ class HipEngine:
         if in2 is not None:
             d.in2, d.in2_ld, d.Cin2, d.Cin2P = (N.ptr(in2.t) if in2.t is not None else None), in2.ld, in2.ld, w2.CinP
             d.wt2, d.bias2 = N.ptr(w2.wt), N.ptr(w2.bias)
+        if bias_frames is not None:
+            d.bias, d.bias_fs = N.ptr(bias_frames[0]), bias_frames[1]
+        if bias2_frames is not None:
+            d.bias2, d.bias2_fs = N.ptr(bias2_frames[0]), bias2_frames[1]
         d.out, d.out_ld, d.out_coff, d.tile_hint = (N.ptr(out.t) if out.t is not None else None), out.ld, out_coff, tile_hint
         if self.use_split and not (tile_hint & N.CONV_FORCE_F32):
             ar = self.arith if arith is None else arith
@@ -729,6 +740,87 @@ class HipEngine:
                 "vs_rmsnorm_act")
         return out
 
+    @staticmethod
+    def _msg_vectors_pack(E, nlat: int, hidden: int) -> dict:
+        """once per weight set (E is dropped by invalidate): the pointwise consumers of the spatially constant message channels get their message
+        part as ONE vector per message instead of as input channels.  res_conv of the first bottleneck block and the first Upsample group's
+        nine-tap GEMM are sliced into the columns that carry information ([latent] resp. [x | latent skip]) and the message columns; the message
+        blocks become further rows of the small GEMM that already produces the border-class products of c0 (rows (tap, n)):
+            rows [0, 9 N)          c0's message columns per tap                                   -> vs_msg_pre
+            rows [9 N, 10 N)       res_conv's message columns, bias = res_conv.bias               -> bias2 of c1, one vector per frame
+            rows [10 N, 10 N + Nu) the Upsample GEMM's message-skip columns x connect_scale       -> bias of that GEMM, one vector per frame"""
+        p, up = E["bott"][0], E["ups"][0]
+        cout, c0, res, gm = p["cout"], p["c0"], p["res"], up["gemm"]
+        w3 = c0.wt.view(cout, 9, c0.CinP)
+        wm = w3[:, :, nlat:nlat + hidden].permute(1, 0, 2).reshape(9 * cout, hidden)      # rows (tap, n)
+        cx = gm.CinP - nlat - hidden                                                      # channels of x in the [x | skip] concat
+        ext = torch.cat([wm, res.wt[:, nlat:nlat + hidden], gm.wt[:, cx + nlat:cx + nlat + hidden] * (2 ** -0.5)], 0).contiguous()
+        bias = torch.zeros(ext.shape[0], device=ext.device)
+        bias[9 * cout:10 * cout] = res.bias
+        return dict(c0_lat=ConvW(w3[:, :, :nlat].reshape(cout, 9 * nlat).contiguous(), c0.bias, cout, 3, 3, nlat),
+                    msg=ConvW(ext, bias, ext.shape[0], 1, 1, hidden),
+                    res_lat=ConvW(res.wt[:, :nlat].contiguous(), None, cout, 1, 1, nlat),
+                    up_xl=ConvW(gm.wt[:, :cx + nlat].contiguous(), None, gm.N, 1, 1, cx + nlat),
+                    off_res=9 * cout, off_up=10 * cout)
+
+    def _msg_vectors_ok(self, B: int, H: int, W: int, E, bn_train: bool) -> bool:
+        """shapes and switches under which the message channels never become a tensor: what _msg0_ok asks of the [latent | message] map, the
+        first Upsample group as the low-resolution GEMM + gather, more than one bottleneck block.  On or off the operand planes: both 3x3 kernels
+        of the first block take bias2 per frame (same epilogue order: the planes chain stays bit-identical to the per-conv path)"""
+        c = self.cfg
+        nlat, hidden = c.zc[-1], c.hidden
+        if not (self.msg_vectors and not bn_train and c.unet_norm != "rms" and c.num_blocks > 1 and E["ups"] and "gemm" in E["ups"][0]):
+            return False
+        p, gm = E["bott"][0], E["ups"][0]["gemm"]
+        cout = p["cout"]
+        full = Act(None, B, H, W, nlat + hidden, nlat + hidden)
+        return (nlat + hidden == c.bott and self._msg0_ok(full, p, nlat) and p["res"].CinP == c.bott and gm.CinP == cout + c.bott and
+                (cout + nlat) % 32 == 0 and gm.N % 4 == 0)
+
+    def resblock_msg0_vec(self, h3: Act, E, tag: str, lat: torch.Tensor, Bm: int):
+        """resblock_msg0 with h3 = the latent alone (no message channels in memory): c0 as there (latent channels + border-class table), c1 with
+        the latent as its 1x1 second phase (K = nlat) and res_conv's message part as a per-frame bias2 -- on operand planes where the rest of the
+        chain runs on them, else on the wave-specialised kernel.  Returns (activation, operand planes of the block's output or None, (P, its row
+        stride)) -- the Upsample GEMM takes its vector from P too."""
+        if "msgv" not in E:
+            E["msgv"] = self._msg_vectors_pack(E, h3.C, self.cfg.hidden)
+        v, p = E["msgv"], E["bott"][0]
+        cout, nlat, hidden = p["cout"], h3.C, self.cfg.hidden
+        nx = v["msg"].N
+        P = Act(self.buf(tag + ".P", Bm * nx), Bm, 1, 1, nx, nx)
+        self.conv(Act(lat, Bm, 1, 1, hidden, hidden), v["msg"], P)
+        pre = self.buf(tag + ".pre", Bm * 9 * cout)          # border-class table [Bm][9][N]
+        N.check(self.lib.vs_msg_pre_rows(N.ptr(P.t), nx, Bm, cout, N.ptr(pre), N.stream()), "vs_msg_pre_rows")
+        fs = 0 if Bm == 1 else nx
+        pre_ld = 0 if Bm == 1 else 9 * cout
+        prof0 = "bott.conv3x3.lat" if self.time_all_convs else None
+        ghost = Act(None, h3.B, h3.H, h3.W, cout, cout)
+        tile = (N.CONV_TILE_HI | 0) if cout % 192 == 0 else 15
+        if not (self.msg0_planes and cout % 192 == 0 and h3.H % 16 == 0 and h3.W % 16 == 0 and self._planes_ok(ghost, E["bott"][1:])):
+            # the per-conv path (planes chain off or not applicable): both convs on the wave-specialised kernel, named by tile -- the tuner's other
+            # candidates for a 3x3 layer have no per-frame bias2
+            t = self.new_act(tag + ".t", h3.B, h3.H, h3.W, cout)
+            self.conv(h3, v["c0_lat"], t, pad=1, act=N.ACT_RELU, a_scale=pre, a_scale_ld=pre_ld, tile_hint=tile | N.CONV_PRE, prof=prof0)
+            out = self.new_act(tag + ".o", h3.B, h3.H, h3.W, cout)
+            self.conv(t, p["c1"], out, pad=1, act=N.ACT_RELU, in2=h3, w2=v["res_lat"], tile_hint=tile, bias2_frames=(P.t[v["off_res"]:], fs))
+            return out, None, (P.t[v["off_up"]:], fs)
+        sk = self._planes_split(ghost)
+        ptile = N.CONV_TILE_HI | 6
+        latpl = self.to_planes(h3, tag + ".latpl")
+        tpl = self.buf("bott.plt", h3.rows * cout).view(torch.int16)
+        xpl = self.buf("bott.pl0", h3.rows * cout).view(torch.int16)
+        if sk == 1:
+            self.conv(Act(None, h3.B, h3.H, h3.W, nlat, nlat), v["c0_lat"], ghost, pad=1, act=N.ACT_RELU, a_scale=pre, a_scale_ld=pre_ld,
+                      tile_hint=ptile | N.CONV_PRE, in_pl=latpl, out_pl=tpl, prof=prof0)
+        else:       # K slices (few key frames): c0 keeps the wave-specialised kernel -- the table epilogue has no K-slice form
+            t = self.new_act(tag + ".t", h3.B, h3.H, h3.W, cout)
+            self.conv(h3, v["c0_lat"], t, pad=1, act=N.ACT_RELU, a_scale=pre, a_scale_ld=pre_ld, tile_hint=tile | N.CONV_PRE, prof=prof0)
+            N.check(self.lib.vs_to_planes(N.ptr(t.t), t.rows, cout, t.ld, A_MUL, N.ptr(tpl), N.stream()), "vs_to_planes")
+        self.conv(ghost, p["c1"], ghost, pad=1, act=N.ACT_RELU, in2=Act(None, h3.B, h3.H, h3.W, nlat, nlat), w2=v["res_lat"], tile_hint=ptile,
+                  in_pl=tpl, in2_pl=latpl, out_pl=xpl, bias2_frames=(P.t[v["off_res"]:], fs), **(dict(split_k=sk) if sk > 1 else {}))
+        self.planes_chain_ran = True
+        return ghost, xpl, (P.t[v["off_up"]:], fs)
+
     def resblock_msg0(self, h3: Act, p, tag: str, lat: torch.Tensor, Bm: int, nlat: int, planes_out: bool = False):
         """planes_out: the caller continues with bottleneck_planes -> returns (activation, its operand planes or None).
         First bottleneck block (unet.py:183-185) on h3 = [latent (nlat channels) | message (spatially constant)]: the 3x3 conv over
@@ -816,10 +908,12 @@ class HipEngine:
         return (x.ld <= k and p["c0"].CinP == k and p["c1"].CinP == k and p["res"].CinP == k and (out is None or out.ld == c) and
                 (c == 16 or self.arith == 2) and bool(self.lib.vs_resblock_thin_supported(x.ld, c, c)))
 
-    def resblock_thin(self, x: Act, p, tag: str, out: Optional[Act] = None) -> Act:
+    def resblock_thin(self, x: Act, p, tag: str, out: Optional[Act] = None, outc: Optional[tuple] = None) -> Optional[Act]:
+        """outc = (w [out_ch][16], b, out_ch, use_tanh, delta): the U-Net's last 1x1 conv (+ tanh) in the block's epilogue -- the block's output
+        is not stored, delta [B][out_ch][H][W] gets the bits of vs_resblock_thin + vs_outc_tanh; returns None"""
         ar, c = self.arith, p["cout"]
         c0, c1, cr = p["c0"].with_split(ar), p["c1"].with_split(ar), p["res"].with_split(ar)
-        if out is None:
+        if out is None and outc is None:
             out = self.new_act(tag + ".o", x.B, x.H, x.W, c)
         d = N.ResblockThinDesc()
         d.x, d.x_ld, d.B, d.H, d.W, d.Cin = N.ptr(x.t), x.ld, x.B, x.H, x.W, x.ld
@@ -827,7 +921,11 @@ class HipEngine:
         d.b0, d.b1, d.br = N.ptr(c0.bias), N.ptr(c1.bias), N.ptr(cr.bias)
         d.arith, d.Cout, d.a_mul = ar, c, A_MUL
         d.acc_mul0, d.acc_mul1, d.acc_mulr = 1.0 / (A_MUL * c0.w_mul), 1.0 / (A_MUL * c1.w_mul), 1.0 / (A_MUL * cr.w_mul)
-        d.out, d.out_ld = N.ptr(out.t), out.ld
+        if outc is not None:
+            ow, ob, d.out_ch, d.use_tanh, delta = outc
+            d.outc_w, d.outc_b, d.delta = N.ptr(ow), N.ptr(ob), N.ptr(delta)
+        else:
+            d.out, d.out_ld = N.ptr(out.t), out.ld
         timed = self.kernel_timers is not None and self.time_all_convs and not torch.cuda.is_current_stream_capturing()
         if timed:
             ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -1001,7 +1099,9 @@ class HipEngine:
             dwn = self.new_act(f"down{i}.d", B, Ho, Wo, c.zc[i + 1])
             self.conv(src, E["downs"][i]["down"], dwn, stride=2, pad=1)
             if i == nlev - 1:     # last level lands in the message-augmented latent [lat | msg]
-                h3 = self.new_act("h3", B, Ho, Wo, c.bott)
+                # ... or, where every consumer of the message channels takes them as per-frame vectors, in the latent alone (_msg_vectors_ok)
+                msgv = self._msg_vectors_ok(B, Ho, Wo, E, bn_train)
+                h3 = self.new_act("h3", B, Ho, Wo, c.zc[-1] if msgv else c.bott)
                 if rms:           # the RMSNorm epilogue writes whole rows: land in a dense map, then copy into columns [0, zc[-1])
                     lat_ = self.resblock(dwn, E["downs"][i]["rb"], f"down{i}")
                     N.check(L.vs_cat2_scale(None, 0, 0, N.ptr(lat_.t), lat_.C, lat_.ld, 1.0, lat_.rows, N.ptr(h3.t), h3.ld, st), "vs_cat2_scale")
@@ -1014,8 +1114,11 @@ class HipEngine:
         Bm = msgs_i32.shape[0]
         lat = self.buf("msg.lat", Bm * c.hidden)
         N.check(L.vs_msg_latent(N.ptr(E["table"]), N.ptr(msgs_i32), Bm, c.nbits, c.hidden, N.ptr(lat), st), "vs_msg_latent")
-        N.check(L.vs_broadcast_channels(N.ptr(lat), Bm, c.hidden, N.ptr(h3.t), B, h3.H * h3.W, h3.ld, c.zc[-1], st),
-                "vs_broadcast_channels")
+        msgv = nlev > 0 and msgv
+        if not msgv:
+            N.check(L.vs_broadcast_channels(N.ptr(lat), Bm, c.hidden, N.ptr(h3.t), B, h3.H * h3.W, h3.ld, c.zc[-1], st),
+                    "vs_broadcast_channels")
+        up0_bias = None
         xcur = h3
         def fused_ok(k: int, c1: int, c2: int) -> bool:
             up_ = E["ups"][k]
@@ -1031,6 +1134,9 @@ class HipEngine:
         xcur_pl = None
         for j in range(c.num_blocks):
             lc = lowres_cat(0, xcur) if j == c.num_blocks - 1 else None
+            if j == 0 and msgv:
+                xcur, xcur_pl, up0_bias = self.resblock_msg0_vec(h3, E, "bott0", lat, Bm)
+                continue
             if j == 0 and lc is None and self._msg0_ok(h3, E["bott"][0], c.zc[-1]):
                 nxt = Act(None, B, h3.H, h3.W, E["bott"][0]["cout"], E["bott"][0]["cout"])
                 chain = c.num_blocks > 1 and not bn_train and self._planes_ok(nxt, E["bott"][1:])
@@ -1060,7 +1166,10 @@ class HipEngine:
                 N.check(L.vs_cat2_scale(None if direct else N.ptr(xcur.t), xcur.C, xcur.ld, N.ptr(skip.t), skip.C, skip.ld, 2 ** -0.5,
                                         lc.rows, N.ptr(lc.t), lc.ld, st), "vs_cat2_scale")
                 z = self.new_act(f"up{k}.z", B, lc.H, lc.W, 9 * co)
-                self.conv(lc, up["gemm"], z, prof=(f"up{k}.gemm9" if self.time_all_convs else None))
+                if k == 0 and up0_bias is not None:       # [x | latent skip]: the message-skip columns arrive as one bias vector per frame
+                    self.conv(lc, E["msgv"]["up_xl"], z, bias_frames=up0_bias, prof=(f"up{k}.gemm9" if self.time_all_convs else None))
+                else:
+                    self.conv(lc, up["gemm"], z, prof=(f"up{k}.gemm9" if self.time_all_convs else None))
                 ln = self.new_act(f"up{k}.ln", B, 2 * lc.H, 2 * lc.W, co)
                 N.check(L.vs_upconv_gather_ln(N.ptr(z.t), z.ld, B, lc.H, lc.W, co, N.ptr(up["lnw"]), N.ptr(up["lnb"]), 1e-6, up_act,
                                               N.ptr(ln.t), ln.ld, st), "vs_upconv_gather_ln")
@@ -1073,6 +1182,12 @@ class HipEngine:
                 ln = self.new_act(f"up{k}.ln", B, cat.H, cat.W, up["conv"].N)
                 self.layernorm(cv, up["lnw"], up["lnb"], ln, act=up_act)
             lc = lowres_cat(k + 1, ln)
+            if (k == nlev - 1 and self.outc_fused and lc is None and up["rb"]["cout"] == 16 and c.out_ch <= 4 and E["outc_w"].shape[1] == 16 and
+                    self._thin_ok(ln, up["rb"], None)):
+                # the last block's 134 MB (32 x 256^2 x 16) were written to be read once by vs_outc_tanh: outc + tanh in its epilogue, same bits
+                delta = self.buf("delta", B * c.out_ch * ln.H * ln.W)
+                self.resblock_thin(ln, up["rb"], f"up{k}", outc=(E["outc_w"], E["outc_b"], c.out_ch, 1 if c.last_tanh else 0, delta))
+                return delta.view(B, c.out_ch, ln.H, ln.W)
             xcur = self.resblock(ln, up["rb"], f"up{k}", out=(Act(lc.t, B, lc.H, lc.W, up["rb"]["cout"], lc.ld) if lc else None))
         delta = self.buf("delta", B * c.out_ch * xcur.H * xcur.W)
         N.check(L.vs_outc_tanh(N.ptr(xcur.t), xcur.H * xcur.W, B, xcur.C, xcur.ld, N.ptr(E["outc_w"]), N.ptr(E["outc_b"]), c.out_ch,

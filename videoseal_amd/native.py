@@ -27,7 +27,7 @@ VIDEO_MODES = {"repeat": 0, "alternate": 1, "interpolate": 2}
 EXPORTS = [
     "vs_version", "vs_arch", "vs_error_string", "vs_sizeof_conv_desc", "vs_sizeof_tail_desc", "vs_debug_set", "vs_debug_key", "vs_debug_get",
     "vs_model_create", "vs_model_destroy", "vs_model_workspace_bytes", "vs_model_embed", "vs_model_detect", "vs_model_set_nv12_color", "vs_nv12_default_color", "vs_conv_gemm", "vs_conv_plan", "vs_cnx_stage_plan", "vs_sizeof_conv_plan", "vs_sizeof_cnx_stage_plan", "vs_to_planes", "vs_to_planes_affine", "vs_layernorm_act", "vs_layernorm_patch2x2", "vs_stem_conv_ln", "vs_rmsnorm_act", "vs_vit_attention", "vs_dwconv7_ln", "vs_dwconv7_ln_planes", "vs_grn_scale", "vs_grn_scale_from_partials", "vs_grn_scale_from_straddle_partials", "vs_grn_apply",
-    "vs_upcat2x", "vs_upconv_supported", "vs_upconv_gather_ln", "vs_cat2_scale", "vs_msg_pre", "vs_upconv_fused_supported", "vs_upconv_fused_preferred", "vs_upconv_fused", "vs_im2col3x3", "vs_msg_latent", "vs_broadcast_channels", "vs_outc_tanh", "vs_pool_linear", "vs_resize_pre", "vs_resize_pre_u8",
+    "vs_upcat2x", "vs_upconv_supported", "vs_upconv_gather_ln", "vs_cat2_scale", "vs_msg_pre", "vs_msg_pre_rows", "vs_upconv_fused_supported", "vs_upconv_fused_preferred", "vs_upconv_fused", "vs_im2col3x3", "vs_msg_latent", "vs_broadcast_channels", "vs_outc_tanh", "vs_pool_linear", "vs_resize_pre", "vs_resize_pre_u8",
     "vs_jnd_heatmap", "vs_embed_tail", "vs_aug_color_scratch_floats", "vs_aug_color", "vs_aug_color_chain", "vs_aug_crop_resize_color", "vs_aug_crop_flip", "vs_aug_warp", "vs_resize_nchw",
     "vs_gaussian_blur", "vs_median_filter", "vs_jpeg_workspace_bytes", "vs_jpeg_roundtrip", "vs_h264_proxy_workspace_bytes", "vs_h264_proxy_roundtrip",
     "vs_bn_partial_doubles", "vs_bn_batch_stats", "vs_bn_partial_sums", "vs_bn_finish_sums", "vs_scale_shift_act", "vs_aug_mask_blend", "vs_aug_add_scaled", "vs_aug_gather_frames", "vs_aug_window_average",
@@ -71,6 +71,7 @@ class ConvDesc(C.Structure):
         ("wt_split", C.c_void_p), ("wt2_split", C.c_void_p), ("wt_blk", C.c_void_p), ("wt2_blk", C.c_void_p),
         ("splitk_ws", C.c_void_p), ("splitk_ld", C.c_int64), ("split_k", C.c_int32), ("arith", C.c_int32),
         ("sumsq_part", C.c_void_p), ("in_pl", C.c_void_p), ("in2_pl", C.c_void_p), ("out_pl", C.c_void_p), ("a_mul", C.c_float), ("acc_mul", C.c_float), ("acc_mul2", C.c_float), ("grn_nchunk", C.c_int32), ("grn_part", C.c_void_p), ("grn_gamma", C.c_void_p), ("sumsq_hw", C.c_int32), ("reserved_", C.c_int32),
+        ("bias_fs", C.c_int64), ("bias2_fs", C.c_int64),
     ]
 
 
@@ -146,6 +147,7 @@ class ResblockThinDesc(C.Structure):
         ("arith", C.c_int32), ("Cout", C.c_int32),
         ("a_mul", C.c_float), ("acc_mul0", C.c_float), ("acc_mul1", C.c_float), ("acc_mulr", C.c_float),
         ("out", C.c_void_p), ("out_ld", C.c_int64),
+        ("outc_w", C.c_void_p), ("outc_b", C.c_void_p), ("out_ch", C.c_int32), ("use_tanh", C.c_int32), ("delta", C.c_void_p),
     ]
 
 
@@ -188,6 +190,7 @@ def lib() -> C.CDLL:
         "vs_upconv_gather_ln": [P, I64, I, I, I, I, P, P, F, I, P, I64, P],
         "vs_cat2_scale": [P, I, I64, P, I, I64, F, I64, P, I64, P],
         "vs_msg_pre": [P, I, I, P, P],
+        "vs_msg_pre_rows": [P, I64, I, I, P, P],
         "vs_upconv_fused_supported": [I, I, I],
         "vs_upconv_fused_preferred": [I, I, I],
         "vs_upconv_fused": [P, I, I64, P, I, I64, F, P, I, I, I, I, P, P, F, I, P, I64, I, F, F, P],

@@ -32,6 +32,9 @@ REGISTRY = {
     "VIDEOSEAL_PW2_SMALL_PC": "0: stage-3 pwconv2 on planes instead of the wave-specialised GEMM",
     "VIDEOSEAL_CNX_FUSED": "0: stage 0 / 1 ConvNeXt blocks unfused (default: h kept on chip, convnext_fused.hip)",
     "VIDEOSEAL_THIN_FUSED": "0: 16-channel ResnetBlocks as separate launches (default: one launch, resblock_thin.hip)",
+    "VIDEOSEAL_MSG_VECTORS": "0: the message channels as a broadcast tensor ([latent | message] map, K = 384 res_conv, K = 768 first Upsample GEMM) "
+                             "instead of per-frame bias vectors (the model-level C host has no such switch)",
+    "VIDEOSEAL_OUTC_FUSED": "0: outc + tanh as its own launch behind the last thin ResnetBlock (default: in that block's epilogue, same bits)",
     "VIDEOSEAL_PLANES_SPLITK": "0: planes chain without K slices for 4 - 8 key frames",
     "VIDEOSEAL_PLANES_SK": "experiments: another K-slice count of the planes conv for launches below 200 tiles (read per call)",
     # ---- tile selection (engine construction)
