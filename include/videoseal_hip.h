@@ -701,6 +701,56 @@ int vs_embed_tail_yuv420(const vs_tail_yuv420_desc_t* d, void* stream);
 int vs_yuv420_default_color(int depth, float* yuv2rgb12, float* rgb2yuv12);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * 4:2:2 and 4:4:4 surfaces beside the 4:2:0 ones: what masters, mezzanine files and capture hardware hold.
+ * Layout.  (planar, depth, msb_aligned, chroma) names the format, chroma = 420, 422 or 444; every other combination answers
+ *   VS_ERR_UNSUPPORTED.  chroma = 420: the four formats above, with the bits of the _yuv420 entry points.  The six others:
+ *     yuv422p    (1,  8, 0, 422)  uint8   plane[0] = Y [H][W], plane[1] = Cb [H][W/2], plane[2] = Cr [H][W/2]
+ *     yuv422p10  (1, 10, 0, 422)  uint16  as yuv422p; sample code = min(word, 1023)
+ *     nv16       (0,  8, 0, 422)  uint8   plane[0] = Y [H][W], plane[1] = [H][W]: samples 2j, 2j+1 of row i are Cb, Cr of block (i, j)
+ *     p210       (0, 10, 1, 422)  uint16  as nv16; sample code = word >> 6 (the low 6 bits are ignored on input and zero on output)
+ *     yuv444p    (1,  8, 0, 444)  uint8   plane[0] = Y, plane[1] = Cb, plane[2] = Cr, each [H][W]
+ *     yuv444p10  (1, 10, 0, 444)  uint16  as yuv444p; sample code = min(word, 1023)
+ *   The size rule comes from the format: 4:2:0 needs H and W even, 4:2:2 needs W even and takes any H >= 1, 4:4:4 takes any H, W >= 1.
+ *   Words, pitches (bytes, any value >= the row's bytes, odd ones included), frame strides and the AVFrame mapping are those of the 4:2:0
+ *   surfaces.  Not supported: packed formats (yuyv422, uyvy422, v210), semi-planar 4:4:4 (nv24, p410), depth 12, and any chroma siting
+ *   other than the block rule below.
+ * Colour.  As for the 4:2:0 surfaces: HOST arrays of 12 floats in code units of the surface's depth (videoseal_amd/yuv420.py::color_affine).
+ * Chroma.  A block is 2 x 2 pixels (4:2:0), 2 x 1 (4:2:2: two neighbouring pixels of one row) or 1 x 1 (4:4:4).  Up: every pixel of a block
+ *   uses the block's (Cb, Cr).  Down: the mean of the block's per-pixel values (four, two, or the value itself), then one rounding.
+ * Range and rounding.  As for the 4:2:0 surfaces: RGB clamped to [0, 1] after decoding, output codes floor(clamp(v, 0, 2^depth - 1) + 0.5)
+ *   (p210 stores code << 6), no intermediate RGB24.
+ *
+ * vs_resize_pre_yuv / vs_embed_tail_yuv: vs_resize_pre_yuv420 / vs_embed_tail_yuv420 on such surfaces -- the same kernel family (the surface
+ *   trait carries the chroma subsampling shifts), the same conversion, filter, JND and blend expressions in the same order for every
+ *   format, so surfaces that decode to the same RGB give the same bits.  The descriptor is vs_tail_yuv420_desc_t with vs_yuv_surface_t
+ *   surfaces.  VS_ERR_UNSUPPORTED: a format outside the ten, two surfaces of different formats, preds_w != NULL, attenuate = 2, a variant
+ *   other than 0 / 1 / 4.  VS_ERR_BAD_ARG (-1): W odd with chroma 420 or 422, H odd with chroma 420, a pitch shorter than its row.  Bytes
+ *   of a destination plane between a row's end and its pitch are never written.  Development switches: keys 0 - 2, as above.
+ */
+typedef struct vs_yuv_surface {
+  void* plane[3];
+  int64_t pitch[3], frame_stride[3];        /* bytes */
+  int32_t planar, depth, msb_aligned, chroma;   /* chroma: 420, 422 or 444 */
+} vs_yuv_surface_t;
+typedef struct vs_tail_yuv_desc {
+  vs_yuv_surface_t src, dst;
+  float* preds_w;
+  const float* delta; const float* hmap_lowres; const float* taps43;   /* taps43: HOST pointer */
+  int32_t F, H, W, S_h, S_w, Cd;
+  int32_t step, video_mode, total_key;
+  int32_t attenuate, clamp, antialias;
+  float scaling_i, scaling_w;
+  int32_t io_u8;
+  int32_t variant;
+  float yuv2rgb12[12], rgb2yuv12[12];
+} vs_tail_yuv_desc_t;
+int vs_sizeof_yuv_surface(void);            /* sizeof(vs_yuv_surface_t) */
+int vs_sizeof_tail_yuv_desc(void);          /* sizeof(vs_tail_yuv_desc_t) */
+int vs_resize_pre_yuv(const vs_yuv_surface_t* src, int B, int H, int W, const float* yuv2rgb12, int oh, int ow, int antialias,
+                      float* dst_rgb, float mul, float add, float* dst_y, int y_step, const float* ymat3, void* stream);
+int vs_embed_tail_yuv(const vs_tail_yuv_desc_t* d, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * Model-level entry points (the granularity a non-Python host would bind): an opaque model built from the card numbers
  * (utils/cfg.py:88-154, embedder.py:243-262, extractor.py:189-208) and the reference state_dict (cfg.py:147-150:
  * checkpoint['model'], HOST fp32 tensors by their reference names, loaded like strict=False: unknown names are ignored,
@@ -752,6 +802,13 @@ int vs_model_embed_yuv420(vs_model_t* m, const vs_yuv420_surface_t* in, const vs
                           int lowres_attenuation, int antialias, void* ws, int64_t ws_bytes, void* stream);
 int vs_model_detect_yuv420(vs_model_t* m, const vs_yuv420_surface_t* in, const float* yuv2rgb12, int frames, int H, int W, int antialias,
                            float* logits, void* ws, int64_t ws_bytes, void* stream);
+/* ... and on surfaces of any of the ten formats (vs_yuv_surface_t): the arguments, defaults and refusals of the two entry points above, the
+ * size rule of the surface's chroma format (4:2:2: W even; 4:4:4: any H, W).  chroma = 420 gives the words and logits of the _yuv420 pair. */
+int vs_model_embed_yuv(vs_model_t* m, const vs_yuv_surface_t* in, const vs_yuv_surface_t* out, const float* yuv2rgb12,
+                       const float* rgb2yuv12, const int32_t* msgs, int n_msgs, int frames, int H, int W, int step, int video_mode,
+                       int lowres_attenuation, int antialias, void* ws, int64_t ws_bytes, void* stream);
+int vs_model_detect_yuv(vs_model_t* m, const vs_yuv_surface_t* in, const float* yuv2rgb12, int frames, int H, int W, int antialias,
+                        float* logits, void* ws, int64_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Augmentations (videoseal/augmentation/valuemetric.py, geometric.py, utils/image.py).  Frames are NCHW fp32 [F][3][H][W]

@@ -47,6 +47,10 @@ def _bind(L):
     L.vs_model_embed_yuv420.restype = I
     L.vs_model_detect_yuv420.argtypes = [P, C.POINTER(N.Yuv420Surface), P, I, I, I, I, P, P, I64, P]
     L.vs_model_detect_yuv420.restype = I
+    L.vs_model_embed_yuv.argtypes = [P, C.POINTER(N.YuvSurface), C.POINTER(N.YuvSurface), P, P, P, I, I, I, I, I, I, I, I, P, I64, P]
+    L.vs_model_embed_yuv.restype = I
+    L.vs_model_detect_yuv.argtypes = [P, C.POINTER(N.YuvSurface), P, I, I, I, I, P, P, I64, P]
+    L.vs_model_detect_yuv.restype = I
     L._model_api_bound = True
 
 
@@ -176,4 +180,32 @@ class CModel:
         sin = N.yuv420_surface(src.planes, fmt)
         N.check(self._L.vs_model_detect_yuv420(self._h, C.byref(sin), dec, F_, H, W, int(antialias), N.ptr(logits), N.ptr(ws), ws.numel(),
                                                N.stream()), "vs_model_detect_yuv420")
+        return logits
+
+    def embed_yuv(self, planes, fmt: str, msgs: torch.Tensor, *, out_planes=None, color=None, step: int = 1, video_mode: int = 0,
+                  lowres_attenuation: bool = False, antialias: bool = True):
+        """vs_model_embed_yuv on device-resident planes of any of the ten formats (yuv.py; any pitches); `out_planes`, `color` and the
+        result as for embed_yuv420."""
+        from . import yuv
+        F_, H, W = yuv.check_clip(planes, fmt)
+        src = yuv.clip(planes, fmt)
+        dst = yuv.clip(out_planes, fmt) if out_planes is not None else src.empty_like()
+        m = msgs.to(device=src.device, dtype=torch.int32).contiguous()
+        ws = self._workspace(F_, H, W, step)
+        dec, enc = self._yuv420_color("p010" if yuv.fmt_info(fmt)[1] == 10 else "nv12", color)          # (the affines depend on the depth alone)
+        sin, sout = N.yuv_surface(src.planes, fmt), N.yuv_surface(dst.planes, fmt)
+        N.check(self._L.vs_model_embed_yuv(self._h, C.byref(sin), C.byref(sout), dec, enc, N.ptr(m), m.shape[0], F_, H, W, step, video_mode,
+                                           int(lowres_attenuation), int(antialias), N.ptr(ws), ws.numel(), N.stream()), "vs_model_embed_yuv")
+        return dst.planes
+
+    def detect_yuv(self, planes, fmt: str, *, color=None, antialias: bool = True) -> torch.Tensor:
+        from . import yuv
+        F_, H, W = yuv.check_clip(planes, fmt)
+        src = yuv.clip(planes, fmt)
+        logits = torch.empty(F_, self.cfg.nbits + 1, device=src.device)
+        ws = self._workspace(F_, H, W, 1)
+        dec, _ = self._yuv420_color("p010" if yuv.fmt_info(fmt)[1] == 10 else "nv12", color)
+        sin = N.yuv_surface(src.planes, fmt)
+        N.check(self._L.vs_model_detect_yuv(self._h, C.byref(sin), dec, F_, H, W, int(antialias), N.ptr(logits), N.ptr(ws), ws.numel(),
+                                            N.stream()), "vs_model_detect_yuv")
         return logits

@@ -322,9 +322,9 @@ struct Runner {
   int64_t cap, used = 0;
   void* st;
   int rc = VS_OK;
-  // io = 3 (vs_model_*_yuv420): the surfaces and their colour affines
-  const vs_yuv420_surface_t* ysrc = nullptr;
-  const vs_yuv420_surface_t* ydst = nullptr;
+  // io = 3 (vs_model_*_yuv, vs_model_*_yuv420): the surfaces and their colour affines
+  const vs_yuv_surface_t* ysrc = nullptr;
+  const vs_yuv_surface_t* ydst = nullptr;
   const float* ydec = nullptr;
   const float* yenc = nullptr;
 
@@ -781,12 +781,12 @@ struct Runner {
     if (live()) chk(vs_pool_linear(hl.p, B, hl.H * hl.W, hl.C, hl.ld, m->lin_w, m->lin_b, c.nbits + 1, logits, st));
   }
   // model.py::_embed_frames_eager
-  // io: 0 = fp32 NCHW, 3 = the 4:2:0 surface `ysrc` (io_u8 = 2 arrives here as a contiguous nv12 surface), any other value = RGB24
+  // io: 0 = fp32 NCHW, 3 = the YUV surface `ysrc` (io_u8 = 2 arrives here as a contiguous nv12 surface), any other value = RGB24
   void resize(const void* imgs, int io, int F, int H, int W, int S, int antialias, float* rgb, float mul, float add, float* key, int step,
               const float* ymat) {
     if (!live()) return;
     const bool u8 = io != 0;
-    if (io == 3) chk(vs_resize_pre_yuv420(ysrc, F, H, W, ydec, S, S, antialias, rgb, mul, add, key, step, ymat, st));
+    if (io == 3) chk(vs_resize_pre_yuv(ysrc, F, H, W, ydec, S, S, antialias, rgb, mul, add, key, step, ymat, st));
     else if (u8) chk(vs_resize_pre_u8(static_cast<const unsigned char*>(imgs), F, H, W, S, S, antialias, rgb, mul, add, key, step, ymat, st));
     else chk(vs_resize_pre(static_cast<const float*>(imgs), F, 3, H, W, S, S, antialias, rgb, mul, add, key, step, ymat, st));
   }
@@ -806,7 +806,7 @@ struct Runner {
       if (live()) chk(vs_jnd_heatmap(rgb.p, F, S, S, (int64_t)S * S * 4, 1, (int64_t)S * 4, 4, m->taps43, hmap, st));
     }
     if (io == 3) {
-      vs_tail_yuv420_desc_t n;
+      vs_tail_yuv_desc_t n;
       std::memset(&n, 0, sizeof(n));
       n.src = *ysrc; n.dst = *ydst; n.preds_w = preds_w; n.delta = delta; n.hmap_lowres = hmap; n.taps43 = m->taps43;
       n.F = F; n.H = H; n.W = W; n.S_h = Sh; n.S_w = Sw; n.Cd = c.out_ch;
@@ -815,7 +815,7 @@ struct Runner {
       n.scaling_i = c.scaling_i; n.scaling_w = c.scaling_w;
       std::memcpy(n.yuv2rgb12, ydec, sizeof(n.yuv2rgb12));
       std::memcpy(n.rgb2yuv12, yenc, sizeof(n.rgb2yuv12));
-      if (live()) chk(vs_embed_tail_yuv420(&n, st));
+      if (live()) chk(vs_embed_tail_yuv(&n, st));
       return;
     }
     const bool u8 = io != 0;
@@ -1048,7 +1048,14 @@ extern "C" int64_t vs_model_workspace_bytes(const vs_model_t* m, int frames, int
 }
 
 // io_u8 = 2: uint8 NV12 [frames][3H/2][W], contiguous (pitch W), as a surface of the 4:2:0 path
-static vs_yuv420_surface_t nv12_contiguous(const void* frames, int H, int W) { return vs_nv12_surface(frames, H, W, (int64_t)W * (H / 2 * 3)); }
+static vs_yuv_surface_t any_surface(const vs_yuv420_surface_t& s) {          // the same surface with its chroma format named
+  vs_yuv_surface_t r;
+  static_assert(sizeof(r) == sizeof(s), "vs_yuv_surface_t is vs_yuv420_surface_t with `chroma` in the reserved member");
+  std::memcpy(&r, &s, sizeof(r));
+  r.chroma = 420;
+  return r;
+}
+static vs_yuv_surface_t nv12_contiguous(const void* frames, int H, int W) { return any_surface(vs_nv12_surface(frames, H, W, (int64_t)W * (H / 2 * 3))); }
 
 extern "C" int vs_model_embed(vs_model_t* m, const void* imgs, const int32_t* msgs, int n_msgs, int frames, int H, int W, int step,
                               int video_mode, int lowres_attenuation, int antialias, int io_u8, void* imgs_w, float* preds_w, void* ws,
@@ -1059,7 +1066,7 @@ extern "C" int vs_model_embed(vs_model_t* m, const void* imgs, const int32_t* ms
   VS_REQUIRE(video_mode >= 0 && video_mode <= 2);
   Runner r{m, static_cast<char*>(ws), ws_bytes, 0, stream};
   if (io_u8) VS_REQUIRE(m->c.clamp);
-  vs_yuv420_surface_t in, out;
+  vs_yuv_surface_t in, out;
   if (io_u8 == 2) {       // the 4:2:0 path on two contiguous nv12 surfaces, with the model's stored colour
     VS_REQUIRE(!(H & 1) && !(W & 1));
     if (preds_w) return VS_ERR_UNSUPPORTED;
@@ -1076,7 +1083,7 @@ extern "C" int vs_model_detect(vs_model_t* m, const void* imgs, int frames, int 
                                int64_t ws_bytes, void* stream) {
   VS_REQUIRE(m && imgs && logits && ws && frames > 0 && H > 0 && W > 0 && ((uintptr_t)ws & 255) == 0);
   Runner r{m, static_cast<char*>(ws), ws_bytes, 0, stream};
-  vs_yuv420_surface_t in;
+  vs_yuv_surface_t in;
   if (io_u8 == 2) {
     VS_REQUIRE(!(H & 1) && !(W & 1));
     in = nv12_contiguous(imgs, H, W);
@@ -1103,6 +1110,43 @@ extern "C" int vs_model_embed_yuv420(vs_model_t* m, const vs_yuv420_surface_t* i
   VS_REQUIRE(m->c.clamp && !(H & 1) && !(W & 1));
   if (!yuv420_format_known(*in) || in->planar != out->planar || in->depth != out->depth || in->msb_aligned != out->msb_aligned)
     return VS_ERR_UNSUPPORTED;
+  const vs_yuv_surface_t sin = any_surface(*in), sout = any_surface(*out);
+  return vs_model_embed_yuv(m, &sin, &sout, yuv2rgb12, rgb2yuv12, msgs, n_msgs, frames, H, W, step, video_mode, lowres_attenuation, antialias, ws,
+                            ws_bytes, stream);
+}
+
+extern "C" int vs_model_detect_yuv420(vs_model_t* m, const vs_yuv420_surface_t* in, const float* yuv2rgb12, int frames, int H, int W,
+                                      int antialias, float* logits, void* ws, int64_t ws_bytes, void* stream) {
+  VS_REQUIRE(m && in && logits && ws && frames > 0 && H > 0 && W > 0 && ((uintptr_t)ws & 255) == 0);
+  VS_REQUIRE(!(H & 1) && !(W & 1));
+  if (!yuv420_format_known(*in)) return VS_ERR_UNSUPPORTED;
+  const vs_yuv_surface_t sin = any_surface(*in);
+  return vs_model_detect_yuv(m, &sin, yuv2rgb12, frames, H, W, antialias, logits, ws, ws_bytes, stream);
+}
+
+// one of the ten formats (the rule of vs_resize_pre_yuv); hm, wm: the low bits of H and W that must be zero
+static bool yuv_format_known(const vs_yuv_surface_t& s, int& hm, int& wm) {
+  const vs_yuv420_surface_t t{{}, {}, {}, s.planar, s.depth, s.msb_aligned, 0};
+  if (!yuv420_format_known(t)) return false;
+  if (s.chroma == 420) { hm = 1; wm = 1; return true; }
+  if (s.chroma == 422) { hm = 0; wm = 1; return true; }
+  if (s.chroma == 444 && s.planar == 1) { hm = 0; wm = 0; return true; }
+  return false;
+}
+
+extern "C" int vs_model_embed_yuv(vs_model_t* m, const vs_yuv_surface_t* in, const vs_yuv_surface_t* out, const float* yuv2rgb12,
+                                  const float* rgb2yuv12, const int32_t* msgs, int n_msgs, int frames, int H, int W, int step, int video_mode,
+                                  int lowres_attenuation, int antialias, void* ws, int64_t ws_bytes, void* stream) {
+  VS_REQUIRE(m && in && out && msgs && ws && frames > 0 && H > 0 && W > 0 && step >= 1 && ((uintptr_t)ws & 255) == 0);
+  VS_REQUIRE(!yuv2rgb12 == !rgb2yuv12);
+  const int nk = (frames + step - 1) / step;
+  VS_REQUIRE(n_msgs == 1 || n_msgs == nk);
+  VS_REQUIRE(video_mode >= 0 && video_mode <= 2);
+  int hm = 0, wm = 0;
+  const bool known = yuv_format_known(*in, hm, wm);
+  VS_REQUIRE(m->c.clamp && (!known || (!(H & hm) && !(W & wm))));
+  if (!known || in->planar != out->planar || in->depth != out->depth || in->msb_aligned != out->msb_aligned || in->chroma != out->chroma)
+    return VS_ERR_UNSUPPORTED;
   float dec[12], enc[12];
   if (!yuv2rgb12) yuv420_default_color(in->depth, dec, enc);
   Runner r{m, static_cast<char*>(ws), ws_bytes, 0, stream};
@@ -1113,11 +1157,12 @@ extern "C" int vs_model_embed_yuv420(vs_model_t* m, const vs_yuv420_surface_t* i
   return r.rc;
 }
 
-extern "C" int vs_model_detect_yuv420(vs_model_t* m, const vs_yuv420_surface_t* in, const float* yuv2rgb12, int frames, int H, int W,
-                                      int antialias, float* logits, void* ws, int64_t ws_bytes, void* stream) {
+extern "C" int vs_model_detect_yuv(vs_model_t* m, const vs_yuv_surface_t* in, const float* yuv2rgb12, int frames, int H, int W, int antialias,
+                                   float* logits, void* ws, int64_t ws_bytes, void* stream) {
   VS_REQUIRE(m && in && logits && ws && frames > 0 && H > 0 && W > 0 && ((uintptr_t)ws & 255) == 0);
-  VS_REQUIRE(!(H & 1) && !(W & 1));
-  if (!yuv420_format_known(*in)) return VS_ERR_UNSUPPORTED;
+  int hm = 0, wm = 0;
+  if (!yuv_format_known(*in, hm, wm)) return VS_ERR_UNSUPPORTED;
+  VS_REQUIRE(!(H & hm) && !(W & wm));
   float dec[12], enc[12];
   if (!yuv2rgb12) yuv420_default_color(in->depth, dec, enc);
   Runner r{m, static_cast<char*>(ws), ws_bytes, 0, stream};

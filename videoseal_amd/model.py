@@ -870,6 +870,46 @@ class Videoseal(Wam):
             return {"preds": torch.zeros((0, self.embedder.cfg.nbits + 1), device=clip.device)}
         return {"preds": self._detect_clip(clip, interpolation)}
 
+    # ---- clips of any of the ten YUV formats (videoseal_amd/yuv.py): the 4:2:0 ones and yuv422p, yuv422p10, nv16, p210, yuv444p, yuv444p10
+    def _yuv_clip(self, planes, fmt: str, what: str, matrix: str, full_range: bool):
+        from . import yuv
+        yuv.check_clip(planes, fmt, what)
+        if matrix not in yuv.MATRICES:
+            raise ValueError(f"{what}: matrix must be one of {sorted(yuv.MATRICES)}, got {matrix!r}")
+        return yuv.clip(planes, fmt, (matrix, bool(full_range)))
+
+    @torch.no_grad()
+    def embed_yuv(self, planes, fmt: str, msgs: torch.Tensor = None, interpolation: dict = None, lowres_attenuation: bool = True,
+                  matrix: str = "bt709", full_range: bool = False) -> dict:
+        """planes: the plane tensors of a clip of format `fmt` (yuv.py: the four 4:2:0 formats of embed_yuv420, "yuv422p", "yuv422p10", "nv16",
+        "p210" -- W even -- and "yuv444p", "yuv444p10" -- any size; last stride 1, any row pitch and frame stride per plane) -> {'planes_w':
+        plane views, 'imgs_w': the packed contiguous buffer they view (2HW samples per frame for 4:2:2, 3HW for 4:4:4), 'msgs'}.  Means:
+        yuv.to_rgb -> embed(..., is_video=True) -> yuv.from_rgb with both conversions and the chroma resampling fused into the resize and tail
+        kernels: no RGB or fp32 frame is written, and a 10-bit clip keeps its 10 bits.  A 4:2:0 `fmt` gives embed_yuv420's words.  `matrix` is
+        "bt601", "bt709" or "bt2020", `full_range` selects full-range codes.  Needs clamp=True."""
+        clip = self._yuv_clip(planes, fmt, "embed_yuv", matrix, full_range)
+        if not self.clamp:
+            raise NotImplementedError("YUV output needs clamp=True (codes are undefined outside [0, 1])")
+        if msgs is None:
+            msgs = self.get_random_msg()
+        else:
+            assert msgs.shape[0] == 1, "Message should be unique"
+        if clip.shape[0] == 0 or clip.numel() == 0:
+            out = clip.clone()
+        else:
+            out = self._embed_clip(clip, msgs, interpolation, lowres_attenuation)
+        return {"planes_w": out.planes, "imgs_w": out.buf, "msgs": msgs[0:1].repeat(len(clip), 1)}
+
+    @torch.no_grad()
+    def detect_yuv(self, planes, fmt: str, interpolation: dict = None, matrix: str = "bt709", full_range: bool = False) -> dict:
+        """planes, fmt as in embed_yuv -> {'preds': [F, 1+nbits]}: detect(yuv.to_rgb(planes, fmt), is_video=True) with the conversion fused
+        into the resize kernel.  A 4:2:0 `fmt` gives detect_yuv420's logits."""
+        clip = self._yuv_clip(planes, fmt, "detect_yuv", matrix, full_range)
+        self._per_frame_rows_only("detect_yuv")
+        if clip.shape[0] == 0:
+            return {"preds": torch.zeros((0, self.embedder.cfg.nbits + 1), device=clip.device)}
+        return {"preds": self._detect_clip(clip, interpolation)}
+
     def extract_message(self, imgs: torch.Tensor, aggregation: str = "avg",
                         interpolation: dict = {"mode": "bilinear", "align_corners": False, "antialias": False}) -> torch.Tensor:
         """videoseal.py:390-428."""

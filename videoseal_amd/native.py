@@ -47,6 +47,7 @@ EXPORTS = [
     "vs_sizeof_tail_nv12_desc", "vs_resize_pre_nv12", "vs_embed_tail_nv12",
     "vs_sizeof_yuv420_surface", "vs_sizeof_tail_yuv420_desc", "vs_resize_pre_yuv420", "vs_embed_tail_yuv420", "vs_yuv420_default_color",
     "vs_model_embed_yuv420", "vs_model_detect_yuv420",
+    "vs_sizeof_yuv_surface", "vs_sizeof_tail_yuv_desc", "vs_resize_pre_yuv", "vs_embed_tail_yuv", "vs_model_embed_yuv", "vs_model_detect_yuv",
 ]
 
 
@@ -138,6 +139,29 @@ def yuv420_surface(planes, fmt: str) -> Yuv420Surface:
     return s
 
 
+class YuvSurface(C.Structure):
+    """mirror of vs_yuv_surface_t: Yuv420Surface with the chroma format (420, 422, 444) as its last member"""
+    _fields_ = Yuv420Surface._fields_[:-1] + [("chroma", C.c_int32)]
+
+
+class TailYuvDesc(C.Structure):
+    """mirror of vs_tail_yuv_desc_t: TailYuv420Desc on two YuvSurface"""
+    _fields_ = [("src", YuvSurface), ("dst", YuvSurface)] + TailYuv420Desc._fields_[2:]
+
+
+def yuv_surface(planes, fmt: str) -> YuvSurface:
+    """the surface of device-resident planes of any of the ten formats (videoseal_amd/yuv.py): addresses and strides, nothing is copied"""
+    from .yuv import fmt_info
+    planar, depth, msb, chroma = fmt_info(fmt)
+    s = YuvSurface()
+    for i, p in enumerate(planes):
+        s.plane[i] = ptr(p)
+        s.pitch[i] = p.stride(1) * p.element_size()
+        s.frame_stride[i] = p.stride(0) * p.element_size()
+    s.planar, s.depth, s.msb_aligned, s.chroma = int(planar), depth, int(msb), chroma
+    return s
+
+
 class ResblockThinDesc(C.Structure):
     """mirror of vs_resblock_thin_desc_t"""
     _fields_ = [
@@ -209,6 +233,8 @@ def lib() -> C.CDLL:
         "vs_resize_pre_yuv420": [C.POINTER(Yuv420Surface), I, I, I, P, I, I, I, P, F, F, P, I, P, P],
         "vs_embed_tail_yuv420": [C.POINTER(TailYuv420Desc), P],
         "vs_yuv420_default_color": [I, P, P],
+        "vs_resize_pre_yuv": [C.POINTER(YuvSurface), I, I, I, P, I, I, I, P, F, F, P, I, P, P],
+        "vs_embed_tail_yuv": [C.POINTER(TailYuvDesc), P],
         "vs_aug_color": [P, P, I, I, I, I, F, P, P],
         "vs_aug_crop_flip": [P, P, I, I, I, I, I, I, I, I, P],
         "vs_aug_color_chain": [P, P, I, I, I, I, C.POINTER(C.c_int), C.POINTER(C.c_float), P, P],
@@ -338,14 +364,16 @@ def lib() -> C.CDLL:
     L.vs_sizeof_tail_desc.restype = C.c_int
     L.vs_sizeof_tail_nv12_desc.restype = C.c_int
     L.vs_sizeof_yuv420_surface.restype = L.vs_sizeof_tail_yuv420_desc.restype = C.c_int
+    L.vs_sizeof_yuv_surface.restype = L.vs_sizeof_tail_yuv_desc.restype = C.c_int
     L.vs_sizeof_conv_plan.restype = L.vs_sizeof_cnx_stage_plan.restype = C.c_int
     if L.vs_version() != 3:
         raise NativeError(f"{LIB_PATH} has ABI version {L.vs_version()}, this binding is written for 3: rebuild (make -C videoseal_amd/csrc)")
     if L.vs_sizeof_conv_desc() != C.sizeof(ConvDesc) or L.vs_sizeof_tail_desc() != C.sizeof(TailDesc) or \
             L.vs_sizeof_tail_nv12_desc() != C.sizeof(TailNv12Desc) or L.vs_sizeof_conv_plan() != C.sizeof(ConvPlan) or \
             L.vs_sizeof_cnx_stage_plan() != C.sizeof(CnxStagePlan) or L.vs_sizeof_yuv420_surface() != C.sizeof(Yuv420Surface) or \
-            L.vs_sizeof_tail_yuv420_desc() != C.sizeof(TailYuv420Desc):
-        raise NativeError("ctypes mirrors of vs_conv_desc_t / vs_tail_desc_t / vs_tail_nv12_desc_t / vs_tail_yuv420_desc_t / the plan structs are out of date with the shared library")
+            L.vs_sizeof_tail_yuv420_desc() != C.sizeof(TailYuv420Desc) or L.vs_sizeof_yuv_surface() != C.sizeof(YuvSurface) or \
+            L.vs_sizeof_tail_yuv_desc() != C.sizeof(TailYuvDesc):
+        raise NativeError("ctypes mirrors of vs_conv_desc_t / vs_tail_desc_t / vs_tail_nv12_desc_t / vs_tail_yuv420_desc_t / vs_tail_yuv_desc_t / the plan structs are out of date with the shared library")
     _lib = L
     return L
 
