@@ -608,6 +608,64 @@ typedef struct vs_tail_desc {
 int vs_embed_tail(const vs_tail_desc_t* d, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * Lists of images of different sizes: the two full-resolution passes around ONE network pass over the whole list (the network runs at
+ * the processing size and does not care how large a picture was).  An image is a base pointer with its own H and W; image i of the list
+ * reads and writes frame i of the processing-size tensors.  Descriptors are a HOST array and travel in the kernel arguments, at most
+ * VS_IMAGES_PER_LAUNCH per launch: nothing is allocated, nothing synchronises, the calls may be captured.  A launch is a flat list of
+ * (image, tile) items -- its grid has exactly as many workgroups as the images of the launch have tiles, a 64 x 64 picture beside a
+ * 2048 x 2048 one costs no empty workgroup -- and a workgroup finds its image in a prefix table (wave-uniform: scalar loads, five steps).
+ * Launches per call: one per group of the plan below, i.e. ceil(images of a form / VS_IMAGES_PER_LAUNCH) summed over the kernel forms
+ * the list needs; never a function of n itself.
+ *   img      fp32 planes [3][H][W], 4-byte aligned; io_u8: uint8 RGB24 [H][W][3], any alignment.  Contiguous.
+ *   out      vs_embed_tail_images: the watermarked image, laid out like img.  Unused by vs_resize_pre_images.
+ *   preds_w  vs_embed_tail_images: fp32 [Cd][H][W] or NULL.  Unused by vs_resize_pre_images.
+ */
+#define VS_IMAGES_PER_LAUNCH 32
+typedef struct vs_image_desc {
+  const void* img; void* out; float* preds_w;
+  int32_t H, W;
+} vs_image_desc_t;
+
+/* vs_resize_pre / vs_resize_pre_u8 (C = 3, y_step = 1) on every image of the list: dst_rgb [n][oh][ow][4] and / or dst_y [n][oh][ow][4],
+ * frame i from image i, with the bits the per-image call gives (every kernel form of the resize computes the same expressions in the same
+ * order).  fp32 images take the row-streaming kernel where its windows fit and the 32 x 8 tile kernel elsewhere, RGB24 images the tile
+ * kernel.  VS_ERR_BAD_ARG without a launch: a null pointer, n <= 0, an image with H or W <= 0, both destinations NULL. */
+int vs_resize_pre_images(const vs_image_desc_t* images, int n, int io_u8, int oh, int ow, int antialias, float* dst_rgb, float mul,
+                         float add, float* dst_y, const float* ymat3, void* stream);
+
+/* vs_embed_tail with F = 1, step = 1, video_mode = VS_VIDEO_REPEAT on every image of the list: image i takes frame i of delta
+ * [n][Cd][S_h][S_w] and, when given, frame i of hmap_lowres [n][S_h][S_w]; out (and preds_w where not NULL) of image i are written.  The
+ * other members mean what they mean in vs_tail_desc_t; the bits are those of the per-image call (16-row tile kernel, separable stencils
+ * with the standard JND taps).  attenuate = 2 (the training order) answers VS_ERR_UNSUPPORTED; VS_ERR_BAD_ARG without a launch: a null
+ * pointer, n <= 0, an image with H or W <= 0, io_u8 without clamp. */
+typedef struct vs_tail_images_desc {
+  const vs_image_desc_t* images;   /* HOST array of n descriptors */
+  const float* delta; const float* hmap_lowres; const float* taps43;   /* taps43: HOST pointer */
+  int32_t n, S_h, S_w, Cd;
+  int32_t attenuate, clamp, antialias, io_u8;
+  float scaling_i, scaling_w;
+} vs_tail_images_desc_t;
+int vs_embed_tail_images(const vs_tail_images_desc_t* d, void* stream);
+
+/* The plan both launchers walk, as data (a pure host function: no GPU, no allocation; the pointers of the descriptors are not read).
+ * kind: the pass; (oh, ow): the processing size -- the destination of the resize, S_h x S_w of the tail.  One group = one launch:
+ * image[k] (k < count) indexes the caller's list, in list order; the workgroups of image[k] are [first_wg[k], first_wg[k + 1]) and
+ * first_wg[count] is the grid; strip: output rows per workgroup of a streaming resize, 0 otherwise.  Groups come form by form.
+ * At most max_groups groups are written (groups may be NULL); *n_groups is the number the list needs.  n = 0 is an empty plan. */
+#define VS_IMAGES_RESIZE 0
+#define VS_IMAGES_TAIL 1
+#define VS_IMAGES_FORM_TILE 0        /* resize: 32 x 8 outputs per workgroup; tail: 256 columns x 16 rows          */
+#define VS_IMAGES_FORM_STREAM128 1   /* resize: 128 output columns x strip rows, row-streaming (scales up to 3.4)   */
+#define VS_IMAGES_FORM_STREAM64 2    /* resize: 64 output columns x strip rows, row-streaming (scales up to 4)      */
+typedef struct vs_images_group {
+  int32_t form, count, strip, reserved_;
+  int32_t image[VS_IMAGES_PER_LAUNCH];
+  int32_t first_wg[VS_IMAGES_PER_LAUNCH + 1];
+} vs_images_group_t;
+int vs_images_plan(const vs_image_desc_t* images, int n, int kind, int io_u8, int oh, int ow, int antialias, vs_images_group_t* groups,
+                   int max_groups, int* n_groups);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * NV12 frames: what a hardware decoder (or ffmpeg in its native pixel format) hands over, 1.5 bytes per pixel.
  * Layout.  A clip is uint8 [F][3H/2][W], H and W even.  Rows 0 .. H-1 of a frame are luma; rows H .. 3H/2-1 are the chroma plane: bytes 2j
  *   and 2j+1 of chroma row i are Cb and Cr of the 2 x 2 pixel block (2i .. 2i+1, 2j .. 2j+1).  Consecutive bytes of a row are adjacent; rows

@@ -16,49 +16,32 @@
 // form to the tile kernel bit for bit.)
 #pragma once
 #include <hip/hip_runtime.h>
+#include "resize_pick.h"
 #include "resize_taps.h"
 #include "vs_common.h"
 
 namespace vs_rs {
 using namespace vs_taps;
 
-constexpr int RS_GI = 8;                                 // input rows per group
-constexpr int RS_WTAB_ROWS = 64;                         // strip rows whose vertical weights are tabulated (taller strips evaluate them per row)
-template <int OW_> struct RsGeo;
-template <> struct RsGeo<128> { static constexpr int INW = 448, MT = 8, RING = 16; };
-template <> struct RsGeo<64> { static constexpr int INW = 288, MT = 10, RING = 32; };
-template <int OW> constexpr size_t rs_lds_bytes() {
-  return (size_t)(RS_GI * 3 * RsGeo<OW>::INW + RsGeo<OW>::RING * 3 * OW + RS_WTAB_ROWS * (RsGeo<OW>::MT + 2)) * sizeof(float);
-}
-// which tile shape serves a resize (0: none -- the caller keeps its per-pixel kernel)
-inline int rs_pick(int H, int W, int oh, int ow, int antialias) {
-  const float sx = (float)W / (float)ow, sy = (float)H / (float)oh;
-  const float supx = antialias ? (sx >= 1.f ? sx : 1.f) : 1.f, supy = antialias ? (sy >= 1.f ? sy : 1.f) : 1.f;
-  auto fits = [&](int OW, int INW, int MT, int RING) {
-    return 2.f * supx + 2.f <= (float)MT && 2.f * supy + 2.f <= (float)MT && (float)OW * sx + 2.f * supx + 4.f + 3.f <= (float)INW &&
-           2.f * supy + 2.f + (float)RS_GI <= (float)RING;
-  };
-  if (fits(128, RsGeo<128>::INW, RsGeo<128>::MT, RsGeo<128>::RING)) return 128;
-  if (fits(64, RsGeo<64>::INW, RsGeo<64>::MT, RsGeo<64>::RING)) return 64;
-  return 0;
-}
-
-// src: frame b's three planes start at src + b * 3 * srcH * srcW; the resize reads the window rows [i0, i0 + H) x columns [j0, j0 + W) of them.
-// epi(b, oy, ox, acc[3]) receives every output pixel of the tile exactly once.
+// One tile: output columns [OW bx, OW bx + OW) x rows [strip by, strip by + strip) of the frame whose three planes start at `frame`; the resize
+// reads the window rows [i0, i0 + H) x columns [j0, j0 + W) of them.  epi(b, oy, ox, acc[3]) receives every output pixel of the tile exactly
+// once.  (bx, by, b) are workgroup-uniform: blockIdx for a clip (resize_stream_body below), a table look-up for a list of images of different
+// sizes (the *_images kernels of shell.hip).  `frame` needs 4-byte alignment only: rows go as 16-byte pieces where srcW % 4 == 0 and the planes are 16-byte
+// aligned, element by element otherwise.
 template <int OW, class Epi>
-__device__ __forceinline__ void resize_stream_body(float* __restrict__ rs_smem, const float* __restrict__ src, const int srcH, const int srcW,
+__device__ __forceinline__ void resize_stream_tile(float* __restrict__ rs_smem, const float* __restrict__ frame, const int srcH, const int srcW,
                                                    const int i0, const int j0, const int H, const int W, const int oh, const int ow,
-                                                   const int antialias, const int strip, const Epi& epi) {
+                                                   const int antialias, const int strip, const Epi& epi, const int bx, const int by, const int b) {
   constexpr int INW = RsGeo<OW>::INW, MT = RsGeo<OW>::MT, RING = RsGeo<OW>::RING, NPART = 256 / OW, RPP = RS_GI / NPART;
   float* In = rs_smem;                                   // [RS_GI][3][INW]
   float* Hr = rs_smem + RS_GI * 3 * INW;                 // [RING][3][OW]
   float* Wy = Hr + RING * 3 * OW;                        // [RS_WTAB_ROWS][MT] vertical weights | [RS_WTAB_ROWS] first row | [RS_WTAB_ROWS] tap count
   int* WyLo = reinterpret_cast<int*>(Wy + RS_WTAB_ROWS * MT);
   int* WyN = WyLo + RS_WTAB_ROWS;
-  const int ox0 = blockIdx.x * OW, oy0 = blockIdx.y * strip, b = blockIdx.z;
+  const int ox0 = bx * OW, oy0 = by * strip;
   const int oy_end = min(oh, oy0 + strip);
   const int64_t plane = (int64_t)srcH * srcW;
-  const float* base = src + (int64_t)b * 3 * plane + (int64_t)i0 * srcW + j0;      // window origin inside the frame
+  const float* base = frame + (int64_t)i0 * srcW + j0;      // window origin inside the frame
   const int tid = threadIdx.x;
   const int oxl = tid & (OW - 1), part = tid / OW;
   const int ox = min(ox0 + oxl, ow - 1);
@@ -74,7 +57,7 @@ __device__ __forceinline__ void resize_stream_body(float* __restrict__ rs_smem, 
   int x_lo, x_hi, n_;
   tap_range(ox0, W, ow, antialias, x_lo, n_);
   tap_range(min(ox0 + OW - 1, ow - 1), W, ow, antialias, x_hi, n_);
-  const bool vec = (srcW & 3) == 0 && (reinterpret_cast<uintptr_t>(src) & 15) == 0;    // block-uniform: 16-byte row pieces
+  const bool vec = (srcW & 3) == 0 && (reinterpret_cast<uintptr_t>(frame) & 15) == 0;    // block-uniform: 16-byte row pieces
   // LDS column 0 <-> window column xa: the 16-byte-aligned ABSOLUTE frame column at or below the window's first one (xa may lie up to three columns
   // left of the tile's window -- still inside the frame row: srcW % 4 == 0 keeps every piece of a row inside the row)
   const int xa = vec ? ((j0 + x_lo) & ~3) - j0 : x_lo;
@@ -181,6 +164,17 @@ __device__ __forceinline__ void resize_stream_body(float* __restrict__ rs_smem, 
       oy_next += NPART;
     }
   }
+}
+
+// src: frame b's three planes start at src + b * 3 * srcH * srcW (srcW % 4 == 0 makes every frame as aligned as the first); workgroup = tile
+// (blockIdx.x, blockIdx.y) of frame blockIdx.z.
+template <int OW, class Epi>
+__device__ __forceinline__ void resize_stream_body(float* __restrict__ rs_smem, const float* __restrict__ src, const int srcH, const int srcW,
+                                                   const int i0, const int j0, const int H, const int W, const int oh, const int ow,
+                                                   const int antialias, const int strip, const Epi& epi) {
+  const int b = blockIdx.z;
+  resize_stream_tile<OW>(rs_smem, src + (int64_t)b * 3 * srcH * srcW, srcH, srcW, i0, j0, H, W, oh, ow, antialias, strip, epi, blockIdx.x,
+                         blockIdx.y, b);
 }
 
 }  // namespace vs_rs

@@ -17,6 +17,11 @@ struct Taps {
 
 __device__ __forceinline__ float tri(float x) { x = fabsf(x); return x < 1.f ? 1.f - x : 0.f; }
 
+// source coordinate of the plain (2-tap) filter.  An explicit fma: left as `scale * (i + 0.5f) - 0.5f` hipcc contracts the expression in one
+// inlined copy and not in another -- inside one kernel, too -- and two forms of a kernel that promise the same bits (the 16-row tile and the
+// row-streaming tail, tap_range's window against make_taps' taps) disagreed in the last bits of the weights at scales that are no power of two.
+__device__ __forceinline__ float plain_src(const float scale, const int i) { return __builtin_fmaf(scale, i + 0.5f, -0.5f); }
+
 __device__ __forceinline__ Taps make_taps(int i, int in, int out, bool antialias) {
   Taps t;
   t.aa = antialias;
@@ -36,7 +41,7 @@ __device__ __forceinline__ Taps make_taps(int i, int in, int out, bool antialias
     t.total = tot;
     t.l1 = 0.f;
   } else {
-    float src = scale * (i + 0.5f) - 0.5f;
+    float src = plain_src(scale, i);
     src = src < 0.f ? 0.f : src;
     int i0 = (int)src;
     i0 = i0 > in - 1 ? in - 1 : i0;
@@ -60,7 +65,7 @@ __device__ __forceinline__ void tap_range(int i, int in, int out, bool antialias
     lo = l;
     n = h - l;
   } else {
-    float src = scale * (i + 0.5f) - 0.5f;
+    float src = plain_src(scale, i);
     src = src < 0.f ? 0.f : src;
     int i0 = (int)src;
     i0 = i0 > in - 1 ? in - 1 : i0;

@@ -4,6 +4,7 @@
 //   vs_embed_tail    : delta up-resize x JND(img) -> blend -> clamp, one pass over the frame
 // These are the HBM-bound kernels (7.08 MB read + 7.08 MB written per 768x768 frame in the tail).
 #include "shell_common.h"
+#include "images_plan.h"
 
 namespace {
 
@@ -31,19 +32,17 @@ template <> struct Px<unsigned char> {
 };
 
 
+// One 32 x 8 tile of resize_pre: output columns from ox0, rows from oy0 of the frame at `base`, stored as frame b of the destinations.
+// (ox0, oy0, b, base) are workgroup-uniform: blockIdx for a clip (resize_pre_kernel), a table look-up for a list of images (the *_images kernels below).
 template <typename T>
-__global__ __launch_bounds__(256) void resize_pre_kernel(const T* __restrict__ src, int B, int C, int H, int W, int oh, int ow,
-                                                         int antialias, float* __restrict__ dst_rgb, float mul, float add,
-                                                         float* __restrict__ dst_key, int key_step, int key_mode, float y0,
-                                                         float y1, float y2) {
+__device__ __forceinline__ void resize_pre_tile(float* __restrict__ Lw, const T* __restrict__ base, const int b, const int ox0, const int oy0,
+                                                int C, int H, int W, int oh, int ow, int antialias, float* __restrict__ dst_rgb, float mul,
+                                                float add, float* __restrict__ dst_key, int key_step, int key_mode, float y0, float y1,
+                                                float y2) {
   // The block's 32 x 8 outputs read an input window of about (32*scale + support) x (8*scale + support) pixels.  Reading it
   // tap by tap from global memory is L1-bound (4-byte loads 12 bytes apart, every line touched ~7 times), so the window is
   // staged once through LDS with coalesced loads whenever it fits; the arithmetic (and its order) is the same either way.
-  __shared__ float Lw[3 * RS_WH * RS_WW];
-  const int ox0 = blockIdx.x * 32, oy0 = blockIdx.y * 8;
-  const int b = blockIdx.z;
   const int64_t plane = (int64_t)H * W;
-  const T* base = src + (int64_t)b * C * plane;
   int x_lo, y_lo, x_hi, y_hi, n_;
   tap_range(ox0, W, ow, antialias, x_lo, n_);
   tap_range(min(ox0 + 31, ow - 1), W, ow, antialias, x_hi, n_);
@@ -165,6 +164,17 @@ __global__ __launch_bounds__(256) void resize_pre_kernel(const T* __restrict__ s
   }
 }
 
+template <typename T>
+__global__ __launch_bounds__(256) void resize_pre_kernel(const T* __restrict__ src, int B, int C, int H, int W, int oh, int ow,
+                                                         int antialias, float* __restrict__ dst_rgb, float mul, float add,
+                                                         float* __restrict__ dst_key, int key_step, int key_mode, float y0,
+                                                         float y1, float y2) {
+  __shared__ float Lw[3 * RS_WH * RS_WW];
+  const int b = blockIdx.z;
+  resize_pre_tile<T>(Lw, src + (int64_t)b * C * H * W, b, blockIdx.x * 32, blockIdx.y * 8, C, H, W, oh, ow, antialias, dst_rgb, mul, add,
+                     dst_key, key_step, key_mode, y0, y1, y2);
+}
+
 // ---- row-streaming separable form of resize_pre (round 4) -------------------------------------------------------------------------------
 // The tile kernel above stages a (32 scale + support) x (8 scale + support) window per 32 x 8 outputs: at 768 -> 256 that is 102 x 30 pixels for
 // 96 x 24 useful ones, and a 408-byte row piece at an arbitrary offset touches 4-5 cache lines -- 1.51 x the frame through HBM (calibrated
@@ -235,8 +245,12 @@ __global__ __launch_bounds__(256) void jnd_heatmap_kernel(const float* __restric
 // fetched from HBM ONCE.  (Calibrated counters, profiles/r03r_hbm_counter_calibration.md: with the second read from global memory the kernel fetches
 // 543 MiB per launch for a 216 MiB batch -- the re-read does not hit in L2 -- and runs at the 4 TB/s the HBM delivers for that traffic; KEEP with
 // 8-row tiles (24 KiB of pixels + 12 luminance rows: still three workgroups per CU) fetches 1.5 x the frame instead of 2.27 x.)
+// (the tile's body: columns from x0, rows from y0 of the frame `img` -> `outf` / `predf`; f names the frame's key frame and its rows of
+// hmap_lowres.  All of them workgroup-uniform: blockIdx for a clip (embed_tail_kernel), a table look-up for a list of images, each with its
+// own a.H x a.W (the *_images kernels below).)
 template <typename T, bool SEP, int TH, bool KEEP>
-__global__ __launch_bounds__(256) void embed_tail_kernel(TailArgs a, JndTaps k) {
+__device__ __forceinline__ void embed_tail_tile(const TailArgs& a, const JndTaps& k, const int x0, const int y0, const int f,
+                                                const T* __restrict__ img, T* __restrict__ outf, float* __restrict__ predf) {
   constexpr int TTH = TH;
   constexpr int DWH = TH == 8 ? 8 : DW_H;              // rows of the watermark's source window (8-row tiles at >= 2x up-scale need <= 8)
   __shared__ float Pk[KEEP ? 3 * TH * TTW : 4];
@@ -245,10 +259,7 @@ __global__ __launch_bounds__(256) void embed_tail_kernel(TailArgs a, JndTaps k) 
   __shared__ int ty_lo[TTH], ty_n[TTH];
   __shared__ float ty_w[TTH][4];
   __shared__ int s_xhi, s_nmax, s_xlo;
-  const int x0 = blockIdx.x * TTW, y0 = blockIdx.y * TTH, f = blockIdx.z;
   const int64_t plane = (int64_t)a.H * a.W;
-  const T* img = static_cast<const T*>(a.imgs) + (int64_t)f * 3 * plane;
-  T* outf = static_cast<T*>(a.out) + (int64_t)f * 3 * plane;
   const bool full_jnd = a.attenuate && !a.hmap_lowres;
   if (threadIdx.x == 0) { s_xhi = 0; s_nmax = 0; }
   __syncthreads();
@@ -429,8 +440,8 @@ __global__ __launch_bounds__(256) void embed_tail_kernel(TailArgs a, JndTaps k) 
           for (int c = 0; c < a.Cd; ++c) d[c] = hm * d[c];
       }
       const int64_t pix = (int64_t)y * a.W + x;
-      if (a.preds_w)
-        for (int c = 0; c < a.Cd; ++c) a.preds_w[((int64_t)f * a.Cd + c) * plane + pix] = d[c];
+      if (predf)
+        for (int c = 0; c < a.Cd; ++c) predf[c * plane + pix] = d[c];
 #pragma unroll
       for (int c = 0; c < 3; ++c) {
         float v = blend_px(a.scaling_i, a.scaling_w, px[q][c], d[a.Cd == 1 ? 0 : c], hm, fwd_order);
@@ -439,6 +450,15 @@ __global__ __launch_bounds__(256) void embed_tail_kernel(TailArgs a, JndTaps k) 
       }
     }
   }
+}
+
+template <typename T, bool SEP, int TH, bool KEEP>
+__global__ __launch_bounds__(256) void embed_tail_kernel(TailArgs a, JndTaps k) {
+  const int f = blockIdx.z;
+  const int64_t plane = (int64_t)a.H * a.W;
+  embed_tail_tile<T, SEP, TH, KEEP>(a, k, blockIdx.x * TTW, blockIdx.y * TH, f, static_cast<const T*>(a.imgs) + (int64_t)f * 3 * plane,
+                                    static_cast<T*>(a.out) + (int64_t)f * 3 * plane,
+                                    a.preds_w ? a.preds_w + (int64_t)f * a.Cd * plane : nullptr);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -685,6 +705,85 @@ __global__ __launch_bounds__(256) void embed_tail_stream_kernel(TailArgs a, JndT
 // (no waves-per-SIMD hint on the JND form: with `__launch_bounds__(256, 3)` or `(256, 4)` hipcc schedules the same body 40 % slower -- 132
 // VGPRs and three waves per SIMD either way, measured 175 -> 245-260 us at 32 x 768^2, profiles/r04_tail_forms.md)
 
+// ---------------------------------------------------------------------------------------------------
+// Lists of images of different sizes (vs_resize_pre_images, vs_embed_tail_images).  The tile bodies above with another way of finding the
+// tile: a launch is a flat list of (image, tile) items, one workgroup each, over at most VS_IMAGES_PER_LAUNCH images whose descriptors and
+// prefix table of first workgroups travel in the kernel arguments (images_plan.h).  The look-up is a function of blockIdx.x and kernel
+// arguments only -- scalar loads and five scalar compare steps -- so the image's pointer, size and frame number stay in SGPRs, as the
+// launch scalars of the clip kernels do.
+static_assert(VS_IMG_RS_TW == 32 && VS_IMG_RS_TH == 8 && VS_IMG_TAIL_TW == TTW && VS_IMG_TAIL_TH == TTH, "images_plan.h counts the tiles of these kernels");
+static_assert(VS_IMAGES_PER_LAUNCH == 32, "images_find: five halving steps");
+
+struct ImgSlot { const void* img; void* out; float* preds_w; int H, W, frame, cols; };      // cols: tiles per tile row of this image
+struct ImagesArgs {
+  int first_wg[VS_IMAGES_PER_LAUNCH + 1];      // entries past the launch's image count hold the grid size: never reached by a workgroup
+  int pad_;
+  ImgSlot slot[VS_IMAGES_PER_LAUNCH];
+};
+static_assert(sizeof(ImagesArgs) + sizeof(TailArgs) + sizeof(JndTaps) <= 3072, "descriptors + tail arguments stay well inside the 4 KiB of kernel arguments");
+
+// the image of workgroup wg: the last k with first_wg[k] <= wg
+__device__ __forceinline__ int images_find(const ImagesArgs& g, const int wg) {
+  int k = 0;
+#pragma unroll
+  for (int s = VS_IMAGES_PER_LAUNCH / 2; s >= 1; s >>= 1)
+    if (wg >= g.first_wg[k + s]) k += s;
+  return k;
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void resize_pre_images_kernel(const ImagesArgs g, const int oh, const int ow, const int antialias,
+                                                                const ResizePreEpi o) {
+  __shared__ float Lw[3 * RS_WH * RS_WW];
+  const int k = images_find(g, blockIdx.x);
+  const int t = blockIdx.x - g.first_wg[k];
+  const int cols = g.slot[k].cols;
+  const int by = t / cols, bx = t - by * cols;
+  resize_pre_tile<T>(Lw, static_cast<const T*>(g.slot[k].img), g.slot[k].frame, bx * VS_IMG_RS_TW, by * VS_IMG_RS_TH, 3, g.slot[k].H,
+                     g.slot[k].W, oh, ow, antialias, o.dst_rgb, o.mul, o.add, o.dst_key, 1, o.key_mode, o.y0c, o.y1c, o.y2c);
+}
+
+template <int OW>
+__global__ __launch_bounds__(256) void resize_pre_images_stream_kernel(const ImagesArgs g, const int oh, const int ow, const int antialias,
+                                                                       const ResizePreEpi epi, const int strip) {
+  extern __shared__ __attribute__((aligned(16))) float rs_smem[];
+  const int k = images_find(g, blockIdx.x);
+  const int t = blockIdx.x - g.first_wg[k];
+  const int cols = g.slot[k].cols;
+  const int by = t / cols, bx = t - by * cols;
+  const int H = g.slot[k].H, W = g.slot[k].W;
+  vs_rs::resize_stream_tile<OW>(rs_smem, static_cast<const float*>(g.slot[k].img), H, W, 0, 0, H, W, oh, ow, antialias, strip, epi, bx, by,
+                                g.slot[k].frame);
+}
+
+template <typename T, bool SEP>
+__global__ __launch_bounds__(256) void embed_tail_images_kernel(const ImagesArgs g, TailArgs a, const JndTaps k) {
+  const int i = images_find(g, blockIdx.x);
+  const int t = blockIdx.x - g.first_wg[i];
+  const int cols = g.slot[i].cols;
+  const int by = t / cols, bx = t - by * cols;
+  a.H = g.slot[i].H;
+  a.W = g.slot[i].W;
+  embed_tail_tile<T, SEP, TTH, false>(a, k, bx * TTW, by * TTH, g.slot[i].frame, static_cast<const T*>(g.slot[i].img),
+                                      static_cast<T*>(g.slot[i].out), g.slot[i].preds_w);
+}
+
+// kernel arguments of one group of the plan
+inline ImagesArgs images_args(const vs_image_desc_t* images, const vs_images_group_t& grp, const int kind, const int oh, const int ow) {
+  ImagesArgs g{};
+  for (int k = 0; k <= VS_IMAGES_PER_LAUNCH; ++k) g.first_wg[k] = grp.first_wg[k];
+  for (int k = 0; k < grp.count; ++k) {
+    const vs_image_desc_t& d = images[grp.image[k]];
+    int cols = (d.W + TTW - 1) / TTW;
+    if (kind == VS_IMAGES_RESIZE) {
+      const int tw = grp.form == VS_IMAGES_FORM_TILE ? VS_IMG_RS_TW : (grp.form == VS_IMAGES_FORM_STREAM128 ? 128 : 64);
+      cols = (ow + tw - 1) / tw;
+    }
+    g.slot[k] = ImgSlot{d.img, d.out, d.preds_w, d.H, d.W, grp.image[k], cols};
+  }
+  return g;
+}
+
 }  // namespace
 
 extern "C" int vs_resize_pre(const float* src, int B, int C, int H, int W, int oh, int ow, int antialias, float* dst_rgb,
@@ -783,4 +882,56 @@ extern "C" int vs_embed_tail(const vs_tail_desc_t* d, void* stream) {
     else hipLaunchKernelGGL((embed_tail_kernel<float, false, 16, false>), grid, dim3(256), 0, (hipStream_t)stream, a, k);
   }
   return vs_launch_status();
+}
+
+extern "C" int vs_resize_pre_images(const vs_image_desc_t* images, int n, int io_u8, int oh, int ow, int antialias, float* dst_rgb, float mul,
+                                    float add, float* dst_key, const float* ymat3, void* stream) {
+  VS_REQUIRE(images && n > 0 && oh > 0 && ow > 0 && (dst_rgb || dst_key));
+  for (int i = 0; i < n; ++i) VS_REQUIRE(images[i].img && images[i].H > 0 && images[i].W > 0);
+  if ((int64_t)vs_rs::rs_lds_bytes<128>() > vs_max_lds_bytes() || (int64_t)vs_rs::rs_lds_bytes<64>() > vs_max_lds_bytes()) return VS_ERR_UNSUPPORTED;
+  int n_groups = 0;      // a dry walk first: a list the plan refuses launches nothing
+  if (const int rc = vs_images_plan(images, n, VS_IMAGES_RESIZE, io_u8, oh, ow, antialias, nullptr, 0, &n_groups); rc != VS_OK) return rc;
+  const int key_mode = ymat3 ? 0 : 1;
+  const float y0 = ymat3 ? ymat3[0] : 0.f, y1 = ymat3 ? ymat3[1] : 0.f, y2 = ymat3 ? ymat3[2] : 0.f;
+  const ResizePreEpi epi{dst_rgb, dst_key, mul, add, 1, key_mode, y0, y1, y2, oh, ow};
+  const int aa = antialias ? 1 : 0;
+  return vs_images_walk(images, n, VS_IMAGES_RESIZE, io_u8 ? 1 : 0, oh, ow, aa, [&](const vs_images_group_t& grp) {
+    const ImagesArgs g = images_args(images, grp, VS_IMAGES_RESIZE, oh, ow);
+    const dim3 grid((unsigned)grp.first_wg[grp.count]);
+    if (grp.form == VS_IMAGES_FORM_STREAM128)
+      hipLaunchKernelGGL(resize_pre_images_stream_kernel<128>, grid, dim3(256), vs_rs::rs_lds_bytes<128>(), (hipStream_t)stream, g, oh, ow, aa, epi, grp.strip);
+    else if (grp.form == VS_IMAGES_FORM_STREAM64)
+      hipLaunchKernelGGL(resize_pre_images_stream_kernel<64>, grid, dim3(256), vs_rs::rs_lds_bytes<64>(), (hipStream_t)stream, g, oh, ow, aa, epi, grp.strip);
+    else if (io_u8)
+      hipLaunchKernelGGL(resize_pre_images_kernel<unsigned char>, grid, dim3(256), 0, (hipStream_t)stream, g, oh, ow, aa, epi);
+    else
+      hipLaunchKernelGGL(resize_pre_images_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, g, oh, ow, aa, epi);
+    return vs_launch_status();
+  });
+}
+
+extern "C" int vs_embed_tail_images(const vs_tail_images_desc_t* d, void* stream) {
+  VS_REQUIRE(d && d->images && d->n > 0 && d->delta && d->S_h > 0 && d->S_w > 0 && (d->Cd == 1 || d->Cd == 3));
+  for (int i = 0; i < d->n; ++i) VS_REQUIRE(d->images[i].img && d->images[i].out && d->images[i].H > 0 && d->images[i].W > 0);
+  VS_REQUIRE(!(d->attenuate && !d->hmap_lowres) || d->taps43);
+  VS_REQUIRE(!d->io_u8 || d->clamp);        // (x * 255).byte() is only defined for x in [0, 1]
+  if (d->attenuate != 0 && d->attenuate != 1) return VS_ERR_UNSUPPORTED;      // (2: the training forward's order, clips only)
+  int n_groups = 0;
+  if (const int rc = vs_images_plan(d->images, d->n, VS_IMAGES_TAIL, d->io_u8, d->S_h, d->S_w, d->antialias, nullptr, 0, &n_groups); rc != VS_OK) return rc;
+  // F = total_key = n, step 1, 'repeat': frame i of delta / hmap_lowres belongs to image i; H and W are the image's (set per workgroup)
+  const TailArgs a{nullptr, nullptr, nullptr, d->delta, d->attenuate ? d->hmap_lowres : nullptr, d->n, 0, 0, d->S_h, d->S_w, d->Cd, 1,
+                   VS_VIDEO_REPEAT, d->n, d->attenuate, d->clamp, d->antialias, d->scaling_i, d->scaling_w};
+  JndTaps k{};
+  if (d->taps43) k = taps_from(d->taps43);
+  const bool full_jnd = d->attenuate && !d->hmap_lowres;
+  const bool sep = full_jnd && standard_jnd_taps(d->taps43);
+  return vs_images_walk(d->images, d->n, VS_IMAGES_TAIL, d->io_u8 ? 1 : 0, d->S_h, d->S_w, d->antialias ? 1 : 0, [&](const vs_images_group_t& grp) {
+    const ImagesArgs g = images_args(d->images, grp, VS_IMAGES_TAIL, d->S_h, d->S_w);
+    const dim3 grid((unsigned)grp.first_wg[grp.count]);
+    // (uint8 images keep the 43-tap form, as uint8 clips do)
+    if (d->io_u8) hipLaunchKernelGGL((embed_tail_images_kernel<unsigned char, false>), grid, dim3(256), 0, (hipStream_t)stream, g, a, k);
+    else if (sep) hipLaunchKernelGGL((embed_tail_images_kernel<float, true>), grid, dim3(256), 0, (hipStream_t)stream, g, a, k);
+    else hipLaunchKernelGGL((embed_tail_images_kernel<float, false>), grid, dim3(256), 0, (hipStream_t)stream, g, a, k);
+    return vs_launch_status();
+  });
 }

@@ -1594,6 +1594,44 @@ class HipEngine:
                        imgs.numel() * imgs.element_size() + 16 * S[0] * S[1] * ((B if rgb else 0) + (nk if key else 0)))
         return rgb, key
 
+    def resize_pre_images(self, imgs, S: Tuple[int, int], antialias: bool, *, want_rgb: bool, mul=1.0, add=0.0, want_key: bool = False,
+                          tag="rs") -> Tuple[Optional[Act], Optional[Act]]:
+        """resize_pre on a list of device images of different sizes (all fp32 [3,H,W] or all uint8 RGB24 [H,W,3], contiguous): image i
+        becomes frame i -> (rgb Act [n,S,S,4] or None, key Act [n,S,S,4] or None), each frame with the bits resize_pre gives that image."""
+        n = len(imgs)
+        u8 = imgs[0].dtype == torch.uint8
+        rgb = self.new_act(tag + ".rgb", n, S[0], S[1], 3, 4) if want_rgb else None
+        key = self.new_act(tag + ".key", n, S[0], S[1], self.cfg.in_ch, 4) if want_key else None
+        ymat = self.ymat if self.cfg.yuv else None
+        descs = N.image_descs(imgs)
+        ev = self._shell_t0()
+        N.check(self.lib.vs_resize_pre_images(descs, n, int(u8), S[0], S[1], 1 if antialias else 0, N.ptr(rgb.t) if rgb else None, mul, add,
+                                              N.ptr(key.t) if key else None, ymat, N.stream()), "vs_resize_pre_images")
+        self._shell_t1(ev, "resize_pre_images_kernel" + ("<u8>" if u8 else ""),
+                       sum(t.numel() * t.element_size() for t in imgs) + 16 * S[0] * S[1] * n * (int(rgb is not None) + int(key is not None)))
+        return rgb, key
+
+    def embed_tail_images(self, imgs, outs, delta, *, hmap_low, attenuate, clamp, antialias, scaling_i, scaling_w, preds_w=None):
+        """embed_tail (one frame, step 1) on a list of device images: image i takes frame i of delta [n,Cd,S,S] and of hmap_low; outs[i]
+        (and preds_w[i], fp32 [Cd,H,W]) are written with the bits embed_tail gives that image."""
+        n = len(imgs)
+        u8 = imgs[0].dtype == torch.uint8
+        for t, o in zip(imgs, outs):
+            if o.dtype != t.dtype or o.shape != t.shape:
+                raise ValueError("every image needs an output of its own shape and dtype")
+        d = N.TailImagesDesc()
+        descs = N.image_descs(imgs, outs, preds_w)
+        d.images, d.n = descs, n
+        d.delta, d.hmap_lowres = N.ptr(delta), N.ptr(hmap_low)
+        d.taps43 = C.cast(self.taps43, C.c_void_p)
+        d.S_h, d.S_w, d.Cd = delta.shape[-2], delta.shape[-1], delta.shape[1]
+        d.attenuate, d.clamp, d.antialias, d.io_u8 = int(attenuate), int(clamp), int(antialias), int(u8)
+        d.scaling_i, d.scaling_w = float(scaling_i), float(scaling_w)
+        ev = self._shell_t0()
+        N.check(self.lib.vs_embed_tail_images(C.byref(d), N.stream()), "vs_embed_tail_images")
+        self._shell_t1(ev, "embed_tail_images_kernel" + ("<u8>" if u8 else ""), 2 * sum(t.numel() * t.element_size() for t in imgs)
+                       + (sum(p.numel() * 4 for p in preds_w) if preds_w is not None else 0) + delta.numel() * 4)
+
     def _shell_t0(self):
         if self.shell_timers is None or torch.cuda.is_current_stream_capturing():
             return None

@@ -565,6 +565,132 @@ class Wam(nn.Module):
             x = N.f32c(imgs.to(eng.dev))
             return {"preds": self._detect_frames(eng, x, (self.img_size, self.img_size), aa).to(imgs.device)}
 
+    # ---- lists of images of different sizes: one network pass per chunk of the list, the two full-resolution passes on the list itself
+    @staticmethod
+    def _image_list(imgs, what: str):
+        """-> (the images as [3, H, W] float or [H, W, 3] uint8 views, uint8?)"""
+        imgs = list(imgs)
+        if not all(torch.is_tensor(t) for t in imgs):
+            raise TypeError(f"{what} wants a sequence of tensors")
+        if len({t.dtype for t in imgs}) > 1:
+            raise ValueError(f"{what}: the images of one call are all fp32 [3, H, W] or all uint8 [H, W, 3], got {sorted({str(t.dtype) for t in imgs})}")
+        u8 = bool(imgs) and imgs[0].dtype == torch.uint8
+        if imgs and not (u8 or imgs[0].is_floating_point()):
+            raise ValueError(f"{what}: images are fp32 [3, H, W] or uint8 [H, W, 3], got {imgs[0].dtype}")
+        views = []
+        for t in imgs:
+            v = t[0] if (not u8 and t.dim() == 4 and t.shape[0] == 1) else t
+            if v.dim() != 3 or v.shape[-1 if u8 else 0] != 3 or 0 in v.shape:
+                raise ValueError(f"{what}: " + ("uint8 images are RGB24 [H, W, 3]" if u8 else "fp32 images are [3, H, W] or [1, 3, H, W]") +
+                                 f", got {tuple(t.shape)}")
+            views.append(v)
+        return views, u8
+
+    def _image_chunks(self, eng: HipEngine, views, u8: bool, fn, restart=None) -> None:
+        """Drive `fn(chunk_on_device, a, b)` over the list in chunks of chunk_size images.  Images that are not on the model's device move one
+        chunk at a time; such a call synchronises before it returns, so the range guard of its passes is read here and a data-dependent
+        overflow repeats the call on the exact split (as _run_chunks does for a clip)."""
+        ck = max(1, int(getattr(self, "chunk_size", 32)))
+        on_dev = all(v.device == eng.dev for v in views)
+        for attempt in range(2):
+            for a in range(0, len(views), ck):
+                b = min(len(views), a + ck)
+                ch = [v if v.device == eng.dev else v.to(eng.dev) for v in views[a:b]]
+                fn([t.contiguous() if u8 else N.f32c(t) for t in ch], a, b)
+            if on_dev:
+                break
+            torch.cuda.current_stream(eng.dev).synchronize()
+            if attempt or not eng.guard_tripped_after_sync():
+                break
+            if restart is not None:
+                restart()
+
+    @torch.no_grad()
+    def embed_images(self, imgs, msgs: torch.Tensor = None, interpolation: dict = None, lowres_attenuation: bool = False) -> dict:
+        """`embed(img[None], msg[None], is_video=False)` (wam.py:134-204) for every image of a list whose images differ in size, with the
+        network running once per chunk_size images instead of once per image.  imgs: n tensors, all fp32 [3, H_i, W_i] (or [1, 3, H_i, W_i])
+        or all uint8 RGB24 [H_i, W_i, 3] (needs clamp=True); msgs [n, k] or None (random).  -> {'imgs_w': list, 'preds_w': list of fp32
+        [Cd, H_i, W_i], 'msgs'}: every result has the shape of its input on its input's device; for device-resident images they are views
+        of one allocation per call.  Per chunk: one resize launch group over the chunk (vs_resize_pre_images), one embedder pass, one
+        low-resolution heat-map when asked, one tail over the chunk (vs_embed_tail_images) -- the pieces of `embed`, so image i equals
+        what the per-image pieces give up to the batch size of the network pass.  Always eager (no hipGraph route)."""
+        imgs = list(imgs)
+        views, u8 = self._image_list(imgs, "embed_images")
+        n = len(views)
+        if u8 and not self.clamp:
+            raise NotImplementedError("uint8 output needs clamp=True ((x * 255).byte() is undefined outside [0, 1])")
+        if msgs is None:
+            msgs = self.get_random_msg(n)
+        elif msgs.shape[0] != n:
+            raise ValueError(f"msgs has {msgs.shape[0]} rows for {n} images")
+        eng = self._engine()
+        aa = _antialias_flag(interpolation)
+        cd = self.embedder.cfg.out_ch
+        if n == 0:
+            return {"msgs": msgs, "preds_w": [], "imgs_w": []}
+        S = (self.img_size, self.img_size)
+        att = self.attenuation is not None
+        lowres = bool(lowres_attenuation)
+        odt = torch.uint8 if u8 else torch.float32
+        hw = [(v.shape[0], v.shape[1]) if u8 else (v.shape[1], v.shape[2]) for v in views]
+        lead = [(1,) if (not u8 and t.dim() == 4) else () for t in imgs]
+        on_dev = all(v.device == eng.dev for v in views)
+        outs, pws = [None] * n, [None] * n
+
+        def carve(a, b):
+            """results of images [a, b) as views of one device allocation each"""
+            o = torch.empty(sum(3 * h * w for h, w in hw[a:b]), dtype=odt, device=eng.dev)
+            p = torch.empty(sum(cd * h * w for h, w in hw[a:b]), dtype=torch.float32, device=eng.dev)
+            oo, pp, io, ip = [], [], 0, 0
+            for h, w in hw[a:b]:
+                oo.append(o[io:io + 3 * h * w].view((h, w, 3) if u8 else (3, h, w)))
+                pp.append(p[ip:ip + cd * h * w].view(cd, h, w))
+                io, ip = io + 3 * h * w, ip + cd * h * w
+            return oo, pp
+
+        with torch.cuda.device(eng.dev):
+            mi = self._msgs_dev(msgs, eng.dev)
+            if on_dev:
+                outs, pws = carve(0, n)
+
+            def one(ch, a, b):
+                oo, pp = (outs[a:b], pws[a:b]) if on_dev else carve(a, b)
+                rgb, key = eng.resize_pre_images(ch, S, aa, want_rgb=(att and lowres), want_key=True)
+                delta = eng.embedder_forward(key, mi[a:b], bn_train=self.embedder.training)
+                hmap = eng.jnd_lowres(rgb) if (att and lowres) else None
+                eng.embed_tail_images(ch, oo, delta, hmap_low=hmap, attenuate=int(att), clamp=self.clamp, antialias=aa,
+                                      scaling_i=self.blender.scaling_i, scaling_w=self.blender.scaling_w, preds_w=pp)
+                if not on_dev:        # back to where each image came from (_image_chunks synchronises before it returns)
+                    for i in range(a, b):
+                        if outs[i] is None:
+                            outs[i] = _result_buffer(oo[i - a].shape, odt, views[i].device)
+                            pws[i] = _result_buffer(pp[i - a].shape, torch.float32, views[i].device)
+                        outs[i].copy_(oo[i - a], non_blocking=True)
+                        pws[i].copy_(pp[i - a], non_blocking=True)
+            self._image_chunks(eng, views, u8, one)
+        return {"msgs": msgs, "preds_w": [p.view(ld + tuple(p.shape)) for p, ld in zip(pws, lead)],
+                "imgs_w": [o.view(ld + tuple(o.shape)) for o, ld in zip(outs, lead)]}
+
+    @torch.no_grad()
+    def detect_images(self, imgs, interpolation: dict = None) -> dict:
+        """`detect` (wam.py:206-234) on a list of images of different sizes (see embed_images): one resize launch group and one extractor pass
+        per chunk_size images -> {'preds'}: what detect returns for n stacked frames of the processing size, on the first image's device."""
+        views, u8 = self._image_list(imgs, "detect_images")
+        eng = self._engine()
+        aa = _antialias_flag(interpolation)
+        if not views:
+            return {"preds": torch.zeros(self._empty_preds_shape())}
+        S = (self.img_size, self.img_size)
+        preds = []
+
+        def one(ch, a, b):
+            rgb, _ = eng.resize_pre_images(ch, S, aa, want_rgb=True, mul=2.0, add=-1.0, tag="det.in")
+            p = eng.extractor_forward(rgb)
+            preds.append(p if eng.preds_owned else p.clone())
+        with torch.cuda.device(eng.dev):
+            self._image_chunks(eng, views, u8, one, restart=preds.clear)
+            return {"preds": torch.cat(preds, dim=0).to(views[0].device)}
+
     def _augment_detect(self, eng: HipEngine, imgs_w: torch.Tensor, imgs: torch.Tensor, masks, is_video: bool, aa: bool):
         """wam.py:115-125 / videoseal.py:231-243: augment -> resize to the processing size -> detector (device tensors)."""
         from . import augmentation as A

@@ -48,6 +48,7 @@ EXPORTS = [
     "vs_sizeof_yuv420_surface", "vs_sizeof_tail_yuv420_desc", "vs_resize_pre_yuv420", "vs_embed_tail_yuv420", "vs_yuv420_default_color",
     "vs_model_embed_yuv420", "vs_model_detect_yuv420",
     "vs_sizeof_yuv_surface", "vs_sizeof_tail_yuv_desc", "vs_resize_pre_yuv", "vs_embed_tail_yuv", "vs_model_embed_yuv", "vs_model_detect_yuv",
+    "vs_resize_pre_images", "vs_embed_tail_images", "vs_images_plan",
 ]
 
 
@@ -162,6 +163,56 @@ def yuv_surface(planes, fmt: str) -> YuvSurface:
     return s
 
 
+IMAGES_PER_LAUNCH = 32                                       # VS_IMAGES_PER_LAUNCH
+IMAGES_RESIZE, IMAGES_TAIL = 0, 1                            # VS_IMAGES_RESIZE / VS_IMAGES_TAIL: the pass a plan is for
+IMAGES_FORM_TILE, IMAGES_FORM_STREAM128, IMAGES_FORM_STREAM64 = 0, 1, 2
+
+
+class ImageDesc(C.Structure):
+    """mirror of vs_image_desc_t: one image of a list, its own base pointer(s) and size"""
+    _fields_ = [("img", C.c_void_p), ("out", C.c_void_p), ("preds_w", C.c_void_p), ("H", C.c_int32), ("W", C.c_int32)]
+
+
+class TailImagesDesc(C.Structure):
+    """mirror of vs_tail_images_desc_t: the tail parameters every image shares and the list"""
+    _fields_ = [
+        ("images", C.POINTER(ImageDesc)), ("delta", C.c_void_p), ("hmap_lowres", C.c_void_p), ("taps43", C.c_void_p),
+        ("n", C.c_int32), ("S_h", C.c_int32), ("S_w", C.c_int32), ("Cd", C.c_int32),
+        ("attenuate", C.c_int32), ("clamp", C.c_int32), ("antialias", C.c_int32), ("io_u8", C.c_int32),
+        ("scaling_i", C.c_float), ("scaling_w", C.c_float),
+    ]
+
+
+class ImagesGroup(C.Structure):
+    """mirror of vs_images_group_t: one launch of the plan"""
+    _fields_ = [("form", C.c_int32), ("count", C.c_int32), ("strip", C.c_int32), ("reserved_", C.c_int32),
+                ("image", C.c_int32 * IMAGES_PER_LAUNCH), ("first_wg", C.c_int32 * (IMAGES_PER_LAUNCH + 1))]
+
+
+def image_descs(imgs, outs=None, preds_w=None):
+    """the HOST descriptor array of a list of device images (fp32 [3, H, W] or uint8 [H, W, 3], contiguous): addresses and sizes, nothing is copied"""
+    arr = (ImageDesc * max(1, len(imgs)))()
+    for i, t in enumerate(imgs):
+        H, W = (t.shape[0], t.shape[1]) if t.dtype == torch.uint8 else (t.shape[-2], t.shape[-1])
+        arr[i].img, arr[i].H, arr[i].W = ptr(t), H, W
+        arr[i].out = ptr(outs[i]) if outs is not None else None
+        arr[i].preds_w = ptr(preds_w[i]) if preds_w is not None else None
+    return arr
+
+
+def images_plan(sizes, kind: int, io_u8: bool, oh: int, ow: int, antialias: bool):
+    """vs_images_plan on a list of (H, W): the launches as [(form, strip, [image indices], [first workgroups ..., grid])] (no GPU involved)"""
+    L = lib()
+    arr = (ImageDesc * max(1, len(sizes)))()
+    for i, (H, W) in enumerate(sizes):
+        arr[i].H, arr[i].W = H, W
+    n = C.c_int(0)
+    check(L.vs_images_plan(arr, len(sizes), kind, int(io_u8), oh, ow, int(antialias), None, 0, C.byref(n)), "vs_images_plan")
+    groups = (ImagesGroup * max(1, n.value))()
+    check(L.vs_images_plan(arr, len(sizes), kind, int(io_u8), oh, ow, int(antialias), groups, n.value, C.byref(n)), "vs_images_plan")
+    return [(g.form, g.strip, list(g.image[:g.count]), list(g.first_wg[:g.count + 1])) for g in groups[:n.value]]
+
+
 class ResblockThinDesc(C.Structure):
     """mirror of vs_resblock_thin_desc_t"""
     _fields_ = [
@@ -235,6 +286,9 @@ def lib() -> C.CDLL:
         "vs_yuv420_default_color": [I, P, P],
         "vs_resize_pre_yuv": [C.POINTER(YuvSurface), I, I, I, P, I, I, I, P, F, F, P, I, P, P],
         "vs_embed_tail_yuv": [C.POINTER(TailYuvDesc), P],
+        "vs_resize_pre_images": [C.POINTER(ImageDesc), I, I, I, I, I, P, F, F, P, P, P],
+        "vs_embed_tail_images": [C.POINTER(TailImagesDesc), P],
+        "vs_images_plan": [C.POINTER(ImageDesc), I, I, I, I, I, I, C.POINTER(ImagesGroup), I, C.POINTER(C.c_int)],
         "vs_aug_color": [P, P, I, I, I, I, F, P, P],
         "vs_aug_crop_flip": [P, P, I, I, I, I, I, I, I, I, P],
         "vs_aug_color_chain": [P, P, I, I, I, I, C.POINTER(C.c_int), C.POINTER(C.c_float), P, P],
