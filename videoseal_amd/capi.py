@@ -146,66 +146,60 @@ class CModel:
         return logits
 
     @staticmethod
-    def _yuv420_color(fmt: str, color):
+    def _yuv_color(depth: int, color):
         """(yuv2rgb12, rgb2yuv12) host arrays for `color` = (matrix, full_range), or (None, None) = the library's default at that depth"""
         if color is None:
             return None, None
-        from .yuv420 import color_affine, fmt_info
-        fwd, inv = color_affine(color[0], bool(color[1]), fmt_info(fmt)[1])
+        from .yuv import color_affine
+        fwd, inv = color_affine(color[0], bool(color[1]), depth)
         return (C.c_float * 12)(*[float(v) for v in inv.reshape(-1)]), (C.c_float * 12)(*[float(v) for v in fwd.reshape(-1)])
+
+    def _embed_yuv(self, module, surface, entry, planes, fmt, msgs, out_planes, color, step, video_mode, lowres_attenuation, antialias):
+        """one body for embed_yuv420 and embed_yuv: `module` checks the format, `surface` makes the surface type of the library's
+        entry point `entry`"""
+        from .yuv import Clip
+        F_, H, W = module.check_clip(planes, fmt)
+        src = Clip(planes, fmt)
+        dst = Clip(out_planes, fmt) if out_planes is not None else src.empty_like()
+        m = msgs.to(device=src.device, dtype=torch.int32).contiguous()
+        ws = self._workspace(F_, H, W, step)
+        dec, enc = self._yuv_color(module.fmt_info(fmt)[1], color)
+        sin, sout = surface(src.planes, fmt), surface(dst.planes, fmt)
+        N.check(entry(self._h, C.byref(sin), C.byref(sout), dec, enc, N.ptr(m), m.shape[0], F_, H, W, step, video_mode, int(lowres_attenuation),
+                      int(antialias), N.ptr(ws), ws.numel(), N.stream()), entry.__name__)
+        return dst.planes
+
+    def _detect_yuv(self, module, surface, entry, planes, fmt, color, antialias) -> torch.Tensor:
+        from .yuv import Clip
+        F_, H, W = module.check_clip(planes, fmt)
+        src = Clip(planes, fmt)
+        logits = torch.empty(F_, self.cfg.nbits + 1, device=src.device)
+        ws = self._workspace(F_, H, W, 1)
+        dec, _ = self._yuv_color(module.fmt_info(fmt)[1], color)
+        sin = surface(src.planes, fmt)
+        N.check(entry(self._h, C.byref(sin), dec, F_, H, W, int(antialias), N.ptr(logits), N.ptr(ws), ws.numel(), N.stream()), entry.__name__)
+        return logits
 
     def embed_yuv420(self, planes, fmt: str, msgs: torch.Tensor, *, out_planes=None, color=None, step: int = 1, video_mode: int = 0,
                      lowres_attenuation: bool = False, antialias: bool = True):
         """vs_model_embed_yuv420 on device-resident planes (any pitches); `out_planes`: where the watermarked clip goes (default: a new
         packed clip).  `color` = (matrix, full_range) or None = NULL affines.  Returns the output planes."""
-        from .yuv420 import Clip420, check_clip
-        F_, H, W = check_clip(planes, fmt)
-        src = Clip420(planes, fmt)
-        dst = Clip420(out_planes, fmt) if out_planes is not None else src.empty_like()
-        m = msgs.to(device=src.device, dtype=torch.int32).contiguous()
-        ws = self._workspace(F_, H, W, step)
-        dec, enc = self._yuv420_color(fmt, color)
-        sin, sout = N.yuv420_surface(src.planes, fmt), N.yuv420_surface(dst.planes, fmt)
-        N.check(self._L.vs_model_embed_yuv420(self._h, C.byref(sin), C.byref(sout), dec, enc, N.ptr(m), m.shape[0], F_, H, W, step, video_mode,
-                                              int(lowres_attenuation), int(antialias), N.ptr(ws), ws.numel(), N.stream()), "vs_model_embed_yuv420")
-        return dst.planes
+        from . import yuv420
+        return self._embed_yuv(yuv420, N.yuv420_surface, self._L.vs_model_embed_yuv420, planes, fmt, msgs, out_planes, color, step, video_mode,
+                               lowres_attenuation, antialias)
 
     def detect_yuv420(self, planes, fmt: str, *, color=None, antialias: bool = True) -> torch.Tensor:
-        from .yuv420 import Clip420, check_clip
-        F_, H, W = check_clip(planes, fmt)
-        src = Clip420(planes, fmt)
-        logits = torch.empty(F_, self.cfg.nbits + 1, device=src.device)
-        ws = self._workspace(F_, H, W, 1)
-        dec, _ = self._yuv420_color(fmt, color)
-        sin = N.yuv420_surface(src.planes, fmt)
-        N.check(self._L.vs_model_detect_yuv420(self._h, C.byref(sin), dec, F_, H, W, int(antialias), N.ptr(logits), N.ptr(ws), ws.numel(),
-                                               N.stream()), "vs_model_detect_yuv420")
-        return logits
+        from . import yuv420
+        return self._detect_yuv(yuv420, N.yuv420_surface, self._L.vs_model_detect_yuv420, planes, fmt, color, antialias)
 
     def embed_yuv(self, planes, fmt: str, msgs: torch.Tensor, *, out_planes=None, color=None, step: int = 1, video_mode: int = 0,
                   lowres_attenuation: bool = False, antialias: bool = True):
         """vs_model_embed_yuv on device-resident planes of any of the ten formats (yuv.py; any pitches); `out_planes`, `color` and the
         result as for embed_yuv420."""
         from . import yuv
-        F_, H, W = yuv.check_clip(planes, fmt)
-        src = yuv.clip(planes, fmt)
-        dst = yuv.clip(out_planes, fmt) if out_planes is not None else src.empty_like()
-        m = msgs.to(device=src.device, dtype=torch.int32).contiguous()
-        ws = self._workspace(F_, H, W, step)
-        dec, enc = self._yuv420_color("p010" if yuv.fmt_info(fmt)[1] == 10 else "nv12", color)          # (the affines depend on the depth alone)
-        sin, sout = N.yuv_surface(src.planes, fmt), N.yuv_surface(dst.planes, fmt)
-        N.check(self._L.vs_model_embed_yuv(self._h, C.byref(sin), C.byref(sout), dec, enc, N.ptr(m), m.shape[0], F_, H, W, step, video_mode,
-                                           int(lowres_attenuation), int(antialias), N.ptr(ws), ws.numel(), N.stream()), "vs_model_embed_yuv")
-        return dst.planes
+        return self._embed_yuv(yuv, N.yuv_surface, self._L.vs_model_embed_yuv, planes, fmt, msgs, out_planes, color, step, video_mode,
+                               lowres_attenuation, antialias)
 
     def detect_yuv(self, planes, fmt: str, *, color=None, antialias: bool = True) -> torch.Tensor:
         from . import yuv
-        F_, H, W = yuv.check_clip(planes, fmt)
-        src = yuv.clip(planes, fmt)
-        logits = torch.empty(F_, self.cfg.nbits + 1, device=src.device)
-        ws = self._workspace(F_, H, W, 1)
-        dec, _ = self._yuv420_color("p010" if yuv.fmt_info(fmt)[1] == 10 else "nv12", color)
-        sin = N.yuv_surface(src.planes, fmt)
-        N.check(self._L.vs_model_detect_yuv(self._h, C.byref(sin), dec, F_, H, W, int(antialias), N.ptr(logits), N.ptr(ws), ws.numel(),
-                                            N.stream()), "vs_model_detect_yuv")
-        return logits
+        return self._detect_yuv(yuv, N.yuv_surface, self._L.vs_model_detect_yuv, planes, fmt, color, antialias)

@@ -332,7 +332,7 @@ class HipEngine:
         self.Et = None         # embedder weights with BatchNorm NOT folded (batch-statistics forward under model.train())
         self.X = None
         self.ymat = self.taps43 = None
-        self._yuv420_arrays = {}         # 4:2:0 clips: the (yuv2rgb12, rgb2yuv12) float arrays per (matrix, full_range, depth)
+        self._yuv_arrays = {}            # YUV clips: the (yuv2rgb12, rgb2yuv12) float arrays per (matrix, full_range, depth)
         self._pack_misc()
 
     def _fetch(self, k: str) -> torch.Tensor:
@@ -1496,61 +1496,51 @@ class HipEngine:
         return self._pixel_decoder(n3, V)
 
     # ------------------------------------------------------------------ shell
-    def yuv420_arrays(self, color, depth: int):
+    def yuv_arrays(self, color, depth: int):
         """(yuv2rgb12, rgb2yuv12) as host arrays of 12 floats for `color` = (matrix, full_range) in code units of a surface's depth; built
-        in float64 by yuv420.color_affine, rounded to fp32 once (the affines depend on the depth alone: 4:2:0, 4:2:2 and 4:4:4 clips share them)"""
+        in float64 by yuv.color_affine, rounded to fp32 once (the affines depend on the depth alone: 4:2:0, 4:2:2 and 4:4:4 clips share them)"""
         key = (color[0], bool(color[1]), int(depth))
-        if key not in self._yuv420_arrays:
-            from .yuv420 import color_affine
+        if key not in self._yuv_arrays:
+            from .yuv import color_affine
             fwd, inv = color_affine(*key)
-            self._yuv420_arrays[key] = ((C.c_float * 12)(*[float(v) for v in inv.reshape(-1)]), (C.c_float * 12)(*[float(v) for v in fwd.reshape(-1)]))
-        return self._yuv420_arrays[key]
+            self._yuv_arrays[key] = ((C.c_float * 12)(*[float(v) for v in inv.reshape(-1)]), (C.c_float * 12)(*[float(v) for v in fwd.reshape(-1)]))
+        return self._yuv_arrays[key]
 
     @staticmethod
-    def _yuv_abi(clip):
-        """the entry points a clip's class selects: yuv420.Clip420 -> the _yuv420 pair, yuv.ClipYuv (4:2:2, 4:4:4) -> the _yuv pair.
-        (surface maker, tail descriptor, suffix of the entry points' names, samples per frame)"""
-        from .yuv import ClipYuv, frame_samples
-        from .yuv420 import Clip420
-        if isinstance(clip, ClipYuv):
-            return N.yuv_surface, N.TailYuvDesc, "yuv", frame_samples(clip.fmt, clip.shape[1], clip.shape[2])
-        if isinstance(clip, Clip420):
-            return N.yuv420_surface, N.TailYuv420Desc, "yuv420", clip.shape[1] * clip.shape[2] * 3 // 2
-        raise TypeError(f"frames must be a tensor, a yuv420.Clip420 or a yuv.ClipYuv, got {type(clip).__name__}")
+    def _yuv_clip(clip):
+        """a non-tensor frames argument is a yuv.Clip (device-resident planes at any pitch, its format and colour choice): (depth, samples per frame)"""
+        from .yuv import Clip, fmt_info, frame_samples
+        if not isinstance(clip, Clip):
+            raise TypeError(f"frames must be a tensor or a yuv.Clip, got {type(clip).__name__}")
+        return fmt_info(clip.fmt)[1], frame_samples(clip.fmt, clip.shape[1], clip.shape[2])
 
-    def _resize_pre_yuv420(self, clip, S, antialias, *, want_rgb, mul, add, want_key, key_step, tag):
-        """resize_pre on a YUV clip (yuv420.Clip420 or yuv.ClipYuv: device-resident planes at any pitch, its format and colour choice)"""
-        from .yuv import fmt_info
+    def _resize_pre_yuv(self, clip, S, antialias, *, want_rgb, mul, add, want_key, key_step, tag):
+        """resize_pre on a YUV clip of any of the ten formats (a 4:2:0 one reaches the _yuv420 launches through the library's forwarder)"""
         B, H, W = clip.shape
-        surface, _, sfx, nsamp = self._yuv_abi(clip)
+        depth, nsamp = self._yuv_clip(clip)
         rgb = self.new_act(tag + ".rgb", B, S[0], S[1], 3, 4) if want_rgb else None
         nk = (B + key_step - 1) // key_step
         key = self.new_act(tag + ".key", nk, S[0], S[1], self.cfg.in_ch, 4) if want_key else None
-        depth = fmt_info(clip.fmt)[1]
-        surf = surface(clip.planes, clip.fmt)
+        surf = N.yuv_surface(clip.planes, clip.fmt)
         ev = self._shell_t0()
-        N.check(getattr(self.lib, "vs_resize_pre_" + sfx)(C.byref(surf), B, H, W, self.yuv420_arrays(clip.color, depth)[0], S[0], S[1],
-                                                          1 if antialias else 0, N.ptr(rgb.t) if rgb else None, mul, add,
-                                                          N.ptr(key.t) if key else None, key_step, self.ymat if self.cfg.yuv else None,
-                                                          N.stream()), "vs_resize_pre_" + sfx)
+        N.check(self.lib.vs_resize_pre_yuv(C.byref(surf), B, H, W, self.yuv_arrays(clip.color, depth)[0], S[0], S[1], 1 if antialias else 0,
+                                           N.ptr(rgb.t) if rgb else None, mul, add, N.ptr(key.t) if key else None, key_step,
+                                           self.ymat if self.cfg.yuv else None, N.stream()), "vs_resize_pre_yuv")
         # algorithmic HBM bytes: the frame's samples (1.5, 2 or 3 per pixel) once + the low-resolution outputs
         self._shell_t1(ev, f"resize_pre_yuv_kernel<{clip.fmt}>",
                        B * nsamp * clip.planes[0].element_size() + 16 * S[0] * S[1] * ((B if rgb else 0) + (nk if key else 0)))
         return rgb, key
 
-    def _embed_tail_yuv420(self, clip, out, delta, *, step, video_mode, hmap_low, attenuate, clamp, antialias, scaling_i, scaling_w, preds_w=None):
-        """embed_tail on YUV clips: `clip` and `out` are yuv420.Clip420 or yuv.ClipYuv of one format and size, each plane with its own pitch"""
-        from .yuv import fmt_info
-        surface, Desc, sfx, nsamp = self._yuv_abi(clip)
+    def _embed_tail_yuv(self, clip, out, delta, *, step, video_mode, hmap_low, attenuate, clamp, antialias, scaling_i, scaling_w, preds_w=None):
+        """embed_tail on YUV clips: `clip` and `out` are yuv.Clip of one format and size, each plane with its own pitch"""
+        depth, nsamp = self._yuv_clip(clip)
         if type(out) is not type(clip) or out.fmt != clip.fmt or out.shape != clip.shape:
-            raise ValueError("4:2:0 frames need an output clip of the same format and size" if sfx == "yuv420" else
-                             "YUV frames need an output clip of the same format and size")
+            raise ValueError("YUV frames need an output clip of the same format and size")
         if preds_w is not None or int(attenuate) == 2:
-            raise NotImplementedError("the 4:2:0 tail has no preds_w and no training order of operations" if sfx == "yuv420" else
-                                      "the YUV tail has no preds_w and no training order of operations")
+            raise NotImplementedError("the YUV tail has no preds_w and no training order of operations")
         F_, H, W = clip.shape
-        d = Desc()
-        d.src, d.dst = surface(clip.planes, clip.fmt), surface(out.planes, out.fmt)
+        d = N.TailYuvDesc()
+        d.src, d.dst = N.yuv_surface(clip.planes, clip.fmt), N.yuv_surface(out.planes, out.fmt)
         d.preds_w = None
         d.delta, d.hmap_lowres = N.ptr(delta), N.ptr(hmap_low)
         d.taps43 = C.cast(self.taps43, C.c_void_p)
@@ -1559,18 +1549,18 @@ class HipEngine:
         d.attenuate, d.clamp, d.antialias = int(attenuate), int(clamp), int(antialias)
         d.scaling_i, d.scaling_w = float(scaling_i), float(scaling_w)
         d.variant = 1 if int(self.tail_variant) in (1, 2, 3) else 0           # (the tile variants of the fp32 tail -> the tile kernel)
-        d.yuv2rgb12, d.rgb2yuv12 = self.yuv420_arrays(clip.color, fmt_info(clip.fmt)[1])
+        d.yuv2rgb12, d.rgb2yuv12 = self.yuv_arrays(clip.color, depth)
         ev = self._shell_t0()
-        N.check(getattr(self.lib, "vs_embed_tail_" + sfx)(C.byref(d), N.stream()), "vs_embed_tail_" + sfx)
+        N.check(self.lib.vs_embed_tail_yuv(C.byref(d), N.stream()), "vs_embed_tail_yuv")
         # algorithmic HBM bytes: the frame's samples (1.5, 2 or 3 per pixel) each way + the low-resolution watermark
         self._shell_t1(ev, f"embed_tail_yuv_kernel<{clip.fmt}>", 2 * (F_ * nsamp) * clip.planes[0].element_size() + delta.numel() * 4)
 
     def resize_pre(self, imgs: torch.Tensor, S: Tuple[int, int], antialias: bool, *, want_rgb: bool, mul=1.0, add=0.0,
                    want_key: bool = False, key_step: int = 1, tag="rs") -> Tuple[Optional[Act], Optional[Act]]:
-        """imgs on device, fp32 NCHW [B,3,H,W], uint8 RGB24 [B,H,W,3] or a YUV clip (yuv420.Clip420, yuv.ClipYuv)
+        """imgs on device, fp32 NCHW [B,3,H,W], uint8 RGB24 [B,H,W,3] or a YUV clip (yuv.Clip)
         -> (rgb Act [B,S,S,4] or None, key Act [ceil(B/step),S,S,4] or None)."""
-        if not torch.is_tensor(imgs):         # a YUV clip carries its own format and colour choice; its class selects the entry points
-            return self._resize_pre_yuv420(imgs, S, antialias, want_rgb=want_rgb, mul=mul, add=add, want_key=want_key, key_step=key_step, tag=tag)
+        if not torch.is_tensor(imgs):         # a YUV clip carries its own format and colour choice
+            return self._resize_pre_yuv(imgs, S, antialias, want_rgb=want_rgb, mul=mul, add=add, want_key=want_key, key_step=key_step, tag=tag)
         u8 = imgs.dtype == torch.uint8
         if u8:
             B, H, W, Cc = imgs.shape
@@ -1660,9 +1650,9 @@ class HipEngine:
 
     def embed_tail(self, imgs, out, delta, *, step, video_mode, hmap_low, attenuate, clamp, antialias, scaling_i, scaling_w,
                    preds_w=None):
-        if not torch.is_tensor(imgs):         # a YUV clip (yuv420.Clip420, yuv.ClipYuv)
-            return self._embed_tail_yuv420(imgs, out, delta, step=step, video_mode=video_mode, hmap_low=hmap_low, attenuate=attenuate, clamp=clamp,
-                                           antialias=antialias, scaling_i=scaling_i, scaling_w=scaling_w, preds_w=preds_w)
+        if not torch.is_tensor(imgs):         # a YUV clip (yuv.Clip)
+            return self._embed_tail_yuv(imgs, out, delta, step=step, video_mode=video_mode, hmap_low=hmap_low, attenuate=attenuate, clamp=clamp,
+                                        antialias=antialias, scaling_i=scaling_i, scaling_w=scaling_w, preds_w=preds_w)
         d = N.TailDesc()
         u8 = imgs.dtype == torch.uint8          # RGB24 [F,H,W,3] in and out
         if u8:

@@ -127,17 +127,20 @@ class TailYuv420Desc(C.Structure):
     ]
 
 
-def yuv420_surface(planes, fmt: str) -> Yuv420Surface:
-    """the surface of device-resident planes (videoseal_amd/yuv420.py): addresses and strides of the tensors, nothing is copied"""
-    from .yuv420 import fmt_info
-    planar, depth, msb = fmt_info(fmt)
-    s = Yuv420Surface()
+def _fill_surface(s, planes, planar: bool, depth: int, msb: bool):
+    """plane addresses, row pitches and frame strides in bytes and the format triple of device-resident planes: nothing is copied"""
     for i, p in enumerate(planes):
         s.plane[i] = ptr(p)
         s.pitch[i] = p.stride(1) * p.element_size()
         s.frame_stride[i] = p.stride(0) * p.element_size()
     s.planar, s.depth, s.msb_aligned = int(planar), depth, int(msb)
     return s
+
+
+def yuv420_surface(planes, fmt: str) -> Yuv420Surface:
+    """the surface of device-resident planes of a 4:2:0 format (videoseal_amd/yuv420.py), for the _yuv420 entry points"""
+    from .yuv420 import fmt_info
+    return _fill_surface(Yuv420Surface(), planes, *fmt_info(fmt))
 
 
 class YuvSurface(C.Structure):
@@ -151,15 +154,11 @@ class TailYuvDesc(C.Structure):
 
 
 def yuv_surface(planes, fmt: str) -> YuvSurface:
-    """the surface of device-resident planes of any of the ten formats (videoseal_amd/yuv.py): addresses and strides, nothing is copied"""
+    """the surface of device-resident planes of any of the ten formats (videoseal_amd/yuv.py)"""
     from .yuv import fmt_info
     planar, depth, msb, chroma = fmt_info(fmt)
-    s = YuvSurface()
-    for i, p in enumerate(planes):
-        s.plane[i] = ptr(p)
-        s.pitch[i] = p.stride(1) * p.element_size()
-        s.frame_stride[i] = p.stride(0) * p.element_size()
-    s.planar, s.depth, s.msb_aligned, s.chroma = int(planar), depth, int(msb), chroma
+    s = _fill_surface(YuvSurface(), planes, planar, depth, msb)
+    s.chroma = chroma
     return s
 
 

@@ -12,7 +12,7 @@ Limited range codes: Y -> 16 + 219 Y, C -> 128 + 224 C; full range codes: Y -> 2
 Chroma.  Up: every pixel of a 2 x 2 block uses that block's (Cb, Cr).  Down: the mean of the four per-pixel chroma values, then one rounding.
 Range and rounding.  After NV12 -> RGB every channel is clamped to [0, 1]; output codes are floor(clamp(v, 0, 255) + 0.5), v in code units.
 
-The arithmetic is yuv420.py's for fmt "nv12" (depth 8) on the planes `clip[:, :H]` and `clip[:, H:]`; this module holds the single-buffer
+The arithmetic is yuv.py's for fmt "nv12" (depth 8) on the planes `clip[:, :H]` and `clip[:, H:]`; this module holds the single-buffer
 layout and the two matrices of the NV12 entry points.
 """
 from __future__ import annotations
@@ -22,10 +22,10 @@ from typing import Tuple
 import numpy as np
 import torch
 
-from . import yuv420
+from . import yuv
 
-MATRICES = {k: yuv420.MATRICES[k] for k in ("bt601", "bt709")}
-DEFAULT_COLOR = yuv420.DEFAULT_COLOR
+MATRICES = {k: yuv.MATRICES[k] for k in ("bt601", "bt709")}
+DEFAULT_COLOR = yuv.DEFAULT_COLOR
 
 
 def _known(matrix: str) -> str:
@@ -37,7 +37,7 @@ def _known(matrix: str) -> str:
 def color_affine(matrix: str = "bt709", full_range: bool = False) -> Tuple[np.ndarray, np.ndarray]:
     """(rgb2yuv, yuv2rgb): two float64 [3, 4] arrays.  rgb2yuv maps (R, G, B, 1) in [0, 1] to (Y, Cb, Cr) in code units, yuv2rgb is its
     inverse (codes -> RGB in [0, 1], before the clamp)."""
-    return yuv420.color_affine(_known(matrix), full_range, 8)
+    return yuv.color_affine(_known(matrix), full_range, 8)
 
 
 def check_clip(clip: torch.Tensor, what: str = "NV12 clip") -> Tuple[int, int, int]:
@@ -60,9 +60,9 @@ def planes(clip: torch.Tensor, what: str = "NV12 clip") -> Tuple[torch.Tensor, t
 
 def nv12_to_rgb(clip: torch.Tensor, matrix: str = "bt709", full_range: bool = False, dtype=torch.float32) -> torch.Tensor:
     """uint8 [F, 3H/2, W] -> `dtype` RGB [F, 3, H, W], clamped to [0, 1]"""
-    return yuv420.to_rgb(planes(clip), "nv12", _known(matrix), full_range, dtype)
+    return yuv.to_rgb(planes(clip), "nv12", _known(matrix), full_range, dtype)
 
 
 def rgb_to_nv12(x01: torch.Tensor, matrix: str = "bt709", full_range: bool = False) -> torch.Tensor:
     """RGB [F, 3, H, W] in [0, 1] (fp32 or float64) -> contiguous uint8 [F, 3H/2, W]"""
-    return torch.cat(yuv420.from_rgb(x01, "nv12", _known(matrix), full_range), dim=1)
+    return torch.cat(yuv.from_rgb(x01, "nv12", _known(matrix), full_range), dim=1)

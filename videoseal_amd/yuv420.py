@@ -1,36 +1,19 @@
-"""4:2:0 clips: the definitions of `Videoseal.embed_yuv420` / `detect_yuv420` as executable text (plain torch, any device).
-
-Layout.  A clip is a tuple of plane tensors on one device, H and W even:
-    fmt          dtype    planes
-    "nv12"       uint8    (y [F, H, W], uv [F, H/2, W])              uv[..., 2j], uv[..., 2j+1] = Cb, Cr of block j
-    "i420"       uint8    (y [F, H, W], u [F, H/2, W/2], v [F, H/2, W/2])
-    "p010"       uint16   as nv12; sample code = word >> 6 (the low 6 bits are ignored on input and zero on output)
-    "yuv420p10"  uint16   as i420; sample code = min(word, 1023)
-Every plane has last stride 1 and its own row pitch (>= the row) and frame stride: `AVFrame.data[i]` / `linesize[i]` map to strided views,
-not copies.  int16 tensors are accepted as the same bits as uint16.  `planes_of` cuts the planes out of a packed per-frame buffer (Y, then
-U, then V -- or Y, then UV: the byte order of ffmpeg's `rawvideo`), `pack` is its inverse.
-
-Colour.  `matrix` is "bt601" (Kr, Kb = 0.299, 0.114), "bt709" (0.2126, 0.0722) or "bt2020" (0.2627, 0.0593), Kg = 1 - Kr - Kb:
-    Y = Kr R + Kg G + Kb B,   Cb = (B - Y) / (2 (1 - Kb)),   Cr = (R - Y) / (2 (1 - Kr))
-Codes at depth 8: limited range Y -> 16 + 219 Y, C -> 128 + 224 C; full range Y -> 255 Y, C -> 128 + 255 C.
-Codes at depth 10: limited range Y -> 64 + 876 Y, C -> 512 + 896 C; full range Y -> 1023 Y, C -> 512 + 1023 C.
-`color_affine` builds the forward 3 x 4 affine (RGB in [0, 1] -> code units) in float64 and inverts it in float64.
-
-Chroma.  Up: every pixel of a 2 x 2 block uses that block's (Cb, Cr).  Down: the mean of the four per-pixel chroma values, then one rounding.
-Range and rounding.  After decoding every RGB channel is clamped to [0, 1]; output codes are floor(clamp(v, 0, 2^depth - 1) + 0.5), v in code
-units -- one rounding, no intermediate RGB24.
+"""4:2:0 clips: the definitions of `Videoseal.embed_yuv420` / `detect_yuv420`.  The text lives in yuv.py (layout, colour, chroma, rounding,
+the arithmetic and the clip class); this module is its restriction to the four 4:2:0 formats "nv12", "i420", "p010" and "yuv420p10" (H and
+W even, 3HW/2 samples per packed frame), under the names and signatures the 4:2:0 callers use.
 """
 from __future__ import annotations
 
 from typing import Sequence, Tuple
 
-import numpy as np
 import torch
 
-MATRICES = {"bt601": (0.299, 0.114), "bt709": (0.2126, 0.0722), "bt2020": (0.2627, 0.0593)}
-DEFAULT_COLOR = ("bt709", False)
+from . import yuv
+from .yuv import DEFAULT_COLOR, MATRICES, _as_words, _codes, _words, color_affine  # noqa: F401  (re-exported: one colour definition)
+
 #            planar, depth, msb_aligned
-FORMATS = {"nv12": (False, 8, False), "i420": (True, 8, False), "p010": (False, 10, True), "yuv420p10": (True, 10, False)}
+FORMATS = {k: v[:3] for k, v in yuv.FORMATS.items() if v[3] == 420}
+Clip420 = yuv.Clip
 
 
 def fmt_info(fmt: str) -> Tuple[bool, int, bool]:
@@ -41,198 +24,34 @@ def fmt_info(fmt: str) -> Tuple[bool, int, bool]:
 
 
 def fmt_dtype(fmt: str) -> torch.dtype:
-    return torch.uint8 if fmt_info(fmt)[1] == 8 else torch.uint16
-
-
-def color_affine(matrix: str = "bt709", full_range: bool = False, depth: int = 8) -> Tuple[np.ndarray, np.ndarray]:
-    """(rgb2yuv, yuv2rgb): two float64 [3, 4] arrays.  rgb2yuv maps (R, G, B, 1) in [0, 1] to (Y, Cb, Cr) in code units of `depth`, yuv2rgb is
-    its inverse (codes -> RGB in [0, 1], before the clamp)."""
-    if matrix not in MATRICES:
-        raise ValueError(f"matrix must be one of {sorted(MATRICES)}, got {matrix!r}")
-    if depth not in (8, 10):
-        raise ValueError(f"depth must be 8 or 10, got {depth!r}")
-    kr, kb = MATRICES[matrix]
-    kg = 1.0 - kr - kb
-    y = np.array([kr, kg, kb], dtype=np.float64)
-    cb = (np.array([0.0, 0.0, 1.0]) - y) / (2.0 * (1.0 - kb))
-    cr = (np.array([1.0, 0.0, 0.0]) - y) / (2.0 * (1.0 - kr))
-    if depth == 8:
-        ys, cs, y0, c0 = (255.0, 255.0, 0.0, 128.0) if full_range else (219.0, 224.0, 16.0, 128.0)
-    else:
-        ys, cs, y0, c0 = (1023.0, 1023.0, 0.0, 512.0) if full_range else (876.0, 896.0, 64.0, 512.0)
-    fwd = np.zeros((3, 4), dtype=np.float64)
-    fwd[0, :3], fwd[0, 3] = ys * y, y0
-    fwd[1, :3], fwd[1, 3] = cs * cb, c0
-    fwd[2, :3], fwd[2, 3] = cs * cr, c0
-    # inverse by cofactors, every product and sum in float64 and in this order: csrc/model_api.hip states the same expressions for
-    # vs_yuv420_default_color, and tests/test_yuv420_cpu.py and tests/test_nv12_cpu.py hold them to the same bits
-    a = [[float(fwd[i, j]) for j in range(3)] for i in range(3)]
-    cof = [[a[(i + 1) % 3][(j + 1) % 3] * a[(i + 2) % 3][(j + 2) % 3] - a[(i + 1) % 3][(j + 2) % 3] * a[(i + 2) % 3][(j + 1) % 3]
-            for j in range(3)] for i in range(3)]
-    det = a[0][0] * cof[0][0] + a[0][1] * cof[0][1] + a[0][2] * cof[0][2]
-    inv = np.zeros((3, 4), dtype=np.float64)
-    for i in range(3):
-        for j in range(3):
-            inv[i, j] = cof[j][i] / det
-        inv[i, 3] = -(inv[i, 0] * float(fwd[0, 3]) + inv[i, 1] * float(fwd[1, 3]) + inv[i, 2] * float(fwd[2, 3]))
-    return fwd, inv
-
-
-def _as_words(p: torch.Tensor) -> torch.Tensor:
-    return p.view(torch.uint16) if torch.is_tensor(p) and p.dtype == torch.int16 else p
+    fmt_info(fmt)
+    return yuv.fmt_dtype(fmt)
 
 
 def check_clip(planes: Sequence[torch.Tensor], fmt: str, what: str = "4:2:0 clip") -> Tuple[int, int, int]:
     """(F, H, W) of a valid clip; ValueError otherwise"""
-    planar, depth, _ = fmt_info(fmt)
-    if not isinstance(planes, (tuple, list)) or len(planes) != (3 if planar else 2) or not all(torch.is_tensor(p) for p in planes):
-        raise ValueError(f"{what}: {fmt} wants a tuple of {3 if planar else 2} plane tensors")
-    planes = [_as_words(p) for p in planes]
-    want = fmt_dtype(fmt)
-    if any(p.dtype != want or p.dim() != 3 for p in planes):
-        raise ValueError(f"{what}: {fmt} planes are {want} tensors [F, rows, samples]")
-    if any(p.device != planes[0].device for p in planes):
-        raise ValueError(f"{what}: the planes must be on one device")
-    F_, H, W = planes[0].shape
-    if H % 2 or W % 2:
-        raise ValueError(f"{what}: H and W must be even (got {H} x {W})")
-    cshape = (F_, H // 2, W // 2) if planar else (F_, H // 2, W)
-    if any(tuple(p.shape) != cshape for p in planes[1:]):
-        raise ValueError(f"{what}: a {fmt} clip with luma {tuple(planes[0].shape)} has chroma planes {cshape}, got {[tuple(p.shape) for p in planes[1:]]}")
-    if any(p.numel() > 0 and p.stride(2) != 1 for p in planes):
-        raise ValueError(f"{what}: the last dimension of every plane must have stride 1")
-    return F_, H, W
+    fmt_info(fmt)
+    return yuv.check_clip(planes, fmt, what)
 
 
 def planes_of(buf: torch.Tensor, fmt: str, H: int, W: int) -> Tuple[torch.Tensor, ...]:
     """plane views of a packed buffer [F, 3HW/2] (or any shape with F leading and 3HW/2 samples per frame): Y, then U, then V (or Y, then UV)"""
-    planar, _, _ = fmt_info(fmt)
-    buf = _as_words(buf)
-    if buf.dtype != fmt_dtype(fmt) or H % 2 or W % 2:
-        raise ValueError(f"planes_of: {fmt} wants a {fmt_dtype(fmt)} buffer and even H, W")
-    F_, n = buf.shape[0], H * W * 3 // 2
-    if buf.numel() != F_ * n or not buf.is_contiguous():
-        raise ValueError(f"planes_of: want a contiguous buffer of {n} samples per frame")
-    flat = buf.reshape(F_, n)
-    y = flat[:, :H * W].view(F_, H, W)
-    if not planar:
-        return y, flat[:, H * W:].view(F_, H // 2, W)
-    q = H * W // 4
-    return y, flat[:, H * W:H * W + q].view(F_, H // 2, W // 2), flat[:, H * W + q:].view(F_, H // 2, W // 2)
+    fmt_info(fmt)
+    return yuv.planes_of(buf, fmt, H, W)
 
 
 def pack(planes: Sequence[torch.Tensor]) -> torch.Tensor:
     """contiguous [F, 3HW/2] buffer holding the planes in order (the inverse of planes_of)"""
-    planes = [_as_words(p) for p in planes]
-    return torch.cat([p.reshape(p.shape[0], -1) for p in planes], dim=1).contiguous()
-
-
-def _codes(p: torch.Tensor, depth: int, msb: bool) -> torch.Tensor:
-    """stored words -> int32 sample codes"""
-    if depth == 8:
-        return p.to(torch.int32)
-    w = _as_words(p).view(torch.int16).to(torch.int32) & 0xFFFF
-    return (w >> 6) if msb else w.clamp(max=1023)
-
-
-def _words(code: torch.Tensor, depth: int, msb: bool) -> torch.Tensor:
-    """integer-valued float codes -> stored words"""
-    if depth == 8:
-        return code.to(torch.uint8)
-    w = code.to(torch.int32)
-    if msb:
-        w = w << 6
-    w = torch.where(w >= 32768, w - 65536, w)          # the same 16 bits as a signed value
-    return w.to(torch.int16).view(torch.uint16)
+    return yuv.pack(planes)
 
 
 def to_rgb(planes: Sequence[torch.Tensor], fmt: str, matrix: str = "bt709", full_range: bool = False, dtype=torch.float32) -> torch.Tensor:
     """clip -> `dtype` RGB [F, 3, H, W], clamped to [0, 1]"""
-    planar, depth, msb = fmt_info(fmt)
-    F_, H, W = check_clip(planes, fmt)
-    fwd, inv = color_affine(matrix, full_range, depth)
-    dev = planes[0].device
-    m = torch.tensor(inv, dtype=dtype, device=dev)
-    # the affine as A^-1 (code - offset): the offsets are subtracted exactly, so no large constant is cancelled in fp32
-    y = _codes(planes[0], depth, msb).to(dtype) - float(fwd[0, 3])
-    if planar:
-        c = torch.stack([_codes(planes[1], depth, msb), _codes(planes[2], depth, msb)], dim=-1).to(dtype)
-    else:
-        c = _codes(planes[1], depth, msb).reshape(F_, H // 2, W // 2, 2).to(dtype)
-    c = c.repeat_interleave(2, dim=1).repeat_interleave(2, dim=2)
-    cb, cr = c[..., 0] - float(fwd[1, 3]), c[..., 1] - float(fwd[2, 3])
-    rgb = torch.stack([m[i, 0] * y + m[i, 1] * cb + m[i, 2] * cr for i in range(3)], dim=1)
-    return rgb.clamp(0.0, 1.0)
+    fmt_info(fmt)
+    return yuv.to_rgb(planes, fmt, matrix, full_range, dtype)
 
 
 def from_rgb(x01: torch.Tensor, fmt: str, matrix: str = "bt709", full_range: bool = False) -> Tuple[torch.Tensor, ...]:
     """RGB [F, 3, H, W] in [0, 1] (fp32 or float64) -> contiguous planes of `fmt`"""
-    planar, depth, msb = fmt_info(fmt)
-    if x01.dim() != 4 or x01.shape[1] != 3 or x01.shape[2] % 2 or x01.shape[3] % 2:
-        raise ValueError("from_rgb wants [F, 3, H, W] with even H and W")
-    F_, _, H, W = x01.shape
-    fwd, _ = color_affine(matrix, full_range, depth)
-    m = torch.tensor(fwd, dtype=x01.dtype, device=x01.device)
-    r, g, b = x01[:, 0], x01[:, 1], x01[:, 2]
-    yuv = [m[i, 0] * r + m[i, 1] * g + m[i, 2] * b + m[i, 3] for i in range(3)]
-    top = float((1 << depth) - 1)
-
-    def words(v):
-        return _words(torch.floor(v.clamp(0.0, top) + 0.5), depth, msb)
-    if planar:
-        u, v = (c.reshape(F_, H // 2, 2, W // 2, 2).mean(dim=(2, 4)) for c in (yuv[1], yuv[2]))
-        return words(yuv[0]), words(u), words(v)
-    cbcr = torch.stack([yuv[1], yuv[2]], dim=-1)                                       # [F, H, W, 2]
-    cbcr = cbcr.reshape(F_, H // 2, 2, W // 2, 2, 2).mean(dim=(2, 4)).reshape(F_, H // 2, W)
-    return words(yuv[0]), words(cbcr)
-
-
-class Clip420:
-    """The planes of a clip with the handful of tensor operations the model's chunk loop uses (slice by frames, move, copy), so that a clip
-    walks `Videoseal._run_chunks` like a tensor does.  `color` = (matrix, full_range) travels with the clip."""
-
-    def __init__(self, planes, fmt: str, color=DEFAULT_COLOR, buf: torch.Tensor = None):
-        self.planes = tuple(_as_words(p) for p in planes)
-        self.fmt, self.color, self.buf = fmt, (color[0], bool(color[1])), buf
-        F_, H, W = self.planes[0].shape
-        self.shape = (F_, H, W)
-
-    dtype = property(lambda self: self.planes[0].dtype)
-    device = property(lambda self: self.planes[0].device)
-    graph_key = property(lambda self: (self.fmt, self.color))
-
-    def dim(self) -> int:
-        return 0            # (not a tensor: no frame layout of the tensor paths applies)
-
-    def numel(self) -> int:
-        return sum(p.numel() for p in self.planes)
-
-    def __len__(self) -> int:
-        return self.shape[0]
-
-    def __getitem__(self, s) -> "Clip420":
-        if not isinstance(s, slice):
-            raise TypeError("a clip is sliced by frame ranges")
-        return Clip420([p[s] for p in self.planes], self.fmt, self.color, self.buf[s] if self.buf is not None else None)
-
-    def empty_like(self, device=None) -> "Clip420":
-        """a new packed clip of the same format and size (the planes are views of one contiguous buffer, `buf`)"""
-        F_, H, W = self.shape
-        buf = torch.empty((F_, H * W * 3 // 2), dtype=self.dtype, device=self.device if device is None else device)
-        return Clip420(planes_of(buf, self.fmt, H, W), self.fmt, self.color, buf)
-
-    def contiguous(self) -> "Clip420":
-        if self.buf is not None and self.buf.is_contiguous():
-            return self
-        return self.clone()
-
-    def clone(self) -> "Clip420":
-        return self.empty_like().copy_(self)
-
-    def to(self, device) -> "Clip420":
-        return Clip420([p.to(device) for p in self.planes], self.fmt, self.color)
-
-    def copy_(self, other: "Clip420", non_blocking: bool = False) -> "Clip420":
-        for d, s in zip(self.planes, other.planes):
-            d.copy_(s, non_blocking=non_blocking)
-        return self
+    fmt_info(fmt)
+    return yuv.from_rgb(x01, fmt, matrix, full_range)
