@@ -7,9 +7,13 @@
 // Nothing but x, y (and the gradient) touches HBM; there are no atomics anywhere: the statistics are per-block partial sums in double, summed in a fixed
 // order by a second tiny launch, and the adjoint is a gather.
 //
-// Conditioning: the variances are shift invariant, so the moments are taken of x - data_range / 2 (|.| <= 0.5 instead of <= 1 for frames in [0, 1]), which
-// quarters the cancellation error of E[x^2] - mu^2 against C2 = 9e-4 in flat regions; the luminance factor adds the shift back, and the terms the shift leaves
-// behind because the fp32 window does not sum to exactly 1 are restored (ssim_point): the same function in exact arithmetic.
+// Conditioning: the variances are shift invariant, so the moments are taken of x - c, c = the smallest pixel of x and y among the rows and columns the
+// WORKGROUP reads (block_shift: one more pass over its input, a min through LDS; a function of the data and the grid alone, so two launches still agree bit
+// for bit).  0 <= x - c <= x: the cancellation error of E[x^2] - mu^2 against C2 = 9e-4 is never above that of the reference's own unshifted fp32 formula, on
+// black frames and letterbox bars (c = 0: the reference's arithmetic itself) as on any other, and far below it on bright flat regions (c ~ the level).  A
+// constant shift of data_range / 2 (what this file did before) quarters the error at mid-grey but turns a black window into 0.25 - 0.25: 100 x the
+// reference's error there (tests/test_gpu_loss_envelope.py, kinds `dark` and `dark-bars`).  The luminance factor adds the shift back, and the terms the
+// shift leaves behind because the fp32 window does not sum to exactly 1 are restored (ssim_point): the same function in exact arithmetic.
 #include "vs_common.h"
 
 namespace {
@@ -27,7 +31,9 @@ inline unsigned gridx(int64_t n, int per = 256, int64_t cap = 4096) {
   return (unsigned)(g > cap ? cap : (g < 1 ? 1 : g));
 }
 
-// horizontal 11-tap filter of the five moments at column t of the raw row in LDS
+// horizontal 11-tap filter of the five moments at column t of the raw row in LDS.  The fused multiply-adds are written out, here and in the vertical
+// filter (vfilter5): left to the compiler's contraction the fifth moment, which has no partner for a packed instruction, was rounded differently from
+// the other four, and for x == y the three second moments must be the same number (cs = 1 to an ulp, as in the reference's fp32 formula).
 __device__ __forceinline__ void hfilter5(const float* __restrict__ rx, const float* __restrict__ ry, int t, const SsimWin& g, float (&h)[5]) {
   h[0] = h[1] = h[2] = h[3] = h[4] = 0.f;
 #pragma unroll
@@ -36,28 +42,66 @@ __device__ __forceinline__ void hfilter5(const float* __restrict__ rx, const flo
     const float px = g.w[j] * xv, py = g.w[j] * yv;
     h[0] += px;
     h[1] += py;
-    h[2] += px * xv;
-    h[3] += py * yv;
-    h[4] += px * yv;
+    h[2] = __builtin_fmaf(px, xv, h[2]);
+    h[3] = __builtin_fmaf(py, yv, h[3]);
+    h[4] = __builtin_fmaf(px, yv, h[4]);
+  }
+}
+// vertical 11-tap filter: the ring's rows s + 1 .. s + 11 (mod 11), oldest first
+__device__ __forceinline__ void vfilter5(const float (&ring)[5][TAPS], int s, const SsimWin& g, float (&m)[5]) {
+  m[0] = m[1] = m[2] = m[3] = m[4] = 0.f;
+#pragma unroll
+  for (int k = 0; k < TAPS; ++k) {
+#pragma unroll
+    for (int q = 0; q < 5; ++q) m[q] = __builtin_fmaf(g.w[k], ring[q][(s + 1 + k) % TAPS], m[q]);
   }
 }
 
 // SSIM and contrast-structure value of one map position from the five filtered moments of the SHIFTED frames (losses/ssim.py:94-103)
 struct SsimPoint { float ssim, cs, l, inv_dc, inv_dl, M1, M2; };
 // The fp32 window does not sum to 1 exactly (S = (sum w)^2 of the separable filter = 1 - O(1e-8)) and the reference's sigmas are sum(w x^2) - (sum(w x))^2 with THAT window, so in
-// terms of the shifted moments (c = shift):  mu = m' + c S,  sigma = (e' - m'^2) + 2 c (1 - S) m' + c^2 S (1 - S)  (k1 = c (1 - S), k2 = c^2 S (1 - S), from
-// the host in double).  The correction is ~1e-8, but it is divided by sigma_x^2 + sigma_y^2 + C2 >= 9e-4: without it the mean SSIM is off by ~1e-6.
+// terms of the shifted moments (c = shift):  mu = m' + c S,  sigma = (e' - m'^2) + 2 c (1 - S) m' + c^2 S (1 - S)  (k1 = c (1 - S), k2 = c^2 S (1 - S), in
+// double from the workgroup's c and the host's S: make_shift).  The correction is ~1e-8, but it is divided by sigma_x^2 + sigma_y^2 + C2 >= 9e-4: without it the mean SSIM is off by ~1e-6.
 struct SsimShift { float c, cS, k1, k2; };
+__device__ __forceinline__ SsimShift make_shift(float c, double S) {
+  const double cd = (double)c;
+  return SsimShift{c, (float)(cd * S), (float)(cd * (1.0 - S)), (float)(cd * cd * S * (1.0 - S))};
+}
+// the workgroup's shift: the smallest value of x and y in rows [row0, row1) at the columns ca (where va) and cb (where vb) of its NT threads -- the very
+// pixels its row loop reads.  lds: NT floats, free again on return.  A plane of NaNs or infinities gets no shift.
+__device__ __forceinline__ float block_shift(const float* __restrict__ xp, const float* __restrict__ yp, int W, int row0, int row1, int ca, bool va, int cb,
+                                             bool vb, float* lds) {
+  const int t = threadIdx.x;
+  float mn = __builtin_inff();
+  for (int r = row0; r < row1; ++r) {
+    const int64_t o = (int64_t)r * W;
+    if (va) mn = fminf(mn, fminf(xp[o + ca], yp[o + ca]));
+    if (vb) mn = fminf(mn, fminf(xp[o + cb], yp[o + cb]));
+  }
+  lds[t] = mn;
+  __syncthreads();
+  for (int o = NT / 2; o > 0; o >>= 1) {
+    if (t < o) lds[t] = fminf(lds[t], lds[t + o]);
+    __syncthreads();
+  }
+  const float c = lds[0];
+  __syncthreads();
+  return fabsf(c) < __builtin_inff() ? c : 0.f;
+}
 __device__ __forceinline__ SsimPoint ssim_point(const float (&m)[5], const SsimShift sh, float C1, float C2) {
   SsimPoint p;
-  const float s1 = (m[2] - m[0] * m[0]) + (2.f * sh.k1 * m[0] + sh.k2), s2 = (m[3] - m[1] * m[1]) + (2.f * sh.k1 * m[1] + sh.k2);
-  const float s12 = (m[4] - m[0] * m[1]) + (sh.k1 * (m[0] + m[1]) + sh.k2);
+  // the three (co)variances by the same fused operations, the three products of the means rounded alike: for x == y numerator and denominator of
+  // both factors are the same number
+  const float s1 = __builtin_fmaf(-m[0], m[0], m[2]) + __builtin_fmaf(2.f * sh.k1, m[0], sh.k2);
+  const float s2 = __builtin_fmaf(-m[1], m[1], m[3]) + __builtin_fmaf(2.f * sh.k1, m[1], sh.k2);
+  const float s12 = __builtin_fmaf(-m[0], m[1], m[4]) + __builtin_fmaf(sh.k1, m[0] + m[1], sh.k2);
   p.M1 = m[0] + sh.cS;
   p.M2 = m[1] + sh.cS;
+  const float q11 = __fmul_rn(p.M1, p.M1), q22 = __fmul_rn(p.M2, p.M2), q12 = __fmul_rn(p.M1, p.M2);
   p.inv_dc = 1.0f / (s1 + s2 + C2);
-  p.inv_dl = 1.0f / (p.M1 * p.M1 + p.M2 * p.M2 + C1);
-  p.cs = (2.f * s12 + C2) * p.inv_dc;
-  p.l = (2.f * p.M1 * p.M2 + C1) * p.inv_dl;
+  p.inv_dl = 1.0f / (__fadd_rn(q11, q22) + C1);
+  p.cs = (__fadd_rn(s12, s12) + C2) * p.inv_dc;
+  p.l = (__fadd_rn(q12, q12) + C1) * p.inv_dl;
   p.ssim = p.l * p.cs;
   return p;
 }
@@ -65,8 +109,7 @@ __device__ __forceinline__ SsimPoint ssim_point(const float (&m)[5], const SsimS
 // ---------------------------------------------------------------------------------------------------------------------------- statistics
 // grid: (strips of NT map columns, chunks of `rows` map rows, planes).  partial[((plane * chunks + chunk) * strips + strip) * 2 + {ssim, cs}]
 __global__ __launch_bounds__(NT) void ssim_stats_kernel(const float* __restrict__ x, const float* __restrict__ y, int H, int W, int rows, SsimWin g,
-                                                        SsimShift sh, float C1, float C2, double* __restrict__ partial) {
-  const float shift = sh.c;
+                                                        double S, float C1, float C2, double* __restrict__ partial) {
   __shared__ float raw[2][2][RAWW];
   __shared__ double red[2][NT];
   const int t = threadIdx.x;
@@ -81,6 +124,8 @@ __global__ __launch_bounds__(NT) void ssim_stats_kernel(const float* __restrict_
   const int ca = m0 + t, cb = m0 + NT + t;
   const bool va = ca < W, vb = t < HALO && cb < W;
   const bool mvalid = ca < Wm;
+  const SsimShift sh = make_shift(block_shift(xp, yp, W, o0, o0 + nin, ca, va, cb, vb, raw[0][0]), S);
+  const float shift = sh.c;
   float ax = 0.f, ay = 0.f, bx = 0.f, by = 0.f;                    // the next row, in flight
   {
     const int64_t r = (int64_t)o0 * W;
@@ -109,12 +154,8 @@ __global__ __launch_bounds__(NT) void ssim_stats_kernel(const float* __restrict_
 #pragma unroll
       for (int q = 0; q < 5; ++q) ring[q][s] = h[q];
       if (i >= HALO) {
-        float m[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int k = 0; k < TAPS; ++k) {
-#pragma unroll
-          for (int q = 0; q < 5; ++q) m[q] += g.w[k] * ring[q][(s + 1 + k) % TAPS];
-        }
+        float m[5];
+        vfilter5(ring, s, g, m);
         const SsimPoint p = ssim_point(m, sh, C1, C2);
         if (mvalid) { acc_s += (double)p.ssim; acc_c += (double)p.cs; }
       }
@@ -153,8 +194,7 @@ __global__ __launch_bounds__(64) void ssim_finish_kernel(const double* __restric
 // c0 - 10 + t twice: as a map column (moments, coefficients) and, 10 columns later in the filter, as a gradient column (t >= 10).
 __global__ __launch_bounds__(NT) void ssim_grad_kernel(const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ g_ssim,
                                                        const float* __restrict__ g_cs, const float* __restrict__ g_coarse, int H, int W, int rows,
-                                                       SsimWin g, SsimShift sh, float C1, float C2, float inv_n, float* __restrict__ dy) {
-  const float shift = sh.c;
+                                                       SsimWin g, double S, float C1, float C2, float inv_n, float* __restrict__ dy) {
   __shared__ float raw[2][2][RAWW];
   __shared__ float coef[3][NT];
   const int t = threadIdx.x;
@@ -173,6 +213,8 @@ __global__ __launch_bounds__(NT) void ssim_grad_kernel(const float* __restrict__
   const bool mcol = cm >= 0 && cm < Wm;
   const bool gcol = t >= HALO && cm < W;
   const int padh = H & 1, padw = W & 1, Wc = (W + padw) / 2, Hc = (H + padh) / 2;
+  const SsimShift sh = make_shift(block_shift(xp, yp, W, max(rin0, 0), min(rin0 + nin, H), cm, va, cb, vb, raw[0][0]), S);
+  const float shift = sh.c;
   float ax = 0.f, ay = 0.f, bx = 0.f, by = 0.f;                    // the next row, in flight (rows outside the plane: zeros, their map rows are masked)
   if (rin0 >= 0) {
     const int64_t r = (int64_t)rin0 * W;
@@ -203,12 +245,8 @@ __global__ __launch_bounds__(NT) void ssim_grad_kernel(const float* __restrict__
       for (int q = 0; q < 5; ++q) ring[q][s] = h[q];
       if (i >= HALO) {                                              // uniform
         const int mo = rin0 + i - HALO;                            // map row finished by this input row; also the gradient row of this step
-        float m[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int k = 0; k < TAPS; ++k) {
-#pragma unroll
-          for (int q = 0; q < 5; ++q) m[q] += g.w[k] * ring[q][(s + 1 + k) % TAPS];
-        }
+        float m[5];
+        vfilter5(ring, s, g, m);
         const SsimPoint p = ssim_point(m, sh, C1, C2);
         // T = gs ssim + gc cs at this position; A = dT/d mu_y, B = dT/d E[y^2], Cc = dT/d E[xy] (moments of the shifted frames)
         const float qv = gs * p.l + gc;                             // dT / d cs
@@ -339,12 +377,10 @@ StatsGrid stats_grid(int P, int H, int W) {
   return q;
 }
 
-SsimShift make_shift(const SsimWin& g, float data_range) {
+double window_sum(const SsimWin& g) {
   double S = 0.0;
   for (int k = 0; k < TAPS; ++k) S += (double)g.w[k];
-  S *= S;                                  // the separable filter's 2-D weights sum to (sum w)^2
-  const double c = 0.5 * (double)data_range;
-  return SsimShift{(float)c, (float)(c * S), (float)(c * (1.0 - S)), (float)(c * c * S * (1.0 - S))};
+  return S * S;                            // the separable filter's 2-D weights sum to (sum w)^2
 }
 
 bool ssim_shape_ok(int P, int H, int W) { return P > 0 && P <= 65535 && H >= TAPS && W >= TAPS && H <= (1 << 20) && W <= (1 << 20); }
@@ -365,7 +401,7 @@ extern "C" int vs_ssim_stats(const float* x, const float* y, int P, int H, int W
   for (int k = 0; k < TAPS; ++k) g.w[k] = win11[k];
   const StatsGrid q = stats_grid(P, H, W);
   const float C1 = (0.01f * data_range) * (0.01f * data_range), C2 = (0.03f * data_range) * (0.03f * data_range);
-  hipLaunchKernelGGL(ssim_stats_kernel, dim3(q.strips, q.chunks, P), dim3(NT), 0, (hipStream_t)stream, x, y, H, W, q.rows, g, make_shift(g, data_range), C1, C2,
+  hipLaunchKernelGGL(ssim_stats_kernel, dim3(q.strips, q.chunks, P), dim3(NT), 0, (hipStream_t)stream, x, y, H, W, q.rows, g, window_sum(g), C1, C2,
                      partial);
   hipLaunchKernelGGL(ssim_finish_kernel, dim3((P + 63) / 64), dim3(64), 0, (hipStream_t)stream, (const double*)partial, P, q.strips * q.chunks,
                      (double)(H - HALO) * (double)(W - HALO), out);
@@ -382,7 +418,7 @@ extern "C" int vs_ssim_grad(const float* x, const float* y, const float* g_ssim,
   const float C1 = (0.01f * data_range) * (0.01f * data_range), C2 = (0.03f * data_range) * (0.03f * data_range);
   const float inv_n = (float)(1.0 / ((double)(H - HALO) * (double)(W - HALO)));
   hipLaunchKernelGGL(ssim_grad_kernel, dim3(strips, (H + rows - 1) / rows, P), dim3(NT), 0, (hipStream_t)stream, x, y, g_ssim, g_cs, g_coarse, H, W, rows, g,
-                     make_shift(g, data_range), C1, C2, inv_n, dy);
+                     window_sum(g), C1, C2, inv_n, dy);
   return vs_launch_status();
 }
 
