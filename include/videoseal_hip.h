@@ -316,7 +316,8 @@ int vs_conv3x3_wgrad(const float* dy, int64_t dy_ld, int N, const float* x, int6
 int vs_pad_embed1(const float* dy, int B, int H, int W, int64_t ld, float* out, void* stream);
 /* ---- backward of the SAM-style ViT extractor of the legacy card (csrc/bwd_vit.hip; vit.py:146-193, 302-360, 436-470).
  * vs_gelu_bwd: dz = dy * gelu'(z) (rows of C values; pad columns of dz are zeroed).
- * vs_vit_attention_bwd: adjoint of vs_vit_attention.  qkv / out: the forward's operand and result, dout: gradient of out; dqkv receives
+ * vs_vit_attention_bwd: adjoint of vs_vit_attention.  qkv / out: the forward's operand and result (out must be a valid pointer but is not read:
+ * D = dO . O is recomputed as sum_j P (dO . v_j) from the same P as dS), dout: gradient of out; dqkv receives
  * (dq | dk | dv) in qkv's layout; drel_h / drel_w [2 * T - 1][hd] the gradients of the two relative-position tables (NULL with rel_h ==
  * NULL).  scratch: vs_vit_attention_bwd_scratch_floats(...) floats.  Deterministic (no atomics). */
 int vs_gelu_bwd(const float* z, int64_t ld, const float* dy, int64_t dy_ld, int64_t rows, int C, float* dz, int64_t dz_ld, void* stream);

@@ -4,7 +4,7 @@ A kernel's error against the float64 reference may exceed the error of a float32
     hip error <= MARGIN * max(yardstick error, floor),     MARGIN = twice the largest ratio measured on an MI355X, never above CAP = 8.
 Every figure is printed before anything is asserted (profiles/*_fp64_envelope.txt are recordings of those lines).  Two forms:
     check_rows   errors per named group of a case, floor U32 = 2^-24 (the final rounding of an fp32 result): the bwd, fwd, img and loss families
-    check_units  errors already in units of 2^-24 of the terms' magnitudes, floor 1: the split and fused families
+    check_units  errors already in units of 2^-24 of the terms' magnitudes, floor 1: the split, fused and detector-backward (_det_bwd_ref) families
 Each family binds a check to its tag and its margin in its own module (functools.partial) and keeps its margin, cases and metrics there (the
 backward family, which has no module of its own besides its two test files, at the end of this one);
 `outside` is the rule at the cap, for the CPU contract tests that show a seeded defect falls outside whatever the margin.  The yardsticks run

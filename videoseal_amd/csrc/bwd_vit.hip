@@ -4,12 +4,16 @@
 //   gelu_bwd                     MLP activation (vit.py:165-169): dz = dy * gelu'(z)
 //   vit_attention_bwd            multi-head self-attention with decomposed relative positions (vit.py:302-360, 436-470), windowed or global.
 //     With P = softmax(S), S[i][j] = scale q_i.k_j + q_i.Rh[yi - yj + Th - 1] + q_i.Rw[xi - xj + Tw - 1] and O = P V:
-//       D_i = dO_i . O_i,  dS[i][j] = P[i][j] (dO_i . v_j - D_i)
+//       D_i = dO_i . O_i = sum_j P[i][j] (dO_i . v_j),  dS[i][j] = P[i][j] (dO_i . v_j - D_i)
 //       dq_i = scale sum_j dS[i][j] k_j + sum_yj gh[i][yj] Rh[yi - yj + Th - 1] + sum_xj gw[i][xj] Rw[xi - xj + Tw - 1]
 //       dk_j = scale sum_i dS[i][j] q_i,   dv_j = sum_i P[i][j] dO_i
 //       dRh[r] = sum over groups, heads, i, yj with yi - yj + Th - 1 = r of gh[i][yj] q_i   (gh[i][yj] = sum_xj dS[i][(yj, xj)]; gw likewise)
-//     Nothing but qkv and O is kept from the forward: the scores are recomputed.  Kernel Q (one thread per query, K / V of the group in LDS):
-//     row maximum, normaliser, dq, gh / gw and the per-query terms kernel K needs.  Kernel K (one thread per key, q / dO of the group in LDS):
+//     Nothing but qkv is kept from the forward: the scores are recomputed, and D_i is taken in its second form from the recomputed P.  (Until the
+//     fp64 envelope of tests/test_gpu_det_bwd_envelope.py it was dO_i . O_i with the forward's O: on a one-hot row dS of the peak key is the
+//     difference dO_i . v_j - D_i of two equal numbers, and O carries the forward's error, which is relative to the largest channel of the row --
+//     many ulps of a small channel that dO happens to single out.  With D from the same P and the same dO . v products the difference cancels to
+//     the rounding of these terms themselves, and sum_j dS[i][j] = 0 holds to rounding.)  Kernel Q (one thread per query, K / V of the group in
+//     LDS): row maximum, normaliser, D, dq, gh / gw and the per-query terms kernel K needs.  Kernel K (one thread per key, q / dO of the group in LDS):
 //     dk and dv.  vit_relpos_grad: the two tables.
 #include "vs_common.h"
 
@@ -49,7 +53,7 @@ struct AttnGeom {
 // ---- kernel Q: thread = query i of the group.  rec[group][i][RP] receives rh / rw (the relative-position terms of the scores), the row maximum,
 // the normaliser and D; gsum[group][i][2 * TMAX] the row sums gh | gw of dS; dqkv the gradient of q.
 template <int HD>
-__global__ __launch_bounds__(256) void vit_attn_bwd_q_kernel(const float* __restrict__ qkv, const float* __restrict__ o, const float* __restrict__ d_o,
+__global__ __launch_bounds__(256) void vit_attn_bwd_q_kernel(const float* __restrict__ qkv, const float* __restrict__ d_o,
                                                              const AttnGeom G, const float* __restrict__ rel_h, const float* __restrict__ rel_w,
                                                              float* __restrict__ dqkv, float* __restrict__ rec, float* __restrict__ gsum) {
   extern __shared__ __attribute__((aligned(16))) float kv[];     // K [T][HD] then V [T][HD]
@@ -70,13 +74,10 @@ __global__ __launch_bounds__(256) void vit_attn_bwd_q_kernel(const float* __rest
   const int yi = i / Tw, xi = i % Tw;
   const int64_t tok = G.token(frame, wy, wx, i);
   f32x4 q[HD / 4], go[HD / 4];
-  float Dq = 0.f;
 #pragma unroll
   for (int c = 0; c < HD / 4; ++c) {
     q[c] = *reinterpret_cast<const f32x4*>(qkv + tok * (3 * D) + head * HD + 4 * c);
     go[c] = *reinterpret_cast<const f32x4*>(d_o + tok * D + head * HD + 4 * c);
-    const f32x4 ov = *reinterpret_cast<const f32x4*>(o + tok * D + head * HD + 4 * c);
-    Dq += go[c][0] * ov[0] + go[c][1] * ov[1] + go[c][2] * ov[2] + go[c][3] * ov[3];
   }
   auto dot = [&](const f32x4 (&a)[HD / 4], const float* p) __attribute__((always_inline)) -> float {
     float s = 0.f;
@@ -96,17 +97,22 @@ __global__ __launch_bounds__(256) void vit_attn_bwd_q_kernel(const float* __rest
   f32x4 qs[HD / 4];
 #pragma unroll
   for (int c = 0; c < HD / 4; ++c) qs[c] = q[c] * scale;
-  // pass 1: row maximum and normaliser
+  // pass 1: row maximum, normaliser and D = sum_j P[i][j] (dO_i . v_j)
   float m = -INFINITY;
   for (int j = 0; j < T; ++j) m = fmaxf(m, dot(qs, Ks + j * HD) + myrec[j / Tw] + myrec[TMAX + j % Tw]);
-  float l = 0.f;
-  for (int j = 0; j < T; ++j) l += __expf(dot(qs, Ks + j * HD) + myrec[j / Tw] + myrec[TMAX + j % Tw] - m);
+  float l = 0.f, Dl = 0.f;
+  for (int j = 0; j < T; ++j) {
+    const float e = __expf(dot(qs, Ks + j * HD) + myrec[j / Tw] + myrec[TMAX + j % Tw] - m);
+    l += e;
+    Dl += e * dot(go, Vs + j * HD);
+  }
+  const float inv = 1.0f / l;
+  const float Dq = Dl * inv;
   myrec[2 * TMAX] = m; myrec[2 * TMAX + 1] = l; myrec[2 * TMAX + 2] = Dq;
   // pass 2: dS, its row sums, dq
   f32x4 dq[HD / 4];
 #pragma unroll
   for (int c = 0; c < HD / 4; ++c) dq[c] = f32x4{0.f, 0.f, 0.f, 0.f};
-  const float inv = 1.0f / l;
   for (int yj = 0; yj < Th; ++yj) {
     float gh = 0.f;
     for (int xj = 0; xj < Tw; ++xj) {
@@ -237,7 +243,7 @@ __global__ __launch_bounds__(256) void vit_relpos_reduce_kernel(const float* __r
 }
 
 template <int HD>
-int launch_attn_bwd(const float* qkv, const float* o, const float* d_o, const AttnGeom& G, int64_t groups, const float* rel_h, const float* rel_w,
+int launch_attn_bwd(const float* qkv, const float* d_o, const AttnGeom& G, int64_t groups, const float* rel_h, const float* rel_w,
                     float* dqkv, float* rec, float* gsum, float* part, float* drel_h, float* drel_w, hipStream_t st) {
   const size_t smem = 2 * (size_t)G.T * HD * sizeof(float);
   auto kq = vit_attn_bwd_q_kernel<HD>;
@@ -249,7 +255,7 @@ int launch_attn_bwd(const float* qkv, const float* o, const float* d_o, const At
     attr = true;
   }
   const unsigned nt = (unsigned)((G.T + 63) / 64 * 64);
-  hipLaunchKernelGGL(kq, dim3((unsigned)groups), dim3(nt), smem, st, qkv, o, d_o, G, rel_h, rel_w, dqkv, rec, gsum);
+  hipLaunchKernelGGL(kq, dim3((unsigned)groups), dim3(nt), smem, st, qkv, d_o, G, rel_h, rel_w, dqkv, rec, gsum);
   hipLaunchKernelGGL(kk, dim3((unsigned)groups), dim3(nt), smem, st, qkv, d_o, G, (const float*)rec, dqkv);
   if (rel_h && rel_w && drel_h && drel_w) {
     const int nh = 2 * G.Th - 1, nw = 2 * G.Tw - 1;
@@ -277,6 +283,7 @@ extern "C" int64_t vs_vit_attention_bwd_scratch_floats(int frames, int H, int W,
 
 extern "C" int vs_vit_attention_bwd(const float* qkv, const float* out, const float* dout, int frames, int H, int W, int heads, int hd, int window,
                                     const float* rel_h, const float* rel_w, float* dqkv, float* scratch, float* drel_h, float* drel_w, void* stream) {
+  // `out` (the forward's result) is part of the contract and checked, but no longer read: D is taken from the recomputed P (see the header comment)
   VS_REQUIRE(qkv && out && dout && dqkv && scratch && frames > 0 && H > 0 && W > 0 && heads > 0 && window >= 0);
   VS_REQUIRE((!rel_h) == (!rel_w) && (!drel_h) == (!drel_w) && (rel_h || !drel_h));
   VS_REQUIRE(((((uintptr_t)qkv) | ((uintptr_t)out) | ((uintptr_t)dout) | ((uintptr_t)dqkv) | ((uintptr_t)scratch)) & 15) == 0);
@@ -293,9 +300,9 @@ extern "C" int vs_vit_attention_bwd(const float* qkv, const float* out, const fl
   float* part = gsum + (int64_t)frames * H * W * heads * (2 * TMAX);
   hipStream_t st = (hipStream_t)stream;
   switch (hd) {
-    case 16: return launch_attn_bwd<16>(qkv, out, dout, G, groups, rel_h, rel_w, dqkv, rec, gsum, part, drel_h, drel_w, st);
-    case 32: return launch_attn_bwd<32>(qkv, out, dout, G, groups, rel_h, rel_w, dqkv, rec, gsum, part, drel_h, drel_w, st);
-    case 64: return launch_attn_bwd<64>(qkv, out, dout, G, groups, rel_h, rel_w, dqkv, rec, gsum, part, drel_h, drel_w, st);
+    case 16: return launch_attn_bwd<16>(qkv, dout, G, groups, rel_h, rel_w, dqkv, rec, gsum, part, drel_h, drel_w, st);
+    case 32: return launch_attn_bwd<32>(qkv, dout, G, groups, rel_h, rel_w, dqkv, rec, gsum, part, drel_h, drel_w, st);
+    case 64: return launch_attn_bwd<64>(qkv, dout, G, groups, rel_h, rel_w, dqkv, rec, gsum, part, drel_h, drel_w, st);
     default: return VS_ERR_UNSUPPORTED;
   }
 }

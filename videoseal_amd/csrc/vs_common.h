@@ -101,7 +101,8 @@ static inline int vs_num_cus() {
 // branches, ~40 instructions, and made the pwconv1 epilogues VALU-bound):
 //   gelu(v) = max(v, 0) - 0.5 |v| erfc(|v|/sqrt2),   erfc(t) = exp(-P(t)),  P(t) = t * Q8(t) fitted to -ln erfc on [0, 4]
 // with the 1/sqrt2 and -log2(e) factors folded into the coefficients (tools/micro/fit_gelu.py).  Max |error| vs the exact
-// function 2.4e-7 over [-9, 9] -- ATen's own fp32 GELU is off by up to 1.2e-6 there -- and exactly v / 0 beyond |v| = 5.66.
+// function 2.4e-7 over [-9, 9] -- ATen's own fp32 GELU is off by up to 1.2e-6 there.  Beyond |v| = 5.66 the argument of the fit is clamped, so
+// erfc stays at 1.5e-8: v >= 5.66 returns v exactly (the correction is below half an ulp of v), v <= -5.66 returns -7.7e-9 |v|, not 0.
 // erfc(a / sqrt2) for a >= 0 (the fitted factor of vs_gelu; shared with its derivative in bwd_ops.hip)
 __device__ __forceinline__ float vs_erfc_sqrt2(float a) {
   const float u = fminf(a, 5.65685424949238f);
