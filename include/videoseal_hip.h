@@ -667,6 +667,67 @@ int vs_images_plan(const vs_image_desc_t* images, int n, int kind, int io_u8, in
                    int max_groups, int* n_groups);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * Lists of clips of different sizes and lengths (appended, vs_version() stays 3): the image lists above with a frame dimension and a
+ * key-frame mapping per list entry, so that the key frames of MANY short clips go through the U-Net as one batch.  A slot is a run of F
+ * consecutive frames of one clip: for the embed passes exactly the piece the per-clip call runs as one chunk (its key frames are its frames
+ * 0, key_step, 2 key_step, ... and the watermark expansion never looks outside it), for the detect pass any run of frames.  Descriptors are
+ * a HOST array, travel in the kernel arguments (at most VS_IMAGES_PER_LAUNCH slots per launch) and are looked up like image descriptors.
+ *   frames       fp32 [F][3][H][W], 4-byte aligned; io_u8: uint8 RGB24 [F][H][W][3].  Contiguous.
+ *   out          vs_embed_tail_clips: the watermarked frames, laid out like frames.  Unused by vs_resize_pre_clips.
+ *   preds_w      vs_embed_tail_clips: fp32 [F][Cd][H][W] or NULL.  Unused by vs_resize_pre_clips.
+ *   first_frame  frame 0 of the slot is frame first_frame of dst_rgb / hmap_lowres
+ *   first_key    its first key frame is frame first_key of dst_key / delta
+ */
+typedef struct vs_clip_desc {
+  const void* frames; void* out; float* preds_w;
+  int32_t F, H, W;
+  int32_t first_frame;
+  int32_t first_key;
+} vs_clip_desc_t;
+
+/* vs_resize_pre / vs_resize_pre_u8 (C = 3) on every slot: frame f of slot s goes to dst_rgb[first_frame + f] when dst_rgb is given and, when
+ * dst_key is given and f % key_step == 0, to dst_key[first_key + f / key_step]; other frames leave dst_key alone.  The bits are those the
+ * per-clip call gives.  fp32 slots take the row-streaming kernel where its windows fit and the 32 x 8 tile kernel elsewhere, RGB24 slots the
+ * tile kernel.  VS_ERR_BAD_ARG without a launch: a null pointer, n <= 0, a slot with F, H or W <= 0, both destinations NULL, dst_key with
+ * key_step < 1, a negative first_frame / first_key. */
+int vs_resize_pre_clips(const vs_clip_desc_t* clips, int n, int io_u8, int oh, int ow, int antialias, float* dst_rgb, float mul, float add,
+                        float* dst_key, int key_step, const float* ymat3, void* stream);
+
+/* vs_embed_tail on every slot: slot s behaves as that call with F = slot.F, total_key = ceil(F / step), its delta starting at frame first_key
+ * of delta [keys][Cd][S_h][S_w] and its hmap_lowres at frame first_frame of hmap_lowres [frames][S_h][S_w]; the other members mean what they
+ * mean in vs_tail_images_desc_t, step and video_mode what they mean in vs_tail_desc_t.  The bits are those of the per-slot call (16-row tile
+ * kernel).  attenuate = 2 answers VS_ERR_UNSUPPORTED; VS_ERR_BAD_ARG without a launch: a null pointer, n <= 0, a slot with F, H or W <= 0,
+ * io_u8 without clamp, step < 1, an unknown video_mode. */
+typedef struct vs_tail_clips_desc {
+  const vs_clip_desc_t* clips;     /* HOST array of n descriptors */
+  const float* delta; const float* hmap_lowres; const float* taps43;   /* taps43: HOST pointer */
+  int32_t n, S_h, S_w, Cd;
+  int32_t attenuate, clamp, antialias, io_u8;
+  float scaling_i, scaling_w;
+  int32_t step, video_mode;
+} vs_tail_clips_desc_t;
+int vs_embed_tail_clips(const vs_tail_clips_desc_t* d, void* stream);
+
+/* vs_images_plan for slots: group.image[k] indexes the caller's slots, the workgroups of a slot are F x tiles, contiguous and frame-major
+ * (workgroup first_wg[k] + f * tiles + t is tile t of frame f), first_wg[count] is the grid.  The strip of a streaming resize follows the
+ * frame count of the group.  VS_ERR_UNSUPPORTED past 2^31 - 1 workgroups in a launch; n = 0 is an empty plan. */
+int vs_clips_plan(const vs_clip_desc_t* clips, int n, int kind, int io_u8, int oh, int ow, int antialias, vs_images_group_t* groups,
+                  int max_groups, int* n_groups);
+
+/* Frame aggregation of the detector's rows per clip (videoseal.py:411-426), all clips of a list in one launch.  logits: fp32 rows of ld floats,
+ * column 0 (the detection logit) is dropped, columns 1 .. nbits are the bits; clip i owns rows [first_row[i], first_row[i + 1]) (first_row:
+ * DEVICE int32 [n + 1], non-decreasing).  out [n][nbits] = the mean over the clip's rows of  x (VS_AGG_AVG),  x |x| (VS_AGG_SQUARED),
+ * x * sum_j |x_j| (VS_AGG_L1NORM),  x * sqrt(sum_j x_j^2) (VS_AGG_L2NORM); a clip without rows gives zeros.  One workgroup per clip, one
+ * thread per bit walking the rows in order; the row norms are a pairwise tree of fixed shape over the bits: the summation order is a
+ * function of nbits alone, never of n or of the launch.  VS_ERR_BAD_ARG: a null pointer, n <= 0, nbits <= 0, ld < 1 + nbits, an unknown
+ * mode; VS_ERR_UNSUPPORTED: nbits > 1024. */
+#define VS_AGG_AVG 0
+#define VS_AGG_SQUARED 1
+#define VS_AGG_L1NORM 2
+#define VS_AGG_L2NORM 3
+int vs_aggregate_clips(const float* logits, int64_t ld, const int32_t* first_row, int n, int nbits, int mode, float* out, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * NV12 frames: what a hardware decoder (or ffmpeg in its native pixel format) hands over, 1.5 bytes per pixel.
  * Layout.  A clip is uint8 [F][3H/2][W], H and W even.  Rows 0 .. H-1 of a frame are luma; rows H .. 3H/2-1 are the chroma plane: bytes 2j
  *   and 2j+1 of chroma row i are Cb and Cr of the 2 x 2 pixel block (2i .. 2i+1, 2j .. 2j+1).  Consecutive bytes of a row are adjacent; rows

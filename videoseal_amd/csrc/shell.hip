@@ -5,6 +5,7 @@
 // These are the HBM-bound kernels (7.08 MB read + 7.08 MB written per 768x768 frame in the tail).
 #include "shell_common.h"
 #include "images_plan.h"
+#include "clips_plan.h"
 
 namespace {
 
@@ -722,8 +723,9 @@ struct ImagesArgs {
 };
 static_assert(sizeof(ImagesArgs) + sizeof(TailArgs) + sizeof(JndTaps) <= 3072, "descriptors + tail arguments stay well inside the 4 KiB of kernel arguments");
 
-// the image of workgroup wg: the last k with first_wg[k] <= wg
-__device__ __forceinline__ int images_find(const ImagesArgs& g, const int wg) {
+// the image (or clip slot) of workgroup wg: the last k with first_wg[k] <= wg
+template <class Args>
+__device__ __forceinline__ int images_find(const Args& g, const int wg) {
   int k = 0;
 #pragma unroll
   for (int s = VS_IMAGES_PER_LAUNCH / 2; s >= 1; s >>= 1)
@@ -780,6 +782,91 @@ inline ImagesArgs images_args(const vs_image_desc_t* images, const vs_images_gro
       cols = (ow + tw - 1) / tw;
     }
     g.slot[k] = ImgSlot{d.img, d.out, d.preds_w, d.H, d.W, grp.image[k], cols};
+  }
+  return g;
+}
+
+// ---------------------------------------------------------------------------------------------------
+// Lists of clips (vs_resize_pre_clips, vs_embed_tail_clips): the image lists with a frame dimension.  A slot is F frames of one size; its
+// workgroups are F x tiles, frame-major (clips_plan.h), and it carries where its frames and its key frames sit in the processing-size
+// tensors.  The tile bodies see a slot as a clip of its own: the slot-local frame number with the destinations (resize) or delta / hmap_lowres
+// (tail) moved to the slot's first frame / first key frame -- all of it workgroup-uniform, so the bodies and their bits are the clip kernels'.
+struct ClipSlot { const void* frames; void* out; float* preds_w; int F, H, W, first_frame, first_key, cols, tiles; };      // tiles: per frame
+struct ClipsArgs {
+  int first_wg[VS_IMAGES_PER_LAUNCH + 1];      // entries past the launch's slot count hold the grid size: never reached by a workgroup
+  int pad_;
+  ClipSlot slot[VS_IMAGES_PER_LAUNCH];
+};
+static_assert(sizeof(ClipsArgs) + sizeof(TailArgs) + sizeof(JndTaps) <= 3072, "descriptors + tail arguments stay well inside the 4 KiB of kernel arguments");
+static_assert(sizeof(ClipsArgs) + sizeof(ResizePreEpi) <= 3072, "descriptors + resize epilogue stay well inside the 4 KiB of kernel arguments");
+
+// (slot k, frame f of it, tile column bx, tile row by) of workgroup wg
+__device__ __forceinline__ void clips_item(const ClipsArgs& g, const int wg, int& k, int& f, int& bx, int& by) {
+  k = images_find(g, wg);
+  const int t = wg - g.first_wg[k];
+  const int tiles = g.slot[k].tiles, cols = g.slot[k].cols;
+  f = t / tiles;
+  const int r = t - f * tiles;
+  by = r / cols;
+  bx = r - by * cols;
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void resize_pre_clips_kernel(const ClipsArgs g, const int oh, const int ow, const int antialias,
+                                                               const ResizePreEpi o) {
+  __shared__ float Lw[3 * RS_WH * RS_WW];
+  int k, f, bx, by;
+  clips_item(g, blockIdx.x, k, f, bx, by);
+  const int H = g.slot[k].H, W = g.slot[k].W;
+  const int64_t fo = (int64_t)oh * ow * 4;
+  resize_pre_tile<T>(Lw, static_cast<const T*>(g.slot[k].frames) + (int64_t)f * 3 * H * W, f, bx * VS_IMG_RS_TW, by * VS_IMG_RS_TH, 3, H, W, oh, ow,
+                     antialias, o.dst_rgb ? o.dst_rgb + g.slot[k].first_frame * fo : nullptr, o.mul, o.add,
+                     o.dst_key ? o.dst_key + g.slot[k].first_key * fo : nullptr, o.key_step, o.key_mode, o.y0c, o.y1c, o.y2c);
+}
+
+template <int OW>
+__global__ __launch_bounds__(256) void resize_pre_clips_stream_kernel(const ClipsArgs g, const int oh, const int ow, const int antialias,
+                                                                      ResizePreEpi epi, const int strip) {
+  extern __shared__ __attribute__((aligned(16))) float rs_smem[];
+  int k, f, bx, by;
+  clips_item(g, blockIdx.x, k, f, bx, by);
+  const int H = g.slot[k].H, W = g.slot[k].W;
+  const int64_t fo = (int64_t)oh * ow * 4;
+  if (epi.dst_rgb) epi.dst_rgb += g.slot[k].first_frame * fo;
+  if (epi.dst_key) epi.dst_key += g.slot[k].first_key * fo;
+  vs_rs::resize_stream_tile<OW>(rs_smem, static_cast<const float*>(g.slot[k].frames) + (int64_t)f * 3 * H * W, H, W, 0, 0, H, W, oh, ow, antialias,
+                                strip, epi, bx, by, f);
+}
+
+template <typename T, bool SEP>
+__global__ __launch_bounds__(256) void embed_tail_clips_kernel(const ClipsArgs g, TailArgs a, const JndTaps k) {
+  int i, f, bx, by;
+  clips_item(g, blockIdx.x, i, f, bx, by);
+  a.F = g.slot[i].F;
+  a.H = g.slot[i].H;
+  a.W = g.slot[i].W;
+  a.total_key = (a.F + a.step - 1) / a.step;
+  const int64_t splane = (int64_t)a.Sh * a.Sw, plane = (int64_t)a.H * a.W;
+  a.delta += g.slot[i].first_key * splane * a.Cd;
+  if (a.hmap_lowres) a.hmap_lowres += g.slot[i].first_frame * splane;
+  embed_tail_tile<T, SEP, TTH, false>(a, k, bx * TTW, by * TTH, f, static_cast<const T*>(g.slot[i].frames) + f * 3 * plane,
+                                      static_cast<T*>(g.slot[i].out) + f * 3 * plane,
+                                      g.slot[i].preds_w ? g.slot[i].preds_w + f * a.Cd * plane : nullptr);
+}
+
+// kernel arguments of one group of the plan
+inline ClipsArgs clips_args(const vs_clip_desc_t* clips, const vs_images_group_t& grp, const int kind, const int oh, const int ow) {
+  ClipsArgs g{};
+  for (int k = 0; k <= VS_IMAGES_PER_LAUNCH; ++k) g.first_wg[k] = grp.first_wg[k];
+  for (int k = 0; k < grp.count; ++k) {
+    const vs_clip_desc_t& d = clips[grp.image[k]];
+    int cols = (d.W + TTW - 1) / TTW;
+    if (kind == VS_IMAGES_RESIZE) {
+      const int tw = grp.form == VS_IMAGES_FORM_TILE ? VS_IMG_RS_TW : (grp.form == VS_IMAGES_FORM_STREAM128 ? 128 : 64);
+      cols = (ow + tw - 1) / tw;
+    }
+    g.slot[k] = ClipSlot{d.frames, d.out, d.preds_w, d.F, d.H, d.W, d.first_frame, d.first_key, cols,
+                         (int)vs_images_tiles(kind, grp.form, grp.strip, d.H, d.W, oh, ow)};
   }
   return g;
 }
@@ -932,6 +1019,64 @@ extern "C" int vs_embed_tail_images(const vs_tail_images_desc_t* d, void* stream
     if (d->io_u8) hipLaunchKernelGGL((embed_tail_images_kernel<unsigned char, false>), grid, dim3(256), 0, (hipStream_t)stream, g, a, k);
     else if (sep) hipLaunchKernelGGL((embed_tail_images_kernel<float, true>), grid, dim3(256), 0, (hipStream_t)stream, g, a, k);
     else hipLaunchKernelGGL((embed_tail_images_kernel<float, false>), grid, dim3(256), 0, (hipStream_t)stream, g, a, k);
+    return vs_launch_status();
+  });
+}
+
+extern "C" int vs_resize_pre_clips(const vs_clip_desc_t* clips, int n, int io_u8, int oh, int ow, int antialias, float* dst_rgb, float mul,
+                                   float add, float* dst_key, int key_step, const float* ymat3, void* stream) {
+  VS_REQUIRE(clips && n > 0 && oh > 0 && ow > 0 && (dst_rgb || dst_key));
+  VS_REQUIRE(!dst_key || key_step >= 1);
+  for (int i = 0; i < n; ++i)
+    VS_REQUIRE(clips[i].frames && clips[i].F > 0 && clips[i].H > 0 && clips[i].W > 0 && clips[i].first_frame >= 0 && clips[i].first_key >= 0);
+  if ((int64_t)vs_rs::rs_lds_bytes<128>() > vs_max_lds_bytes() || (int64_t)vs_rs::rs_lds_bytes<64>() > vs_max_lds_bytes()) return VS_ERR_UNSUPPORTED;
+  int n_groups = 0;      // a dry walk first: a list the plan refuses launches nothing
+  if (const int rc = vs_clips_plan(clips, n, VS_IMAGES_RESIZE, io_u8, oh, ow, antialias, nullptr, 0, &n_groups); rc != VS_OK) return rc;
+  const int key_mode = ymat3 ? 0 : 1;
+  const float y0 = ymat3 ? ymat3[0] : 0.f, y1 = ymat3 ? ymat3[1] : 0.f, y2 = ymat3 ? ymat3[2] : 0.f;
+  const ResizePreEpi epi{dst_rgb, dst_key, mul, add, key_step < 1 ? 1 : key_step, key_mode, y0, y1, y2, oh, ow};
+  const int aa = antialias ? 1 : 0;
+  return vs_clips_walk(clips, n, VS_IMAGES_RESIZE, io_u8 ? 1 : 0, oh, ow, aa, [&](const vs_images_group_t& grp) {
+    const ClipsArgs g = clips_args(clips, grp, VS_IMAGES_RESIZE, oh, ow);
+    const dim3 grid((unsigned)grp.first_wg[grp.count]);
+    if (grp.form == VS_IMAGES_FORM_STREAM128)
+      hipLaunchKernelGGL(resize_pre_clips_stream_kernel<128>, grid, dim3(256), vs_rs::rs_lds_bytes<128>(), (hipStream_t)stream, g, oh, ow, aa, epi, grp.strip);
+    else if (grp.form == VS_IMAGES_FORM_STREAM64)
+      hipLaunchKernelGGL(resize_pre_clips_stream_kernel<64>, grid, dim3(256), vs_rs::rs_lds_bytes<64>(), (hipStream_t)stream, g, oh, ow, aa, epi, grp.strip);
+    else if (io_u8)
+      hipLaunchKernelGGL(resize_pre_clips_kernel<unsigned char>, grid, dim3(256), 0, (hipStream_t)stream, g, oh, ow, aa, epi);
+    else
+      hipLaunchKernelGGL(resize_pre_clips_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, g, oh, ow, aa, epi);
+    return vs_launch_status();
+  });
+}
+
+extern "C" int vs_embed_tail_clips(const vs_tail_clips_desc_t* d, void* stream) {
+  VS_REQUIRE(d && d->clips && d->n > 0 && d->delta && d->S_h > 0 && d->S_w > 0 && (d->Cd == 1 || d->Cd == 3));
+  VS_REQUIRE(d->step >= 1 && d->video_mode >= 0 && d->video_mode <= 2);
+  for (int i = 0; i < d->n; ++i) {
+    const vs_clip_desc_t& c = d->clips[i];
+    VS_REQUIRE(c.frames && c.out && c.F > 0 && c.H > 0 && c.W > 0 && c.first_frame >= 0 && c.first_key >= 0);
+  }
+  VS_REQUIRE(!(d->attenuate && !d->hmap_lowres) || d->taps43);
+  VS_REQUIRE(!d->io_u8 || d->clamp);        // (x * 255).byte() is only defined for x in [0, 1]
+  if (d->attenuate != 0 && d->attenuate != 1) return VS_ERR_UNSUPPORTED;      // (2: the training forward's order, single clips only)
+  int n_groups = 0;
+  if (const int rc = vs_clips_plan(d->clips, d->n, VS_IMAGES_TAIL, d->io_u8, d->S_h, d->S_w, d->antialias, nullptr, 0, &n_groups); rc != VS_OK) return rc;
+  // F, H, W, total_key and the first frames of delta / hmap_lowres are the slot's (set per workgroup)
+  const TailArgs a{nullptr, nullptr, nullptr, d->delta, d->attenuate ? d->hmap_lowres : nullptr, 0, 0, 0, d->S_h, d->S_w, d->Cd, d->step,
+                   d->video_mode, 0, d->attenuate, d->clamp, d->antialias, d->scaling_i, d->scaling_w};
+  JndTaps k{};
+  if (d->taps43) k = taps_from(d->taps43);
+  const bool full_jnd = d->attenuate && !d->hmap_lowres;
+  const bool sep = full_jnd && standard_jnd_taps(d->taps43);
+  return vs_clips_walk(d->clips, d->n, VS_IMAGES_TAIL, d->io_u8 ? 1 : 0, d->S_h, d->S_w, d->antialias ? 1 : 0, [&](const vs_images_group_t& grp) {
+    const ClipsArgs g = clips_args(d->clips, grp, VS_IMAGES_TAIL, d->S_h, d->S_w);
+    const dim3 grid((unsigned)grp.first_wg[grp.count]);
+    // (uint8 clips keep the 43-tap form, as vs_embed_tail does)
+    if (d->io_u8) hipLaunchKernelGGL((embed_tail_clips_kernel<unsigned char, false>), grid, dim3(256), 0, (hipStream_t)stream, g, a, k);
+    else if (sep) hipLaunchKernelGGL((embed_tail_clips_kernel<float, true>), grid, dim3(256), 0, (hipStream_t)stream, g, a, k);
+    else hipLaunchKernelGGL((embed_tail_clips_kernel<float, false>), grid, dim3(256), 0, (hipStream_t)stream, g, a, k);
     return vs_launch_status();
   });
 }

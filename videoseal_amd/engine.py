@@ -1622,6 +1622,57 @@ class HipEngine:
         self._shell_t1(ev, "embed_tail_images_kernel" + ("<u8>" if u8 else ""), 2 * sum(t.numel() * t.element_size() for t in imgs)
                        + (sum(p.numel() * 4 for p in preds_w) if preds_w is not None else 0) + delta.numel() * 4)
 
+    def resize_pre_clips(self, slots, S: Tuple[int, int], antialias: bool, *, want_rgb: bool, mul=1.0, add=0.0, want_key: bool = False,
+                         key_step: int = 1, tag="rs") -> Tuple[Optional[Act], Optional[Act]]:
+        """resize_pre on a list of slots [(frames, first_frame, first_key)] (clips.py; frames a device tensor fp32 [F,3,H,W] or uint8 RGB24
+        [F,H,W,3], contiguous, all of one dtype) -> (rgb Act [frames of the pass,S,S,4] or None, key Act [key frames of the pass,S,S,4] or None),
+        every frame with the bits resize_pre gives its clip."""
+        u8 = slots[0][0].dtype == torch.uint8
+        nf = max(ff + t.shape[0] for t, ff, _ in slots)
+        nk = max(fk + (t.shape[0] + key_step - 1) // key_step for t, _, fk in slots)
+        rgb = self.new_act(tag + ".rgb", nf, S[0], S[1], 3, 4) if want_rgb else None
+        key = self.new_act(tag + ".key", nk, S[0], S[1], self.cfg.in_ch, 4) if want_key else None
+        ymat = self.ymat if self.cfg.yuv else None
+        descs = N.clip_descs(slots)
+        ev = self._shell_t0()
+        N.check(self.lib.vs_resize_pre_clips(descs, len(slots), int(u8), S[0], S[1], 1 if antialias else 0, N.ptr(rgb.t) if rgb else None, mul, add,
+                                             N.ptr(key.t) if key else None, key_step, ymat, N.stream()), "vs_resize_pre_clips")
+        self._shell_t1(ev, "resize_pre_clips_kernel" + ("<u8>" if u8 else ""),
+                       sum(t.numel() * t.element_size() for t, _, _ in slots) + 16 * S[0] * S[1] * ((nf if rgb else 0) + (nk if key else 0)))
+        return rgb, key
+
+    def embed_tail_clips(self, slots, outs, delta, *, step, video_mode, hmap_low, attenuate, clamp, antialias, scaling_i, scaling_w, preds_w=None):
+        """embed_tail on a list of slots [(frames, first_frame, first_key)]: slot s is a clip of its own whose delta starts at key frame
+        first_key of delta [keys,Cd,S,S] and whose heat-map at frame first_frame of hmap_low; outs[s] (and preds_w[s], fp32 [F,Cd,H,W]) are
+        written with the bits embed_tail gives that slot."""
+        u8 = slots[0][0].dtype == torch.uint8
+        for (t, _, _), o in zip(slots, outs):
+            if o.dtype != t.dtype or o.shape != t.shape:
+                raise ValueError("every slot needs an output of its own shape and dtype")
+        d = N.TailClipsDesc()
+        descs = N.clip_descs(slots, outs, preds_w)
+        d.clips, d.n = descs, len(slots)
+        d.delta, d.hmap_lowres = N.ptr(delta), N.ptr(hmap_low)
+        d.taps43 = C.cast(self.taps43, C.c_void_p)
+        d.S_h, d.S_w, d.Cd = delta.shape[-2], delta.shape[-1], delta.shape[1]
+        d.attenuate, d.clamp, d.antialias, d.io_u8 = int(attenuate), int(clamp), int(antialias), int(u8)
+        d.scaling_i, d.scaling_w = float(scaling_i), float(scaling_w)
+        d.step, d.video_mode = int(step), int(video_mode)
+        ev = self._shell_t0()
+        N.check(self.lib.vs_embed_tail_clips(C.byref(d), N.stream()), "vs_embed_tail_clips")
+        self._shell_t1(ev, "embed_tail_clips_kernel" + ("<u8>" if u8 else ""), 2 * sum(t.numel() * t.element_size() for t, _, _ in slots)
+                       + (sum(p.numel() * 4 for p in preds_w) if preds_w is not None else 0) + delta.numel() * 4)
+
+    def aggregate_clips(self, logits: torch.Tensor, first_row: torch.Tensor, aggregation: str) -> torch.Tensor:
+        """aggregate_bits per clip: logits fp32 [rows, 1+nbits] on the device, first_row int32 [n+1] on the device -> fp32 [n, nbits]"""
+        if aggregation not in N.AGGREGATIONS:
+            raise ValueError(f"unknown aggregation {aggregation}")
+        n, nbits = first_row.numel() - 1, logits.shape[1] - 1
+        out = torch.empty(n, nbits, device=self.dev, dtype=torch.float32)
+        N.check(self.lib.vs_aggregate_clips(N.ptr(logits), logits.stride(0), N.ptr(first_row), n, nbits, N.AGGREGATIONS[aggregation], N.ptr(out),
+                                            N.stream()), "vs_aggregate_clips")
+        return out
+
     def _shell_t0(self):
         if self.shell_timers is None or torch.cuda.is_current_stream_capturing():
             return None

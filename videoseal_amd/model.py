@@ -912,6 +912,156 @@ class Videoseal(Wam):
             return {"preds": torch.zeros((0, self.embedder.cfg.nbits + 1), device=clip.device)}
         return {"preds": self._detect_clip(clip.contiguous(), interpolation)}
 
+    # ---- lists of clips of different sizes and lengths, a message per clip: the key frames of many short clips share a U-Net pass (clips.py)
+    @staticmethod
+    def _clip_list(clips, what: str):
+        """-> (the clips as given, uint8?) after the checks: all fp32 [F, 3, H, W] or all uint8 RGB24 [F, H, W, 3]; F may be 0"""
+        clips = list(clips)
+        if not all(torch.is_tensor(t) for t in clips):
+            raise TypeError(f"{what} wants a sequence of tensors")
+        if len({t.dtype for t in clips}) > 1:
+            raise ValueError(f"{what}: the clips of one call are all fp32 [F, 3, H, W] or all uint8 [F, H, W, 3], got {sorted({str(t.dtype) for t in clips})}")
+        u8 = bool(clips) and clips[0].dtype == torch.uint8
+        if clips and not (u8 or clips[0].is_floating_point()):
+            raise ValueError(f"{what}: clips are fp32 [F, 3, H, W] or uint8 [F, H, W, 3], got {clips[0].dtype}")
+        for t in clips:
+            if t.dim() != 4 or t.shape[-1 if u8 else 1] != 3 or 0 in t.shape[1:]:
+                raise ValueError(f"{what}: " + ("uint8 clips are RGB24 [F, H, W, 3]" if u8 else "fp32 clips are [F, 3, H, W]") + f", got {tuple(t.shape)}")
+        return clips, u8
+
+    def _clip_passes(self, eng: HipEngine, clips, u8: bool, passes, fn, restart=None) -> None:
+        """Drive `fn(slots, extra, frames)` over `passes` = [(slots, extra)] of clips.py: frames[s] is slot s of the pass on the device, contiguous.  Device-resident clips
+        are sliced in place; others move pass by pass, and such a call synchronises before it returns, so the range guard of its passes is read
+        here and a data-dependent overflow repeats the call on the exact split (as _image_chunks does for a list of images)."""
+        on_dev = all(t.device == eng.dev for t in clips if t.shape[0])
+        res = [(t.contiguous() if u8 else N.f32c(t)) if (t.device == eng.dev and t.shape[0]) else t for t in clips]
+        for attempt in range(2):
+            for slots, extra in passes:
+                frames = []
+                for s in slots:
+                    ch = res[s[0]][s[1]:s[1] + s[2]]
+                    if ch.device != eng.dev:
+                        ch = ch.to(eng.dev)
+                        ch = ch.contiguous() if u8 else N.f32c(ch)
+                    frames.append(ch)
+                fn(slots, extra, frames)
+            if on_dev:
+                break
+            torch.cuda.current_stream(eng.dev).synchronize()
+            if attempt or not eng.guard_tripped_after_sync():
+                break
+            if restart is not None:
+                restart()
+
+    @torch.no_grad()
+    def embed_clips(self, clips, msgs: torch.Tensor = None, interpolation: dict = None, lowres_attenuation: bool = False) -> dict:
+        """`embed(clip_i, msgs[i:i+1], is_video=True)` (`embed_u8` for uint8) for every clip of a list whose clips differ in size and length, with
+        the key frames of many clips going through the U-Net as one batch (up to streaming.KEY_BATCH per pass) instead of chunk_size per clip.
+        clips: n tensors, all fp32 [F_i, 3, H_i, W_i] or all uint8 RGB24 [F_i, H_i, W_i, 3] (needs clamp=True), F_i >= 0; msgs [n, k] (row i for
+        clip i) or None (random).  -> {'imgs_w': list, 'msgs'}: result i has the shape, dtype and device of clip i; for device-resident clips
+        the results are views of one allocation per call.  Per pass (clips.py): one resize launch group (vs_resize_pre_clips), one embedder pass
+        with one message row per key frame, one low-resolution heat-map when asked, one tail launch group (vs_embed_tail_clips).  The watermark
+        expansion restarts at every span as in the per-clip call, so clip i equals that call up to the summation order of the dense layers (a K
+        split is a function of the batch shape, see embed_group).  Always eager (no hipGraph route)."""
+        from . import clips as CL
+        if self.video_mode not in N.VIDEO_MODES:
+            raise ValueError(f"unknown video_mode {self.video_mode}")
+        clips, u8 = self._clip_list(clips, "embed_clips")
+        n = len(clips)
+        if u8 and not self.clamp:
+            raise NotImplementedError("uint8 output needs clamp=True ((x * 255).byte() is undefined outside [0, 1])")
+        if msgs is None:
+            msgs = self.get_random_msg(n)
+        elif msgs.shape[0] != n:
+            raise ValueError(f"msgs has {msgs.shape[0]} rows for {n} clips")
+        eng = self._engine()
+        aa = _antialias_flag(interpolation)
+        if n == 0:
+            return {"msgs": msgs, "imgs_w": []}
+        S = (self.img_size, self.img_size)
+        att = self.attenuation is not None
+        lowres = bool(lowres_attenuation)
+        step, vm = int(self.step_size), N.VIDEO_MODES[self.video_mode]
+        odt = torch.uint8 if u8 else torch.float32
+        passes = CL.embed_passes([t.shape[0] for t in clips], step, max(1, int(self.chunk_size)))
+        on_dev = all(t.device == eng.dev for t in clips if t.shape[0])
+        with torch.cuda.device(eng.dev):
+            if on_dev:          # one allocation, clip after clip
+                flat = torch.empty(sum(t.numel() for t in clips), dtype=odt, device=eng.dev)
+                outs, pos = [], 0
+                for t in clips:
+                    outs.append(flat[pos:pos + t.numel()].view(t.shape))
+                    pos += t.numel()
+            else:
+                outs = [_result_buffer(t.shape, odt, t.device) if t.shape[0] else torch.empty(t.shape, dtype=odt, device=t.device) for t in clips]
+            if passes:
+                mi = self._msgs_dev(msgs, eng.dev)
+
+            def one(slots, rows, frames):
+                dst = [outs[c][a:a + f] if on_dev else torch.empty_like(fr) for (c, a, f, _, _), fr in zip(slots, frames)]
+                desc = [(fr, ff, fk) for (_, _, _, ff, fk), fr in zip(slots, frames)]
+                rgb, key = eng.resize_pre_clips(desc, S, aa, want_rgb=(att and lowres), want_key=True, key_step=step)
+                delta = eng.embedder_forward(key, mi.index_select(0, torch.tensor(rows, device=eng.dev)), bn_train=self.embedder.training)
+                hmap = eng.jnd_lowres(rgb) if (att and lowres) else None
+                eng.embed_tail_clips(desc, dst, delta, step=step, video_mode=vm, hmap_low=hmap, attenuate=int(att), clamp=self.clamp, antialias=aa,
+                                     scaling_i=self.blender.scaling_i, scaling_w=self.blender.scaling_w)
+                if not on_dev:        # back to where each clip came from (_clip_passes synchronises before it returns)
+                    for (c, a, f, _, _), o in zip(slots, dst):
+                        outs[c][a:a + f].copy_(o, non_blocking=True)
+            self._clip_passes(eng, clips, u8, passes, one)
+        return {"msgs": msgs, "imgs_w": outs}
+
+    def _detect_clip_rows(self, eng: HipEngine, clips, u8: bool, aa: bool) -> Optional[torch.Tensor]:
+        """the detector's output for every frame of the flattened list, on the device (None for a list without frames): one resize launch group
+        and one extractor pass per streaming.DET_BATCH frames, whichever clips they belong to"""
+        from . import clips as CL
+        S = (self.img_size, self.img_size)
+        preds = []
+
+        def one(slots, _, frames):
+            rgb, _ = eng.resize_pre_clips([(fr, ff, 0) for (_, _, _, ff), fr in zip(slots, frames)], S, aa, want_rgb=True, mul=2.0, add=-1.0, tag="det.in")
+            p = eng.extractor_forward(rgb)
+            preds.append(p if eng.preds_owned else p.clone())
+        self._clip_passes(eng, clips, u8, [(s, None) for s in CL.detect_passes([t.shape[0] for t in clips])], one, restart=preds.clear)
+        return torch.cat(preds, dim=0) if preds else None
+
+    @torch.no_grad()
+    def detect_clips(self, clips, interpolation: dict = None) -> dict:
+        """`detect(clip_i, is_video=True)` for every clip of a list (see embed_clips) -> {'preds': list of [F_i, 1+nbits]}, entry i on clip i's
+        device; the extractor runs on up to streaming.DET_BATCH frames of the flattened list at a time."""
+        from . import clips as CL
+        clips, u8 = self._clip_list(clips, "detect_clips")
+        eng = self._engine()
+        aa = _antialias_flag(interpolation)
+        with torch.cuda.device(eng.dev):
+            rows = self._detect_clip_rows(eng, clips, u8, aa)
+            first = CL.first_rows([t.shape[0] for t in clips])
+            return {"preds": [rows[first[i]:first[i + 1]].to(t.device) if t.shape[0] else torch.zeros(self._empty_preds_shape(), device=t.device)
+                              for i, t in enumerate(clips)]}
+
+    @torch.no_grad()
+    def extract_messages(self, clips, aggregation: str = "avg",
+                         interpolation: dict = {"mode": "bilinear", "align_corners": False, "antialias": False}) -> torch.Tensor:
+        """`extract_message(clip_i, aggregation, interpolation)` for every clip of a list -> bool [n, nbits], row i for clip i (on the first
+        clip's device): detect_clips' passes, then the frame aggregation of all clips in one launch (vs_aggregate_clips); a clip without
+        frames aggregates to zeros, i.e. to all-False."""
+        from . import clips as CL
+        self._per_frame_rows_only("extract_messages")
+        if aggregation not in N.AGGREGATIONS:
+            raise ValueError(f"unknown aggregation {aggregation}")
+        clips, u8 = self._clip_list(clips, "extract_messages")
+        eng = self._engine()
+        aa = _antialias_flag(interpolation)
+        n, k = len(clips), self.embedder.cfg.nbits
+        if n == 0:
+            return torch.zeros((0, k), dtype=torch.bool)
+        with torch.cuda.device(eng.dev):
+            rows = self._detect_clip_rows(eng, clips, u8, aa)
+            if rows is None:
+                return torch.zeros((n, k), dtype=torch.bool, device=clips[0].device)
+            first = torch.tensor(CL.first_rows([t.shape[0] for t in clips]), dtype=torch.int32, device=eng.dev)
+            return (eng.aggregate_clips(rows.contiguous(), first, aggregation) > 0).to(clips[0].device)
+
     # ---- YUV clips (videoseal_amd/yuv.py): one body for the three pairs of methods below
     def _yuv_clip(self, planes, fmt: str, what: str, matrix: str, full_range: bool, module):
         """the validated planes as a yuv.Clip; `module` (yuv or its restriction yuv420) has the formats and matrices `what` accepts"""

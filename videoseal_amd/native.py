@@ -49,6 +49,7 @@ EXPORTS = [
     "vs_model_embed_yuv420", "vs_model_detect_yuv420",
     "vs_sizeof_yuv_surface", "vs_sizeof_tail_yuv_desc", "vs_resize_pre_yuv", "vs_embed_tail_yuv", "vs_model_embed_yuv", "vs_model_detect_yuv",
     "vs_resize_pre_images", "vs_embed_tail_images", "vs_images_plan",
+    "vs_resize_pre_clips", "vs_embed_tail_clips", "vs_clips_plan", "vs_aggregate_clips",
 ]
 
 
@@ -212,6 +213,51 @@ def images_plan(sizes, kind: int, io_u8: bool, oh: int, ow: int, antialias: bool
     return [(g.form, g.strip, list(g.image[:g.count]), list(g.first_wg[:g.count + 1])) for g in groups[:n.value]]
 
 
+AGGREGATIONS = {"avg": 0, "squared_avg": 1, "l1norm_avg": 2, "l2norm_avg": 3}      # VS_AGG_*
+
+
+class ClipDesc(C.Structure):
+    """mirror of vs_clip_desc_t: one slot of a clip list -- a run of frames of one clip and where it sits in the processing-size tensors"""
+    _fields_ = [("frames", C.c_void_p), ("out", C.c_void_p), ("preds_w", C.c_void_p), ("F", C.c_int32), ("H", C.c_int32), ("W", C.c_int32),
+                ("first_frame", C.c_int32), ("first_key", C.c_int32)]
+
+
+class TailClipsDesc(C.Structure):
+    """mirror of vs_tail_clips_desc_t: vs_tail_images_desc_t's members over slots, then step and video_mode"""
+    _fields_ = [
+        ("clips", C.POINTER(ClipDesc)), ("delta", C.c_void_p), ("hmap_lowres", C.c_void_p), ("taps43", C.c_void_p),
+        ("n", C.c_int32), ("S_h", C.c_int32), ("S_w", C.c_int32), ("Cd", C.c_int32),
+        ("attenuate", C.c_int32), ("clamp", C.c_int32), ("antialias", C.c_int32), ("io_u8", C.c_int32),
+        ("scaling_i", C.c_float), ("scaling_w", C.c_float), ("step", C.c_int32), ("video_mode", C.c_int32),
+    ]
+
+
+def clip_descs(slots, outs=None, preds_w=None):
+    """the HOST descriptor array of a list of slots [(frames, first_frame, first_key)]: frames a device tensor fp32 [F, 3, H, W] or uint8
+    [F, H, W, 3], contiguous; outs / preds_w: one tensor per slot or None.  Addresses and sizes, nothing is copied"""
+    arr = (ClipDesc * max(1, len(slots)))()
+    for i, (t, first_frame, first_key) in enumerate(slots):
+        H, W = (t.shape[1], t.shape[2]) if t.dtype == torch.uint8 else (t.shape[-2], t.shape[-1])
+        arr[i].frames, arr[i].F, arr[i].H, arr[i].W = ptr(t), t.shape[0], H, W
+        arr[i].first_frame, arr[i].first_key = first_frame, first_key
+        arr[i].out = ptr(outs[i]) if outs is not None else None
+        arr[i].preds_w = ptr(preds_w[i]) if preds_w is not None else None
+    return arr
+
+
+def clips_plan(sizes, kind: int, io_u8: bool, oh: int, ow: int, antialias: bool):
+    """vs_clips_plan on a list of (F, H, W): the launches as [(form, strip, [slot indices], [first workgroups ..., grid])] (no GPU involved)"""
+    L = lib()
+    arr = (ClipDesc * max(1, len(sizes)))()
+    for i, (F_, H, W) in enumerate(sizes):
+        arr[i].F, arr[i].H, arr[i].W = F_, H, W
+    n = C.c_int(0)
+    check(L.vs_clips_plan(arr, len(sizes), kind, int(io_u8), oh, ow, int(antialias), None, 0, C.byref(n)), "vs_clips_plan")
+    groups = (ImagesGroup * max(1, n.value))()
+    check(L.vs_clips_plan(arr, len(sizes), kind, int(io_u8), oh, ow, int(antialias), groups, n.value, C.byref(n)), "vs_clips_plan")
+    return [(g.form, g.strip, list(g.image[:g.count]), list(g.first_wg[:g.count + 1])) for g in groups[:n.value]]
+
+
 class ResblockThinDesc(C.Structure):
     """mirror of vs_resblock_thin_desc_t"""
     _fields_ = [
@@ -288,6 +334,10 @@ def lib() -> C.CDLL:
         "vs_resize_pre_images": [C.POINTER(ImageDesc), I, I, I, I, I, P, F, F, P, P, P],
         "vs_embed_tail_images": [C.POINTER(TailImagesDesc), P],
         "vs_images_plan": [C.POINTER(ImageDesc), I, I, I, I, I, I, C.POINTER(ImagesGroup), I, C.POINTER(C.c_int)],
+        "vs_resize_pre_clips": [C.POINTER(ClipDesc), I, I, I, I, I, P, F, F, P, I, P, P],
+        "vs_embed_tail_clips": [C.POINTER(TailClipsDesc), P],
+        "vs_clips_plan": [C.POINTER(ClipDesc), I, I, I, I, I, I, C.POINTER(ImagesGroup), I, C.POINTER(C.c_int)],
+        "vs_aggregate_clips": [P, I64, P, I, I, I, P, P],
         "vs_aug_color": [P, P, I, I, I, I, F, P, P],
         "vs_aug_crop_flip": [P, P, I, I, I, I, I, I, I, I, P],
         "vs_aug_color_chain": [P, P, I, I, I, I, C.POINTER(C.c_int), C.POINTER(C.c_float), P, P],
