@@ -871,6 +871,68 @@ int vs_resize_pre_yuv(const vs_yuv_surface_t* src, int B, int H, int W, const fl
 int vs_embed_tail_yuv(const vs_tail_yuv_desc_t* d, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * Packed RGB surfaces: what capture, compositors, image decoders and HDR swap chains hold.  vs_resize_pre / vs_embed_tail with the
+ * decode and the encode fused in, alpha / X carried through.
+ * Layout.  `format` is one of VS_RGB_* (ffmpeg's pix_fmt names without the "le"; everything little-endian); every other value answers
+ *   VS_ERR_UNSUPPORTED.  A frame is [H][W] pixels, pixel stride = the pixel's bytes, component stride = the component's bytes:
+ *     rgb24, bgr24              3 x uint8    R G B / B G R
+ *     rgba, bgra, argb, abgr    4 x uint8    R G B A / B G R A / A R G B / A B G R
+ *     rgb48, bgr48              3 x uint16   words R G B / B G R
+ *     rgba64, bgra64            4 x uint16   words R G B A / B G R A
+ *     x2rgb10, x2bgr10          1 x uint32   bits 31-30 X, 29-20 R (B), 19-10 G, 9-0 B (R)
+ *   `data` is the first byte of frame 0, `pitch` the bytes from a row to the next (any value >= W x the pixel's bytes, odd ones included),
+ *   `frame_stride` the bytes from a frame to the next (frames must not overlap).  Any base address works: a 16-bit word may sit at an odd
+ *   address.  Frame bytes move as 16-byte pieces where a piece lies inside its row and its address is aligned, byte by byte elsewhere.
+ * Rules, with top = 2^depth - 1 and depth = 8, 16 or 10 (the 10:10:10:2 word):
+ *   Decode: component = float(code) / float(top), the IEEE quotient (what `clip.float() / 255.0` gives for depth 8).
+ *   Encode: floor(clamp(x, 0, 1) * float(top)) -- the truncation of `(x * 255).byte()` (inference_streaming.py:31), extended to 10 and 16
+ *     bits.  floor((c / top) * top) == c for every code of the three depths: a pixel the watermark leaves alone keeps its word.
+ *   Alpha / X: the alpha component (the two X bits) of an output pixel is the source pixel's, bit for bit; it never enters arithmetic.
+ *     RGB is straight, not premultiplied.
+ * vs_resize_pre_rgb / vs_embed_tail_rgb: vs_resize_pre / vs_embed_tail on such surfaces.  Between decode and encode the filter, JND, key-frame
+ *   and blend expressions and their order are those of the fp32 kernels of the same form: a packed clip gives the bits of the fp32 path on
+ *   its decoded frames.  The descriptor is vs_tail_yuv_desc_t on two vs_rgb_surface_t, without the colour arrays.  variant: 0 = row-streaming
+ *   form where it applies and the tile form elsewhere, 1 = tile form, 4 = row-streaming form (VS_ERR_UNSUPPORTED where it does not apply).
+ *   VS_ERR_UNSUPPORTED: an unknown format, src.format != dst.format, preds_w != NULL, attenuate = 2, a variant other than 0 / 1 / 4.
+ *   VS_ERR_BAD_ARG (-1), without a launch: a null pointer, non-positive sizes, a pitch shorter than its row, clamp != 1, dst.data == src.data
+ *   (the JND reads a halo of the source).  Bytes of the destination between a row's end and its pitch are never written.  Development
+ *   switches: keys 0 - 2, as for vs_resize_pre / vs_embed_tail.
+ */
+#define VS_RGB_RGB24 0
+#define VS_RGB_BGR24 1
+#define VS_RGB_RGBA 2
+#define VS_RGB_BGRA 3
+#define VS_RGB_ARGB 4
+#define VS_RGB_ABGR 5
+#define VS_RGB_RGB48 6
+#define VS_RGB_BGR48 7
+#define VS_RGB_RGBA64 8
+#define VS_RGB_BGRA64 9
+#define VS_RGB_X2RGB10 10
+#define VS_RGB_X2BGR10 11
+typedef struct vs_rgb_surface {
+  void* data;
+  int64_t pitch, frame_stride;              /* bytes */
+  int32_t format, reserved_;                /* VS_RGB_*; 0 */
+} vs_rgb_surface_t;
+typedef struct vs_tail_rgb_desc {
+  vs_rgb_surface_t src, dst;
+  float* preds_w;
+  const float* delta; const float* hmap_lowres; const float* taps43;   /* taps43: HOST pointer */
+  int32_t F, H, W, S_h, S_w, Cd;
+  int32_t step, video_mode, total_key;
+  int32_t attenuate, clamp, antialias;
+  float scaling_i, scaling_w;
+  int32_t io_u8;
+  int32_t variant;
+} vs_tail_rgb_desc_t;
+int vs_sizeof_rgb_surface(void);            /* sizeof(vs_rgb_surface_t) */
+int vs_sizeof_tail_rgb_desc(void);          /* sizeof(vs_tail_rgb_desc_t) */
+int vs_resize_pre_rgb(const vs_rgb_surface_t* src, int B, int H, int W, int oh, int ow, int antialias, float* dst_rgb, float mul, float add,
+                      float* dst_y, int y_step, const float* ymat3, void* stream);
+int vs_embed_tail_rgb(const vs_tail_rgb_desc_t* d, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * Model-level entry points (the granularity a non-Python host would bind): an opaque model built from the card numbers
  * (utils/cfg.py:88-154, embedder.py:243-262, extractor.py:189-208) and the reference state_dict (cfg.py:147-150:
  * checkpoint['model'], HOST fp32 tensors by their reference names, loaded like strict=False: unknown names are ignored,
@@ -929,6 +991,14 @@ int vs_model_embed_yuv(vs_model_t* m, const vs_yuv_surface_t* in, const vs_yuv_s
                        int lowres_attenuation, int antialias, void* ws, int64_t ws_bytes, void* stream);
 int vs_model_detect_yuv(vs_model_t* m, const vs_yuv_surface_t* in, const float* yuv2rgb12, int frames, int H, int W, int antialias,
                         float* logits, void* ws, int64_t ws_bytes, void* stream);
+/* ... and on packed RGB surfaces (vs_rgb_surface_t, any pitches): `in` and `out` hold the same format and are different buffers; alpha / X of
+ * `out` are those of `in`.  The model must clamp (VS_ERR_BAD_ARG otherwise); an unknown format or two different ones answer
+ * VS_ERR_UNSUPPORTED.  There is no preds_w. */
+int vs_model_embed_rgb(vs_model_t* m, const vs_rgb_surface_t* in, const vs_rgb_surface_t* out, const int32_t* msgs, int n_msgs, int frames,
+                       int H, int W, int step, int video_mode, int lowres_attenuation, int antialias, void* ws, int64_t ws_bytes,
+                       void* stream);
+int vs_model_detect_rgb(vs_model_t* m, const vs_rgb_surface_t* in, int frames, int H, int W, int antialias, float* logits, void* ws,
+                        int64_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Augmentations (videoseal/augmentation/valuemetric.py, geometric.py, utils/image.py).  Frames are NCHW fp32 [F][3][H][W]

@@ -51,6 +51,10 @@ def _bind(L):
     L.vs_model_embed_yuv.restype = I
     L.vs_model_detect_yuv.argtypes = [P, C.POINTER(N.YuvSurface), P, I, I, I, I, P, P, I64, P]
     L.vs_model_detect_yuv.restype = I
+    L.vs_model_embed_rgb.argtypes = [P, C.POINTER(N.RgbSurface), C.POINTER(N.RgbSurface), P, I, I, I, I, I, I, I, I, P, I64, P]
+    L.vs_model_embed_rgb.restype = I
+    L.vs_model_detect_rgb.argtypes = [P, C.POINTER(N.RgbSurface), I, I, I, I, P, P, I64, P]
+    L.vs_model_detect_rgb.restype = I
     L._model_api_bound = True
 
 
@@ -203,3 +207,31 @@ class CModel:
     def detect_yuv(self, planes, fmt: str, *, color=None, antialias: bool = True) -> torch.Tensor:
         from . import yuv
         return self._detect_yuv(yuv, N.yuv_surface, self._L.vs_model_detect_yuv, planes, fmt, color, antialias)
+
+    def embed_rgb(self, clip: torch.Tensor, fmt: str, msgs: torch.Tensor, *, out: Optional[torch.Tensor] = None, step: int = 1,
+                  video_mode: int = 0, lowres_attenuation: bool = False, antialias: bool = True) -> torch.Tensor:
+        """vs_model_embed_rgb on a device-resident packed RGB clip of format `fmt` (rgbpack.py; any pitch); `out`: where the watermarked clip
+        goes (default: a new compact clip).  Returns the output clip."""
+        from . import rgbpack
+        F_, H, W = rgbpack.check_clip(clip, fmt)
+        src = rgbpack.Clip(clip, fmt)
+        if out is not None:
+            rgbpack.check_clip(out, fmt, "out")
+        dst = rgbpack.Clip(out, fmt) if out is not None else src.empty_like()
+        m = msgs.to(device=src.device, dtype=torch.int32).contiguous()
+        ws = self._workspace(F_, H, W, step)
+        sin, sout = N.rgb_surface(src.tensor, fmt), N.rgb_surface(dst.tensor, fmt)
+        N.check(self._L.vs_model_embed_rgb(self._h, C.byref(sin), C.byref(sout), N.ptr(m), m.shape[0], F_, H, W, step, video_mode,
+                                           int(lowres_attenuation), int(antialias), N.ptr(ws), ws.numel(), N.stream()), "vs_model_embed_rgb")
+        return dst.tensor
+
+    def detect_rgb(self, clip: torch.Tensor, fmt: str, *, antialias: bool = True) -> torch.Tensor:
+        from . import rgbpack
+        F_, H, W = rgbpack.check_clip(clip, fmt)
+        src = rgbpack.Clip(clip, fmt)
+        logits = torch.empty(F_, self.cfg.nbits + 1, device=src.device)
+        ws = self._workspace(F_, H, W, 1)
+        sin = N.rgb_surface(src.tensor, fmt)
+        N.check(self._L.vs_model_detect_rgb(self._h, C.byref(sin), F_, H, W, int(antialias), N.ptr(logits), N.ptr(ws), ws.numel(), N.stream()),
+                "vs_model_detect_rgb")
+        return logits

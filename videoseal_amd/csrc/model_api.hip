@@ -327,6 +327,9 @@ struct Runner {
   const vs_yuv_surface_t* ydst = nullptr;
   const float* ydec = nullptr;
   const float* yenc = nullptr;
+  // io = 4 (vs_model_*_rgb): the packed RGB surfaces
+  const vs_rgb_surface_t* psrc = nullptr;
+  const vs_rgb_surface_t* pdst = nullptr;
 
   float* alloc(int64_t floats) {
     const int64_t bytes = (floats * 4 + 255) & ~(int64_t)255;
@@ -781,12 +784,14 @@ struct Runner {
     if (live()) chk(vs_pool_linear(hl.p, B, hl.H * hl.W, hl.C, hl.ld, m->lin_w, m->lin_b, c.nbits + 1, logits, st));
   }
   // model.py::_embed_frames_eager
-  // io: 0 = fp32 NCHW, 3 = the YUV surface `ysrc` (io_u8 = 2 arrives here as a contiguous nv12 surface), any other value = RGB24
+  // io: 0 = fp32 NCHW, 3 = the YUV surface `ysrc` (io_u8 = 2 arrives here as a contiguous nv12 surface), 4 = the packed RGB surface `psrc`,
+  // any other value = RGB24
   void resize(const void* imgs, int io, int F, int H, int W, int S, int antialias, float* rgb, float mul, float add, float* key, int step,
               const float* ymat) {
     if (!live()) return;
     const bool u8 = io != 0;
     if (io == 3) chk(vs_resize_pre_yuv(ysrc, F, H, W, ydec, S, S, antialias, rgb, mul, add, key, step, ymat, st));
+    else if (io == 4) chk(vs_resize_pre_rgb(psrc, F, H, W, S, S, antialias, rgb, mul, add, key, step, ymat, st));
     else if (u8) chk(vs_resize_pre_u8(static_cast<const unsigned char*>(imgs), F, H, W, S, S, antialias, rgb, mul, add, key, step, ymat, st));
     else chk(vs_resize_pre(static_cast<const float*>(imgs), F, 3, H, W, S, S, antialias, rgb, mul, add, key, step, ymat, st));
   }
@@ -816,6 +821,17 @@ struct Runner {
       std::memcpy(n.yuv2rgb12, ydec, sizeof(n.yuv2rgb12));
       std::memcpy(n.rgb2yuv12, yenc, sizeof(n.rgb2yuv12));
       if (live()) chk(vs_embed_tail_yuv(&n, st));
+      return;
+    }
+    if (io == 4) {
+      vs_tail_rgb_desc_t n;
+      std::memset(&n, 0, sizeof(n));
+      n.src = *psrc; n.dst = *pdst; n.preds_w = preds_w; n.delta = delta; n.hmap_lowres = hmap; n.taps43 = m->taps43;
+      n.F = F; n.H = H; n.W = W; n.S_h = Sh; n.S_w = Sw; n.Cd = c.out_ch;
+      n.step = step; n.video_mode = video_mode; n.total_key = nk;
+      n.attenuate = att ? 1 : 0; n.clamp = c.clamp; n.antialias = antialias;
+      n.scaling_i = c.scaling_i; n.scaling_w = c.scaling_w;
+      if (live()) chk(vs_embed_tail_rgb(&n, st));
       return;
     }
     const bool u8 = io != 0;
@@ -1169,5 +1185,31 @@ extern "C" int vs_model_detect_yuv(vs_model_t* m, const vs_yuv_surface_t* in, co
   r.ysrc = in;
   r.ydec = yuv2rgb12 ? yuv2rgb12 : dec;
   r.detect(nullptr, 3, frames, H, W, antialias, logits);
+  return r.rc;
+}
+
+// ---- packed RGB surfaces (rgbpack.hip): the two entry points above with the surfaces of vs_resize_pre_rgb / vs_embed_tail_rgb
+extern "C" int vs_model_embed_rgb(vs_model_t* m, const vs_rgb_surface_t* in, const vs_rgb_surface_t* out, const int32_t* msgs, int n_msgs,
+                                  int frames, int H, int W, int step, int video_mode, int lowres_attenuation, int antialias, void* ws,
+                                  int64_t ws_bytes, void* stream) {
+  VS_REQUIRE(m && in && out && in->data && out->data && msgs && ws && frames > 0 && H > 0 && W > 0 && step >= 1 && ((uintptr_t)ws & 255) == 0);
+  const int nk = (frames + step - 1) / step;
+  VS_REQUIRE(n_msgs == 1 || n_msgs == nk);
+  VS_REQUIRE(video_mode >= 0 && video_mode <= 2);
+  VS_REQUIRE(m->c.clamp && in->data != out->data);
+  if (in->format < VS_RGB_RGB24 || in->format > VS_RGB_X2BGR10 || in->format != out->format) return VS_ERR_UNSUPPORTED;
+  Runner r{m, static_cast<char*>(ws), ws_bytes, 0, stream};
+  r.psrc = in; r.pdst = out;
+  r.embed(nullptr, 4, msgs, n_msgs, frames, H, W, step, video_mode, lowres_attenuation, antialias, nullptr, nullptr);
+  return r.rc;
+}
+
+extern "C" int vs_model_detect_rgb(vs_model_t* m, const vs_rgb_surface_t* in, int frames, int H, int W, int antialias, float* logits, void* ws,
+                                   int64_t ws_bytes, void* stream) {
+  VS_REQUIRE(m && in && in->data && logits && ws && frames > 0 && H > 0 && W > 0 && ((uintptr_t)ws & 255) == 0);
+  if (in->format < VS_RGB_RGB24 || in->format > VS_RGB_X2BGR10) return VS_ERR_UNSUPPORTED;
+  Runner r{m, static_cast<char*>(ws), ws_bytes, 0, stream};
+  r.psrc = in;
+  r.detect(nullptr, 4, frames, H, W, antialias, logits);
   return r.rc;
 }

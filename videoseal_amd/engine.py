@@ -1514,6 +1514,14 @@ class HipEngine:
             raise TypeError(f"frames must be a tensor or a yuv.Clip, got {type(clip).__name__}")
         return fmt_info(clip.fmt)[1], frame_samples(clip.fmt, clip.shape[1], clip.shape[2])
 
+    @staticmethod
+    def _rgb_clip(x) -> bool:
+        """a packed RGB clip (rgbpack.Clip)?  It is a yuv.Clip by inheritance, so the frame routes ask this first"""
+        if torch.is_tensor(x):
+            return False
+        from .rgbpack import Clip
+        return isinstance(x, Clip)
+
     def _resize_pre_yuv(self, clip, S, antialias, *, want_rgb, mul, add, want_key, key_step, tag):
         """resize_pre on a YUV clip of any of the ten formats (a 4:2:0 one reaches the _yuv420 launches through the library's forwarder)"""
         B, H, W = clip.shape
@@ -1555,10 +1563,53 @@ class HipEngine:
         # algorithmic HBM bytes: the frame's samples (1.5, 2 or 3 per pixel) each way + the low-resolution watermark
         self._shell_t1(ev, f"embed_tail_yuv_kernel<{clip.fmt}>", 2 * (F_ * nsamp) * clip.planes[0].element_size() + delta.numel() * 4)
 
+    # ---- packed RGB clips (videoseal_amd/rgbpack.py): one tensor at any pitch, twelve formats
+    def _resize_pre_rgb(self, clip, S, antialias, *, want_rgb, mul, add, want_key, key_step, tag):
+        """resize_pre on a packed RGB clip (rgbpack.Clip): the decode is fused into the kernel"""
+        from .rgbpack import pixel_bytes
+        B, H, W = clip.shape
+        rgb = self.new_act(tag + ".rgb", B, S[0], S[1], 3, 4) if want_rgb else None
+        nk = (B + key_step - 1) // key_step
+        key = self.new_act(tag + ".key", nk, S[0], S[1], self.cfg.in_ch, 4) if want_key else None
+        surf = N.rgb_surface(clip.tensor, clip.fmt)
+        ev = self._shell_t0()
+        N.check(self.lib.vs_resize_pre_rgb(C.byref(surf), B, H, W, S[0], S[1], 1 if antialias else 0, N.ptr(rgb.t) if rgb else None, mul, add,
+                                           N.ptr(key.t) if key else None, key_step, self.ymat if self.cfg.yuv else None, N.stream()),
+                "vs_resize_pre_rgb")
+        # algorithmic HBM bytes: the frame's pixels once + the low-resolution outputs
+        self._shell_t1(ev, f"resize_pre_rgb_kernel<{clip.fmt}>",
+                       B * H * W * pixel_bytes(clip.fmt) + 16 * S[0] * S[1] * ((B if rgb else 0) + (nk if key else 0)))
+        return rgb, key
+
+    def _embed_tail_rgb(self, clip, out, delta, *, step, video_mode, hmap_low, attenuate, clamp, antialias, scaling_i, scaling_w, preds_w=None):
+        """embed_tail on packed RGB clips: `clip` and `out` are rgbpack.Clip of one format and size, each at its own pitch"""
+        from .rgbpack import pixel_bytes
+        if type(out) is not type(clip) or out.fmt != clip.fmt or out.shape != clip.shape:
+            raise ValueError("packed RGB frames need an output clip of the same format and size")
+        if preds_w is not None or int(attenuate) == 2:
+            raise NotImplementedError("the packed RGB tail has no preds_w and no training order of operations")
+        F_, H, W = clip.shape
+        d = N.TailRgbDesc()
+        d.src, d.dst = N.rgb_surface(clip.tensor, clip.fmt), N.rgb_surface(out.tensor, out.fmt)
+        d.preds_w = None
+        d.delta, d.hmap_lowres = N.ptr(delta), N.ptr(hmap_low)
+        d.taps43 = C.cast(self.taps43, C.c_void_p)
+        d.F, d.H, d.W, d.S_h, d.S_w, d.Cd = F_, H, W, delta.shape[-2], delta.shape[-1], delta.shape[1]
+        d.step, d.video_mode, d.total_key = step, video_mode, delta.shape[0]
+        d.attenuate, d.clamp, d.antialias = int(attenuate), int(clamp), int(antialias)
+        d.scaling_i, d.scaling_w = float(scaling_i), float(scaling_w)
+        d.variant = 1 if int(self.tail_variant) in (1, 2, 3) else 0           # (the tile variants of the fp32 tail -> the tile kernel)
+        ev = self._shell_t0()
+        N.check(self.lib.vs_embed_tail_rgb(C.byref(d), N.stream()), "vs_embed_tail_rgb")
+        # algorithmic HBM bytes: the frame's pixels each way + the low-resolution watermark
+        self._shell_t1(ev, f"embed_tail_rgb_kernel<{clip.fmt}>", 2 * F_ * H * W * pixel_bytes(clip.fmt) + delta.numel() * 4)
+
     def resize_pre(self, imgs: torch.Tensor, S: Tuple[int, int], antialias: bool, *, want_rgb: bool, mul=1.0, add=0.0,
                    want_key: bool = False, key_step: int = 1, tag="rs") -> Tuple[Optional[Act], Optional[Act]]:
-        """imgs on device, fp32 NCHW [B,3,H,W], uint8 RGB24 [B,H,W,3] or a YUV clip (yuv.Clip)
+        """imgs on device, fp32 NCHW [B,3,H,W], uint8 RGB24 [B,H,W,3], a YUV clip (yuv.Clip) or a packed RGB clip (rgbpack.Clip)
         -> (rgb Act [B,S,S,4] or None, key Act [ceil(B/step),S,S,4] or None)."""
+        if self._rgb_clip(imgs):
+            return self._resize_pre_rgb(imgs, S, antialias, want_rgb=want_rgb, mul=mul, add=add, want_key=want_key, key_step=key_step, tag=tag)
         if not torch.is_tensor(imgs):         # a YUV clip carries its own format and colour choice
             return self._resize_pre_yuv(imgs, S, antialias, want_rgb=want_rgb, mul=mul, add=add, want_key=want_key, key_step=key_step, tag=tag)
         u8 = imgs.dtype == torch.uint8
@@ -1701,6 +1752,9 @@ class HipEngine:
 
     def embed_tail(self, imgs, out, delta, *, step, video_mode, hmap_low, attenuate, clamp, antialias, scaling_i, scaling_w,
                    preds_w=None):
+        if self._rgb_clip(imgs):
+            return self._embed_tail_rgb(imgs, out, delta, step=step, video_mode=video_mode, hmap_low=hmap_low, attenuate=attenuate, clamp=clamp,
+                                        antialias=antialias, scaling_i=scaling_i, scaling_w=scaling_w, preds_w=preds_w)
         if not torch.is_tensor(imgs):         # a YUV clip (yuv.Clip)
             return self._embed_tail_yuv(imgs, out, delta, step=step, video_mode=video_mode, hmap_low=hmap_low, attenuate=attenuate, clamp=clamp,
                                         antialias=antialias, scaling_i=scaling_i, scaling_w=scaling_w, preds_w=preds_w)

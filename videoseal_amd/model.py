@@ -47,7 +47,8 @@ def _result_buffer(shape, dtype, device) -> torch.Tensor:
 
 
 def _raw_frames(x) -> bool:
-    """frames that travel in their own format: uint8 tensors (RGB24) and YUV clips (yuv.Clip, NV12 clips among them); everything else is fp32 NCHW"""
+    """frames that travel in their own format: uint8 tensors (RGB24), YUV clips (yuv.Clip, NV12 clips among them) and packed RGB clips
+    (rgbpack.Clip); everything else is fp32 NCHW"""
     return not torch.is_tensor(x) or x.dtype == torch.uint8
 
 
@@ -1168,6 +1169,29 @@ class Videoseal(Wam):
         into the resize kernel.  A 4:2:0 `fmt` gives detect_yuv420's logits."""
         from . import yuv
         return self._detect_yuv(self._yuv_clip(planes, fmt, "detect_yuv", matrix, full_range, yuv), "detect_yuv", interpolation)
+
+    # ---- packed RGB clips (videoseal_amd/rgbpack.py): what capture, compositors and image decoders hold, alpha / X carried through
+    @torch.no_grad()
+    def embed_rgb(self, clip: torch.Tensor, fmt: str, msgs: torch.Tensor = None, interpolation: dict = None,
+                  lowres_attenuation: bool = True) -> dict:
+        """clip: a packed RGB clip of format `fmt` (rgbpack.py: "rgb24", "bgr24", "rgba", "bgra", "argb", "abgr" uint8 [F, H, W, 3 | 4];
+        "rgb48", "bgr48", "rgba64", "bgra64" uint16 [F, H, W, 3 | 4]; "x2rgb10", "x2bgr10" int32 [F, H, W]; compact pixels, any row pitch and
+        frame stride) -> {'imgs_w': a contiguous clip of the same dtype and shape, 'msgs'}.  Means: rgbpack.to_rgb -> embed(..., is_video=True)
+        -> rgbpack.from_rgb(like=clip) with both conversions fused into the resize and tail kernels: no fp32 frame is written, a 16-bit clip
+        keeps its 16 bits, and alpha / X of the result are the clip's, bit for bit."""
+        from . import rgbpack
+        rgbpack.check_clip(clip, fmt, "embed_rgb")
+        out, msgs = self._embed_yuv(rgbpack.Clip(clip, fmt), "embed_rgb", msgs, interpolation, lowres_attenuation)
+        res = out.tensor
+        return {"imgs_w": res.view(clip.dtype) if res.dtype != clip.dtype else res, "msgs": msgs}
+
+    @torch.no_grad()
+    def detect_rgb(self, clip: torch.Tensor, fmt: str, interpolation: dict = None) -> dict:
+        """clip, fmt as in embed_rgb -> {'preds': [F, 1+nbits]}: detect(rgbpack.to_rgb(clip, fmt), is_video=True) with the conversion fused
+        into the resize kernel."""
+        from . import rgbpack
+        rgbpack.check_clip(clip, fmt, "detect_rgb")
+        return self._detect_yuv(rgbpack.Clip(clip, fmt), "detect_rgb", interpolation)
 
     def extract_message(self, imgs: torch.Tensor, aggregation: str = "avg",
                         interpolation: dict = {"mode": "bilinear", "align_corners": False, "antialias": False}) -> torch.Tensor:

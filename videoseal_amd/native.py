@@ -48,6 +48,7 @@ EXPORTS = [
     "vs_sizeof_yuv420_surface", "vs_sizeof_tail_yuv420_desc", "vs_resize_pre_yuv420", "vs_embed_tail_yuv420", "vs_yuv420_default_color",
     "vs_model_embed_yuv420", "vs_model_detect_yuv420",
     "vs_sizeof_yuv_surface", "vs_sizeof_tail_yuv_desc", "vs_resize_pre_yuv", "vs_embed_tail_yuv", "vs_model_embed_yuv", "vs_model_detect_yuv",
+    "vs_sizeof_rgb_surface", "vs_sizeof_tail_rgb_desc", "vs_resize_pre_rgb", "vs_embed_tail_rgb", "vs_model_embed_rgb", "vs_model_detect_rgb",
     "vs_resize_pre_images", "vs_embed_tail_images", "vs_images_plan",
     "vs_resize_pre_clips", "vs_embed_tail_clips", "vs_clips_plan", "vs_aggregate_clips",
 ]
@@ -160,6 +161,27 @@ def yuv_surface(planes, fmt: str) -> YuvSurface:
     planar, depth, msb, chroma = fmt_info(fmt)
     s = _fill_surface(YuvSurface(), planes, planar, depth, msb)
     s.chroma = chroma
+    return s
+
+
+class RgbSurface(C.Structure):
+    """mirror of vs_rgb_surface_t: the first byte, row pitch and frame stride in bytes, the format (VS_RGB_*)"""
+    _fields_ = [("data", C.c_void_p), ("pitch", C.c_int64), ("frame_stride", C.c_int64), ("format", C.c_int32), ("reserved_", C.c_int32)]
+
+
+class TailRgbDesc(C.Structure):
+    """mirror of vs_tail_rgb_desc_t: two surfaces, then TailDesc's members from preds_w on"""
+    _fields_ = [("src", RgbSurface), ("dst", RgbSurface)] + TailDesc._fields_[2:]
+
+
+def rgb_surface(clip, fmt: str) -> RgbSurface:
+    """the surface of a device-resident packed RGB clip (videoseal_amd/rgbpack.py): a strided view stays one, nothing is copied"""
+    from .rgbpack import fmt_info
+    s = RgbSurface()
+    s.data = ptr(clip)
+    s.pitch = clip.stride(1) * clip.element_size()
+    s.frame_stride = clip.stride(0) * clip.element_size()
+    s.format = fmt_info(fmt)[0]
     return s
 
 
@@ -331,6 +353,8 @@ def lib() -> C.CDLL:
         "vs_yuv420_default_color": [I, P, P],
         "vs_resize_pre_yuv": [C.POINTER(YuvSurface), I, I, I, P, I, I, I, P, F, F, P, I, P, P],
         "vs_embed_tail_yuv": [C.POINTER(TailYuvDesc), P],
+        "vs_resize_pre_rgb": [C.POINTER(RgbSurface), I, I, I, I, I, I, P, F, F, P, I, P, P],
+        "vs_embed_tail_rgb": [C.POINTER(TailRgbDesc), P],
         "vs_resize_pre_images": [C.POINTER(ImageDesc), I, I, I, I, I, P, F, F, P, P, P],
         "vs_embed_tail_images": [C.POINTER(TailImagesDesc), P],
         "vs_images_plan": [C.POINTER(ImageDesc), I, I, I, I, I, I, C.POINTER(ImagesGroup), I, C.POINTER(C.c_int)],
@@ -468,6 +492,7 @@ def lib() -> C.CDLL:
     L.vs_sizeof_tail_nv12_desc.restype = C.c_int
     L.vs_sizeof_yuv420_surface.restype = L.vs_sizeof_tail_yuv420_desc.restype = C.c_int
     L.vs_sizeof_yuv_surface.restype = L.vs_sizeof_tail_yuv_desc.restype = C.c_int
+    L.vs_sizeof_rgb_surface.restype = L.vs_sizeof_tail_rgb_desc.restype = C.c_int
     L.vs_sizeof_conv_plan.restype = L.vs_sizeof_cnx_stage_plan.restype = C.c_int
     if L.vs_version() != 3:
         raise NativeError(f"{LIB_PATH} has ABI version {L.vs_version()}, this binding is written for 3: rebuild (make -C videoseal_amd/csrc)")
@@ -475,8 +500,9 @@ def lib() -> C.CDLL:
             L.vs_sizeof_tail_nv12_desc() != C.sizeof(TailNv12Desc) or L.vs_sizeof_conv_plan() != C.sizeof(ConvPlan) or \
             L.vs_sizeof_cnx_stage_plan() != C.sizeof(CnxStagePlan) or L.vs_sizeof_yuv420_surface() != C.sizeof(Yuv420Surface) or \
             L.vs_sizeof_tail_yuv420_desc() != C.sizeof(TailYuv420Desc) or L.vs_sizeof_yuv_surface() != C.sizeof(YuvSurface) or \
-            L.vs_sizeof_tail_yuv_desc() != C.sizeof(TailYuvDesc):
-        raise NativeError("ctypes mirrors of vs_conv_desc_t / vs_tail_desc_t / vs_tail_nv12_desc_t / vs_tail_yuv420_desc_t / vs_tail_yuv_desc_t / the plan structs are out of date with the shared library")
+            L.vs_sizeof_tail_yuv_desc() != C.sizeof(TailYuvDesc) or L.vs_sizeof_rgb_surface() != C.sizeof(RgbSurface) or \
+            L.vs_sizeof_tail_rgb_desc() != C.sizeof(TailRgbDesc):
+        raise NativeError("ctypes mirrors of vs_conv_desc_t / vs_tail_desc_t / vs_tail_nv12_desc_t / vs_tail_yuv420_desc_t / vs_tail_yuv_desc_t / vs_tail_rgb_desc_t / the plan structs are out of date with the shared library")
     _lib = L
     return L
 
