@@ -608,6 +608,36 @@ typedef struct vs_tail_desc {
 } vs_tail_desc_t;
 int vs_embed_tail(const vs_tail_desc_t* d, void* stream);
 
+/*
+ * Embedding to a target PSNR: the watermark's strength per frame, chosen on the device.  With d the perturbation of a pixel as above (the
+ * value preds_w receives for attenuate 0 / 1), for frame f of H x W pixels
+ *   E_f  = (3 / Cd) * sum_{c < Cd, y, x} d^2                      energy of the RGB perturbation, float64
+ *   s_f  = 10^(-T / 20) * sqrt(3 H W / E_f)                       T = target PSNR in dB at data range 1;  s_f = 0 where E_f == 0
+ *   s_f  = min(s_f, max_scale)                                    when max_scale > 0
+ *   out  = clamp(scaling_i * imgs + s_f * d, 0, 1)
+ * per_clip: one s for all frames, from sum_f E_f over 3 F H W elements (the PSNR of the clip as one signal).
+ * Before the clamp and with scaling_i = 1 the PSNR of out against imgs is T, unless the ceiling binds; the clamp only moves pixels towards
+ * imgs (PSNR >= T); uint8 output adds its quantisation noise.  Neither is corrected for.
+ *   vs_embed_tail_energy : E[F] of the descriptor's tail -- d from the tail's own expressions in the tail's own form (row-streaming where the
+ *       default dispatch takes it, 16-row tiles elsewhere), d * d and all sums in float64, no frame stored.  Every workgroup writes one
+ *       partial into `partials` (vs_tail_energy_partial_doubles(F, H, W) doubles, no need to clear them), a second launch adds a frame's
+ *       partials in a fixed order: no atomics, two runs give the same bits.  out, preds_w, scaling_w and clamp of the descriptor are ignored.
+ *   vs_psnr_scale        : E[F] -> scale[F] (fp32) by the formula above, evaluated in float64 and rounded once.  VS_ERR_BAD_ARG for a
+ *       non-finite target_db.
+ *   vs_embed_tail_scaled : vs_embed_tail with scaling_w replaced by frame_scale[f], read from device memory; bit for bit vs_embed_tail at
+ *       scaling_w = frame_scale[f] for every frame.
+ * The three are ordinary launches on `stream`: chained, they need no host synchronisation.  variant 0, 1, 2 and 4 select the form they select for
+ * vs_embed_tail; variant 3 (the 8-row A/B form) and attenuate = 2 answer VS_ERR_UNSUPPORTED.  The process-wide VIDEOSEAL_TAIL=v1 is followed;
+ * under VIDEOSEAL_TAIL=keep the three take the 16-row tiles with the same separable stencils, which give the bits of the 8-row form.
+ * vs_tail_energy_partial_doubles sizes `partials` for the shortest strip any switch can ask for (4 rows); a default launch writes a 4th to a
+ * 24th of it.
+ */
+int64_t vs_tail_energy_partial_doubles(int F, int H, int W);
+int vs_embed_tail_energy(const vs_tail_desc_t* d, double* partials, double* energy /* [F] */, void* stream);
+int vs_psnr_scale(const double* energy, int F, int H, int W, int per_clip, float target_db, float max_scale /* <= 0: none */,
+                  float* scale /* [F] */, void* stream);
+int vs_embed_tail_scaled(const vs_tail_desc_t* d, const float* frame_scale /* [F] */, void* stream);
+
 /* ------------------------------------------------------------------------------------------------------------------
  * Lists of images of different sizes: the two full-resolution passes around ONE network pass over the whole list (the network runs at
  * the processing size and does not care how large a picture was).  An image is a base pointer with its own H and W; image i of the list
@@ -972,6 +1002,14 @@ int vs_model_embed(vs_model_t* m, const void* imgs, const int32_t* msgs, int n_m
                    int64_t ws_bytes, void* stream);
 int vs_model_detect(vs_model_t* m, const void* imgs, int frames, int H, int W, int antialias, int io_u8, float* logits, void* ws,
                     int64_t ws_bytes, void* stream);
+/* vs_model_embed to a target PSNR (Videoseal.embed_psnr on one chunk; see vs_embed_tail_energy): the model's scaling_w is replaced by a
+ * strength per frame -- or one for the chunk, per_clip = 1 -- that puts the unclamped watermarked frame at target_db against imgs, capped at
+ * max_scale when max_scale > 0.  The strengths applied are left in scale_out (DEVICE, fp32 [frames]).  io_u8 0 and 1; other values answer
+ * VS_ERR_UNSUPPORTED.  The workspace is vs_model_embed_psnr_workspace_bytes(...) bytes; no host synchronisation inside. */
+int64_t vs_model_embed_psnr_workspace_bytes(const vs_model_t* m, int frames, int H, int W, int step);
+int vs_model_embed_psnr(vs_model_t* m, const void* imgs, const int32_t* msgs, int n_msgs, int frames, int H, int W, int step,
+                        int video_mode, int lowres_attenuation, int antialias, int io_u8, float target_db, int per_clip, float max_scale,
+                        void* imgs_w, float* preds_w, float* scale_out, void* ws, int64_t ws_bytes, void* stream);
 /* colour affines of io_u8 = 2 (HOST arrays of 12 floats, row-major 3 x 4: codes -> RGB in [0,1] and its inverse, see vs_resize_pre_nv12) */
 int vs_model_set_nv12_color(vs_model_t* m, const float* yuv2rgb12, const float* rgb2yuv12);
 /* the pair a fresh model holds (BT.709 limited range), written to two HOST arrays of 12 floats; needs no GPU */

@@ -39,6 +39,10 @@ def _bind(L):
     L.vs_model_workspace_bytes.restype = I64
     L.vs_model_embed.argtypes = [P, P, P, I, I, I, I, I, I, I, I, I, P, P, P, I64, P]
     L.vs_model_embed.restype = I
+    L.vs_model_embed_psnr_workspace_bytes.argtypes = [P, I, I, I, I]
+    L.vs_model_embed_psnr_workspace_bytes.restype = I64
+    L.vs_model_embed_psnr.argtypes = [P, P, P, I, I, I, I, I, I, I, I, I, C.c_float, I, C.c_float, P, P, P, P, I64, P]
+    L.vs_model_embed_psnr.restype = I
     L.vs_model_detect.argtypes = [P, P, I, I, I, I, I, P, P, I64, P]
     L.vs_model_detect.restype = I
     L.vs_model_set_nv12_color.argtypes = [P, P, P]
@@ -140,6 +144,23 @@ class CModel:
         N.check(self._L.vs_model_embed(self._h, N.ptr(x), N.ptr(m), m.shape[0], F_, H, W, step, video_mode, int(lowres_attenuation),
                                        int(antialias), int(u8), N.ptr(out), N.ptr(pw), N.ptr(ws), ws.numel(), N.stream()), "vs_model_embed")
         return (out, pw) if want_preds_w else out
+
+    def embed_psnr(self, imgs: torch.Tensor, msgs: torch.Tensor, target_psnr: float, *, per_clip: bool = False,
+                   max_scaling_w: Optional[float] = None, step: int = 1, video_mode: int = 0, lowres_attenuation: bool = False,
+                   antialias: bool = True):
+        """vs_model_embed_psnr on one chunk of fp32 NCHW or uint8 RGB24 frames -> (imgs_w, the strengths applied: fp32 [F] on the device)"""
+        x, F_, H, W, u8 = self._frames(imgs)
+        m = msgs.to(device=x.device, dtype=torch.int32).contiguous()
+        out = torch.empty_like(x)
+        scale = torch.empty(F_, device=x.device, dtype=torch.float32)
+        need = int(self._L.vs_model_embed_psnr_workspace_bytes(self._h, F_, H, W, step))
+        if need < 0:
+            raise N.NativeError("vs_model_embed_psnr_workspace_bytes failed")
+        ws = torch.empty(need, dtype=torch.uint8, device=x.device)
+        N.check(self._L.vs_model_embed_psnr(self._h, N.ptr(x), N.ptr(m), m.shape[0], F_, H, W, step, video_mode, int(lowres_attenuation),
+                                            int(antialias), int(u8), float(target_psnr), int(per_clip), float(max_scaling_w or 0.0),
+                                            N.ptr(out), None, N.ptr(scale), N.ptr(ws), ws.numel(), N.stream()), "vs_model_embed_psnr")
+        return out, scale
 
     def detect(self, imgs: torch.Tensor, antialias: bool = True) -> torch.Tensor:
         x, F_, H, W, u8 = self._frames(imgs)

@@ -330,6 +330,9 @@ struct Runner {
   // io = 4 (vs_model_*_rgb): the packed RGB surfaces
   const vs_rgb_surface_t* psrc = nullptr;
   const vs_rgb_surface_t* pdst = nullptr;
+  // vs_model_embed_psnr: the strength of every frame comes from a target PSNR (scale_out: device, [frames])
+  struct Psnr { float target_db; int per_clip; float max_scale; float* scale_out; };
+  const Psnr* psnr = nullptr;
 
   float* alloc(int64_t floats) {
     const int64_t bytes = (floats * 4 + 255) & ~(int64_t)255;
@@ -843,6 +846,15 @@ struct Runner {
     d.attenuate = att ? 1 : 0; d.clamp = c.clamp; d.antialias = antialias;
     d.scaling_i = c.scaling_i; d.scaling_w = c.scaling_w;
     d.io_u8 = u8 ? 1 : 0;
+    if (psnr) {           // model.py::embed_psnr on one chunk: energy pass -> strengths -> scaled tail, three launches on `st`
+      const int64_t np = vs_tail_energy_partial_doubles(F, H, W);
+      double* partials = reinterpret_cast<double*>(alloc(2 * np));
+      double* energy = reinterpret_cast<double*>(alloc(2 * (int64_t)F));
+      if (live()) chk(vs_embed_tail_energy(&d, partials, energy, st));
+      if (live()) chk(vs_psnr_scale(energy, F, H, W, psnr->per_clip, psnr->target_db, psnr->max_scale, psnr->scale_out, st));
+      if (live()) chk(vs_embed_tail_scaled(&d, psnr->scale_out, st));
+      return;
+    }
     if (live()) chk(vs_embed_tail(&d, st));
   }
   void detect(const void* imgs, int io, int F, int H, int W, int antialias, float* logits) {
@@ -1091,6 +1103,33 @@ extern "C" int vs_model_embed(vs_model_t* m, const void* imgs, const int32_t* ms
     r.ysrc = &in; r.ydst = &out; r.ydec = m->yuv2rgb12; r.yenc = m->rgb2yuv12;
     io_u8 = 3;
   }
+  r.embed(imgs, io_u8, msgs, n_msgs, frames, H, W, step, video_mode, lowres_attenuation, antialias, imgs_w, preds_w);
+  return r.rc;
+}
+
+extern "C" int64_t vs_model_embed_psnr_workspace_bytes(const vs_model_t* m, int frames, int H, int W, int step) {
+  if (!m || frames <= 0 || H <= 0 || W <= 0 || step < 1) return -1;
+  const Runner::Psnr p{42.f, 0, 0.f, nullptr};
+  Runner e{const_cast<vs_model_t*>(m), nullptr, 0, 0, nullptr};
+  e.psnr = &p;
+  e.embed(nullptr, 0, nullptr, 1, frames, H, W, step, 0, 1, 1, nullptr, nullptr);
+  return e.used + 256;
+}
+
+extern "C" int vs_model_embed_psnr(vs_model_t* m, const void* imgs, const int32_t* msgs, int n_msgs, int frames, int H, int W, int step,
+                                   int video_mode, int lowres_attenuation, int antialias, int io_u8, float target_db, int per_clip,
+                                   float max_scale, void* imgs_w, float* preds_w, float* scale_out, void* ws, int64_t ws_bytes,
+                                   void* stream) {
+  VS_REQUIRE(m && imgs && msgs && imgs_w && scale_out && ws && frames > 0 && H > 0 && W > 0 && step >= 1 && ((uintptr_t)ws & 255) == 0);
+  VS_REQUIRE(std::isfinite(target_db));
+  const int nk = (frames + step - 1) / step;
+  VS_REQUIRE(n_msgs == 1 || n_msgs == nk);
+  VS_REQUIRE(video_mode >= 0 && video_mode <= 2);
+  if (io_u8 != 0 && io_u8 != 1) return VS_ERR_UNSUPPORTED;      // (the YUV and packed RGB routes keep the fixed strength)
+  if (io_u8) VS_REQUIRE(m->c.clamp);
+  const Runner::Psnr p{target_db, per_clip ? 1 : 0, max_scale, scale_out};
+  Runner r{m, static_cast<char*>(ws), ws_bytes, 0, stream};
+  r.psnr = &p;
   r.embed(imgs, io_u8, msgs, n_msgs, frames, H, W, step, video_mode, lowres_attenuation, antialias, imgs_w, preds_w);
   return r.rc;
 }

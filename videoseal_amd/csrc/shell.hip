@@ -6,10 +6,38 @@
 #include "shell_common.h"
 #include "images_plan.h"
 #include "clips_plan.h"
+#include <cmath>
+#include <type_traits>
 
 namespace {
 
 using namespace vs_taps;
+
+// ---- modes of the tail bodies.  BLEND is vs_embed_tail.  SCALED (vs_embed_tail_scaled) takes the watermark's strength of frame f from
+// frame_scale[f] in device memory instead of scaling_w.  ENERGY (vs_embed_tail_energy) computes the same d and stores no frame: every thread
+// adds d * d of its pixels in float64 (the product of two fp32 values is exact there) and the workgroup writes ONE partial sum into
+// partials[f][blockIdx.y][blockIdx.x]; no atomics, the order of every addition is fixed, so two runs give the same bits.
+// The new members ride behind TailArgs in a derived struct, so the kernel arguments of the BLEND instantiations are what they were.
+constexpr int TAIL_BLEND = 0, TAIL_SCALED = 1, TAIL_ENERGY = 2;
+struct TailArgsX : TailArgs { const float* frame_scale; double* partials; };
+template <int MODE> using tail_args_t = std::conditional_t<MODE == TAIL_BLEND, TailArgs, TailArgsX>;
+
+template <int MODE>
+__device__ __forceinline__ float tail_strength(const tail_args_t<MODE>& a, const int f) {
+  if constexpr (MODE == TAIL_SCALED) return a.frame_scale[f];
+  else return a.scaling_w;
+}
+
+// the workgroup's partial of a clip kernel (grid = tile columns x tile rows x frames): lanes, then the four waves, in a fixed order
+__device__ __forceinline__ void tail_energy_store(const double e, double* __restrict__ partials, const int f) {
+  __shared__ double red[4];
+  double v = e;
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) v += __shfl_down(v, o, 64);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  if (threadIdx.x == 0) partials[((int64_t)f * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
+}
 
 // ---- frame element access: fp32 NCHW planes, or uint8 RGB24 (HWC, what inference_streaming.py:26 reads from the ffmpeg
 // pipe).  uint8 -> float is exactly `torch.tensor(clip, dtype=float32) / 255.0`; float -> uint8 is `(x * 255.0).byte()`
@@ -249,8 +277,8 @@ __global__ __launch_bounds__(256) void jnd_heatmap_kernel(const float* __restric
 // (the tile's body: columns from x0, rows from y0 of the frame `img` -> `outf` / `predf`; f names the frame's key frame and its rows of
 // hmap_lowres.  All of them workgroup-uniform: blockIdx for a clip (embed_tail_kernel), a table look-up for a list of images, each with its
 // own a.H x a.W (the *_images kernels below).)
-template <typename T, bool SEP, int TH, bool KEEP>
-__device__ __forceinline__ void embed_tail_tile(const TailArgs& a, const JndTaps& k, const int x0, const int y0, const int f,
+template <typename T, bool SEP, int TH, bool KEEP, int MODE = TAIL_BLEND>
+__device__ __forceinline__ void embed_tail_tile(const tail_args_t<MODE>& a, const JndTaps& k, const int x0, const int y0, const int f,
                                                 const T* __restrict__ img, T* __restrict__ outf, float* __restrict__ predf) {
   constexpr int TTH = TH;
   constexpr int DWH = TH == 8 ? 8 : DW_H;              // rows of the watermark's source window (8-row tiles at >= 2x up-scale need <= 8)
@@ -358,7 +386,10 @@ __device__ __forceinline__ void embed_tail_tile(const TailArgs& a, const JndTaps
     }
   }
   __syncthreads();      // L, Dw
-  if (x >= a.W) return;
+  if (MODE != TAIL_ENERGY && x >= a.W) return;
+  const float sw = tail_strength<MODE>(a, f);
+  double e = 0.0;                                     // ENERGY: this thread's sum of d * d
+  const int lasty_t = (MODE == TAIL_ENERGY && x >= a.W) ? -1 : lasty;      // (ENERGY: every thread stays for the workgroup's sum)
 
   auto tap = [&](const int sp, const float wx, float (&r)[3]) __attribute__((always_inline)) {
     const float hm = hml ? hml[sp] : 1.f;
@@ -371,11 +402,11 @@ __device__ __forceinline__ void embed_tail_tile(const TailArgs& a, const JndTaps
   // rows in groups of RG: the frame loads of a whole group are issued before any of it is consumed -- with one row (3 loads) in
   // flight per wave and ~16 waves per CU the kernel cannot cover the HBM latency (measured 2 TB/s)
   constexpr int RG = 4;
-  for (int lyg = 0; lyg <= lasty; lyg += RG) {      // no workgroup barrier below this line
+  for (int lyg = 0; lyg <= lasty_t; lyg += RG) {      // no workgroup barrier below this line
     float px[RG][3];
 #pragma unroll
     for (int q = 0; q < RG; ++q)
-      if (lyg + q <= lasty) {
+      if (MODE != TAIL_ENERGY && lyg + q <= lasty) {
         const int64_t pix = (int64_t)(y0 + lyg + q) * a.W + x;
 #pragma unroll
         for (int c = 0; c < 3; ++c) px[q][c] = (KEEP && full_jnd) ? Pk[(c * TTH + lyg + q) * TTW + lx] : Px<T>::ld(img, plane, c, pix);
@@ -440,24 +471,29 @@ __device__ __forceinline__ void embed_tail_tile(const TailArgs& a, const JndTaps
         if (!fwd_order)
           for (int c = 0; c < a.Cd; ++c) d[c] = hm * d[c];
       }
+      if (MODE == TAIL_ENERGY) {
+        for (int c = 0; c < a.Cd; ++c) e += (double)d[c] * (double)d[c];
+        continue;
+      }
       const int64_t pix = (int64_t)y * a.W + x;
       if (predf)
         for (int c = 0; c < a.Cd; ++c) predf[c * plane + pix] = d[c];
 #pragma unroll
       for (int c = 0; c < 3; ++c) {
-        float v = blend_px(a.scaling_i, a.scaling_w, px[q][c], d[a.Cd == 1 ? 0 : c], hm, fwd_order);
+        float v = blend_px(a.scaling_i, sw, px[q][c], d[a.Cd == 1 ? 0 : c], hm, fwd_order);
         if (a.clamp) v = v <= 0.f ? 0.f : (v >= 1.f ? 1.f : v);      // (NaN passes: fminf / fmaxf would turn it into 0)
         Px<T>::st(outf, plane, c, pix, v);
       }
     }
   }
+  if constexpr (MODE == TAIL_ENERGY) tail_energy_store(e, a.partials, f);      // (clip kernel only: the slot is the workgroup's place in the grid)
 }
 
-template <typename T, bool SEP, int TH, bool KEEP>
-__global__ __launch_bounds__(256) void embed_tail_kernel(TailArgs a, JndTaps k) {
+template <typename T, bool SEP, int TH, bool KEEP, int MODE = TAIL_BLEND>
+__global__ __launch_bounds__(256) void embed_tail_kernel(tail_args_t<MODE> a, JndTaps k) {
   const int f = blockIdx.z;
   const int64_t plane = (int64_t)a.H * a.W;
-  embed_tail_tile<T, SEP, TH, KEEP>(a, k, blockIdx.x * TTW, blockIdx.y * TH, f, static_cast<const T*>(a.imgs) + (int64_t)f * 3 * plane,
+  embed_tail_tile<T, SEP, TH, KEEP, MODE>(a, k, blockIdx.x * TTW, blockIdx.y * TH, f, static_cast<const T*>(a.imgs) + (int64_t)f * 3 * plane,
                                     static_cast<T*>(a.out) + (int64_t)f * 3 * plane,
                                     a.preds_w ? a.preds_w + (int64_t)f * a.Cd * plane : nullptr);
 }
@@ -482,8 +518,8 @@ __global__ __launch_bounds__(256) void embed_tail_kernel(TailArgs a, JndTaps k) 
 // (No waves-per-SIMD hint and no wrapper around the body: `__launch_bounds__(256, 3 | 4)` as well as a __forceinline__ body called from two
 // __global__ wrappers made hipcc spill 16-40 bytes per lane; a scratch reload waits for every older global load -- the row prefetch -- and the
 // JND form ran 40 % slower: 175-180 -> 245-265 us at 32 x 768^2, profiles/r04_tail_forms.md.)
-template <bool JND, int CD>
-__global__ __launch_bounds__(256) void embed_tail_stream_kernel(TailArgs a, JndTaps k, const int strip) {
+template <bool JND, int CD, int MODE = TAIL_BLEND>
+__global__ __launch_bounds__(256) void embed_tail_stream_kernel(tail_args_t<MODE> a, JndTaps k, const int strip) {
   extern __shared__ float dyn_smem[];
   float* Lr = dyn_smem;                                        // [RING][TLW] luminance ring (JND only)
   float* DwB = dyn_smem + (JND ? RING * TLW : 0);              // [2][Cd][DW_H][DW_W] watermark source windows
@@ -600,6 +636,11 @@ __global__ __launch_bounds__(256) void embed_tail_stream_kernel(TailArgs a, JndT
   auto load_rows = [&](const int r0) __attribute__((always_inline)) {     // rows r0 .. r0 + SG - 1 of the own (and halo) column -> pf / pfh
 #pragma unroll
     for (int q = 0; q < SG; ++q) {
+      if constexpr (MODE == TAIL_ENERGY && !JND) {          // d does not depend on the frame: nothing of it is read
+#pragma unroll
+        for (int c = 0; c < 3; ++c) pf[q][c] = 0.f;
+        continue;
+      }
       const int gy = r0 + q;
       const int cy = gy < 0 ? 0 : (gy > ymax_need ? ymax_need : gy);       // always a valid address; rows outside are zeroed when used
       const int64_t pix = (int64_t)cy * a.W;
@@ -618,6 +659,8 @@ __global__ __launch_bounds__(256) void embed_tail_stream_kernel(TailArgs a, JndT
 #pragma unroll
   for (int i = 0; i < 2 * SG; ++i) { acc_la[i] = 0.f; acc_gx[i] = 0.f; acc_gy[i] = 0.f; }
   float hist[2][3] = {{0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}};
+  const float sw = tail_strength<MODE>(a, f);
+  double e = 0.0;                                              // ENERGY: this thread's sum of d * d
   load_rows(y0 - HALO);
   stage(0, 0);
   for (int it = -1; it < niter; ++it) {
@@ -680,6 +723,11 @@ __global__ __launch_bounds__(256) void embed_tail_stream_kernel(TailArgs a, JndT
         if (JND && !fwd_order)
 #pragma unroll
           for (int c = 0; c < CD; ++c) d[c] = hm * d[c];
+        if (MODE == TAIL_ENERGY) {
+#pragma unroll
+          for (int c = 0; c < CD; ++c) e += (double)d[c] * (double)d[c];
+          continue;
+        }
         const int64_t pix = (int64_t)y * a.W + x;
         if (a.preds_w)
 #pragma unroll
@@ -687,7 +735,7 @@ __global__ __launch_bounds__(256) void embed_tail_stream_kernel(TailArgs a, JndT
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
           const float p = j < 2 ? hist[j][c] : cu[j - 2][c];
-          float v = blend_px(a.scaling_i, a.scaling_w, p, d[CD == 1 ? 0 : c], hm, fwd_order);
+          float v = blend_px(a.scaling_i, sw, p, d[CD == 1 ? 0 : c], hm, fwd_order);
           if (a.clamp) v = v <= 0.f ? 0.f : (v >= 1.f ? 1.f : v);      // (NaN passes)
           outf[c * plane + pix] = v;
         }
@@ -701,6 +749,7 @@ __global__ __launch_bounds__(256) void embed_tail_stream_kernel(TailArgs a, JndT
 #pragma unroll
     for (int c = 0; c < 3; ++c) { hist[0][c] = cu[2][c]; hist[1][c] = cu[3][c]; }
   }
+  if constexpr (MODE == TAIL_ENERGY) tail_energy_store(e, a.partials, f);
 }
 
 // (no waves-per-SIMD hint on the JND form: with `__launch_bounds__(256, 3)` or `(256, 4)` hipcc schedules the same body 40 % slower -- 132
@@ -926,13 +975,29 @@ extern "C" int vs_jnd_heatmap(const float* img, int B, int H, int W, int64_t sb,
   return vs_launch_status();
 }
 
-extern "C" int vs_embed_tail(const vs_tail_desc_t* d, void* stream) {
-  VS_REQUIRE(d && d->imgs && d->out && d->delta && d->F > 0 && d->H > 0 && d->W > 0 && d->S_h > 0 && d->S_w > 0);
+namespace {
+
+// The one dispatch of the clip tail for its three modes (vs_embed_tail, vs_embed_tail_scaled, vs_embed_tail_energy): the same rule picks the
+// form in every mode, so the energy pass and the scaled tail compute the d of the tail they stand beside.  `slots`: partials per frame.
+template <int MODE>
+int tail_launch(const vs_tail_desc_t* d, const float* frame_scale, double* partials, int* slots, void* stream) {
+  VS_REQUIRE(d && d->imgs && (MODE == TAIL_ENERGY || d->out) && d->delta && d->F > 0 && d->H > 0 && d->W > 0 && d->S_h > 0 && d->S_w > 0);
   VS_REQUIRE((d->Cd == 1 || d->Cd == 3) && d->step >= 1 && d->total_key >= 1);
   VS_REQUIRE(d->video_mode >= 0 && d->video_mode <= 2);
   VS_REQUIRE(!(d->attenuate && !d->hmap_lowres) || d->taps43);
-  TailArgs a{d->imgs, d->out, d->preds_w, d->delta, d->attenuate ? d->hmap_lowres : nullptr, d->F, d->H, d->W, d->S_h, d->S_w,
-             d->Cd, d->step, d->video_mode, d->total_key, d->attenuate, d->clamp, d->antialias, d->scaling_i, d->scaling_w};
+  int form = d->variant >= 1 && d->variant <= 4 ? d->variant : vs_debug_get(VS_DBG_TAIL_FORM);
+  if (MODE != TAIL_BLEND) {
+    // the training order of operations; the 8-row A/B form asked per call.  (The 8-row body is not built in the new modes: with them beside
+    // it hipcc allocates the registers of its BLEND instantiation differently, 125 -> 126 VGPRs.)
+    if (d->attenuate == 2 || d->variant == 3) return VS_ERR_UNSUPPORTED;
+    if (form == 3) form = 2;      // process-wide VIDEOSEAL_TAIL=keep: the 16-row tiles with the same separable stencils, the same bits
+  }
+  const TailArgs base{d->imgs, MODE == TAIL_ENERGY ? nullptr : d->out, MODE == TAIL_ENERGY ? nullptr : d->preds_w, d->delta,
+                      d->attenuate ? d->hmap_lowres : nullptr, d->F, d->H, d->W, d->S_h, d->S_w,
+                      d->Cd, d->step, d->video_mode, d->total_key, d->attenuate, d->clamp, d->antialias, d->scaling_i, d->scaling_w};
+  tail_args_t<MODE> a;
+  if constexpr (MODE == TAIL_BLEND) a = base;
+  else a = TailArgsX{base, frame_scale, partials};
   JndTaps k{};
   if (d->taps43) k = taps_from(d->taps43);
   dim3 grid((d->W + TTW - 1) / TTW, (d->H + TTH - 1) / TTH, d->F);
@@ -943,7 +1008,6 @@ extern "C" int vs_embed_tail(const vs_tail_desc_t* d, void* stream) {
   // barriers before the first output row), not HBM traffic, is what the tail pays for (profiles/r03s_shell_keep_form.log)
   // VIDEOSEAL_TAIL: stream (default) = the row-streaming kernel where it applies, sep = separable stencils on 16-row tiles (round 3's default),
   // v1 = 43-tap form, keep = 8-row tiles with the pixels parked in LDS.  d->variant (1 = v1, 2 = sep, 3 = keep, 4 = stream) overrides it per call.
-  const int form = d->variant >= 1 && d->variant <= 4 ? d->variant : vs_debug_get(VS_DBG_TAIL_FORM);
   const int mode = form >= 1 && form <= 4 ? form - 1 : 3;
   const bool full_jnd = d->attenuate && !d->hmap_lowres;
   const bool sep = mode > 0 && full_jnd && d->taps43 && standard_jnd_taps(d->taps43);
@@ -951,23 +1015,94 @@ extern "C" int vs_embed_tail(const vs_tail_desc_t* d, void* stream) {
     const int64_t cols = (d->W + TTW - 1) / TTW;
     const int strip = tail_strip(full_jnd, d->F, d->H, d->W);
     dim3 gs((unsigned)cols, (d->H + strip - 1) / strip, d->F);
+    if (slots) *slots = (int)(gs.x * gs.y);
     const size_t lds_w = (size_t)2 * d->Cd * DW_W * DW_H * sizeof(float);
     const size_t lds_j = lds_w + RING * TLW * sizeof(float);
-    if (full_jnd && d->Cd == 1) hipLaunchKernelGGL((embed_tail_stream_kernel<true, 1>), gs, dim3(256), lds_j, (hipStream_t)stream, a, k, strip);
-    else if (full_jnd) hipLaunchKernelGGL((embed_tail_stream_kernel<true, 3>), gs, dim3(256), lds_j, (hipStream_t)stream, a, k, strip);
-    else if (d->Cd == 1) hipLaunchKernelGGL((embed_tail_stream_kernel<false, 1>), gs, dim3(256), lds_w, (hipStream_t)stream, a, k, strip);
-    else hipLaunchKernelGGL((embed_tail_stream_kernel<false, 3>), gs, dim3(256), lds_w, (hipStream_t)stream, a, k, strip);
+    if (full_jnd && d->Cd == 1) hipLaunchKernelGGL((embed_tail_stream_kernel<true, 1, MODE>), gs, dim3(256), lds_j, (hipStream_t)stream, a, k, strip);
+    else if (full_jnd) hipLaunchKernelGGL((embed_tail_stream_kernel<true, 3, MODE>), gs, dim3(256), lds_j, (hipStream_t)stream, a, k, strip);
+    else if (d->Cd == 1) hipLaunchKernelGGL((embed_tail_stream_kernel<false, 1, MODE>), gs, dim3(256), lds_w, (hipStream_t)stream, a, k, strip);
+    else hipLaunchKernelGGL((embed_tail_stream_kernel<false, 3, MODE>), gs, dim3(256), lds_w, (hipStream_t)stream, a, k, strip);
     return vs_launch_status();
   }
+  if (slots) *slots = (int)(grid.x * grid.y);
   if (d->io_u8) {
-    VS_REQUIRE(d->clamp);        // (x * 255).byte() is only defined for x in [0, 1]
+    VS_REQUIRE(MODE == TAIL_ENERGY || d->clamp);        // (x * 255).byte() is only defined for x in [0, 1]
     // (uint8 frames keep the 43-tap form: measured 215 us against 248 us for the separable one, profiles/r03i_shell_separable.log)
-    hipLaunchKernelGGL((embed_tail_kernel<unsigned char, false, 16, false>), grid, dim3(256), 0, (hipStream_t)stream, a, k);
+    hipLaunchKernelGGL((embed_tail_kernel<unsigned char, false, 16, false, MODE>), grid, dim3(256), 0, (hipStream_t)stream, a, k);
   } else {
-    if (sep && mode == 2) hipLaunchKernelGGL((embed_tail_kernel<float, true, 8, true>), grid8, dim3(256), 0, (hipStream_t)stream, a, k);
-    else if (sep) hipLaunchKernelGGL((embed_tail_kernel<float, true, 16, false>), grid, dim3(256), 0, (hipStream_t)stream, a, k);
-    else hipLaunchKernelGGL((embed_tail_kernel<float, false, 16, false>), grid, dim3(256), 0, (hipStream_t)stream, a, k);
+    if constexpr (MODE == TAIL_BLEND) {
+      if (sep && mode == 2) {
+        hipLaunchKernelGGL((embed_tail_kernel<float, true, 8, true>), grid8, dim3(256), 0, (hipStream_t)stream, a, k);
+        return vs_launch_status();
+      }
+    }
+    if (sep) hipLaunchKernelGGL((embed_tail_kernel<float, true, 16, false, MODE>), grid, dim3(256), 0, (hipStream_t)stream, a, k);
+    else hipLaunchKernelGGL((embed_tail_kernel<float, false, 16, false, MODE>), grid, dim3(256), 0, (hipStream_t)stream, a, k);
   }
+  return vs_launch_status();
+}
+
+// one wave per frame: lane l adds the frame's partials l, l + 64, ... in that order, then the lanes are added in a fixed tree
+__global__ __launch_bounds__(64) void tail_energy_finish_kernel(const double* __restrict__ partials, const int slots, const double mul,
+                                                                double* __restrict__ energy) {
+  const double* p = partials + (int64_t)blockIdx.x * slots;
+  double v = 0.0;
+  for (int i = threadIdx.x; i < slots; i += 64) v += p[i];
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) v += __shfl_down(v, o, 64);
+  if (threadIdx.x == 0) energy[blockIdx.x] = mul * v;
+}
+
+// scale[f] = amp * sqrt(n / E) in float64, rounded once; E = energy[f] over n = 3 H W elements, or the clip's sum over 3 F H W
+__global__ __launch_bounds__(256) void psnr_scale_kernel(const double* __restrict__ energy, const int F, const double n_frame, const int per_clip,
+                                                         const double amp, const float max_scale, float* __restrict__ scale) {
+  __shared__ double s_tot;
+  if (per_clip) {
+    if (threadIdx.x == 0) {
+      double t = 0.0;
+      for (int f = 0; f < F; ++f) t += energy[f];
+      s_tot = t;
+    }
+    __syncthreads();
+  }
+  for (int f = threadIdx.x; f < F; f += 256) {
+    const double E = per_clip ? s_tot : energy[f];
+    const double n = per_clip ? n_frame * (double)F : n_frame;
+    const double s = E == 0.0 ? 0.0 : amp * sqrt(n / E);
+    scale[f] = (max_scale > 0.f && s > (double)max_scale) ? max_scale : (float)s;
+  }
+}
+
+}  // namespace
+
+extern "C" int vs_embed_tail(const vs_tail_desc_t* d, void* stream) { return tail_launch<TAIL_BLEND>(d, nullptr, nullptr, nullptr, stream); }
+
+extern "C" int vs_embed_tail_scaled(const vs_tail_desc_t* d, const float* frame_scale, void* stream) {
+  VS_REQUIRE(frame_scale);
+  return tail_launch<TAIL_SCALED>(d, frame_scale, nullptr, nullptr, stream);
+}
+
+// strips of the row-streaming form are at least four rows tall (tail_strip), tiles sixteen: the bound holds for every form.  Four rows is the
+// floor of the VS_TAIL_STRIP development switch; the strips the library picks are 32 - 96 rows and tiles 16, so a launch uses a 4th to a 24th
+// of this workspace (768^2: 576 doubles per frame sized, 24 - 144 written).  Small next to a frame, and a size function may not depend on a switch.
+extern "C" int64_t vs_tail_energy_partial_doubles(int F, int H, int W) {
+  if (F <= 0 || H <= 0 || W <= 0) return -1;
+  return (int64_t)F * ((W + TTW - 1) / TTW) * ((H + 3) / 4);
+}
+
+extern "C" int vs_embed_tail_energy(const vs_tail_desc_t* d, double* partials, double* energy, void* stream) {
+  VS_REQUIRE(partials && energy);
+  int slots = 0;
+  if (const int rc = tail_launch<TAIL_ENERGY>(d, nullptr, partials, &slots, stream); rc != VS_OK) return rc;
+  hipLaunchKernelGGL(tail_energy_finish_kernel, dim3(d->F), dim3(64), 0, (hipStream_t)stream, partials, slots, 3.0 / d->Cd, energy);
+  return vs_launch_status();
+}
+
+extern "C" int vs_psnr_scale(const double* energy, int F, int H, int W, int per_clip, float target_db, float max_scale, float* scale,
+                             void* stream) {
+  VS_REQUIRE(energy && scale && F > 0 && H > 0 && W > 0 && std::isfinite(target_db));
+  const double amp = std::pow(10.0, -(double)target_db / 20.0);      // (host libm: the device evaluates one division and one square root)
+  hipLaunchKernelGGL(psnr_scale_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, energy, F, 3.0 * H * W, per_clip ? 1 : 0, amp, max_scale, scale);
   return vs_launch_status();
 }
 

@@ -1750,19 +1750,13 @@ class HipEngine:
                 "vs_jnd_heatmap")
         return h
 
-    def embed_tail(self, imgs, out, delta, *, step, video_mode, hmap_low, attenuate, clamp, antialias, scaling_i, scaling_w,
-                   preds_w=None):
-        if self._rgb_clip(imgs):
-            return self._embed_tail_rgb(imgs, out, delta, step=step, video_mode=video_mode, hmap_low=hmap_low, attenuate=attenuate, clamp=clamp,
-                                        antialias=antialias, scaling_i=scaling_i, scaling_w=scaling_w, preds_w=preds_w)
-        if not torch.is_tensor(imgs):         # a YUV clip (yuv.Clip)
-            return self._embed_tail_yuv(imgs, out, delta, step=step, video_mode=video_mode, hmap_low=hmap_low, attenuate=attenuate, clamp=clamp,
-                                        antialias=antialias, scaling_i=scaling_i, scaling_w=scaling_w, preds_w=preds_w)
+    def _tail_desc(self, imgs, out, delta, *, step, video_mode, hmap_low, attenuate, clamp, antialias, scaling_i, scaling_w, preds_w=None):
+        """vs_tail_desc_t of fp32 NCHW [F,3,H,W] or uint8 RGB24 [F,H,W,3] frames -> (descriptor, is uint8)"""
         d = N.TailDesc()
         u8 = imgs.dtype == torch.uint8          # RGB24 [F,H,W,3] in and out
         if u8:
             F_, H, W, _ = imgs.shape
-            if out.dtype != torch.uint8 or out.shape != imgs.shape:
+            if out is not None and (out.dtype != torch.uint8 or out.shape != imgs.shape):
                 raise ValueError("uint8 frames need a uint8 output of the same shape")
             d.io_u8 = 1
         else:
@@ -1775,8 +1769,57 @@ class HipEngine:
         d.attenuate, d.clamp, d.antialias = int(attenuate), int(clamp), int(antialias)
         d.scaling_i, d.scaling_w = float(scaling_i), float(scaling_w)
         d.variant = int(self.tail_variant)
+        return d, u8
+
+    def tail_energy(self, imgs, delta, *, step, video_mode, hmap_low, attenuate, antialias, energy: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """vs_embed_tail_energy: float64 [F], (3 / Cd) * the sum of d * d over the frame, d the perturbation embed_tail computes with the same
+        arguments (its preds_w for attenuate 0 / 1).  No frame is stored, nothing is synchronised.  `energy`: where the result goes."""
+        if not torch.is_tensor(imgs):
+            raise NotImplementedError("the energy pass covers fp32 NCHW and uint8 RGB24 frames")
+        d, u8 = self._tail_desc(imgs, None, delta, step=step, video_mode=video_mode, hmap_low=hmap_low, attenuate=attenuate, clamp=True,
+                                antialias=antialias, scaling_i=1.0, scaling_w=1.0)
+        if energy is None:
+            energy = torch.empty(d.F, device=self.dev, dtype=torch.float64)
+        n = int(self.lib.vs_tail_energy_partial_doubles(d.F, d.H, d.W))
+        part = self.buf("tail.energy", 2 * n).view(torch.float64)
         ev = self._shell_t0()
-        N.check(self.lib.vs_embed_tail(C.byref(d), N.stream()), "vs_embed_tail")
+        N.check(self.lib.vs_embed_tail_energy(C.byref(d), N.ptr(part), N.ptr(energy), N.stream()), "vs_embed_tail_energy")
+        # algorithmic HBM bytes: the frame once where the full-resolution heat-map needs its luminance, the low-resolution watermark otherwise
+        self._shell_t1(ev, "embed_tail_energy_kernel" + ("<u8>" if u8 else ""),
+                       (imgs.numel() * imgs.element_size() if (attenuate and hmap_low is None) else 0) + delta.numel() * 4)
+        return energy
+
+    def psnr_scale(self, energy: torch.Tensor, H: int, W: int, target_psnr: float, *, per_clip: bool = False, max_scale: Optional[float] = None,
+                   scale: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """vs_psnr_scale: float64 [F] energies of H x W frames -> fp32 [F] strengths that put every frame (per_clip: the clip) at target_psnr"""
+        F_ = energy.numel()
+        if scale is None:
+            scale = torch.empty(F_, device=self.dev, dtype=torch.float32)
+        N.check(self.lib.vs_psnr_scale(N.ptr(energy), F_, H, W, int(per_clip), float(target_psnr), float(max_scale) if max_scale else 0.0,
+                                       N.ptr(scale), N.stream()), "vs_psnr_scale")
+        return scale
+
+    def embed_tail(self, imgs, out, delta, *, step, video_mode, hmap_low, attenuate, clamp, antialias, scaling_i, scaling_w,
+                   preds_w=None, frame_scale: Optional[torch.Tensor] = None):
+        """frame_scale (fp32 [F] on the device, fp32 NCHW / uint8 RGB24 frames only): the strength of frame f instead of scaling_w"""
+        if frame_scale is not None and not torch.is_tensor(imgs):
+            raise NotImplementedError("per-frame strengths cover fp32 NCHW and uint8 RGB24 frames")
+        if self._rgb_clip(imgs):
+            return self._embed_tail_rgb(imgs, out, delta, step=step, video_mode=video_mode, hmap_low=hmap_low, attenuate=attenuate, clamp=clamp,
+                                        antialias=antialias, scaling_i=scaling_i, scaling_w=scaling_w, preds_w=preds_w)
+        if not torch.is_tensor(imgs):         # a YUV clip (yuv.Clip)
+            return self._embed_tail_yuv(imgs, out, delta, step=step, video_mode=video_mode, hmap_low=hmap_low, attenuate=attenuate, clamp=clamp,
+                                        antialias=antialias, scaling_i=scaling_i, scaling_w=scaling_w, preds_w=preds_w)
+        d, u8 = self._tail_desc(imgs, out, delta, step=step, video_mode=video_mode, hmap_low=hmap_low, attenuate=attenuate, clamp=clamp,
+                                antialias=antialias, scaling_i=scaling_i, scaling_w=scaling_w, preds_w=preds_w)
+        if frame_scale is not None and (frame_scale.dtype != torch.float32 or frame_scale.numel() != d.F or not frame_scale.is_contiguous()):
+            raise ValueError("frame_scale must be a contiguous fp32 tensor with one strength per frame")
+        ev = self._shell_t0()
+        if frame_scale is not None:
+            N.check(self.lib.vs_embed_tail_scaled(C.byref(d), N.ptr(frame_scale), N.stream()), "vs_embed_tail_scaled")
+        else:
+            N.check(self.lib.vs_embed_tail(C.byref(d), N.stream()), "vs_embed_tail")
         # algorithmic HBM bytes: frame read + watermarked frame written (+ preds_w); the 256^2 delta / heat-map reads are cache hits
-        self._shell_t1(ev, "embed_tail_kernel" + ("<u8>" if u8 else ""), imgs.numel() * imgs.element_size() + out.numel() * out.element_size()
+        self._shell_t1(ev, ("embed_tail_scaled_kernel" if frame_scale is not None else "embed_tail_kernel") + ("<u8>" if u8 else ""),
+                       imgs.numel() * imgs.element_size() + out.numel() * out.element_size()
                        + (preds_w.numel() * 4 if preds_w is not None else 0) + delta.numel() * 4)

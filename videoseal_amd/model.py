@@ -76,6 +76,40 @@ def _antialias_flag(interpolation: Optional[dict]) -> bool:
     return bool(it.get("antialias", False))
 
 
+def psnr_strength(energy: float, n: int, target_psnr: float, max_scaling_w: Optional[float] = None) -> float:
+    """The strength that puts a perturbation of energy `energy` (the sum of its squares over `n` elements, data range 1, at strength 1) at
+    `target_psnr` dB: 10^(-T / 20) * sqrt(n / energy) in float64, 0 for a zero perturbation, at most `max_scaling_w`.  The host statement
+    of what vs_psnr_scale evaluates on the device (there rounded once to fp32)."""
+    import math
+    if energy == 0.0:
+        return 0.0
+    s = 10.0 ** (-float(target_psnr) / 20.0) * math.sqrt(float(n) / float(energy))
+    return min(s, float(max_scaling_w)) if max_scaling_w is not None else s
+
+
+def check_psnr_args(target_psnr, per: str, max_scaling_w) -> None:
+    """the argument checks of Videoseal.embed_psnr that need neither frames nor a device"""
+    import math
+
+    def number(v, what):        # Python and numpy scalars, 0-dim tensors; a bool or a string is not a number of dB
+        if isinstance(v, (bool, str, bytes)):
+            raise ValueError(f"{what} must be a number (got {v!r})")
+        try:
+            return float(v)
+        except (TypeError, ValueError, RuntimeError) as e:
+            raise ValueError(f"{what} must be a number (got {v!r}: {e})") from None
+
+    t = number(target_psnr, "target_psnr")
+    if not math.isfinite(t) or t <= 0:
+        raise ValueError(f"target_psnr must be finite and positive, in dB (got {target_psnr!r})")
+    if per not in ("frame", "clip"):
+        raise ValueError(f'per must be "frame" or "clip" (got {per!r})')
+    if max_scaling_w is not None:
+        c = number(max_scaling_w, "max_scaling_w")
+        if not math.isfinite(c) or c <= 0:
+            raise ValueError(f"max_scaling_w must be finite and positive, or None (got {max_scaling_w!r})")
+
+
 class _EngineOwner:
     """Lazily (re)builds the packed-weight engine when parameters, device or mode change."""
 
@@ -447,6 +481,15 @@ class Wam(nn.Module):
         self._embed_frames_eager(eng, fr, msgs_i32, out, step=step, video_mode=video_mode, antialias=antialias, lowres=lowres,
                                  preds_w=preds_w, fwd_order=fwd_order, tail_span=tail_span)
 
+    def _embed_front(self, eng: HipEngine, fr: torch.Tensor, msgs_i32: torch.Tensor, *, step: int, antialias: bool, lowres: bool):
+        """everything before the tail: resize -> key frames -> U-Net -> (delta [keys,Cd,S,S], low-resolution heat-map or None), both in the
+        engine's workspace (overwritten by the next call)"""
+        S = (self.img_size, self.img_size)
+        att = self.attenuation is not None
+        rgb, key = eng.resize_pre(fr, S, antialias, want_rgb=(att and lowres), want_key=True, key_step=step)
+        delta = eng.embedder_forward(key, msgs_i32, bn_train=self.embedder.training)
+        return delta, (eng.jnd_lowres(rgb) if (att and lowres) else None)
+
     def _embed_frames_eager(self, eng: HipEngine, fr: torch.Tensor, msgs_i32: torch.Tensor, out: torch.Tensor, *, step: int,
                             video_mode: int, antialias: bool, lowres: bool, preds_w: Optional[torch.Tensor] = None,
                             fwd_order: bool = False, tail_span: int = 0, on_tail=None, tail_batch: int = 0) -> None:
@@ -454,11 +497,9 @@ class Wam(nn.Module):
         whole group go through the U-Net as one batch (the matrix kernels want >= 32 key frames to fill 256 CUs), the watermark is then
         expanded chunk by chunk exactly as the per-chunk calls would do it (videoseal.py:303-344: the last key frame of a chunk has no
         successor in 'interpolate' mode), so the group equals the sequence of per-chunk calls up to the summation order of the dense layers."""
-        S = (self.img_size, self.img_size)
         att = self.attenuation is not None
-        rgb, key = eng.resize_pre(fr, S, antialias, want_rgb=(att and lowres), want_key=True, key_step=step)
-        delta = eng.embedder_forward(key, msgs_i32, bn_train=self.embedder.training)
-        hmap = eng.jnd_lowres(rgb) if (att and lowres) else None
+        delta, hmap = self._embed_front(eng, fr, msgs_i32, step=step, antialias=antialias, lowres=lowres)
+        S = (self.img_size, self.img_size)
         kw = dict(step=step, video_mode=video_mode, attenuate=(2 if (att and fwd_order and not lowres) else int(att)), clamp=self.clamp,
                   antialias=antialias, scaling_i=self.blender.scaling_i, scaling_w=self.blender.scaling_w)
         F_ = fr.shape[0]
@@ -901,6 +942,87 @@ class Videoseal(Wam):
             assert msgs.shape[0] == 1, "Message should be unique"
         out = self._embed_clip(clip.contiguous(), msgs, interpolation, lowres_attenuation)
         return {"imgs_w": out, "msgs": msgs[0:1].repeat(len(clip), 1)}
+
+    # ---- embedding to a target PSNR: the watermark's strength per frame, chosen on the device
+    @torch.no_grad()
+    def embed_psnr(self, imgs: torch.Tensor, target_psnr: float, msgs: torch.Tensor = None, is_video: bool = True, per: str = "frame",
+                   max_scaling_w: Optional[float] = None, interpolation: dict = None, lowres_attenuation: bool = False) -> dict:
+        """`embed` / `embed_u8` with `blender.scaling_w` replaced by the strength that puts each frame at `target_psnr` dB against `imgs`.
+        imgs: fp32 [F,3,H,W] (as `embed`; is_video=False: one message per frame) or uint8 RGB24 [F,H,W,3] (as `embed_u8`).  With d the
+        perturbation of frame f at scaling_w = 1 (`preds_w` of `embed`), E_f = (3 / Cd) * sum d^2 in float64 and
+            s_f = 10^(-target_psnr / 20) * sqrt(3 H W / E_f),   0 where E_f == 0,   at most max_scaling_w when one is given;
+        per="clip": one s for all frames from sum_f E_f over 3 F H W elements (`metrics.psnr(..., is_video=True)`).  Frame f is then
+        `embed` of its chunk at blender.scaling_w = s_f, bit for bit.
+        Returns {'imgs_w': dtype, shape and device of imgs, 'msgs', 'scaling_w': fp32 [F] the strengths applied, 'energy': float64 [F]}.
+        Before the clamp and at scaling_i = 1 the PSNR of imgs_w equals target_psnr (up to the fp32 rounding of s and of the blend) unless the
+        ceiling binds.  The clamp only moves pixels towards imgs, so the clamped fp32 result is at or above the target; a uint8 result also
+        carries its quantisation noise.  Neither is corrected for.
+        An energy pass (the tail's own d, reduced per frame, no frame stored), the strengths and the tail follow each other on the stream
+        without a host synchronisation; the call runs eagerly even where VIDEOSEAL_GRAPHS is set.  per="frame" walks the clip in the chunks
+        of `embed` (host-resident frames move one chunk at a time); per="clip" keeps the watermark and the low-resolution heat-map of all
+        chunks on the device between its two sweeps and needs frames resident on the model's device.
+        The YUV, packed-RGB, image-list and clip-list routes keep the fixed strength: they are not covered here."""
+        check_psnr_args(target_psnr, per, max_scaling_w)
+        if not torch.is_tensor(imgs) or imgs.dim() != 4:
+            raise ValueError("embed_psnr wants fp32 frames [F, 3, H, W] or a uint8 RGB24 clip [F, H, W, 3]")
+        u8 = imgs.dtype == torch.uint8
+        if (u8 and imgs.shape[-1] != 3) or (not u8 and (imgs.dtype != torch.float32 or imgs.shape[1] != 3)):
+            raise ValueError("embed_psnr wants fp32 frames [F, 3, H, W] or a uint8 RGB24 clip [F, H, W, 3]")
+        if u8 and not self.clamp:
+            raise ValueError("uint8 output needs clamp=True ((x * 255).byte() is undefined outside [0, 1])")
+        if is_video and self.video_mode not in N.VIDEO_MODES:
+            raise ValueError(f"unknown video_mode {self.video_mode}")
+        F_ = imgs.shape[0]
+        if msgs is None:
+            msgs = self.get_random_msg() if is_video else self.get_random_msg(F_)
+        elif msgs.shape[0] != (1 if is_video else F_):
+            raise ValueError("one message for a clip (is_video=True), one per frame otherwise")
+        msgs_out = msgs[0:1].repeat(F_, 1) if is_video else msgs
+        if F_ == 0:
+            return {"imgs_w": imgs.clone(), "msgs": msgs_out, "scaling_w": imgs.new_zeros(0, dtype=torch.float32),
+                    "energy": imgs.new_zeros(0, dtype=torch.float64)}
+        if u8:
+            imgs = imgs.contiguous()          # (as embed_u8: the kernels read packed RGB24; a permuted or strided view of a clip is packed first)
+        eng = self._engine()
+        if per == "clip" and imgs.device != eng.dev:
+            raise ValueError('per="clip" keeps the watermark of the whole clip on the device: it wants frames resident on the model\'s device')
+        aa = _antialias_flag(interpolation)
+        step = int(self.step_size) if is_video else 1
+        span = int(self.chunk_size) * step if is_video else max(1, int(getattr(self, "chunk_size", 32)))
+        vm = N.VIDEO_MODES[self.video_mode] if is_video else 0
+        H, W = (imgs.shape[1], imgs.shape[2]) if u8 else (imgs.shape[2], imgs.shape[3])
+        cap = float(max_scaling_w) if max_scaling_w is not None else None
+        with torch.cuda.device(eng.dev):
+            mi = self._msgs_dev(msgs, eng.dev)
+            energy = torch.empty(F_, device=eng.dev, dtype=torch.float64)
+            scale = torch.empty(F_, device=eng.dev, dtype=torch.float32)
+            ekw = dict(step=step, video_mode=vm, attenuate=int(self.attenuation is not None), antialias=aa)
+            tkw = dict(clamp=self.clamp, scaling_i=self.blender.scaling_i, scaling_w=self.blender.scaling_w, **ekw)
+
+            def front(fr, a, b):
+                return self._embed_front(eng, fr, mi if is_video else mi[a:b], step=step, antialias=aa, lowres=lowres_attenuation)
+
+            if per == "frame":
+                def one(fr, oc, a, b):
+                    delta, hmap = front(fr, a, b)
+                    eng.tail_energy(fr, delta, hmap_low=hmap, energy=energy[a:b], **ekw)
+                    eng.psnr_scale(energy[a:b], H, W, target_psnr, max_scale=cap, scale=scale[a:b])
+                    eng.embed_tail(fr, oc, delta, hmap_low=hmap, frame_scale=scale[a:b], **tkw)
+                out = self._run_chunks(eng, imgs, span, one)
+            else:
+                src = imgs if u8 else N.f32c(imgs)
+                out = torch.empty_like(src)
+                kept = []
+                for a in range(0, F_, span):
+                    b = min(F_, a + span)
+                    delta, hmap = front(src[a:b], a, b)
+                    delta, hmap = delta.clone(), (hmap.clone() if hmap is not None else None)
+                    eng.tail_energy(src[a:b], delta, hmap_low=hmap, energy=energy[a:b], **ekw)
+                    kept.append((a, b, delta, hmap))
+                eng.psnr_scale(energy, H, W, target_psnr, per_clip=True, max_scale=cap, scale=scale)
+                for a, b, delta, hmap in kept:
+                    eng.embed_tail(src[a:b], out[a:b], delta, hmap_low=hmap, frame_scale=scale[a:b], **tkw)
+        return {"imgs_w": out, "msgs": msgs_out, "scaling_w": scale.to(imgs.device), "energy": energy.to(imgs.device)}
 
     @torch.no_grad()
     def detect_u8(self, clip: torch.Tensor, interpolation: dict = None) -> dict:

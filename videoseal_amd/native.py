@@ -51,6 +51,8 @@ EXPORTS = [
     "vs_sizeof_rgb_surface", "vs_sizeof_tail_rgb_desc", "vs_resize_pre_rgb", "vs_embed_tail_rgb", "vs_model_embed_rgb", "vs_model_detect_rgb",
     "vs_resize_pre_images", "vs_embed_tail_images", "vs_images_plan",
     "vs_resize_pre_clips", "vs_embed_tail_clips", "vs_clips_plan", "vs_aggregate_clips",
+    "vs_tail_energy_partial_doubles", "vs_embed_tail_energy", "vs_psnr_scale", "vs_embed_tail_scaled",
+    "vs_model_embed_psnr", "vs_model_embed_psnr_workspace_bytes",
 ]
 
 
@@ -345,6 +347,9 @@ def lib() -> C.CDLL:
         "vs_resize_pre_u8": [P, I, I, I, I, I, I, P, F, F, P, I, P, P],
         "vs_jnd_heatmap": [P, I, I, I, I64, I64, I64, I64, P, P, P],
         "vs_embed_tail": [C.POINTER(TailDesc), P],
+        "vs_embed_tail_energy": [C.POINTER(TailDesc), P, P, P],
+        "vs_psnr_scale": [P, I, I, I, I, F, F, P, P],
+        "vs_embed_tail_scaled": [C.POINTER(TailDesc), P, P],
         "vs_nv12_default_color": [P, P],
         "vs_resize_pre_nv12": [P, I, I, I, I64, I64, P, I, I, I, P, F, F, P, I, P, P],
         "vs_embed_tail_nv12": [C.POINTER(TailNv12Desc), P],
@@ -471,6 +476,8 @@ def lib() -> C.CDLL:
     for name in ("vs_aug_color_bwd_scratch_floats", "vs_percep_partial_doubles", "vs_ssim_partial_doubles", "vs_jnd_loss_partial_doubles"):
         getattr(L, name).restype = C.c_int64
         getattr(L, name).argtypes = [I, I, I]
+    L.vs_tail_energy_partial_doubles.restype = C.c_int64
+    L.vs_tail_energy_partial_doubles.argtypes = [I, I, I]
     L.vs_cnx_block_image_bytes.restype = C.c_int64
     L.vs_cnx_block_image_bytes.argtypes = [I]
     L.vs_bn_partial_doubles.restype = C.c_int64
