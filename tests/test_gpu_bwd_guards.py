@@ -3,7 +3,9 @@ to vs_percep_mse_grad; the ones with a workspace are in tests/test_gpu_scratch_c
 vs_nhwc_to_nchw_scaled / vs_patchify_s / vs_unpatch_s / vs_gaussian_blur_bwd in tests/test_gpu_entry_points.py) between red zones: inputs
 between NaN bands, outputs between -7.0 bands, every buffer exactly as large as the header says -- parameter vectors included -- and the pad
 lanes [C, ld) of the inputs zero, as the engine keeps them.  The result must equal the unguarded call bit for bit (a value read from a band
-would make it NaN) and every band must survive.  Values are checked by the unit tests of tests/test_gpu_bwd*.py / test_gpu_train.py; the
+would make it NaN) and every band must survive.  Values are checked by the unit tests of tests/test_gpu_bwd*.py / test_gpu_train.py and, for the
+U-Net glue that runs here for memory safety only (vs_relu_bwd, vs_pad_embed1, vs_reflect_fold1, vs_col2im3x3_reflect, vs_dilate2,
+vs_im2col3x3_strided, vs_upcat2x_bwd, vs_msg_table_grad, vs_outc_tanh_bwd), by tests/test_gpu_unet_envelope.py on hard inputs; the
 shapes here are ragged on purpose: rows no multiple of 4, W odd and below 4, C in {1, 3, 6, 130} with ld = 4 ceil(C / 4) and larger, 2 x 2
 maps for the reflection kernels, one frame."""
 import ctypes

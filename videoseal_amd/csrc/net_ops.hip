@@ -892,24 +892,30 @@ __global__ __launch_bounds__(256) void cat2_scale_kernel(const float* __restrict
 __global__ __launch_bounds__(256) void msg_latent_kernel(const float* __restrict__ table, const int32_t* __restrict__ msgs,
                                                          int nbits, int hidden, float* __restrict__ lat) {
   // the row index of every bit first (LDS), so that the table loads below do not depend on a load each: 16 of them are in
-  // flight at a time instead of 2 x nbits serial round trips; the summation order (k ascending) is unchanged
+  // flight at a time instead of 2 x nbits serial round trips
   __shared__ int rowsel[1024];
   const int b = blockIdx.y;
   for (int k = threadIdx.x; k < nbits; k += 256) rowsel[k] = 2 * k + (msgs[(int64_t)b * nbits + k] != 0);
   __syncthreads();
   const int c = blockIdx.x * 256 + threadIdx.x;
   if (c >= hidden) return;
-  float s = 0.f;
+  // sixteen rows as a pairwise tree in fp32, the batch totals and the tail rows in a double: a strictly sequential fp32 sum of 1000 rows of one
+  // sign was 25 units of 2^-24 sum |t| away from the exact latent, 11 times ATen's fp32 sum (tests/test_gpu_unet_envelope.py); the loads, not
+  // the adds, bound the kernel
+  double s = 0.0;
   int k = 0;
   for (; k + 16 <= nbits; k += 16) {
     float v[16];
 #pragma unroll
     for (int j = 0; j < 16; ++j) v[j] = table[(int64_t)rowsel[k + j] * hidden + c];
 #pragma unroll
-    for (int j = 0; j < 16; ++j) s += v[j];
+    for (int w = 1; w < 16; w <<= 1)
+#pragma unroll
+      for (int j = 0; j < 16; j += 2 * w) v[j] += v[j + w];
+    s += (double)v[0];
   }
-  for (; k < nbits; ++k) s += table[(int64_t)rowsel[k] * hidden + c];
-  lat[(int64_t)b * hidden + c] = s;
+  for (; k < nbits; ++k) s += (double)table[(int64_t)rowsel[k] * hidden + c];
+  lat[(int64_t)b * hidden + c] = (float)s;
 }
 // four channels per thread (hidden, ld, coff multiples of 4 and 16-byte aligned pointers: every shipped card): 16-byte stores, a quarter of the index
 // arithmetic -- the one-float form ran at 1.4 TB/s of stores
@@ -969,13 +975,15 @@ __global__ __launch_bounds__(256) void pool_linear_kernel(const float* __restric
   const int b = blockIdx.x;
   const float* xb = x + (int64_t)b * HW * ld;
   // round 6: a thread owns a 16-byte group of four channels and requests sixteen rows before the first is added -- 4 round trips for the 64 rows of
-  // an 8 x 8 map instead of 3 channels x 8 (the kernel was 32 us for a 6 MB tensor, a chain of dependent L2 round trips).  Per channel the rows are
-  // still added in row order: the same sums, bit for bit.  (ld is a multiple of 4 and the pad lanes are zero: vs_pool_linear checks alignment)
+  // an 8 x 8 map instead of 3 channels x 8 (the kernel was 32 us for a 6 MB tensor, a chain of dependent L2 round trips).  The sixteen rows are
+  // added as a pairwise tree in fp32 and the batch totals (and the tail rows) in a double: rows added strictly in order in fp32 left the mean of a
+  // 961-row map of mean 30 / std 0.5 (ChunkySeal's head) 17 times further from the exact mean than ATen's fp32 mean
+  // (tests/test_gpu_unet_envelope.py).  (ld is a multiple of 4 and the pad lanes are zero: vs_pool_linear checks alignment)
   const int C4 = (C + 3) >> 2;
   const bool vec = (ld & 3) == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0;
   if (vec) {
     for (int g = threadIdx.x; g < C4; g += 256) {
-      f32x4 s = {0.f, 0.f, 0.f, 0.f};
+      double s[4] = {0.0, 0.0, 0.0, 0.0};
       const float* xg = xb + 4 * g;
       int r = 0;
       for (; r + 16 <= HW; r += 16) {
@@ -983,18 +991,37 @@ __global__ __launch_bounds__(256) void pool_linear_kernel(const float* __restric
 #pragma unroll
         for (int q = 0; q < 16; ++q) v[q] = *reinterpret_cast<const f32x4*>(xg + (int64_t)(r + q) * ld);
 #pragma unroll
-        for (int q = 0; q < 16; ++q) s += v[q];
+        for (int w_ = 1; w_ < 16; w_ <<= 1)
+#pragma unroll
+          for (int q = 0; q < 16; q += 2 * w_) v[q] += v[q + w_];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) s[e] += (double)v[0][e];
       }
-      for (; r < HW; ++r) s += *reinterpret_cast<const f32x4*>(xg + (int64_t)r * ld);
+      for (; r < HW; ++r) {
+        const f32x4 v = *reinterpret_cast<const f32x4*>(xg + (int64_t)r * ld);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) s[e] += (double)v[e];
+      }
 #pragma unroll
       for (int e = 0; e < 4; ++e)
-        if (4 * g + e < C) pooled[4 * g + e] = s[e] / (float)HW;
+        if (4 * g + e < C) pooled[4 * g + e] = (float)(s[e] / (double)HW);
     }
   } else {
     for (int c = threadIdx.x; c < C; c += 256) {
-      float s = 0.f;
-      for (int r = 0; r < HW; ++r) s += xb[(int64_t)r * ld + c];
-      pooled[c] = s / (float)HW;
+      double s = 0.0;
+      int r = 0;
+      for (; r + 16 <= HW; r += 16) {
+        float v[16];
+#pragma unroll
+        for (int q = 0; q < 16; ++q) v[q] = xb[(int64_t)(r + q) * ld + c];
+#pragma unroll
+        for (int w_ = 1; w_ < 16; w_ <<= 1)
+#pragma unroll
+          for (int q = 0; q < 16; q += 2 * w_) v[q] += v[q + w_];
+        s += (double)v[0];
+      }
+      for (; r < HW; ++r) s += (double)xb[(int64_t)r * ld + c];
+      pooled[c] = (float)(s / (double)HW);
     }
   }
   __syncthreads();
