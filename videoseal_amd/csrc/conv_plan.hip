@@ -59,8 +59,13 @@ extern "C" int vs_conv_plan(const vs_conv_desc_t* dp, int grn_hw, int grn_c4, vs
   }
   *out = {routes, sk, d.tile_hint, 0, 0};
   if (sk > 1) {
-    // + the slice of the 1x1 second phase (told by its weights: a host that only counts workspace has no activations yet)
-    out->ws_slices = sk + (((patch_pc || d.in_pl) && d.wt2) ? 1 : 0);
+    // + the slice of the 1x1 second phase (told by its weights: a host that only counts workspace has no activations yet).  Counted wherever the
+    // wave-specialised 3x3 kernel CAN take the launch, not only where it is chosen unasked: a caller that names tile 15 / 16 reaches it on any
+    // frame size (vs_conv_gemm's patch_ok has no frame condition), and that kernel always writes slice `split_k` for a second phase.  With the
+    // frame-aligned `patch_pc` route alone the count was one slice short on ragged frames and the kernel wrote M * splitk_ld floats past the
+    // workspace (found by tests/test_gpu_frame_bias_envelope.py at 24 x 40, 2 K slices)
+    const bool pc_named = same3 && d.wt_blk && (!d.in2 || d.wt2_blk);
+    out->ws_slices = sk + (((pc_named || d.in_pl) && d.wt2) ? 1 : 0);
     if (d.tile_hint == 0)       // the kernels that implement the K-slice plan
       out->tile_hint = d.KH == 3 ? (d.N % 192 == 0 ? (VS_CONV_TILE_HI | 0) : 15) : (VS_CONV_TILE_HI | (d.N % 192 == 0 ? 2 : 1));
   }
