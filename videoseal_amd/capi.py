@@ -162,6 +162,12 @@ class CModel:
                                             N.ptr(out), None, N.ptr(scale), N.ptr(ws), ws.numel(), N.stream()), "vs_model_embed_psnr")
         return out, scale
 
+    def embed_regions(self, *args, **kwargs):
+        raise NotImplementedError("the model-level C-ABI (vs_model_*) has no region-wise entry point: label maps go through the operator-level "
+                                  "entry points of include/videoseal_regions.h (Videoseal.embed_regions / decode_regions / detect_regions)")
+
+    decode_regions = detect_regions = embed_regions
+
     def detect(self, imgs: torch.Tensor, antialias: bool = True) -> torch.Tensor:
         x, F_, H, W, u8 = self._frames(imgs)
         logits = torch.empty(F_, self.cfg.nbits + 1, device=x.device)

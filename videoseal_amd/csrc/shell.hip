@@ -6,6 +6,7 @@
 #include "shell_common.h"
 #include "images_plan.h"
 #include "clips_plan.h"
+#include "videoseal_regions.h"
 #include <cmath>
 #include <type_traits>
 
@@ -18,12 +19,24 @@ using namespace vs_taps;
 // adds d * d of its pixels in float64 (the product of two fp32 values is exact there) and the workgroup writes ONE partial sum into
 // partials[f][blockIdx.y][blockIdx.x]; no atomics, the order of every addition is fixed, so two runs give the same bits.
 // The new members ride behind TailArgs in a derived struct, so the kernel arguments of the BLEND instantiations are what they were.
-constexpr int TAIL_BLEND = 0, TAIL_SCALED = 1, TAIL_ENERGY = 2;
+// REGIONS (vs_embed_tail_regions) reads a label per pixel: label r in 1..R takes the watermark of plane set key * R + r - 1, label 0 keeps the
+// pixel of imgs bit for bit.  The tile body runs once per label present in the tile (a workgroup-uniform walk, embed_tail_regions_kernel), each
+// time with that label's source window in the one LDS window, and stores the pixels of its label only: LDS does not grow with R.
+// (The walk is over workgroups, not a loop in one: see embed_tail_regions_kernel.)
+constexpr int TAIL_BLEND = 0, TAIL_SCALED = 1, TAIL_ENERGY = 2, TAIL_REGIONS = 3;
 struct TailArgsX : TailArgs { const float* frame_scale; double* partials; };
-template <int MODE> using tail_args_t = std::conditional_t<MODE == TAIL_BLEND, TailArgs, TailArgsX>;
+struct TailArgsR : TailArgs { const unsigned char* labels; int R; };
+template <int MODE> using tail_args_t = std::conditional_t<MODE == TAIL_BLEND, TailArgs, TailArgsX>;      // (REGIONS: TailArgsR, named by its kernel)
 
-template <int MODE>
-__device__ __forceinline__ float tail_strength(const tail_args_t<MODE>& a, const int f) {
+// first plane set of key frame `key`: [total_key][Cd] planes, or [total_key * R][Cd] with the region's set behind its key frame
+template <int MODE, class Args>
+__device__ __forceinline__ int64_t tail_plane_set(const Args& a, const int key, const int region) {
+  if constexpr (MODE == TAIL_REGIONS) return (int64_t)key * a.R + (region - 1);
+  else return (int64_t)key;
+}
+
+template <int MODE, class Args>
+__device__ __forceinline__ float tail_strength(const Args& a, const int f) {
   if constexpr (MODE == TAIL_SCALED) return a.frame_scale[f];
   else return a.scaling_w;
 }
@@ -277,9 +290,11 @@ __global__ __launch_bounds__(256) void jnd_heatmap_kernel(const float* __restric
 // (the tile's body: columns from x0, rows from y0 of the frame `img` -> `outf` / `predf`; f names the frame's key frame and its rows of
 // hmap_lowres.  All of them workgroup-uniform: blockIdx for a clip (embed_tail_kernel), a table look-up for a list of images, each with its
 // own a.H x a.W (the *_images kernels below).)
-template <typename T, bool SEP, int TH, bool KEEP, int MODE = TAIL_BLEND>
-__device__ __forceinline__ void embed_tail_tile(const tail_args_t<MODE>& a, const JndTaps& k, const int x0, const int y0, const int f,
-                                                const T* __restrict__ img, T* __restrict__ outf, float* __restrict__ predf) {
+// REGIONS: `region` is the label this pass blends, bit ly of `sel` says that row ly of this thread's column carries it; nothing else is stored.
+template <typename T, bool SEP, int TH, bool KEEP, int MODE = TAIL_BLEND, class Args = tail_args_t<MODE>>
+__device__ __forceinline__ void embed_tail_tile(const Args& a, const JndTaps& k, const int x0, const int y0, const int f,
+                                                const T* __restrict__ img, T* __restrict__ outf, float* __restrict__ predf,
+                                                const int region = 0, const unsigned sel = 0) {
   constexpr int TTH = TH;
   constexpr int DWH = TH == 8 ? 8 : DW_H;              // rows of the watermark's source window (8-row tiles at >= 2x up-scale need <= 8)
   __shared__ float Pk[KEEP ? 3 * TH * TTW : 4];
@@ -362,8 +377,8 @@ __device__ __forceinline__ void embed_tail_tile(const tail_args_t<MODE>& a, cons
   if (ka >= a.total_key) ka = a.total_key - 1;
   if (kb >= a.total_key) kb = a.total_key - 1;
   const int splane = a.Sh * a.Sw;
-  const float* dka = a.delta + (int64_t)ka * a.Cd * splane;
-  const float* dkb = a.delta + (int64_t)kb * a.Cd * splane;
+  const float* dka = a.delta + tail_plane_set<MODE>(a, ka, region) * a.Cd * splane;
+  const float* dkb = a.delta + tail_plane_set<MODE>(a, kb, region) * a.Cd * splane;
   const float* hml = a.hmap_lowres ? a.hmap_lowres + (int64_t)f * splane : nullptr;
 
   // source window -> LDS, already combined: Dw[c] = hm * (wa*key_a + wb*key_b)  (the per-tap operand of wam.py:184-190)
@@ -386,10 +401,12 @@ __device__ __forceinline__ void embed_tail_tile(const tail_args_t<MODE>& a, cons
     }
   }
   __syncthreads();      // L, Dw
-  if (MODE != TAIL_ENERGY && x >= a.W) return;
+  if (MODE != TAIL_ENERGY && MODE != TAIL_REGIONS && x >= a.W) return;
   const float sw = tail_strength<MODE>(a, f);
   double e = 0.0;                                     // ENERGY: this thread's sum of d * d
-  const int lasty_t = (MODE == TAIL_ENERGY && x >= a.W) ? -1 : lasty;      // (ENERGY: every thread stays for the workgroup's sum)
+  // (ENERGY: every thread stays for the workgroup's sum.  REGIONS: every thread stays for the barriers of the next label's pass; a column
+  // without a pixel of this label has nothing to do)
+  const int lasty_t = (MODE == TAIL_ENERGY && x >= a.W) || (MODE == TAIL_REGIONS && sel == 0u) ? -1 : lasty;
 
   auto tap = [&](const int sp, const float wx, float (&r)[3]) __attribute__((always_inline)) {
     const float hm = hml ? hml[sp] : 1.f;
@@ -403,6 +420,7 @@ __device__ __forceinline__ void embed_tail_tile(const tail_args_t<MODE>& a, cons
   // flight per wave and ~16 waves per CU the kernel cannot cover the HBM latency (measured 2 TB/s)
   constexpr int RG = 4;
   for (int lyg = 0; lyg <= lasty_t; lyg += RG) {      // no workgroup barrier below this line
+    if (MODE == TAIL_REGIONS && ((sel >> lyg) & ((1u << RG) - 1u)) == 0u) continue;
     float px[RG][3];
 #pragma unroll
     for (int q = 0; q < RG; ++q)
@@ -446,6 +464,7 @@ __device__ __forceinline__ void embed_tail_tile(const tail_args_t<MODE>& a, cons
     for (int q = 0; q < RG; ++q) {
       const int ly = lyg + q;
       if (ly > lasty) break;
+      if (MODE == TAIL_REGIONS && !((sel >> ly) & 1u)) continue;
       const int y = y0 + ly;
       float d[3] = {0.f, 0.f, 0.f};
       const int ylo = ty_lo[ly], yn = ty_n[ly];
@@ -496,6 +515,64 @@ __global__ __launch_bounds__(256) void embed_tail_kernel(tail_args_t<MODE> a, Jn
   embed_tail_tile<T, SEP, TH, KEEP, MODE>(a, k, blockIdx.x * TTW, blockIdx.y * TH, f, static_cast<const T*>(a.imgs) + (int64_t)f * 3 * plane,
                                     static_cast<T*>(a.out) + (int64_t)f * 3 * plane,
                                     a.preds_w ? a.preds_w + (int64_t)f * a.Cd * plane : nullptr);
+}
+
+// Region-wise tail (vs_embed_tail_regions): the 16-row tile of embed_tail_kernel with a label per pixel.  A tile belongs to R workgroups, one per
+// label (blockIdx.x = tile column * R + r - 1: the R of a tile are dispatched together and share its lines in L2).  Every thread reads the labels
+// of its column (16 bytes), the workgroup ORs the set of labels present, and the workgroup of a label that is absent from the tile ends there
+// -- before it forms an address into delta.  The workgroup of a present label runs the tile body with that label's plane set behind a.delta --
+// the same body, the same expressions, so a pixel of label r has the bits vs_embed_tail gives it with plane set r as delta -- and stores
+// the pixels of its label only.  Background pixels are copied by the workgroup of label 1 (no clamp, no arithmetic), their preds_w is 0.
+// (A loop over the present labels around the body in ONE workgroup was built first: hipcc hoists the body's frame loads out of that loop and
+// the kernel needs 232 - 256 VGPRs, one wave per SIMD, against 108 - 119 for this form.)
+template <typename T>
+__device__ __forceinline__ int64_t raw_index(const int64_t plane, const int c, const int64_t pix) {
+  return sizeof(T) == 1 ? pix * 3 + c : c * plane + pix;
+}
+
+template <typename T, bool SEP>
+__global__ __launch_bounds__(256) void embed_tail_regions_kernel(TailArgsR a, JndTaps k) {
+  __shared__ unsigned s_present;
+  const int col = blockIdx.x / a.R, r = blockIdx.x - col * a.R + 1;
+  const int f = blockIdx.z, x0 = col * TTW, y0 = blockIdx.y * TTH;
+  const int64_t plane = (int64_t)a.H * a.W;
+  const T* img = static_cast<const T*>(a.imgs) + (int64_t)f * 3 * plane;
+  T* outf = static_cast<T*>(a.out) + (int64_t)f * 3 * plane;
+  float* predf = a.preds_w ? a.preds_w + (int64_t)f * a.Cd * plane : nullptr;
+  const unsigned char* lab = a.labels + (int64_t)f * plane;
+  const int x = x0 + (int)threadIdx.x;
+  if (threadIdx.x == 0) s_present = 0u;
+  __syncthreads();
+  unsigned sel = 0u, bg = 0u, present = 0u;       // bit ly: row ly of this thread's column carries label r / is background
+  if (x < a.W) {
+    unsigned l[TTH];
+#pragma unroll
+    for (int ly = 0; ly < TTH; ++ly) l[ly] = y0 + ly < a.H ? lab[(int64_t)(y0 + ly) * a.W + x] : 0u;      // guarded: the last band is ragged
+#pragma unroll
+    for (int ly = 0; ly < TTH; ++ly)
+      if (y0 + ly < a.H) {
+        const unsigned v = l[ly] > (unsigned)a.R ? 0u : l[ly];
+        sel |= (v == (unsigned)r ? 1u : 0u) << ly;
+        bg |= (v == 0u ? 1u : 0u) << ly;
+        present |= 1u << v;
+      }
+  }
+  if (present) atomicOr(&s_present, present);
+  __syncthreads();
+  const unsigned mask = __builtin_amdgcn_readfirstlane(s_present);      // workgroup-uniform: the body's barriers sit behind a uniform branch
+  if (r == 1 && (mask & 1u)) {
+#pragma unroll
+    for (int ly = 0; ly < TTH; ++ly)
+      if ((bg >> ly) & 1u) {
+        const int64_t pix = (int64_t)(y0 + ly) * a.W + x;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) outf[raw_index<T>(plane, c, pix)] = img[raw_index<T>(plane, c, pix)];
+        if (predf)
+          for (int c = 0; c < a.Cd; ++c) predf[c * plane + pix] = 0.f;
+      }
+  }
+  if (!((mask >> r) & 1u)) return;
+  embed_tail_tile<T, SEP, TTH, false, TAIL_REGIONS, TailArgsR>(a, k, x0, y0, f, img, outf, predf, r, sel);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -1076,6 +1153,32 @@ __global__ __launch_bounds__(256) void psnr_scale_kernel(const double* __restric
 }  // namespace
 
 extern "C" int vs_embed_tail(const vs_tail_desc_t* d, void* stream) { return tail_launch<TAIL_BLEND>(d, nullptr, nullptr, nullptr, stream); }
+
+// The region-wise tail is built on the 16-row tiles (43-tap and separable stencils; uint8 keeps the 43-tap form, as the plain tail does).  The
+// row-streaming form is not built for it: variant 0 and 4 take the separable tiles, which give the bits of the streaming form.
+extern "C" int vs_embed_tail_regions(const vs_tail_desc_t* d, const uint8_t* labels, int R, void* stream) {
+  VS_REQUIRE(labels && R >= 1 && R <= VS_REGIONS_MAX);
+  VS_REQUIRE(d && d->imgs && d->out && d->delta && d->F > 0 && d->H > 0 && d->W > 0 && d->S_h > 0 && d->S_w > 0);
+  VS_REQUIRE((d->Cd == 1 || d->Cd == 3) && d->step >= 1 && d->total_key >= 1);
+  VS_REQUIRE(d->video_mode >= 0 && d->video_mode <= 2);
+  VS_REQUIRE(!(d->attenuate && !d->hmap_lowres) || d->taps43);
+  VS_REQUIRE(!d->io_u8 || d->clamp);        // (x * 255).byte() is only defined for x in [0, 1]
+  if (d->attenuate == 2 || d->variant == 3) return VS_ERR_UNSUPPORTED;
+  const int form = d->variant >= 1 && d->variant <= 4 ? d->variant : vs_debug_get(VS_DBG_TAIL_FORM);
+  const TailArgs base{d->imgs, d->out, d->preds_w, d->delta, d->attenuate ? d->hmap_lowres : nullptr, d->F, d->H, d->W, d->S_h, d->S_w,
+                      d->Cd, d->step, d->video_mode, d->total_key, d->attenuate, d->clamp, d->antialias, d->scaling_i, d->scaling_w};
+  const TailArgsR a{base, labels, R};
+  JndTaps k{};
+  if (d->taps43) k = taps_from(d->taps43);
+  const bool full_jnd = d->attenuate && !d->hmap_lowres;
+  const bool sep = form != 1 && full_jnd && d->taps43 && standard_jnd_taps(d->taps43);
+  VS_REQUIRE(d->F <= 65535 && (d->H + TTH - 1) / TTH <= 65535);
+  dim3 grid(((d->W + TTW - 1) / TTW) * R, (d->H + TTH - 1) / TTH, d->F);
+  if (d->io_u8) hipLaunchKernelGGL((embed_tail_regions_kernel<unsigned char, false>), grid, dim3(256), 0, (hipStream_t)stream, a, k);
+  else if (sep) hipLaunchKernelGGL((embed_tail_regions_kernel<float, true>), grid, dim3(256), 0, (hipStream_t)stream, a, k);
+  else hipLaunchKernelGGL((embed_tail_regions_kernel<float, false>), grid, dim3(256), 0, (hipStream_t)stream, a, k);
+  return vs_launch_status();
+}
 
 extern "C" int vs_embed_tail_scaled(const vs_tail_desc_t* d, const float* frame_scale, void* stream) {
   VS_REQUIRE(frame_scale);

@@ -1823,3 +1823,66 @@ class HipEngine:
         self._shell_t1(ev, ("embed_tail_scaled_kernel" if frame_scale is not None else "embed_tail_kernel") + ("<u8>" if u8 else ""),
                        imgs.numel() * imgs.element_size() + out.numel() * out.element_size()
                        + (preds_w.numel() * 4 if preds_w is not None else 0) + delta.numel() * 4)
+
+    # ---- region-wise watermarks (include/videoseal_regions.h; the torch definition is videoseal_amd/regions.py)
+    def repeat_keys(self, key: Act, R: int) -> Act:
+        """key frames [keys,S,S,ld] -> [keys * R,S,S,ld] with frame k * R + r = key frame k: the U-Net batch of `keys` frames x R messages
+        (torch plumbing on a processing-size tensor, into a named workspace so a captured graph finds it again)"""
+        if R == 1:
+            return key
+        rep = self.new_act("rg.key", key.B * R, key.H, key.W, key.C, key.ld)
+        rep.t.view(key.B, R, -1).copy_(key.t.view(key.B, 1, -1).expand(key.B, R, key.H * key.W * key.ld))
+        return rep
+
+    def embed_tail_regions(self, imgs, out, delta, labels, R: int, *, step, video_mode, hmap_low, attenuate, clamp, antialias, scaling_i, scaling_w,
+                           preds_w=None):
+        """vs_embed_tail_regions: embed_tail with a label per pixel.  delta [keys * R,Cd,S,S] (plane set k * R + r - 1 for label r of key frame k),
+        labels uint8 [F,H,W] on the device; label 0 keeps the pixel of imgs bit for bit"""
+        if not torch.is_tensor(imgs):
+            raise NotImplementedError("region-wise tails cover fp32 NCHW and uint8 RGB24 frames")
+        d, u8 = self._tail_desc(imgs, out, delta, step=step, video_mode=video_mode, hmap_low=hmap_low, attenuate=attenuate, clamp=clamp,
+                                antialias=antialias, scaling_i=scaling_i, scaling_w=scaling_w, preds_w=preds_w)
+        if delta.shape[0] % R:
+            raise ValueError(f"delta has {delta.shape[0]} plane sets for {R} regions")
+        d.total_key = delta.shape[0] // R
+        if labels.dtype != torch.uint8 or tuple(labels.shape) != (d.F, d.H, d.W) or not labels.is_contiguous():
+            raise ValueError(f"labels must be a contiguous uint8 tensor [{d.F}, {d.H}, {d.W}]")
+        ev = self._shell_t0()
+        N.check(self.lib.vs_embed_tail_regions(C.byref(d), N.ptr(labels), int(R), N.stream()), "vs_embed_tail_regions")
+        # algorithmic HBM bytes: frame read + frame written (+ preds_w) + one label byte per pixel; the low-resolution planes are cache hits
+        self._shell_t1(ev, "embed_tail_regions_kernel" + ("<u8>" if u8 else ""), imgs.numel() * imgs.element_size() + out.numel() * out.element_size()
+                       + (preds_w.numel() * 4 if preds_w is not None else 0) + delta.numel() * 4 + labels.numel())
+
+    def pixel_vote_regions(self, preds: torch.Tensor, labels: torch.Tensor, R: int, threshold: float = 0.0):
+        """vs_pixel_vote_regions: preds fp32 [B,K,S_h,S_w] (may be a channel slice `p[:, 1:]` of a contiguous tensor: read in place), labels uint8
+        [B,H,W] -> (votes int32 [B,R,K], nsel int32 [B,R], sums float64 [B,R,K]) in one pass over preds"""
+        B, K, Sh, Sw = preds.shape
+        HW = Sh * Sw
+        s = preds.stride()
+        if preds.dtype != torch.float32 or (s[1], s[2], s[3]) != (HW, Sw, 1) or (B > 1 and s[0] < K * HW):
+            preds = N.f32c(preds).contiguous()
+            s = preds.stride()
+        bs = s[0] if B > 1 else K * HW
+        if labels.dtype != torch.uint8 or labels.dim() != 3 or labels.shape[0] != B or not labels.is_contiguous():
+            raise ValueError(f"labels must be a contiguous uint8 tensor [{B}, H, W]")
+        votes = torch.empty(B, R, K, device=preds.device, dtype=torch.int32)
+        nsel = torch.empty(B, R, device=preds.device, dtype=torch.int32)
+        sums = torch.empty(B, R, K, device=preds.device, dtype=torch.float64)
+        n = int(self.lib.vs_pixel_vote_regions_partial_doubles(B, K, HW, int(R)))
+        if n < 0:
+            raise ValueError(f"vs_pixel_vote_regions_partial_doubles refuses B={B} K={K} HW={HW} R={R}")
+        part = torch.empty(n, device=preds.device, dtype=torch.float64)
+        ev = self._shell_t0()
+        N.check(self.lib.vs_pixel_vote_regions(N.ptr(preds), bs, N.ptr(labels), B, K, Sh, Sw, labels.shape[1], labels.shape[2], int(R), float(threshold),
+                                               N.ptr(votes), N.ptr(nsel), N.ptr(sums), N.ptr(part), N.stream()), "vs_pixel_vote_regions")
+        self._shell_t1(ev, "vote_regions_kernel", B * K * HW * 4)
+        return votes, nsel, sums
+
+    def label_boxes(self, labels: torch.Tensor, R: int) -> torch.Tensor:
+        """vs_label_boxes: uint8 [F,H,W] on the device -> int32 [F,R,4] = (y0, x0, y1, x1), exclusive ends, zeros for an absent label"""
+        if labels.dtype != torch.uint8 or labels.dim() != 3 or not labels.is_contiguous():
+            raise ValueError("labels must be a contiguous uint8 tensor [F, H, W]")
+        F_, H, W = labels.shape
+        boxes = torch.empty(F_, R, 4, device=labels.device, dtype=torch.int32)
+        N.check(self.lib.vs_label_boxes(N.ptr(labels), F_, H, W, int(R), N.ptr(boxes), N.stream()), "vs_label_boxes")
+        return boxes

@@ -943,6 +943,161 @@ class Videoseal(Wam):
         out = self._embed_clip(clip.contiguous(), msgs, interpolation, lowres_attenuation)
         return {"imgs_w": out, "msgs": msgs[0:1].repeat(len(clip), 1)}
 
+    # ---- region-wise watermarks: a label map ties message r - 1 to the pixels of label r (videoseal_amd/regions.py holds the definition)
+    def _embed_regions_eager(self, eng: HipEngine, fr: torch.Tensor, lab: torch.Tensor, msgs_i32: torch.Tensor, out: torch.Tensor, R: int, *,
+                             step: int, video_mode: int, antialias: bool, lowres: bool, preds_w: Optional[torch.Tensor]) -> None:
+        """one chunk on the device: the resize runs once per frame, the key frames go through the U-Net R times in ONE batch (frame k * R + r
+        = key frame k with message r; msgs_i32 [keys * R, k] in that order), the tail picks the plane set of every pixel's label"""
+        S = (self.img_size, self.img_size)
+        att = self.attenuation is not None
+        rgb, key = eng.resize_pre(fr, S, antialias, want_rgb=(att and lowres), want_key=True, key_step=step)
+        delta = eng.embedder_forward(eng.repeat_keys(key, R), msgs_i32, bn_train=False)
+        hmap = eng.jnd_lowres(rgb) if (att and lowres) else None
+        eng.embed_tail_regions(fr, out, delta, lab, R, step=step, video_mode=video_mode, hmap_low=hmap, attenuate=int(att), clamp=self.clamp,
+                               antialias=antialias, scaling_i=self.blender.scaling_i, scaling_w=self.blender.scaling_w, preds_w=preds_w)
+
+    def _embed_regions_frames(self, eng: HipEngine, fr, lab, msgs_i32, out, R: int, *, step, video_mode, antialias, lowres, preds_w) -> None:
+        kw = dict(step=step, video_mode=video_mode, antialias=antialias, lowres=lowres)
+        if self.use_graphs and not torch.cuda.is_current_stream_capturing():
+            def run(si):
+                o = _empty_like(si["fr"])
+                pw = torch.empty_like(preds_w) if preds_w is not None else None
+                self._embed_regions_eager(eng, si["fr"], si["lab"], si["msgs"], o, R, preds_w=pw, **kw)
+                return {"out": o, "pw": pw}
+
+            def key():           # R is part of the key: the U-Net batch is keys * R frames
+                return ("embr", R, fr.dtype, tuple(fr.shape), tuple(msgs_i32.shape), step, video_mode, antialias, lowres, preds_w is not None,
+                        self.img_size, self.clamp, float(self.blender.scaling_i), float(self.blender.scaling_w), self.attenuation is not None,
+                        id(eng), eng.arith_net["E"])
+            res = self._graphed(key(), {"fr": fr, "lab": lab, "msgs": msgs_i32}, run, rekey=key)
+            eng.note_guard()
+            out.copy_(res["out"])
+            if preds_w is not None:
+                preds_w.copy_(res["pw"])
+            return
+        self._embed_regions_eager(eng, fr, lab, msgs_i32, out, R, preds_w=preds_w, **kw)
+
+    @torch.no_grad()
+    def embed_regions(self, imgs: torch.Tensor, labels: torch.Tensor, msgs: torch.Tensor, is_video: bool = True, interpolation: dict = None,
+                      lowres_attenuation: bool = False) -> dict:
+        """A message per region of the frame.  imgs fp32 [F,3,H,W] or uint8 RGB24 [F,H,W,3]; labels uint8 [F,H,W] (0 = background, r in 1..R =
+        message r - 1, above R = background); msgs [R,k], or [F,R,k] with is_video=False (video mode keeps one message per region).
+        A pixel of label r is the pixel of `embed(imgs, msgs[r - 1])`, a pixel of label 0 is the pixel of imgs bit for bit (regions.embed_regions).
+        -> {'imgs_w', 'msgs' [F,R,k]} and, with is_video=False, 'preds_w' fp32 [F,Cd,H,W] (0 on background), as `embed` returns them.
+        The key frames of a chunk pass the U-Net once per region in one batch: chunks hold min(chunk_size, 32 // R) key frames.  Frames that
+        are not on the model's device move chunk by chunk, and their labels with them.  The embedder runs in eval mode.  The strength is
+        blender.scaling_w for every region: `embed_psnr` takes no label map (its strength comes from the energy of ONE watermark over the frame)."""
+        from . import regions as RG
+        F_, H, W, u8 = RG.check_frames(imgs, "embed_regions")
+        RG.check_labels(labels, F_, H, W)
+        R = RG.check_msgs(msgs, F_, is_video)
+        if u8 and not self.clamp:
+            raise NotImplementedError("uint8 output needs clamp=True ((x * 255).byte() is undefined outside [0, 1])")
+        if is_video and self.video_mode not in N.VIDEO_MODES:
+            raise ValueError(f"unknown video_mode {self.video_mode}")
+        eng = self._engine()
+        aa = _antialias_flag(interpolation)
+        cd = self.embedder.cfg.out_ch
+        msgs_out = msgs if msgs.dim() == 3 else msgs[None].repeat(F_, 1, 1)
+        if F_ == 0:
+            res = {"imgs_w": imgs.clone(), "msgs": msgs_out}
+            if not is_video:
+                res["preds_w"] = torch.zeros((0, cd, H, W), dtype=torch.float32, device=imgs.device)
+            return res
+        step = int(self.step_size) if is_video else 1
+        ck = max(1, min(int(getattr(self, "chunk_size", 32)), RG.UNET_FRAMES // R))
+        vm = N.VIDEO_MODES[self.video_mode] if is_video else 0
+        with torch.cuda.device(eng.dev):
+            mi = _msgs_i32(msgs.reshape(-1, msgs.shape[-1]), eng.dev)         # [R, k] or [F * R, k], rows in (frame, region) order
+            on_dev = imgs.device == eng.dev
+            preds_w = None if is_video else _result_buffer((F_, cd, H, W), torch.float32, imgs.device)
+
+            def one(fr, oc, a, b):
+                lab = labels[a:b].to(eng.dev).contiguous()
+                keys = (b - a + step - 1) // step
+                m = mi.repeat(keys, 1) if msgs.dim() == 2 else mi[a * R:b * R]
+                pw = None
+                if preds_w is not None:
+                    pw = preds_w[a:b] if on_dev else torch.empty(b - a, cd, H, W, device=eng.dev, dtype=torch.float32)
+                self._embed_regions_frames(eng, fr, lab, m, oc, R, step=step, video_mode=vm, antialias=aa, lowres=lowres_attenuation, preds_w=pw)
+                if pw is not None and not on_dev:
+                    preds_w[a:b].copy_(pw, non_blocking=True)       # _run_chunks synchronises before it returns
+            out = self._run_chunks(eng, imgs.contiguous() if u8 else imgs, ck * step, one)
+        res = {"imgs_w": out, "msgs": msgs_out}
+        if preds_w is not None:
+            res["preds_w"] = preds_w
+        return res
+
+    @torch.no_grad()
+    def decode_regions(self, imgs: torch.Tensor, labels: torch.Tensor, method: str = "hard", threshold: float = 0.0, per: str = "frame",
+                       is_video: bool = True, interpolation: dict = None, R: Optional[int] = None) -> dict:
+        """The message of every region, for pixel-wise detectors: `detect`'s pass chunk by chunk, then ONE pass of the vote kernel over channels
+        1.. of the chunk's maps for all regions (the maps never leave the device and are not kept).  labels uint8 [F,H,W] at frame resolution:
+        a map pixel looks at the label under its centre (regions.label_index).  R: the number of regions; None reads labels.max() (one host
+        synchronisation).  -> {'msgs' bool [F,R,k], 'score' float64 [F,R,k], 'count' int32 [F,R]} on imgs.device, following
+        evals/metrics.py:208-256: 'hard': score = votes above `threshold` / pixels; 'semihard': score = mean logit; the bit is score > 0.5 in
+        BOTH -- the reference compares the mean logit with 0.5 as well (line 252), and that is kept.  'soft' raises: a label map has no
+        fractional weights.  An empty region has a NaN score, False bits and count 0.  per='clip' adds votes, sums and counts over the
+        frames first and answers [1,R,k]."""
+        from . import regions as RG
+        RG.check_decode(method, per)
+        F_, H, W, _ = RG.check_frames(imgs, "decode_regions")
+        RG.check_labels(labels, F_, H, W)
+        if not self.pixelwise:
+            raise NotImplementedError("decode_regions votes over [F, 1+nbits, S, S] maps: this detector predicts one row of logits per frame "
+                                      "(use detect_regions: the detector on the bounding box of every region)")
+        if R is None:
+            R = max(1, min(RG.REGIONS_MAX, int(labels.max()))) if F_ else 1
+        R = RG.check_regions(R)
+        eng = self._engine()
+        aa = _antialias_flag(interpolation)
+        S = (self.img_size, self.img_size)
+        k = self.embedder.cfg.nbits
+        if F_ == 0:
+            return RG.decide(torch.zeros(0, R, k, dtype=torch.int64), torch.zeros(0, R, dtype=torch.int64), torch.zeros(0, R, k, dtype=torch.float64),
+                             method, per)
+        parts = []
+
+        def one(fr, oc, a, b):
+            p = self._detect_frames(eng, fr, S, aa)
+            parts.append(eng.pixel_vote_regions(p[:, 1:], labels[a:b].to(eng.dev).contiguous(), R, threshold))
+        with torch.cuda.device(eng.dev):
+            self._run_chunks(eng, imgs, max(1, int(self.chunk_size)) if is_video else F_, one, want_out=False, extra=parts.clear)
+            votes, nsel, sums = (torch.cat([p[i] for p in parts], 0) for i in range(3))
+            res = RG.decide(votes, nsel, sums, method, per)
+        return {n: t.to(imgs.device) for n, t in res.items()}
+
+    @torch.no_grad()
+    def detect_regions(self, imgs: torch.Tensor, labels: torch.Tensor, R: int, interpolation: dict = None) -> dict:
+        """The logits of every region, for per-frame detectors.  By definition `detect_images` on the crops imgs[f, :, y0:y1, x0:x1] of the
+        bounding boxes of the present regions, in (f, r) order: NOTHING is masked inside a box, a region that is not a rectangle shares its
+        crop with whatever else lies in its box.  The boxes come from one launch on the label map and one copy to the host.
+        -> {'preds' fp32 [F,R,1+k] with NaN rows for absent regions, 'boxes' int32 [F,R,4] = (y0, x0, y1, x1), exclusive ends}."""
+        from . import regions as RG
+        F_, H, W, u8 = RG.check_frames(imgs, "detect_regions")
+        RG.check_labels(labels, F_, H, W)
+        R = RG.check_regions(R)
+        if self.pixelwise:
+            raise NotImplementedError("detect_regions runs a per-frame detector on the box of every region: this detector predicts [F, 1+nbits, S, S] "
+                                      "maps (use decode_regions: the vote of every region's pixels)")
+        eng = self._engine()
+        k1 = self.embedder.cfg.nbits + 1
+        preds = torch.full((F_, R, k1), float("nan"), dtype=torch.float32, device=imgs.device)
+        if F_ == 0:
+            return {"preds": preds, "boxes": torch.zeros(0, R, 4, dtype=torch.int32, device=imgs.device)}
+        with torch.cuda.device(eng.dev):
+            boxes = eng.label_boxes(labels.to(eng.dev).contiguous(), R).cpu()
+        where, crops = [], []
+        for f, r, (y0, x0, y1, x1) in ((f, r, boxes[f, r].tolist()) for f in range(F_) for r in range(R)):
+            if y1 > y0:
+                where.append((f, r))
+                crops.append(imgs[f, y0:y1, x0:x1, :] if u8 else imgs[f, :, y0:y1, x0:x1])
+        if crops:
+            rows = self.detect_images(crops, interpolation)["preds"].to(imgs.device)
+            idx = torch.tensor(where, dtype=torch.int64, device=imgs.device)
+            preds[idx[:, 0], idx[:, 1]] = rows
+        return {"preds": preds, "boxes": boxes.to(imgs.device)}
+
     # ---- embedding to a target PSNR: the watermark's strength per frame, chosen on the device
     @torch.no_grad()
     def embed_psnr(self, imgs: torch.Tensor, target_psnr: float, msgs: torch.Tensor = None, is_video: bool = True, per: str = "frame",

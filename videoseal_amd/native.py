@@ -55,6 +55,10 @@ EXPORTS = [
     "vs_model_embed_psnr", "vs_model_embed_psnr_workspace_bytes",
 ]
 
+# the entry points of include/videoseal_regions.h (a header of its own: tests/test_host.py holds EXPORTS to what videoseal_hip.h declares)
+REGION_EXPORTS = ["vs_embed_tail_regions", "vs_pixel_vote_regions_partial_doubles", "vs_pixel_vote_regions", "vs_label_boxes"]
+REGIONS_MAX = 8                                              # VS_REGIONS_MAX
+
 
 class NativeError(RuntimeError):
     pass
@@ -450,6 +454,9 @@ def lib() -> C.CDLL:
         "vs_pixel_linear_bwd": [P, P, P, I64, I, I64, I, P, I, P, I64, P, P, P, P],
         "vs_pixel_bce": [P, P, P, I, I, I, I64, F, F, F, P, P, P, P],
         "vs_pixel_vote": [P, I64, P, I, I, I64, F, P, P, P],
+        "vs_embed_tail_regions": [C.POINTER(TailDesc), P, I, P],
+        "vs_pixel_vote_regions": [P, I64, P, I, I, I, I, I, I, I, F, P, P, P, P, P],
+        "vs_label_boxes": [P, I, I, I, I, P, P],
         "vs_disc_input": [P, I, I, I, P, P, P],
         "vs_disc_input_bwd": [P, I, I, I, P, P, P],
         "vs_groupnorm_lrelu": [P, I64, I, I, I, I, P, P, F, F, P, P, P, P, I64, P],
@@ -490,6 +497,8 @@ def lib() -> C.CDLL:
     L.vs_pixel_linear_bwd_partial_floats.argtypes = [I64, I, I]
     L.vs_pixel_bce_partial_doubles.restype = C.c_int64
     L.vs_pixel_bce_partial_doubles.argtypes = [I, I, I64]
+    L.vs_pixel_vote_regions_partial_doubles.restype = C.c_int64
+    L.vs_pixel_vote_regions_partial_doubles.argtypes = [I, I, I64, I]
     L.vs_groupnorm_partial_doubles.restype = C.c_int64
     L.vs_groupnorm_partial_doubles.argtypes = [I, I, I]
     L.vs_conv4x4_wgrad_partial_floats.restype = C.c_int64
