@@ -11,9 +11,11 @@
 // 1024 -> 256, BASELINE configs[4]); (3) the source may be a crop window (i0, j0, H x W) of a larger frame (srcH x srcW) -- the crop is an index
 // offset, the cropped clip is never written; (4) the vertical tap weights of the strip's rows are tabulated ONCE per workgroup in LDS (a weight is a
 // triangle and an IEEE division: evaluated per thread and output row they were ~a third of the kernel's instructions); (5) the store is a functor.
-// (yuv420.hip::resize_pre_yuv_stream_kernel restates the passes below behind a 4:2:0 loader, and yuv_rs_pick restates rs_pick with a wider
-// column margin: a change to the body or to rs_pick belongs there as well -- tests/test_gpu_nv12.py and tests/test_gpu_yuv420.py hold that
-// form to the tile kernel bit for bit.)
+// The YUV and packed RGB kernels (yuv_surf.h, rgb_surf.h: resize_pre_*_stream_kernel) keep bodies of their own with this structure behind their
+// loaders: as one tile function over a loader policy the statements were the same, but hipcc gave the packed RGB kernels 2 - 8 more VGPRs (four
+// instantiations lost a wave per SIMD) and the i420 kernel ran 6 % slower (profiles/shell_phases_codegen.md, profiles/shell_phases_ab.md).  A change
+// to the passes below belongs there as well; rs_pick(.., margin) of resize_pick.h is the launch rule of all three, and tests/test_gpu_nv12.py,
+// test_gpu_yuv420.py, test_gpu_yuv.py, test_gpu_rgbpack.py and test_gpu_shell_digests.py hold those forms to the tile kernels and to recorded bits.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "resize_pick.h"

@@ -20,7 +20,7 @@
 // Between decode and encode the filter taps, the JND, the key-frame expansion and the blend are the expressions of the fp32 kernels of the
 // same form in the same order (shell_common.h): a packed clip gives the bits of the fp32 path on its decoded frames.
 #pragma once
-#include "shell_common.h"
+#include "tail_phases.h"
 
 namespace {
 
@@ -267,23 +267,13 @@ __global__ __launch_bounds__(256) void resize_pre_rgb_kernel(RgbPlane s, RgbPos 
   }
 }
 
-// Row-streaming form of the resize: vs_rs::resize_stream_body (resize_stream.h) with another loader, as resize_pre_yuv_stream_kernel restates
-// it.  A workgroup owns OW output columns x a strip of output rows and walks the input rows eight at a time.  The window starts on a multiple
-// of 16 columns (a byte offset that is a multiple of 16 for every BPP); a load task is 16 pixels of one of the group's eight rows = BPP pieces,
-// requested one group ahead: <= 28 tasks x 8 rows, one per thread.  The thread that holds a task decodes its pixels straight from registers
-// into the [8][3][INW] fp32 window; the two passes, their expressions and their order are resize_stream_body's and the tile kernel's: the
-// same bits.  (yuv_rs_pick(.., 16) of yuv_surf.h is the launch rule: rs_pick with a 16-column margin for the aligned window start.)
-inline int rgb_rs_pick(int H, int W, int oh, int ow, int antialias) {
-  const float sx = (float)W / (float)ow, sy = (float)H / (float)oh;
-  const float supx = antialias ? (sx >= 1.f ? sx : 1.f) : 1.f, supy = antialias ? (sy >= 1.f ? sy : 1.f) : 1.f;
-  auto fits = [&](int OW, int INW, int MT, int RING) {
-    return 2.f * supx + 2.f <= (float)MT && 2.f * supy + 2.f <= (float)MT && (float)OW * sx + 2.f * supx + 4.f + 16.f <= (float)INW &&
-           2.f * supy + 2.f + (float)vs_rs::RS_GI <= (float)RING;
-  };
-  if (fits(128, vs_rs::RsGeo<128>::INW, vs_rs::RsGeo<128>::MT, vs_rs::RsGeo<128>::RING)) return 128;
-  if (fits(64, vs_rs::RsGeo<64>::INW, vs_rs::RsGeo<64>::MT, vs_rs::RsGeo<64>::RING)) return 64;
-  return 0;
-}
+// Row-streaming form of the resize: the structure of vs_rs::resize_stream_tile (resize_stream.h) with its own loader.  A workgroup owns OW
+// output columns x a strip of output rows and walks the input rows eight at a time.  The window starts on a multiple of 16 columns (a byte
+// offset that is a multiple of 16 for every BPP); a load task is 16 pixels of one of the group's eight rows = BPP pieces, requested one group
+// ahead: <= 28 tasks x 8 rows, one per thread.  The thread that holds a task decodes its pixels straight from registers into the [8][3][INW]
+// fp32 window.  This kernel keeps its OWN copy of the two passes (the note at the top of resize_stream.h says why): a change to the passes of
+// resize_stream_tile belongs here as well.
+constexpr int RGB_RS_ALIGN = 16;                           // window start and load task, in columns: the margin of vs_rs::rs_pick
 template <class SF, int OW>
 __global__ __launch_bounds__(256) void resize_pre_rgb_stream_kernel(RgbPlane s, RgbPos pos, int H, int W, int oh, int ow, int antialias,
                                                                     ResizePreEpi epi, int strip) {
@@ -316,7 +306,7 @@ __global__ __launch_bounds__(256) void resize_pre_rgb_stream_kernel(RgbPlane s, 
   tap_range(ox0, W, ow, antialias, x_lo, n_);
   tap_range(min(ox0 + OW - 1, ow - 1), W, ow, antialias, x_hi, n_);
   const int xa = x_lo & ~(CW - 1);                       // LDS column 0 <-> frame column xa
-  const int ww = min(x_hi + n_ - xa, INW);               // (<= INW: rgb_rs_pick)
+  const int ww = min(x_hi + n_ - xa, INW);               // (<= INW: rs_pick with a margin of 16)
   const int npc = (ww + CW - 1) / CW;
   int y_lo, y_hi;
   tap_range(oy0, H, oh, antialias, y_lo, n_);
@@ -494,31 +484,10 @@ __global__ __launch_bounds__(256) void embed_tail_rgb_kernel(TailArgs a, JndTaps
   }
   __syncthreads();
 
-  // key-frame expansion (videoseal.py:80-118): value = wa*key[ka] + wb*key[kb]   (same as embed_tail_kernel)
-  int ka = 0, kb = 0;
-  float wa = 1.f, wb = 0.f;
-  if (a.video_mode == VS_VIDEO_REPEAT) {
-    ka = f / a.step;
-  } else if (a.video_mode == VS_VIDEO_ALTERNATE) {
-    ka = f / a.step;
-    wa = (f % a.step) == 0 ? 1.f : 0.f;
-  } else {
-    const int ninter = ((a.F - 1) / a.step) * a.step;
-    if (f < ninter) {
-      ka = f / a.step; kb = ka + 1;
-      const int j = f % a.step;
-      const float lin = a.step > 1 ? (float)j / (float)(a.step - 1) : 0.f;
-      wa = 1.f - lin; wb = 1.f - wa;
-    } else {
-      ka = a.total_key - 1;
-    }
-  }
-  if (ka >= a.total_key) ka = a.total_key - 1;
-  if (kb >= a.total_key) kb = a.total_key - 1;
+  const KeyMix km = key_mix(a, f, a.Cd);                 // value = wa*key[ka] + wb*key[kb]
+  const float wa = km.wa, wb = km.wb;
+  const float *dka = km.dka, *dkb = km.dkb, *hml = km.hml;
   const int splane = a.Sh * a.Sw;
-  const float* dka = a.delta + (int64_t)ka * a.Cd * splane;
-  const float* dkb = a.delta + (int64_t)kb * a.Cd * splane;
-  const float* hml = a.hmap_lowres ? a.hmap_lowres + (int64_t)f * splane : nullptr;
 
   const int lasty = min(TTH, a.H - y0) - 1;
   const int wx0 = s_xlo, wy0 = ty_lo[0];
@@ -671,31 +640,10 @@ __global__ __launch_bounds__(256) void embed_tail_rgb_stream_kernel(TailArgs a, 
   Pieces pv = load_piece(-1);
   stash(0, pv);
 
-  // key-frame expansion (videoseal.py:80-118): value = wa*key[ka] + wb*key[kb]   (same as the tile kernel)
-  int ka = 0, kb = 0;
-  float wa = 1.f, wb = 0.f;
-  if (a.video_mode == VS_VIDEO_REPEAT) {
-    ka = f / a.step;
-  } else if (a.video_mode == VS_VIDEO_ALTERNATE) {
-    ka = f / a.step;
-    wa = (f % a.step) == 0 ? 1.f : 0.f;
-  } else {
-    const int ninter = ((a.F - 1) / a.step) * a.step;
-    if (f < ninter) {
-      ka = f / a.step; kb = ka + 1;
-      const int j = f % a.step;
-      const float lin = a.step > 1 ? (float)j / (float)(a.step - 1) : 0.f;
-      wa = 1.f - lin; wb = 1.f - wa;
-    } else {
-      ka = a.total_key - 1;
-    }
-  }
-  if (ka >= a.total_key) ka = a.total_key - 1;
-  if (kb >= a.total_key) kb = a.total_key - 1;
+  const KeyMix km = key_mix(a, f, CD);                   // value = wa*key[ka] + wb*key[kb]
+  const float wa = km.wa, wb = km.wb;
+  const float *dka = km.dka, *dkb = km.dkb, *hml = km.hml;
   const int splane = a.Sh * a.Sw;
-  const float* dka = a.delta + (int64_t)ka * CD * splane;
-  const float* dkb = a.delta + (int64_t)kb * CD * splane;
-  const float* hml = a.hmap_lowres ? a.hmap_lowres + (int64_t)f * splane : nullptr;
   __syncthreads();                                             // s_xlo / s_xhi, byte stage of group -1
   const int wx0 = s_xlo, dww = s_xhi - s_xlo;
 

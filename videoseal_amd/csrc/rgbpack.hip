@@ -43,49 +43,15 @@ bool rgb_surface_ok(const vs_rgb_surface_t& s, int bpp, int F, int H, int W) {
 }
 RgbPlane dev_plane(const vs_rgb_surface_t& s) { return RgbPlane{static_cast<const unsigned char*>(s.data), s.pitch, s.frame_stride}; }
 
+// the kernels of one layout, for launch_resize / launch_tail (shell_common.h)
 template <class SF>
-int launch_resize_rgb(const RgbPlane& s, const RgbPos& pos, int B, int H, int W, int oh, int ow, int antialias, float* dst_rgb, float mul,
-                      float add, float* dst_y, int y_step, int key_mode, float y0, float y1, float y2, hipStream_t st) {
-  // row-streaming form where its windows fit (the development switches of vs_resize_pre apply: form, strip height), the tile form elsewhere
-  const int OWsel = rgb_rs_pick(H, W, oh, ow, antialias);
-  if (vs_debug_get(VS_DBG_RESIZE_FORM) != 1 && OWsel) {
-    const int cols = (ow + OWsel - 1) / OWsel;
-    int strip = 8;          // (the strip rule of the YUV resize: ~512 workgroups, down to 8 rows for the short launches of detect)
-    for (int cand : {64, 48, 32, 24, 16, 12})
-      if ((int64_t)cols * ((oh + cand - 1) / cand) * B >= 512) { strip = cand; break; }
-    if (const int v = vs_debug_get(VS_DBG_RESIZE_STRIP); v >= 1) strip = v;
-    dim3 gs(cols, (oh + strip - 1) / strip, B);
-    const size_t lds = OWsel == 128 ? vs_rs::rs_lds_bytes<128>() : vs_rs::rs_lds_bytes<64>();
-    const ResizePreEpi epi{dst_rgb, dst_y, mul, add, y_step, key_mode, y0, y1, y2, oh, ow};
-    if ((int64_t)lds <= vs_max_lds_bytes()) {
-      if (OWsel == 128) hipLaunchKernelGGL((resize_pre_rgb_stream_kernel<SF, 128>), gs, dim3(256), lds, st, s, pos, H, W, oh, ow, antialias, epi, strip);
-      else hipLaunchKernelGGL((resize_pre_rgb_stream_kernel<SF, 64>), gs, dim3(256), lds, st, s, pos, H, W, oh, ow, antialias, epi, strip);
-      return vs_launch_status();
-    }
-  }
-  dim3 grid((ow + 31) / 32, (oh + 7) / 8, B);
-  hipLaunchKernelGGL(resize_pre_rgb_kernel<SF>, grid, dim3(256), 0, st, s, pos, B, H, W, oh, ow, antialias, dst_rgb, mul, add, dst_y, y_step,
-                     key_mode, y0, y1, y2);
-  return vs_launch_status();
-}
-
-template <class SF>
-int launch_tail_rgb(const TailArgs& a, const JndTaps& k, const RgbGeo& g, bool stream_form, bool full_jnd, hipStream_t st) {
-  if (stream_form) {
-    const int strip = tail_strip(full_jnd, a.F, a.H, a.W);
-    dim3 gs((a.W + TTW - 1) / TTW, (a.H + strip - 1) / strip, a.F);
-    const size_t lds_w = (size_t)2 * a.Cd * DW_W * DW_H * sizeof(float);
-    const size_t lds_j = lds_w + RING * TLW * sizeof(float);
-    if (full_jnd && a.Cd == 1) hipLaunchKernelGGL((embed_tail_rgb_stream_kernel<SF, true, 1>), gs, dim3(256), lds_j, st, a, k, g, strip);
-    else if (full_jnd) hipLaunchKernelGGL((embed_tail_rgb_stream_kernel<SF, true, 3>), gs, dim3(256), lds_j, st, a, k, g, strip);
-    else if (a.Cd == 1) hipLaunchKernelGGL((embed_tail_rgb_stream_kernel<SF, false, 1>), gs, dim3(256), lds_w, st, a, k, g, strip);
-    else hipLaunchKernelGGL((embed_tail_rgb_stream_kernel<SF, false, 3>), gs, dim3(256), lds_w, st, a, k, g, strip);
-    return vs_launch_status();
-  }
-  dim3 grid((a.W + TTW - 1) / TTW, (a.H + TTH - 1) / TTH, a.F);
-  hipLaunchKernelGGL(embed_tail_rgb_kernel<SF>, grid, dim3(256), 0, st, a, k, g);
-  return vs_launch_status();
-}
+struct RgbKernels {
+  static constexpr int ALIGN = RGB_RS_ALIGN;
+  template <int OW> static auto resize_stream() { return resize_pre_rgb_stream_kernel<SF, OW>; }
+  static auto resize_tile() { return resize_pre_rgb_kernel<SF>; }
+  template <bool JND, int CD> static auto tail_stream() { return embed_tail_rgb_stream_kernel<SF, JND, CD>; }
+  static auto tail_tile() { return embed_tail_rgb_kernel<SF>; }
+};
 
 }  // namespace
 
@@ -101,46 +67,35 @@ extern "C" int vs_resize_pre_rgb(const vs_rgb_surface_t* src, int B, int H, int 
   if (!rgb_format(src->format, layout, bpp, pos)) return VS_ERR_UNSUPPORTED;
   VS_REQUIRE(rgb_surface_ok(*src, bpp, B, H, W));
   const RgbPlane s = dev_plane(*src);
-  const int ks = y_step < 1 ? 1 : y_step, km = ymat3 ? 0 : 1;
-  const float y0 = ymat3 ? ymat3[0] : 0.f, y1 = ymat3 ? ymat3[1] : 0.f, y2 = ymat3 ? ymat3[2] : 0.f;
+  const ResizeOut o = resize_out(dst_rgb, mul, add, dst_y, y_step, ymat3);
   hipStream_t st = (hipStream_t)stream;
   switch (layout) {
-    case 0: return launch_resize_rgb<Rgb3>(s, pos, B, H, W, oh, ow, antialias, dst_rgb, mul, add, dst_y, ks, km, y0, y1, y2, st);
-    case 1: return launch_resize_rgb<Rgb4>(s, pos, B, H, W, oh, ow, antialias, dst_rgb, mul, add, dst_y, ks, km, y0, y1, y2, st);
-    case 2: return launch_resize_rgb<Rgb6>(s, pos, B, H, W, oh, ow, antialias, dst_rgb, mul, add, dst_y, ks, km, y0, y1, y2, st);
-    case 3: return launch_resize_rgb<Rgb8>(s, pos, B, H, W, oh, ow, antialias, dst_rgb, mul, add, dst_y, ks, km, y0, y1, y2, st);
-    default: return launch_resize_rgb<RgbX2>(s, pos, B, H, W, oh, ow, antialias, dst_rgb, mul, add, dst_y, ks, km, y0, y1, y2, st);
+    case 0: return launch_resize<RgbKernels<Rgb3>>(B, H, W, oh, ow, antialias, o, st, s, pos);
+    case 1: return launch_resize<RgbKernels<Rgb4>>(B, H, W, oh, ow, antialias, o, st, s, pos);
+    case 2: return launch_resize<RgbKernels<Rgb6>>(B, H, W, oh, ow, antialias, o, st, s, pos);
+    case 3: return launch_resize<RgbKernels<Rgb8>>(B, H, W, oh, ow, antialias, o, st, s, pos);
+    default: return launch_resize<RgbKernels<RgbX2>>(B, H, W, oh, ow, antialias, o, st, s, pos);
   }
 }
 
 extern "C" int vs_embed_tail_rgb(const vs_tail_rgb_desc_t* d, void* stream) {
   VS_REQUIRE(d && d->src.data && d->dst.data && d->delta && d->F > 0 && d->H > 0 && d->W > 0 && d->S_h > 0 && d->S_w > 0);
-  VS_REQUIRE((d->Cd == 1 || d->Cd == 3) && d->step >= 1 && d->total_key >= 1);
-  VS_REQUIRE(d->video_mode >= 0 && d->video_mode <= 2);
+  if (const int rc = tail_desc_numbers(d); rc != VS_OK) return rc;
   VS_REQUIRE(d->clamp == 1);                              // codes are only defined for values in [0, 1]
   VS_REQUIRE(d->dst.data != d->src.data);                 // the JND reads a halo of the source
   int layout, bpp;
   RgbPos pos;
   if (!rgb_format(d->src.format, layout, bpp, pos) || d->dst.format != d->src.format) return VS_ERR_UNSUPPORTED;
   VS_REQUIRE(rgb_surface_ok(d->src, bpp, d->F, d->H, d->W) && rgb_surface_ok(d->dst, bpp, d->F, d->H, d->W));
-  if (d->preds_w || d->attenuate == 2 || (d->variant != 0 && d->variant != 1 && d->variant != 4)) return VS_ERR_UNSUPPORTED;
-  VS_REQUIRE(!(d->attenuate && !d->hmap_lowres) || d->taps43);
-  const TailArgs a{nullptr, nullptr, nullptr, d->delta, d->attenuate ? d->hmap_lowres : nullptr, d->F, d->H, d->W, d->S_h, d->S_w,
-                   d->Cd, d->step, d->video_mode, d->total_key, d->attenuate, d->clamp, d->antialias, d->scaling_i, d->scaling_w};
-  JndTaps k{};
-  if (d->taps43) k = taps_from(d->taps43);
+  TailForm t;
+  if (const int rc = tail_desc_form(d, t); rc != VS_OK) return rc;
   const RgbGeo g{dev_plane(d->src), dev_plane(d->dst), pos};
-  // row-streaming form (default) where vs_embed_tail's applies, the 16-row tile form elsewhere and with variant = 1
-  const bool full_jnd = d->attenuate && !d->hmap_lowres;
-  const bool can_stream = tail_can_stream(full_jnd, d->taps43, d->H, d->W, d->S_h, d->S_w);
-  if (d->variant == 4 && !can_stream) return VS_ERR_UNSUPPORTED;
-  const bool sf = d->variant != 1 && can_stream;
   hipStream_t st = (hipStream_t)stream;
   switch (layout) {
-    case 0: return launch_tail_rgb<Rgb3>(a, k, g, sf, full_jnd, st);
-    case 1: return launch_tail_rgb<Rgb4>(a, k, g, sf, full_jnd, st);
-    case 2: return launch_tail_rgb<Rgb6>(a, k, g, sf, full_jnd, st);
-    case 3: return launch_tail_rgb<Rgb8>(a, k, g, sf, full_jnd, st);
-    default: return launch_tail_rgb<RgbX2>(a, k, g, sf, full_jnd, st);
+    case 0: return launch_tail<RgbKernels<Rgb3>>(t.a, t.k, g, t.stream_form, t.full_jnd, st);
+    case 1: return launch_tail<RgbKernels<Rgb4>>(t.a, t.k, g, t.stream_form, t.full_jnd, st);
+    case 2: return launch_tail<RgbKernels<Rgb6>>(t.a, t.k, g, t.stream_form, t.full_jnd, st);
+    case 3: return launch_tail<RgbKernels<Rgb8>>(t.a, t.k, g, t.stream_form, t.full_jnd, st);
+    default: return launch_tail<RgbKernels<RgbX2>>(t.a, t.k, g, t.stream_form, t.full_jnd, st);
   }
 }

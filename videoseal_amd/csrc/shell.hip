@@ -355,7 +355,8 @@ __device__ __forceinline__ void embed_tail_tile(const Args& a, const JndTaps& k,
   }
   __syncthreads();
 
-  // key-frame expansion (videoseal.py:80-118): value = wa*key[ka] + wb*key[kb]
+  // key-frame expansion (videoseal.py:80-118): value = wa*key[ka] + wb*key[kb]   (second spelling: key_mix of tail_phases.h, which the
+  // surface kernels call -- a change to the rule is made in both)
   int ka = 0, kb = 0;
   float wa = 1.f, wb = 0.f;
   if (a.video_mode == VS_VIDEO_REPEAT) {
@@ -628,7 +629,7 @@ __global__ __launch_bounds__(256) void embed_tail_stream_kernel(tail_args_t<MODE
   const bool hin = hal && hgx >= 0 && hgx < a.W;
   const int hcx = hgx < 0 ? 0 : (hgx >= a.W ? a.W - 1 : hgx);
 
-  // key-frame expansion (videoseal.py:80-118): value = wa*key[ka] + wb*key[kb]   (same as the tile kernel)
+  // key-frame expansion (videoseal.py:80-118): value = wa*key[ka] + wb*key[kb]   (same as the tile kernel; second spelling: key_mix of tail_phases.h)
   int ka = 0, kb = 0;
   float wa = 1.f, wb = 0.f;
   if (a.video_mode == VS_VIDEO_REPEAT) {
@@ -657,6 +658,8 @@ __global__ __launch_bounds__(256) void embed_tail_stream_kernel(tail_args_t<MODE
   const int wx0 = s_xlo, dww = s_xhi - s_xlo;
 
   auto stage = [&](const int sub, const int b) __attribute__((always_inline)) {      // source window + row taps of output rows [16 sub, 16 sub + 16)
+    // (embed_tail_yuv_stream_kernel and embed_tail_rgb_stream_kernel carry this lambda, the accumulate / shift of acc_la, acc_gx, acc_gy and
+    // the jump test below word for word: a change here is made there as well)
     const int sy0 = y0 + SUBR * sub;
     const int lasty = min(SUBR, ys_end - sy0) - 1;
     int wy0, n0, wyl, nl;

@@ -1,6 +1,7 @@
-// What the shell kernels of shell.hip and yuv420.hip share: tile geometry, the resize_pre epilogue, the JND and blend expressions (every kernel
-// calls the SAME functions, so its forms agree bit for bit), the tail arguments, the launch rule of the row-streaming tail and the colour
-// affines of the 4:2:0 kernels.
+// What the shell kernels of shell.hip, the YUV family (yuv_surf.h) and the packed RGB family (rgb_surf.h) share: tile geometry, the resize_pre
+// epilogue, the JND and blend expressions (every kernel calls the SAME functions, so its forms agree bit for bit), the tail arguments, the
+// colour affines of the YUV kernels and, on the host, the launch rules: which tail form, which strip heights, and the one launcher of each
+// phase for the two surface families.  (The phases of the surface tails are tail_phases.h.)
 #pragma once
 #include "vs_common.h"
 #include "resize_taps.h"
@@ -227,6 +228,88 @@ inline JndTaps taps_from(const float* t43) {
   for (int i = 0; i < 25; ++i) k.lum[i] = t43[i];
   for (int i = 0; i < 9; ++i) { k.sx[i] = t43[25 + i]; k.sy[i] = t43[34 + i]; }
   return k;
+}
+
+
+// ---- the surface families (YUV, packed RGB) on the host: one launcher per phase.  K names a family's kernels for one surface trait --
+//   K::ALIGN, K::resize_stream<OW>(), K::resize_tile(), K::tail_stream<JND, CD>(), K::tail_tile()
+// -- and `surf...` are the leading kernel arguments that describe the source (YUV: planes, decode affine; RGB: plane, component positions).
+struct ResizeOut { float* dst_rgb; float mul, add; float* dst_key; int key_step, key_mode; float y0, y1, y2; };
+inline ResizeOut resize_out(float* dst_rgb, float mul, float add, float* dst_key, int key_step, const float* ymat3) {
+  return ResizeOut{dst_rgb, mul, add, dst_key, key_step < 1 ? 1 : key_step, ymat3 ? 0 : 1, ymat3 ? ymat3[0] : 0.f, ymat3 ? ymat3[1] : 0.f, ymat3 ? ymat3[2] : 0.f};
+}
+// strip of the surfaces' row-streaming resize: the tallest that still launches ~512 workgroups (two per CU), down to 8 rows for the 8-frame
+// launches of detect: the fastest height of every batch size in `tools/bench_nv12.py --sweep` (profiles/nv12_resize_strip_sweep.json)
+inline int surf_resize_strip(int cols, int oh, int B) {
+  int strip = 8;
+  for (int cand : {64, 48, 32, 24, 16, 12})
+    if ((int64_t)cols * ((oh + cand - 1) / cand) * B >= 512) { strip = cand; break; }
+  if (const int v = vs_debug_get(VS_DBG_RESIZE_STRIP); v >= 1) strip = v;
+  return strip;
+}
+template <class K, class... SurfArgs>
+int launch_resize(int B, int H, int W, int oh, int ow, int antialias, const ResizeOut& o, hipStream_t st, const SurfArgs&... surf) {
+  // row-streaming form where its windows fit (the development switches of vs_resize_pre apply: form, strip height), the tile form elsewhere
+  const int OWsel = vs_rs::rs_pick(H, W, oh, ow, antialias, K::ALIGN);
+  if (vs_debug_get(VS_DBG_RESIZE_FORM) != 1 && OWsel) {
+    const int cols = (ow + OWsel - 1) / OWsel;
+    const int strip = surf_resize_strip(cols, oh, B);
+    dim3 gs(cols, (oh + strip - 1) / strip, B);
+    const size_t lds = OWsel == 128 ? vs_rs::rs_lds_bytes<128>() : vs_rs::rs_lds_bytes<64>();
+    const ResizePreEpi epi{o.dst_rgb, o.dst_key, o.mul, o.add, o.key_step, o.key_mode, o.y0, o.y1, o.y2, oh, ow};
+    if ((int64_t)lds <= vs_max_lds_bytes()) {
+      if (OWsel == 128) hipLaunchKernelGGL(K::template resize_stream<128>(), gs, dim3(256), lds, st, surf..., H, W, oh, ow, antialias, epi, strip);
+      else hipLaunchKernelGGL(K::template resize_stream<64>(), gs, dim3(256), lds, st, surf..., H, W, oh, ow, antialias, epi, strip);
+      return vs_launch_status();
+    }
+  }
+  dim3 grid((ow + 31) / 32, (oh + 7) / 8, B);
+  hipLaunchKernelGGL(K::resize_tile(), grid, dim3(256), 0, st, surf..., B, H, W, oh, ow, antialias, o.dst_rgb, o.mul, o.add, o.dst_key, o.key_step,
+                     o.key_mode, o.y0, o.y1, o.y2);
+  return vs_launch_status();
+}
+template <class K, class Geo>
+int launch_tail(const TailArgs& a, const JndTaps& k, const Geo& g, bool stream_form, bool full_jnd, hipStream_t st) {
+  if (stream_form) {
+    const int strip = tail_strip(full_jnd, a.F, a.H, a.W);
+    dim3 gs((a.W + TTW - 1) / TTW, (a.H + strip - 1) / strip, a.F);
+    const size_t lds_w = (size_t)2 * a.Cd * DW_W * DW_H * sizeof(float);
+    const size_t lds_j = lds_w + RING * TLW * sizeof(float);
+    if (full_jnd && a.Cd == 1) hipLaunchKernelGGL((K::template tail_stream<true, 1>()), gs, dim3(256), lds_j, st, a, k, g, strip);
+    else if (full_jnd) hipLaunchKernelGGL((K::template tail_stream<true, 3>()), gs, dim3(256), lds_j, st, a, k, g, strip);
+    else if (a.Cd == 1) hipLaunchKernelGGL((K::template tail_stream<false, 1>()), gs, dim3(256), lds_w, st, a, k, g, strip);
+    else hipLaunchKernelGGL((K::template tail_stream<false, 3>()), gs, dim3(256), lds_w, st, a, k, g, strip);
+    return vs_launch_status();
+  }
+  dim3 grid((a.W + TTW - 1) / TTW, (a.H + TTH - 1) / TTH, a.F);
+  hipLaunchKernelGGL(K::tail_tile(), grid, dim3(256), 0, st, a, k, g);
+  return vs_launch_status();
+}
+
+// The checks of a surface tail descriptor that do not depend on the surface, in the order vs_embed_tail_yuv420 has always applied them
+// around its own: tail_desc_numbers first, then the family's size, format and surface checks, then tail_desc_form -- what the tail cannot do,
+// the taps, the kernel arguments and the form (row-streaming by default where vs_embed_tail's applies, the 16-row tiles elsewhere and with
+// variant = 1).
+struct TailForm { TailArgs a; JndTaps k; bool stream_form, full_jnd; };
+template <class DESC>
+int tail_desc_numbers(const DESC* d) {
+  VS_REQUIRE((d->Cd == 1 || d->Cd == 3) && d->step >= 1 && d->total_key >= 1);
+  VS_REQUIRE(d->video_mode >= 0 && d->video_mode <= 2);
+  return VS_OK;
+}
+template <class DESC>
+int tail_desc_form(const DESC* d, TailForm& t) {
+  if (d->preds_w || d->attenuate == 2 || (d->variant != 0 && d->variant != 1 && d->variant != 4)) return VS_ERR_UNSUPPORTED;
+  VS_REQUIRE(!(d->attenuate && !d->hmap_lowres) || d->taps43);
+  t.a = TailArgs{nullptr, nullptr, nullptr, d->delta, d->attenuate ? d->hmap_lowres : nullptr, d->F, d->H, d->W, d->S_h, d->S_w,
+                 d->Cd, d->step, d->video_mode, d->total_key, d->attenuate, d->clamp, d->antialias, d->scaling_i, d->scaling_w};
+  t.k = JndTaps{};
+  if (d->taps43) t.k = taps_from(d->taps43);
+  t.full_jnd = d->attenuate && !d->hmap_lowres;
+  const bool can_stream = tail_can_stream(t.full_jnd, d->taps43, d->H, d->W, d->S_h, d->S_w);
+  if (d->variant == 4 && !can_stream) return VS_ERR_UNSUPPORTED;
+  t.stream_form = d->variant != 1 && can_stream;
+  return VS_OK;
 }
 
 }  // namespace

@@ -15,7 +15,7 @@
 // aligned, sample by sample, guarded, elsewhere -- padding bytes are neither used nor written.  Conversion, filter taps, JND and blend are the
 // same expressions in the same order for every trait (shell_common.h), so layouts that hold the same codes give the same bits.
 #pragma once
-#include "shell_common.h"
+#include "tail_phases.h"
 
 #include <type_traits>
 
@@ -225,7 +225,7 @@ struct Surf {
 // pieces of both rows and the chroma they share), converted from registers into the fp32 window in LDS; the window of at most RS_WW x RS_WH
 // pixels spans <= 15 chunks x 17 pairs, tasks taken in turn by the 256 threads.  A window that does not fit is filtered straight from the frame.
 template <class SF>
-__global__ __launch_bounds__(256) void resize_pre_yuv_kernel(YuvSurf s, int B, int H, int W, Nv12Mat dec, int oh, int ow, int antialias,
+__global__ __launch_bounds__(256) void resize_pre_yuv_kernel(YuvSurf s, Nv12Mat dec, int B, int H, int W, int oh, int ow, int antialias,
                                                              float* __restrict__ dst_rgb, float mul, float add, float* __restrict__ dst_key,
                                                              int key_step, int key_mode, float y0, float y1, float y2) {
   __shared__ float Lw[3 * RS_WH * RS_WW];
@@ -354,7 +354,7 @@ __global__ __launch_bounds__(256) void resize_pre_yuv_kernel(YuvSurf s, int B, i
   }
 }
 
-// Row-streaming form of the resize: vs_rs::resize_stream_body (resize_stream.h) with another loader.  A workgroup owns OW output columns x a
+// Row-streaming form of the resize: the structure of vs_rs::resize_stream_tile (resize_stream.h) with another loader (see the note there).  A workgroup owns OW output columns x a
 // strip of output rows and walks the input rows eight at a time, groups starting on an EVEN row: a group is four row pairs.  The window starts
 // on a multiple of `align` = max(16, Surf::CW) columns (luma and chroma pieces stay 16-byte aligned); a load task is one piece of SPP columns
 // x one row pair of the group's four (Surf::SChunk: two luma pieces and one chroma piece -- with SY = 0 one per row of the pair, for 4:4:4 a U
@@ -363,24 +363,14 @@ __global__ __launch_bounds__(256) void resize_pre_yuv_kernel(YuvSurf s, int B, i
 // row is fetched once per column tile (+ the first window of a strip).  The thread that holds a task converts its pixels straight from
 // registers into the [8][3][INW] fp32 window; the horizontal and vertical passes, their expressions and their order are resize_stream_body's
 // and the tile kernel's: the same bits.
-inline int yuv_rs_pick(int H, int W, int oh, int ow, int antialias, int align) {          // vs_rs::rs_pick with an `align`-column-aligned window start
-  const float sx = (float)W / (float)ow, sy = (float)H / (float)oh;
-  const float supx = antialias ? (sx >= 1.f ? sx : 1.f) : 1.f, supy = antialias ? (sy >= 1.f ? sy : 1.f) : 1.f;
-  auto fits = [&](int OW, int INW, int MT, int RING) {
-    return 2.f * supx + 2.f <= (float)MT && 2.f * supy + 2.f <= (float)MT && (float)OW * sx + 2.f * supx + 4.f + (float)align <= (float)INW &&
-           2.f * supy + 2.f + (float)vs_rs::RS_GI <= (float)RING;
-  };
-  if (fits(128, vs_rs::RsGeo<128>::INW, vs_rs::RsGeo<128>::MT, vs_rs::RsGeo<128>::RING)) return 128;
-  if (fits(64, vs_rs::RsGeo<64>::INW, vs_rs::RsGeo<64>::MT, vs_rs::RsGeo<64>::RING)) return 64;
-  return 0;
-}
+template <class SF> constexpr int yuv_rs_align() { return SF::CW > 16 ? SF::CW : 16; }      // window start, in columns: the margin of vs_rs::rs_pick
 template <class SF, int OW>
-__global__ __launch_bounds__(256) void resize_pre_yuv_stream_kernel(YuvSurf s, int H, int W, Nv12Mat dec, int oh, int ow, int antialias,
+__global__ __launch_bounds__(256) void resize_pre_yuv_stream_kernel(YuvSurf s, Nv12Mat dec, int H, int W, int oh, int ow, int antialias,
                                                                     ResizePreEpi epi, int strip) {
   using namespace vs_rs;
   extern __shared__ __attribute__((aligned(16))) float rs_smem[];
   constexpr int INW = RsGeo<OW>::INW, MT = RsGeo<OW>::MT, RING = RsGeo<OW>::RING, NPART = 256 / OW, RPP = RS_GI / NPART;
-  constexpr int CW = SF::SPP, ALIGN = SF::CW > 16 ? SF::CW : 16;
+  constexpr int CW = SF::SPP, ALIGN = yuv_rs_align<SF>();
   static_assert(INW % (2 * CW) == 0 && 4 * (INW / CW) <= 256, "a piece (and a pair of them) ends inside the window row; one load task per thread");
   float* In = rs_smem;                                   // [RS_GI][3][INW]
   float* Hr = rs_smem + RS_GI * 3 * INW;                 // [RING][3][OW]
@@ -408,7 +398,7 @@ __global__ __launch_bounds__(256) void resize_pre_yuv_stream_kernel(YuvSurf s, i
   tap_range(ox0, W, ow, antialias, x_lo, n_);
   tap_range(min(ox0 + OW - 1, ow - 1), W, ow, antialias, x_hi, n_);
   const int xa = x_lo & ~(ALIGN - 1);                    // LDS column 0 <-> frame column xa
-  const int ww = min(x_hi + n_ - xa, INW);               // (<= INW: yuv_rs_pick)
+  const int ww = min(x_hi + n_ - xa, INW);               // (<= INW: rs_pick with a margin of ALIGN)
   const int npc = SF::PSUB ? ((ww + 2 * CW - 1) / (2 * CW)) * 2 : (ww + CW - 1) / CW;       // (shared chroma pieces: tid and pi have the same parity)
   int y_lo, y_hi;
   tap_range(oy0, H, oh, antialias, y_lo, n_);
@@ -606,31 +596,10 @@ __global__ __launch_bounds__(256) void embed_tail_yuv_kernel(TailArgs a, JndTaps
   }
   __syncthreads();
 
-  // key-frame expansion (videoseal.py:80-118): value = wa*key[ka] + wb*key[kb]   (same as embed_tail_kernel)
-  int ka = 0, kb = 0;
-  float wa = 1.f, wb = 0.f;
-  if (a.video_mode == VS_VIDEO_REPEAT) {
-    ka = f / a.step;
-  } else if (a.video_mode == VS_VIDEO_ALTERNATE) {
-    ka = f / a.step;
-    wa = (f % a.step) == 0 ? 1.f : 0.f;
-  } else {
-    const int ninter = ((a.F - 1) / a.step) * a.step;
-    if (f < ninter) {
-      ka = f / a.step; kb = ka + 1;
-      const int j = f % a.step;
-      const float lin = a.step > 1 ? (float)j / (float)(a.step - 1) : 0.f;
-      wa = 1.f - lin; wb = 1.f - wa;
-    } else {
-      ka = a.total_key - 1;
-    }
-  }
-  if (ka >= a.total_key) ka = a.total_key - 1;
-  if (kb >= a.total_key) kb = a.total_key - 1;
+  const KeyMix km = key_mix(a, f, a.Cd);                 // value = wa*key[ka] + wb*key[kb]
+  const float wa = km.wa, wb = km.wb;
+  const float *dka = km.dka, *dkb = km.dkb, *hml = km.hml;
   const int splane = a.Sh * a.Sw;
-  const float* dka = a.delta + (int64_t)ka * a.Cd * splane;
-  const float* dkb = a.delta + (int64_t)kb * a.Cd * splane;
-  const float* hml = a.hmap_lowres ? a.hmap_lowres + (int64_t)f * splane : nullptr;
 
   const int lasty = min(TTH, a.H - y0) - 1;              // odd where H is even (SY = 1); with an odd H the last row has no partner
   const int wx0 = s_xlo, wy0 = ty_lo[0];
@@ -820,31 +789,10 @@ __global__ __launch_bounds__(256) void embed_tail_yuv_stream_kernel(TailArgs a, 
   Pieces pv = load_piece(-1);
   stash(0, pv);
 
-  // key-frame expansion (videoseal.py:80-118): value = wa*key[ka] + wb*key[kb]   (same as the tile kernel)
-  int ka = 0, kb = 0;
-  float wa = 1.f, wb = 0.f;
-  if (a.video_mode == VS_VIDEO_REPEAT) {
-    ka = f / a.step;
-  } else if (a.video_mode == VS_VIDEO_ALTERNATE) {
-    ka = f / a.step;
-    wa = (f % a.step) == 0 ? 1.f : 0.f;
-  } else {
-    const int ninter = ((a.F - 1) / a.step) * a.step;
-    if (f < ninter) {
-      ka = f / a.step; kb = ka + 1;
-      const int j = f % a.step;
-      const float lin = a.step > 1 ? (float)j / (float)(a.step - 1) : 0.f;
-      wa = 1.f - lin; wb = 1.f - wa;
-    } else {
-      ka = a.total_key - 1;
-    }
-  }
-  if (ka >= a.total_key) ka = a.total_key - 1;
-  if (kb >= a.total_key) kb = a.total_key - 1;
+  const KeyMix km = key_mix(a, f, CD);                   // value = wa*key[ka] + wb*key[kb]
+  const float wa = km.wa, wb = km.wb;
+  const float *dka = km.dka, *dkb = km.dkb, *hml = km.hml;
   const int splane = a.Sh * a.Sw;
-  const float* dka = a.delta + (int64_t)ka * CD * splane;
-  const float* dkb = a.delta + (int64_t)kb * CD * splane;
-  const float* hml = a.hmap_lowres ? a.hmap_lowres + (int64_t)f * splane : nullptr;
   __syncthreads();                                             // s_xlo / s_xhi, word stage of group -1
   const int wx0 = s_xlo, dww = s_xhi - s_xlo;
 
@@ -1051,11 +999,18 @@ YuvSurf dev_surface(const SURFACE& s) {
   return d;
 }
 
-// the arguments of a resize launch after the checks every entry point applies, in the order vs_resize_pre_yuv420 has always applied them
-struct ResizeCall {
-  YuvSurf s; int B, H, W; Nv12Mat dec; int oh, ow, antialias; float* dst_rgb; float mul, add; float* dst_y; int ks, key_mode; float y0, y1, y2;
-  hipStream_t st; int fmt;
+// the kernels of one surface trait, for launch_resize / launch_tail (shell_common.h)
+template <class SF>
+struct YuvKernels {
+  static constexpr int ALIGN = yuv_rs_align<SF>();
+  template <int OW> static auto resize_stream() { return resize_pre_yuv_stream_kernel<SF, OW>; }
+  static auto resize_tile() { return resize_pre_yuv_kernel<SF>; }
+  template <bool JND, int CD> static auto tail_stream() { return embed_tail_yuv_stream_kernel<SF, JND, CD>; }
+  static auto tail_tile() { return embed_tail_yuv_kernel<SF>; }
 };
+
+// the arguments of a resize launch after the checks every entry point applies, in the order vs_resize_pre_yuv420 has always applied them
+struct ResizeCall { YuvSurf s; Nv12Mat dec; int B, H, W, oh, ow, antialias; ResizeOut o; hipStream_t st; int fmt; };
 template <class SURFACE>
 int prep_resize(const SURFACE* src, int sx, int sy, int B, int H, int W, const float* yuv2rgb12, int oh, int ow, int antialias, float* dst_rgb,
                 float mul, float add, float* dst_y, int y_step, const float* ymat3, void* stream, ResizeCall& c) {
@@ -1065,92 +1020,32 @@ int prep_resize(const SURFACE* src, int sx, int sy, int B, int H, int W, const f
   const int fmt = surface_format(*src);
   if (fmt < 0) return VS_ERR_UNSUPPORTED;
   VS_REQUIRE(surface_ok(*src, sx, sy, B, H, W));
-  c = ResizeCall{dev_surface(*src), B, H, W, {}, oh, ow, antialias, dst_rgb, mul, add, dst_y, y_step < 1 ? 1 : y_step, ymat3 ? 0 : 1,
-                 ymat3 ? ymat3[0] : 0.f, ymat3 ? ymat3[1] : 0.f, ymat3 ? ymat3[2] : 0.f, (hipStream_t)stream, fmt};
+  c = ResizeCall{dev_surface(*src), {}, B, H, W, oh, ow, antialias, resize_out(dst_rgb, mul, add, dst_y, y_step, ymat3), (hipStream_t)stream, fmt};
   for (int i = 0; i < 12; ++i) c.dec.m[i] = yuv2rgb12[i];
   return VS_OK;
 }
 
 // ... and of a tail launch (vs_embed_tail_yuv420's checks in its order)
-struct TailCall { TailArgs a; JndTaps k; YuvGeo g; bool sf, full_jnd; hipStream_t st; int fmt; };
+struct TailCall { TailForm t; YuvGeo g; hipStream_t st; int fmt; };
 template <class DESC>
 int prep_tail(const DESC* d, int sx, int sy, void* stream, TailCall& c) {
   VS_REQUIRE(d && d->delta && d->F > 0 && d->H > 0 && d->W > 0 && d->S_h > 0 && d->S_w > 0);
-  VS_REQUIRE((d->Cd == 1 || d->Cd == 3) && d->step >= 1 && d->total_key >= 1);
-  VS_REQUIRE(d->video_mode >= 0 && d->video_mode <= 2);
+  if (const int rc = tail_desc_numbers(d); rc != VS_OK) return rc;
   VS_REQUIRE(!(d->H & ((1 << sy) - 1)) && !(d->W & ((1 << sx) - 1)) && d->clamp);        // codes are only defined for values in [0, 1]
   const int fmt = surface_format(d->src);
   if (fmt < 0 || surface_format(d->dst) != fmt) return VS_ERR_UNSUPPORTED;
   VS_REQUIRE(surface_ok(d->src, sx, sy, d->F, d->H, d->W) && surface_ok(d->dst, sx, sy, d->F, d->H, d->W));
-  if (d->preds_w || d->attenuate == 2 || (d->variant != 0 && d->variant != 1 && d->variant != 4)) return VS_ERR_UNSUPPORTED;
-  VS_REQUIRE(!(d->attenuate && !d->hmap_lowres) || d->taps43);
-  c.a = TailArgs{nullptr, nullptr, nullptr, d->delta, d->attenuate ? d->hmap_lowres : nullptr, d->F, d->H, d->W, d->S_h, d->S_w,
-                 d->Cd, d->step, d->video_mode, d->total_key, d->attenuate, d->clamp, d->antialias, d->scaling_i, d->scaling_w};
-  c.k = JndTaps{};
-  if (d->taps43) c.k = taps_from(d->taps43);
+  if (const int rc = tail_desc_form(d, c.t); rc != VS_OK) return rc;
   c.g = YuvGeo{dev_surface(d->src), dev_surface(d->dst), {}, {}};
   for (int i = 0; i < 12; ++i) { c.g.dec.m[i] = d->yuv2rgb12[i]; c.g.enc.m[i] = d->rgb2yuv12[i]; }
-  // row-streaming form (default) where vs_embed_tail's applies, the 16-row tile form elsewhere and with variant = 1
-  c.full_jnd = d->attenuate && !d->hmap_lowres;
-  const bool can_stream = tail_can_stream(c.full_jnd, d->taps43, d->H, d->W, d->S_h, d->S_w);
-  if (d->variant == 4 && !can_stream) return VS_ERR_UNSUPPORTED;
-  c.sf = d->variant != 1 && can_stream;
   c.st = (hipStream_t)stream;
   c.fmt = fmt;
   return VS_OK;
 }
 
 template <class SF>
-int launch_resize(const YuvSurf& s, int B, int H, int W, const Nv12Mat& dec, int oh, int ow, int antialias, float* dst_rgb, float mul, float add,
-                  float* dst_y, int y_step, int key_mode, float y0, float y1, float y2, hipStream_t st) {
-  // row-streaming form where its windows fit (the development switches of vs_resize_pre apply: form, strip height), the tile form elsewhere
-  const int OWsel = yuv_rs_pick(H, W, oh, ow, antialias, SF::CW > 16 ? SF::CW : 16);
-  if (vs_debug_get(VS_DBG_RESIZE_FORM) != 1 && OWsel) {
-    const int cols = (ow + OWsel - 1) / OWsel;
-    // tallest strip that still launches ~512 workgroups (two per CU), down to 8 rows for the 8-frame launches of detect: the fastest height of
-    // every batch size in `tools/bench_nv12.py --sweep` (profiles/nv12_resize_strip_sweep.json)
-    int strip = 8;
-    for (int cand : {64, 48, 32, 24, 16, 12})
-      if ((int64_t)cols * ((oh + cand - 1) / cand) * B >= 512) { strip = cand; break; }
-    if (const int v = vs_debug_get(VS_DBG_RESIZE_STRIP); v >= 1) strip = v;
-    dim3 gs(cols, (oh + strip - 1) / strip, B);
-    const size_t lds = OWsel == 128 ? vs_rs::rs_lds_bytes<128>() : vs_rs::rs_lds_bytes<64>();
-    const ResizePreEpi epi{dst_rgb, dst_y, mul, add, y_step, key_mode, y0, y1, y2, oh, ow};
-    if ((int64_t)lds <= vs_max_lds_bytes()) {
-      if (OWsel == 128) hipLaunchKernelGGL((resize_pre_yuv_stream_kernel<SF, 128>), gs, dim3(256), lds, st, s, H, W, dec, oh, ow, antialias, epi, strip);
-      else hipLaunchKernelGGL((resize_pre_yuv_stream_kernel<SF, 64>), gs, dim3(256), lds, st, s, H, W, dec, oh, ow, antialias, epi, strip);
-      return vs_launch_status();
-    }
-  }
-  dim3 grid((ow + 31) / 32, (oh + 7) / 8, B);
-  hipLaunchKernelGGL(resize_pre_yuv_kernel<SF>, grid, dim3(256), 0, st, s, B, H, W, dec, oh, ow, antialias, dst_rgb, mul, add, dst_y, y_step,
-                     key_mode, y0, y1, y2);
-  return vs_launch_status();
-}
-
+int run_resize(const ResizeCall& c) { return launch_resize<YuvKernels<SF>>(c.B, c.H, c.W, c.oh, c.ow, c.antialias, c.o, c.st, c.s, c.dec); }
 template <class SF>
-int launch_tail(const TailArgs& a, const JndTaps& k, const YuvGeo& g, bool stream_form, bool full_jnd, hipStream_t st) {
-  if (stream_form) {
-    const int strip = tail_strip(full_jnd, a.F, a.H, a.W);
-    dim3 gs((a.W + TTW - 1) / TTW, (a.H + strip - 1) / strip, a.F);
-    const size_t lds_w = (size_t)2 * a.Cd * DW_W * DW_H * sizeof(float);
-    const size_t lds_j = lds_w + RING * TLW * sizeof(float);
-    if (full_jnd && a.Cd == 1) hipLaunchKernelGGL((embed_tail_yuv_stream_kernel<SF, true, 1>), gs, dim3(256), lds_j, st, a, k, g, strip);
-    else if (full_jnd) hipLaunchKernelGGL((embed_tail_yuv_stream_kernel<SF, true, 3>), gs, dim3(256), lds_j, st, a, k, g, strip);
-    else if (a.Cd == 1) hipLaunchKernelGGL((embed_tail_yuv_stream_kernel<SF, false, 1>), gs, dim3(256), lds_w, st, a, k, g, strip);
-    else hipLaunchKernelGGL((embed_tail_yuv_stream_kernel<SF, false, 3>), gs, dim3(256), lds_w, st, a, k, g, strip);
-    return vs_launch_status();
-  }
-  dim3 grid((a.W + TTW - 1) / TTW, (a.H + TTH - 1) / TTH, a.F);
-  hipLaunchKernelGGL(embed_tail_yuv_kernel<SF>, grid, dim3(256), 0, st, a, k, g);
-  return vs_launch_status();
-}
-
-template <class SF>
-int run_resize(const ResizeCall& c) {
-  return launch_resize<SF>(c.s, c.B, c.H, c.W, c.dec, c.oh, c.ow, c.antialias, c.dst_rgb, c.mul, c.add, c.dst_y, c.ks, c.key_mode, c.y0, c.y1, c.y2, c.st);
-}
-template <class SF>
-int run_tail(const TailCall& c) { return launch_tail<SF>(c.a, c.k, c.g, c.sf, c.full_jnd, c.st); }
+int run_tail(const TailCall& c) { return launch_tail<YuvKernels<SF>>(c.t.a, c.t.k, c.g, c.t.stream_form, c.t.full_jnd, c.st); }
 
 }  // namespace

@@ -17,7 +17,7 @@ import ctypes as C
 import math
 import os
 from dataclasses import dataclass
-from typing import Dict, List, Optional, Tuple
+from typing import Callable, Dict, List, NamedTuple, Optional, Tuple
 
 import torch
 
@@ -30,6 +30,16 @@ def rup(x: int, m: int) -> int:
 
 
 TUNED_TILES = os.path.join(os.path.dirname(os.path.abspath(__file__)), "tuned_tiles_gfx950.json")
+
+
+class _SurfaceRoute(NamedTuple):
+    """what differs between the clip classes on the way to the shell kernels (HipEngine._surface_route)"""
+    kind: str                  # entry points vs_resize_pre_<kind> / vs_embed_tail_<kind>, timer labels <phase>_<kind>_kernel<fmt>
+    what: str                  # the clip class in messages
+    surface: Callable          # clip -> its ctypes surface (addresses, pitches, format: nothing is copied)
+    desc: type                 # ctypes class of the tail descriptor
+    frame_bytes: int           # algorithmic bytes of one frame
+    affines: Optional[tuple]   # (yuv2rgb12, rgb2yuv12) where the kernels convert colours: an extra resize argument, two descriptor members
 
 
 @dataclass
@@ -1522,33 +1532,44 @@ class HipEngine:
         from .rgbpack import Clip
         return isinstance(x, Clip)
 
-    def _resize_pre_yuv(self, clip, S, antialias, *, want_rgb, mul, add, want_key, key_step, tag):
-        """resize_pre on a YUV clip of any of the ten formats (a 4:2:0 one reaches the _yuv420 launches through the library's forwarder)"""
-        B, H, W = clip.shape
+    def _surface_route(self, clip) -> "_SurfaceRoute":
+        """how a non-tensor frames argument reaches the library: a packed RGB clip (rgbpack.Clip: one tensor at any pitch, twelve formats) or
+        a YUV clip of any of the ten formats (a 4:2:0 one reaches the _yuv420 launches through the library's forwarder)"""
+        _, H, W = clip.shape
+        if self._rgb_clip(clip):
+            from .rgbpack import pixel_bytes
+            return _SurfaceRoute("rgb", "packed RGB", lambda c: N.rgb_surface(c.tensor, c.fmt), N.TailRgbDesc, H * W * pixel_bytes(clip.fmt), None)
         depth, nsamp = self._yuv_clip(clip)
+        return _SurfaceRoute("yuv", "YUV", lambda c: N.yuv_surface(c.planes, c.fmt), N.TailYuvDesc, nsamp * clip.planes[0].element_size(),
+                             self.yuv_arrays(clip.color, depth))
+
+    def _resize_pre_surface(self, clip, S, antialias, *, want_rgb, mul, add, want_key, key_step, tag):
+        """resize_pre on a YUV or packed RGB clip: the decode is fused into the kernel"""
+        r = self._surface_route(clip)
+        B, H, W = clip.shape
         rgb = self.new_act(tag + ".rgb", B, S[0], S[1], 3, 4) if want_rgb else None
         nk = (B + key_step - 1) // key_step
         key = self.new_act(tag + ".key", nk, S[0], S[1], self.cfg.in_ch, 4) if want_key else None
-        surf = N.yuv_surface(clip.planes, clip.fmt)
+        surf = r.surface(clip)
+        entry = f"vs_resize_pre_{r.kind}"
         ev = self._shell_t0()
-        N.check(self.lib.vs_resize_pre_yuv(C.byref(surf), B, H, W, self.yuv_arrays(clip.color, depth)[0], S[0], S[1], 1 if antialias else 0,
-                                           N.ptr(rgb.t) if rgb else None, mul, add, N.ptr(key.t) if key else None, key_step,
-                                           self.ymat if self.cfg.yuv else None, N.stream()), "vs_resize_pre_yuv")
-        # algorithmic HBM bytes: the frame's samples (1.5, 2 or 3 per pixel) once + the low-resolution outputs
-        self._shell_t1(ev, f"resize_pre_yuv_kernel<{clip.fmt}>",
-                       B * nsamp * clip.planes[0].element_size() + 16 * S[0] * S[1] * ((B if rgb else 0) + (nk if key else 0)))
+        N.check(getattr(self.lib, entry)(C.byref(surf), B, H, W, *(r.affines[:1] if r.affines else ()), S[0], S[1], 1 if antialias else 0,
+                                         N.ptr(rgb.t) if rgb else None, mul, add, N.ptr(key.t) if key else None, key_step,
+                                         self.ymat if self.cfg.yuv else None, N.stream()), entry)
+        # algorithmic HBM bytes: the frame's samples or pixels once + the low-resolution outputs
+        self._shell_t1(ev, f"resize_pre_{r.kind}_kernel<{clip.fmt}>", B * r.frame_bytes + 16 * S[0] * S[1] * ((B if rgb else 0) + (nk if key else 0)))
         return rgb, key
 
-    def _embed_tail_yuv(self, clip, out, delta, *, step, video_mode, hmap_low, attenuate, clamp, antialias, scaling_i, scaling_w, preds_w=None):
-        """embed_tail on YUV clips: `clip` and `out` are yuv.Clip of one format and size, each plane with its own pitch"""
-        depth, nsamp = self._yuv_clip(clip)
+    def _embed_tail_surface(self, clip, out, delta, *, step, video_mode, hmap_low, attenuate, clamp, antialias, scaling_i, scaling_w, preds_w=None):
+        """embed_tail on YUV or packed RGB clips: `clip` and `out` are clips of one class, format and size, each at its own pitch(es)"""
+        r = self._surface_route(clip)
         if type(out) is not type(clip) or out.fmt != clip.fmt or out.shape != clip.shape:
-            raise ValueError("YUV frames need an output clip of the same format and size")
+            raise ValueError(f"{r.what} frames need an output clip of the same format and size")
         if preds_w is not None or int(attenuate) == 2:
-            raise NotImplementedError("the YUV tail has no preds_w and no training order of operations")
+            raise NotImplementedError(f"the {r.what} tail has no preds_w and no training order of operations")
         F_, H, W = clip.shape
-        d = N.TailYuvDesc()
-        d.src, d.dst = N.yuv_surface(clip.planes, clip.fmt), N.yuv_surface(out.planes, out.fmt)
+        d = r.desc()
+        d.src, d.dst = r.surface(clip), r.surface(out)
         d.preds_w = None
         d.delta, d.hmap_lowres = N.ptr(delta), N.ptr(hmap_low)
         d.taps43 = C.cast(self.taps43, C.c_void_p)
@@ -1557,61 +1578,20 @@ class HipEngine:
         d.attenuate, d.clamp, d.antialias = int(attenuate), int(clamp), int(antialias)
         d.scaling_i, d.scaling_w = float(scaling_i), float(scaling_w)
         d.variant = 1 if int(self.tail_variant) in (1, 2, 3) else 0           # (the tile variants of the fp32 tail -> the tile kernel)
-        d.yuv2rgb12, d.rgb2yuv12 = self.yuv_arrays(clip.color, depth)
+        if r.affines:
+            d.yuv2rgb12, d.rgb2yuv12 = r.affines
+        entry = f"vs_embed_tail_{r.kind}"
         ev = self._shell_t0()
-        N.check(self.lib.vs_embed_tail_yuv(C.byref(d), N.stream()), "vs_embed_tail_yuv")
-        # algorithmic HBM bytes: the frame's samples (1.5, 2 or 3 per pixel) each way + the low-resolution watermark
-        self._shell_t1(ev, f"embed_tail_yuv_kernel<{clip.fmt}>", 2 * (F_ * nsamp) * clip.planes[0].element_size() + delta.numel() * 4)
-
-    # ---- packed RGB clips (videoseal_amd/rgbpack.py): one tensor at any pitch, twelve formats
-    def _resize_pre_rgb(self, clip, S, antialias, *, want_rgb, mul, add, want_key, key_step, tag):
-        """resize_pre on a packed RGB clip (rgbpack.Clip): the decode is fused into the kernel"""
-        from .rgbpack import pixel_bytes
-        B, H, W = clip.shape
-        rgb = self.new_act(tag + ".rgb", B, S[0], S[1], 3, 4) if want_rgb else None
-        nk = (B + key_step - 1) // key_step
-        key = self.new_act(tag + ".key", nk, S[0], S[1], self.cfg.in_ch, 4) if want_key else None
-        surf = N.rgb_surface(clip.tensor, clip.fmt)
-        ev = self._shell_t0()
-        N.check(self.lib.vs_resize_pre_rgb(C.byref(surf), B, H, W, S[0], S[1], 1 if antialias else 0, N.ptr(rgb.t) if rgb else None, mul, add,
-                                           N.ptr(key.t) if key else None, key_step, self.ymat if self.cfg.yuv else None, N.stream()),
-                "vs_resize_pre_rgb")
-        # algorithmic HBM bytes: the frame's pixels once + the low-resolution outputs
-        self._shell_t1(ev, f"resize_pre_rgb_kernel<{clip.fmt}>",
-                       B * H * W * pixel_bytes(clip.fmt) + 16 * S[0] * S[1] * ((B if rgb else 0) + (nk if key else 0)))
-        return rgb, key
-
-    def _embed_tail_rgb(self, clip, out, delta, *, step, video_mode, hmap_low, attenuate, clamp, antialias, scaling_i, scaling_w, preds_w=None):
-        """embed_tail on packed RGB clips: `clip` and `out` are rgbpack.Clip of one format and size, each at its own pitch"""
-        from .rgbpack import pixel_bytes
-        if type(out) is not type(clip) or out.fmt != clip.fmt or out.shape != clip.shape:
-            raise ValueError("packed RGB frames need an output clip of the same format and size")
-        if preds_w is not None or int(attenuate) == 2:
-            raise NotImplementedError("the packed RGB tail has no preds_w and no training order of operations")
-        F_, H, W = clip.shape
-        d = N.TailRgbDesc()
-        d.src, d.dst = N.rgb_surface(clip.tensor, clip.fmt), N.rgb_surface(out.tensor, out.fmt)
-        d.preds_w = None
-        d.delta, d.hmap_lowres = N.ptr(delta), N.ptr(hmap_low)
-        d.taps43 = C.cast(self.taps43, C.c_void_p)
-        d.F, d.H, d.W, d.S_h, d.S_w, d.Cd = F_, H, W, delta.shape[-2], delta.shape[-1], delta.shape[1]
-        d.step, d.video_mode, d.total_key = step, video_mode, delta.shape[0]
-        d.attenuate, d.clamp, d.antialias = int(attenuate), int(clamp), int(antialias)
-        d.scaling_i, d.scaling_w = float(scaling_i), float(scaling_w)
-        d.variant = 1 if int(self.tail_variant) in (1, 2, 3) else 0           # (the tile variants of the fp32 tail -> the tile kernel)
-        ev = self._shell_t0()
-        N.check(self.lib.vs_embed_tail_rgb(C.byref(d), N.stream()), "vs_embed_tail_rgb")
-        # algorithmic HBM bytes: the frame's pixels each way + the low-resolution watermark
-        self._shell_t1(ev, f"embed_tail_rgb_kernel<{clip.fmt}>", 2 * F_ * H * W * pixel_bytes(clip.fmt) + delta.numel() * 4)
+        N.check(getattr(self.lib, entry)(C.byref(d), N.stream()), entry)
+        # algorithmic HBM bytes: the frame's samples or pixels each way + the low-resolution watermark
+        self._shell_t1(ev, f"embed_tail_{r.kind}_kernel<{clip.fmt}>", 2 * F_ * r.frame_bytes + delta.numel() * 4)
 
     def resize_pre(self, imgs: torch.Tensor, S: Tuple[int, int], antialias: bool, *, want_rgb: bool, mul=1.0, add=0.0,
                    want_key: bool = False, key_step: int = 1, tag="rs") -> Tuple[Optional[Act], Optional[Act]]:
         """imgs on device, fp32 NCHW [B,3,H,W], uint8 RGB24 [B,H,W,3], a YUV clip (yuv.Clip) or a packed RGB clip (rgbpack.Clip)
         -> (rgb Act [B,S,S,4] or None, key Act [ceil(B/step),S,S,4] or None)."""
-        if self._rgb_clip(imgs):
-            return self._resize_pre_rgb(imgs, S, antialias, want_rgb=want_rgb, mul=mul, add=add, want_key=want_key, key_step=key_step, tag=tag)
-        if not torch.is_tensor(imgs):         # a YUV clip carries its own format and colour choice
-            return self._resize_pre_yuv(imgs, S, antialias, want_rgb=want_rgb, mul=mul, add=add, want_key=want_key, key_step=key_step, tag=tag)
+        if not torch.is_tensor(imgs):         # a YUV or packed RGB clip carries its own format (and colour choice)
+            return self._resize_pre_surface(imgs, S, antialias, want_rgb=want_rgb, mul=mul, add=add, want_key=want_key, key_step=key_step, tag=tag)
         u8 = imgs.dtype == torch.uint8
         if u8:
             B, H, W, Cc = imgs.shape
@@ -1804,12 +1784,9 @@ class HipEngine:
         """frame_scale (fp32 [F] on the device, fp32 NCHW / uint8 RGB24 frames only): the strength of frame f instead of scaling_w"""
         if frame_scale is not None and not torch.is_tensor(imgs):
             raise NotImplementedError("per-frame strengths cover fp32 NCHW and uint8 RGB24 frames")
-        if self._rgb_clip(imgs):
-            return self._embed_tail_rgb(imgs, out, delta, step=step, video_mode=video_mode, hmap_low=hmap_low, attenuate=attenuate, clamp=clamp,
-                                        antialias=antialias, scaling_i=scaling_i, scaling_w=scaling_w, preds_w=preds_w)
-        if not torch.is_tensor(imgs):         # a YUV clip (yuv.Clip)
-            return self._embed_tail_yuv(imgs, out, delta, step=step, video_mode=video_mode, hmap_low=hmap_low, attenuate=attenuate, clamp=clamp,
-                                        antialias=antialias, scaling_i=scaling_i, scaling_w=scaling_w, preds_w=preds_w)
+        if not torch.is_tensor(imgs):         # a YUV clip (yuv.Clip) or a packed RGB clip (rgbpack.Clip)
+            return self._embed_tail_surface(imgs, out, delta, step=step, video_mode=video_mode, hmap_low=hmap_low, attenuate=attenuate, clamp=clamp,
+                                            antialias=antialias, scaling_i=scaling_i, scaling_w=scaling_w, preds_w=preds_w)
         d, u8 = self._tail_desc(imgs, out, delta, step=step, video_mode=video_mode, hmap_low=hmap_low, attenuate=attenuate, clamp=clamp,
                                 antialias=antialias, scaling_i=scaling_i, scaling_w=scaling_w, preds_w=preds_w)
         if frame_scale is not None and (frame_scale.dtype != torch.float32 or frame_scale.numel() != d.F or not frame_scale.is_contiguous()):
