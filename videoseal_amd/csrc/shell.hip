@@ -7,6 +7,7 @@
 #include "images_plan.h"
 #include "clips_plan.h"
 #include "videoseal_regions.h"
+#include "videoseal_lists_psnr.h"
 #include <cmath>
 #include <type_traits>
 
@@ -42,6 +43,8 @@ __device__ __forceinline__ float tail_strength(const Args& a, const int f) {
 }
 
 // the workgroup's partial of a clip kernel (grid = tile columns x tile rows x frames): lanes, then the four waves, in a fixed order
+// (FLAT: the list kernels, whose grid is a flat run of (item, tile) workgroups -- the slot is the workgroup's place in that run)
+template <bool FLAT = false>
 __device__ __forceinline__ void tail_energy_store(const double e, double* __restrict__ partials, const int f) {
   __shared__ double red[4];
   double v = e;
@@ -49,7 +52,8 @@ __device__ __forceinline__ void tail_energy_store(const double e, double* __rest
   for (int o = 32; o >= 1; o >>= 1) v += __shfl_down(v, o, 64);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
   __syncthreads();
-  if (threadIdx.x == 0) partials[((int64_t)f * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
+  if (threadIdx.x == 0)
+    partials[FLAT ? (int64_t)blockIdx.x : ((int64_t)f * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
 }
 
 // ---- frame element access: fp32 NCHW planes, or uint8 RGB24 (HWC, what inference_streaming.py:26 reads from the ffmpeg
@@ -291,7 +295,7 @@ __global__ __launch_bounds__(256) void jnd_heatmap_kernel(const float* __restric
 // hmap_lowres.  All of them workgroup-uniform: blockIdx for a clip (embed_tail_kernel), a table look-up for a list of images, each with its
 // own a.H x a.W (the *_images kernels below).)
 // REGIONS: `region` is the label this pass blends, bit ly of `sel` says that row ly of this thread's column carries it; nothing else is stored.
-template <typename T, bool SEP, int TH, bool KEEP, int MODE = TAIL_BLEND, class Args = tail_args_t<MODE>>
+template <typename T, bool SEP, int TH, bool KEEP, int MODE = TAIL_BLEND, class Args = tail_args_t<MODE>, bool FLAT = false>
 __device__ __forceinline__ void embed_tail_tile(const Args& a, const JndTaps& k, const int x0, const int y0, const int f,
                                                 const T* __restrict__ img, T* __restrict__ outf, float* __restrict__ predf,
                                                 const int region = 0, const unsigned sel = 0) {
@@ -506,7 +510,7 @@ __device__ __forceinline__ void embed_tail_tile(const Args& a, const JndTaps& k,
       }
     }
   }
-  if constexpr (MODE == TAIL_ENERGY) tail_energy_store(e, a.partials, f);      // (clip kernel only: the slot is the workgroup's place in the grid)
+  if constexpr (MODE == TAIL_ENERGY) tail_energy_store<FLAT>(e, a.partials, f);      // (the slot is the workgroup's place in the grid)
 }
 
 template <typename T, bool SEP, int TH, bool KEEP, int MODE = TAIL_BLEND>
@@ -850,7 +854,7 @@ struct ImagesArgs {
   int pad_;
   ImgSlot slot[VS_IMAGES_PER_LAUNCH];
 };
-static_assert(sizeof(ImagesArgs) + sizeof(TailArgs) + sizeof(JndTaps) <= 3072, "descriptors + tail arguments stay well inside the 4 KiB of kernel arguments");
+static_assert(sizeof(ImagesArgs) + sizeof(TailArgsX) + sizeof(JndTaps) <= 3072, "descriptors + tail arguments (every mode) stay well inside the 4 KiB of kernel arguments");
 
 // the image (or clip slot) of workgroup wg: the last k with first_wg[k] <= wg
 template <class Args>
@@ -887,16 +891,19 @@ __global__ __launch_bounds__(256) void resize_pre_images_stream_kernel(const Ima
                                 g.slot[k].frame);
 }
 
-template <typename T, bool SEP>
-__global__ __launch_bounds__(256) void embed_tail_images_kernel(const ImagesArgs g, TailArgs a, const JndTaps k) {
+// MODE (vs_embed_tail_images_scaled / _energy, videoseal_lists_psnr.h): SCALED reads the strength of the image at frame_scale[its index in the
+// caller's list] -- the body's frame number, a scalar load; ENERGY writes the workgroup's partial at partials[blockIdx.x], the launch's flat
+// grid (the launcher moves `partials` to the launch's first slot), and stores no image.
+template <typename T, bool SEP, int MODE = TAIL_BLEND>
+__global__ __launch_bounds__(256) void embed_tail_images_kernel(const ImagesArgs g, tail_args_t<MODE> a, const JndTaps k) {
   const int i = images_find(g, blockIdx.x);
   const int t = blockIdx.x - g.first_wg[i];
   const int cols = g.slot[i].cols;
   const int by = t / cols, bx = t - by * cols;
   a.H = g.slot[i].H;
   a.W = g.slot[i].W;
-  embed_tail_tile<T, SEP, TTH, false>(a, k, bx * TTW, by * TTH, g.slot[i].frame, static_cast<const T*>(g.slot[i].img),
-                                      static_cast<T*>(g.slot[i].out), g.slot[i].preds_w);
+  embed_tail_tile<T, SEP, TTH, false, MODE, tail_args_t<MODE>, true>(a, k, bx * TTW, by * TTH, g.slot[i].frame, static_cast<const T*>(g.slot[i].img),
+                                                                     static_cast<T*>(g.slot[i].out), g.slot[i].preds_w);
 }
 
 // kernel arguments of one group of the plan
@@ -926,7 +933,7 @@ struct ClipsArgs {
   int pad_;
   ClipSlot slot[VS_IMAGES_PER_LAUNCH];
 };
-static_assert(sizeof(ClipsArgs) + sizeof(TailArgs) + sizeof(JndTaps) <= 3072, "descriptors + tail arguments stay well inside the 4 KiB of kernel arguments");
+static_assert(sizeof(ClipsArgs) + sizeof(TailArgsX) + sizeof(JndTaps) <= 3072, "descriptors + tail arguments (every mode) stay well inside the 4 KiB of kernel arguments");
 static_assert(sizeof(ClipsArgs) + sizeof(ResizePreEpi) <= 3072, "descriptors + resize epilogue stay well inside the 4 KiB of kernel arguments");
 
 // (slot k, frame f of it, tile column bx, tile row by) of workgroup wg
@@ -967,8 +974,10 @@ __global__ __launch_bounds__(256) void resize_pre_clips_stream_kernel(const Clip
                                 strip, epi, bx, by, f);
 }
 
-template <typename T, bool SEP>
-__global__ __launch_bounds__(256) void embed_tail_clips_kernel(const ClipsArgs g, TailArgs a, const JndTaps k) {
+// MODE (vs_embed_tail_clips_scaled / _energy): SCALED moves frame_scale to the slot's first frame, as hmap_lowres is moved, so the body's
+// frame_scale[f] is the caller's frame_scale[first_frame + f]; ENERGY as in embed_tail_images_kernel, one partial per workgroup of the flat grid.
+template <typename T, bool SEP, int MODE = TAIL_BLEND>
+__global__ __launch_bounds__(256) void embed_tail_clips_kernel(const ClipsArgs g, tail_args_t<MODE> a, const JndTaps k) {
   int i, f, bx, by;
   clips_item(g, blockIdx.x, i, f, bx, by);
   a.F = g.slot[i].F;
@@ -978,9 +987,11 @@ __global__ __launch_bounds__(256) void embed_tail_clips_kernel(const ClipsArgs g
   const int64_t splane = (int64_t)a.Sh * a.Sw, plane = (int64_t)a.H * a.W;
   a.delta += g.slot[i].first_key * splane * a.Cd;
   if (a.hmap_lowres) a.hmap_lowres += g.slot[i].first_frame * splane;
-  embed_tail_tile<T, SEP, TTH, false>(a, k, bx * TTW, by * TTH, f, static_cast<const T*>(g.slot[i].frames) + f * 3 * plane,
-                                      static_cast<T*>(g.slot[i].out) + f * 3 * plane,
-                                      g.slot[i].preds_w ? g.slot[i].preds_w + f * a.Cd * plane : nullptr);
+  if constexpr (MODE == TAIL_SCALED) a.frame_scale += g.slot[i].first_frame;
+  embed_tail_tile<T, SEP, TTH, false, MODE, tail_args_t<MODE>, true>(a, k, bx * TTW, by * TTH, f,
+                                                                     static_cast<const T*>(g.slot[i].frames) + f * 3 * plane,
+                                                                     static_cast<T*>(g.slot[i].out) + f * 3 * plane,
+                                                                     g.slot[i].preds_w ? g.slot[i].preds_w + f * a.Cd * plane : nullptr);
 }
 
 // kernel arguments of one group of the plan
@@ -998,6 +1009,71 @@ inline ClipsArgs clips_args(const vs_clip_desc_t* clips, const vs_images_group_t
                          (int)vs_images_tiles(kind, grp.form, grp.strip, d.H, d.W, oh, ow)};
   }
   return g;
+}
+
+// ---------------------------------------------------------------------------------------------------
+// Target PSNR on the lists (videoseal_lists_psnr.h).  The energy pass of a launch group leaves one partial per workgroup in the group's run of
+// `partials`; one finish launch per group adds the partials of every item of the group: an image owns [first_wg[k], first_wg[k + 1]), frame f
+// of a clip slot owns [first_wg[k] + f * tiles, + tiles).  One wave per item, lane l adds partials l, l + 64, ... in that order, then the
+// lanes in a fixed tree (tail_energy_finish_kernel's order): no atomics, every slot of a range was written by the pass before it is read.
+struct ListFinishArgs {
+  int first_wg[VS_IMAGES_PER_LAUNCH];      // first partial of item k of the group
+  int frames[VS_IMAGES_PER_LAUNCH];        // 1 for an image
+  int tiles[VS_IMAGES_PER_LAUNCH];         // partials per frame
+  int dst[VS_IMAGES_PER_LAUNCH];           // energy[dst + f]: the image's index in the list, the slot's first_frame
+};
+static_assert(sizeof(ListFinishArgs) <= 3072, "the finish kernel's table travels in the kernel arguments");
+
+// grid = (most frames of an item of the group, items of the group)
+__global__ __launch_bounds__(64) void tail_list_energy_finish_kernel(const ListFinishArgs g, const double* __restrict__ partials, const double mul,
+                                                                     double* __restrict__ energy) {
+  const int k = blockIdx.y, f = blockIdx.x;
+  if (f >= g.frames[k]) return;
+  const int n = g.tiles[k];
+  const double* p = partials + g.first_wg[k] + (int64_t)f * n;
+  double v = 0.0;
+  for (int i = threadIdx.x; i < n; i += 64) v += p[i];
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) v += __shfl_down(v, o, 64);
+  if (threadIdx.x == 0) energy[g.dst[k] + f] = mul * v;
+}
+
+// scale[i] = amp * sqrt(n_g / E_g) in float64, rounded once: E_g, n_g the sums of energy / elems over the items of i's group, added in index
+// order by one thread (the values come through LDS 256 at a time, so the loads of a long group are not a dependent chain).  One workgroup per
+// group [first_item[g], first_item[g + 1]); an empty group writes nothing.
+__global__ __launch_bounds__(256) void psnr_scale_groups_kernel(const double* __restrict__ energy, const double* __restrict__ elems,
+                                                                const int* __restrict__ first_item, const int n_items, const double amp,
+                                                                const float max_scale, float* __restrict__ scale) {
+  __shared__ double s_e[256], s_n[256], s_E, s_N;
+  // (workgroup-uniform; held inside [0, n_items]: a prefix that is wrong on the device must not turn into an access outside the arrays)
+  const int lo = max(0, first_item[blockIdx.x]), hi = min(n_items, first_item[blockIdx.x + 1]);
+  double E = 0.0, n = 0.0;
+  for (int base = lo; base < hi; base += 256) {
+    const int i = base + (int)threadIdx.x;
+    if (i < hi) { s_e[threadIdx.x] = energy[i]; s_n[threadIdx.x] = elems[i]; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      const int m = min(256, hi - base);
+      for (int j = 0; j < m; ++j) { E += s_e[j]; n += s_n[j]; }
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) { s_E = E; s_N = n; }
+  __syncthreads();
+  const double Eg = s_E, ng = s_N;
+  const double s = Eg == 0.0 ? 0.0 : amp * sqrt(ng / Eg);
+  const float r = (max_scale > 0.f && s > (double)max_scale) ? max_scale : (float)s;
+  for (int i = lo + (int)threadIdx.x; i < hi; i += 256) scale[i] = r;
+}
+
+// (first_item == NULL: every item is a group of its own)
+__global__ __launch_bounds__(256) void psnr_scale_items_kernel(const double* __restrict__ energy, const double* __restrict__ elems, const int n_items,
+                                                               const double amp, const float max_scale, float* __restrict__ scale) {
+  const int i = blockIdx.x * 256 + (int)threadIdx.x;
+  if (i >= n_items) return;
+  const double E = energy[i];
+  const double s = E == 0.0 ? 0.0 : amp * sqrt(elems[i] / E);
+  scale[i] = (max_scale > 0.f && s > (double)max_scale) ? max_scale : (float)s;
 }
 
 }  // namespace
@@ -1238,30 +1314,82 @@ extern "C" int vs_resize_pre_images(const vs_image_desc_t* images, int n, int io
   });
 }
 
-extern "C" int vs_embed_tail_images(const vs_tail_images_desc_t* d, void* stream) {
+namespace {
+
+// The one dispatch of the image-list tail for its three modes (vs_embed_tail_images, vs_embed_tail_images_scaled, vs_embed_tail_images_energy):
+// the same checks, the same plan and the same choice of stencils, so the energy pass and the scaled tail compute the d of the tail they stand
+// beside.  ENERGY: the partials of a launch group follow those of the groups before it, and a finish launch follows every group's pass.
+template <int MODE>
+int tail_images_launch(const vs_tail_images_desc_t* d, const float* scale, double* partials, double* energy, void* stream) {
   VS_REQUIRE(d && d->images && d->n > 0 && d->delta && d->S_h > 0 && d->S_w > 0 && (d->Cd == 1 || d->Cd == 3));
-  for (int i = 0; i < d->n; ++i) VS_REQUIRE(d->images[i].img && d->images[i].out && d->images[i].H > 0 && d->images[i].W > 0);
+  for (int i = 0; i < d->n; ++i)
+    VS_REQUIRE(d->images[i].img && (MODE == TAIL_ENERGY || d->images[i].out) && d->images[i].H > 0 && d->images[i].W > 0);
   VS_REQUIRE(!(d->attenuate && !d->hmap_lowres) || d->taps43);
-  VS_REQUIRE(!d->io_u8 || d->clamp);        // (x * 255).byte() is only defined for x in [0, 1]
+  VS_REQUIRE(MODE == TAIL_ENERGY || !d->io_u8 || d->clamp);        // (x * 255).byte() is only defined for x in [0, 1]
   if (d->attenuate != 0 && d->attenuate != 1) return VS_ERR_UNSUPPORTED;      // (2: the training forward's order, clips only)
   int n_groups = 0;
   if (const int rc = vs_images_plan(d->images, d->n, VS_IMAGES_TAIL, d->io_u8, d->S_h, d->S_w, d->antialias, nullptr, 0, &n_groups); rc != VS_OK) return rc;
   // F = total_key = n, step 1, 'repeat': frame i of delta / hmap_lowres belongs to image i; H and W are the image's (set per workgroup)
-  const TailArgs a{nullptr, nullptr, nullptr, d->delta, d->attenuate ? d->hmap_lowres : nullptr, d->n, 0, 0, d->S_h, d->S_w, d->Cd, 1,
-                   VS_VIDEO_REPEAT, d->n, d->attenuate, d->clamp, d->antialias, d->scaling_i, d->scaling_w};
+  const TailArgs base{nullptr, nullptr, nullptr, d->delta, d->attenuate ? d->hmap_lowres : nullptr, d->n, 0, 0, d->S_h, d->S_w, d->Cd, 1,
+                      VS_VIDEO_REPEAT, d->n, d->attenuate, d->clamp, d->antialias, d->scaling_i, d->scaling_w};
+  tail_args_t<MODE> a;
+  if constexpr (MODE == TAIL_BLEND) a = base;
+  else a = TailArgsX{base, scale, partials};
   JndTaps k{};
   if (d->taps43) k = taps_from(d->taps43);
   const bool full_jnd = d->attenuate && !d->hmap_lowres;
   const bool sep = full_jnd && standard_jnd_taps(d->taps43);
   return vs_images_walk(d->images, d->n, VS_IMAGES_TAIL, d->io_u8 ? 1 : 0, d->S_h, d->S_w, d->antialias ? 1 : 0, [&](const vs_images_group_t& grp) {
-    const ImagesArgs g = images_args(d->images, grp, VS_IMAGES_TAIL, d->S_h, d->S_w);
+    ImagesArgs g = images_args(d->images, grp, VS_IMAGES_TAIL, d->S_h, d->S_w);
+    if (MODE == TAIL_ENERGY)
+      for (int s = 0; s < grp.count; ++s) g.slot[s].out = nullptr, g.slot[s].preds_w = nullptr;
     const dim3 grid((unsigned)grp.first_wg[grp.count]);
     // (uint8 images keep the 43-tap form, as uint8 clips do)
-    if (d->io_u8) hipLaunchKernelGGL((embed_tail_images_kernel<unsigned char, false>), grid, dim3(256), 0, (hipStream_t)stream, g, a, k);
-    else if (sep) hipLaunchKernelGGL((embed_tail_images_kernel<float, true>), grid, dim3(256), 0, (hipStream_t)stream, g, a, k);
-    else hipLaunchKernelGGL((embed_tail_images_kernel<float, false>), grid, dim3(256), 0, (hipStream_t)stream, g, a, k);
+    if (d->io_u8) hipLaunchKernelGGL((embed_tail_images_kernel<unsigned char, false, MODE>), grid, dim3(256), 0, (hipStream_t)stream, g, a, k);
+    else if (sep) hipLaunchKernelGGL((embed_tail_images_kernel<float, true, MODE>), grid, dim3(256), 0, (hipStream_t)stream, g, a, k);
+    else hipLaunchKernelGGL((embed_tail_images_kernel<float, false, MODE>), grid, dim3(256), 0, (hipStream_t)stream, g, a, k);
+    if constexpr (MODE == TAIL_ENERGY) {
+      if (const int rc = vs_launch_status(); rc != VS_OK) return rc;
+      ListFinishArgs fa{};
+      for (int s = 0; s < grp.count; ++s) {
+        fa.first_wg[s] = grp.first_wg[s];
+        fa.frames[s] = 1;
+        fa.tiles[s] = grp.first_wg[s + 1] - grp.first_wg[s];
+        fa.dst[s] = grp.image[s];
+      }
+      hipLaunchKernelGGL(tail_list_energy_finish_kernel, dim3(1, grp.count), dim3(64), 0, (hipStream_t)stream, fa, a.partials, 3.0 / d->Cd, energy);
+      a.partials += grp.first_wg[grp.count];
+    }
     return vs_launch_status();
   });
+}
+
+}  // namespace
+
+extern "C" int vs_embed_tail_images(const vs_tail_images_desc_t* d, void* stream) {
+  return tail_images_launch<TAIL_BLEND>(d, nullptr, nullptr, nullptr, stream);
+}
+
+extern "C" int vs_embed_tail_images_scaled(const vs_tail_images_desc_t* d, const float* image_scale, void* stream) {
+  VS_REQUIRE(image_scale);
+  return tail_images_launch<TAIL_SCALED>(d, image_scale, nullptr, nullptr, stream);
+}
+
+extern "C" int vs_embed_tail_images_energy(const vs_tail_images_desc_t* d, double* partials, double* energy, void* stream) {
+  VS_REQUIRE(partials && energy);
+  return tail_images_launch<TAIL_ENERGY>(d, nullptr, partials, energy, stream);
+}
+
+extern "C" int64_t vs_tail_images_energy_partial_doubles(const vs_image_desc_t* images, int n, int io_u8, int S_h, int S_w, int antialias) {
+  if (n < 0 || (n > 0 && !images) || S_h <= 0 || S_w <= 0) return -1;
+  for (int i = 0; i < n; ++i)
+    if (images[i].H <= 0 || images[i].W <= 0) return -1;
+  int64_t total = 0;
+  const int rc = vs_images_walk(images, n, VS_IMAGES_TAIL, io_u8 ? 1 : 0, S_h, S_w, antialias ? 1 : 0, [&](const vs_images_group_t& grp) {
+    total += grp.first_wg[grp.count];
+    return (int)VS_OK;
+  });
+  return rc == VS_OK ? total : -1;
 }
 
 extern "C" int vs_resize_pre_clips(const vs_clip_desc_t* clips, int n, int io_u8, int oh, int ow, int antialias, float* dst_rgb, float mul,
@@ -1292,32 +1420,99 @@ extern "C" int vs_resize_pre_clips(const vs_clip_desc_t* clips, int n, int io_u8
   });
 }
 
-extern "C" int vs_embed_tail_clips(const vs_tail_clips_desc_t* d, void* stream) {
+namespace {
+
+// tail_images_launch for slots.  n_frames (SCALED, ENERGY): the length of frame_scale / energy; a slot that reaches past it is refused before
+// any launch.
+template <int MODE>
+int tail_clips_launch(const vs_tail_clips_desc_t* d, const float* scale, double* partials, double* energy, int n_frames, void* stream) {
   VS_REQUIRE(d && d->clips && d->n > 0 && d->delta && d->S_h > 0 && d->S_w > 0 && (d->Cd == 1 || d->Cd == 3));
   VS_REQUIRE(d->step >= 1 && d->video_mode >= 0 && d->video_mode <= 2);
   for (int i = 0; i < d->n; ++i) {
     const vs_clip_desc_t& c = d->clips[i];
-    VS_REQUIRE(c.frames && c.out && c.F > 0 && c.H > 0 && c.W > 0 && c.first_frame >= 0 && c.first_key >= 0);
+    VS_REQUIRE(c.frames && (MODE == TAIL_ENERGY || c.out) && c.F > 0 && c.H > 0 && c.W > 0 && c.first_frame >= 0 && c.first_key >= 0);
+    VS_REQUIRE(MODE == TAIL_BLEND || (int64_t)c.first_frame + c.F <= n_frames);
   }
   VS_REQUIRE(!(d->attenuate && !d->hmap_lowres) || d->taps43);
-  VS_REQUIRE(!d->io_u8 || d->clamp);        // (x * 255).byte() is only defined for x in [0, 1]
+  VS_REQUIRE(MODE == TAIL_ENERGY || !d->io_u8 || d->clamp);        // (x * 255).byte() is only defined for x in [0, 1]
   if (d->attenuate != 0 && d->attenuate != 1) return VS_ERR_UNSUPPORTED;      // (2: the training forward's order, single clips only)
   int n_groups = 0;
   if (const int rc = vs_clips_plan(d->clips, d->n, VS_IMAGES_TAIL, d->io_u8, d->S_h, d->S_w, d->antialias, nullptr, 0, &n_groups); rc != VS_OK) return rc;
   // F, H, W, total_key and the first frames of delta / hmap_lowres are the slot's (set per workgroup)
-  const TailArgs a{nullptr, nullptr, nullptr, d->delta, d->attenuate ? d->hmap_lowres : nullptr, 0, 0, 0, d->S_h, d->S_w, d->Cd, d->step,
-                   d->video_mode, 0, d->attenuate, d->clamp, d->antialias, d->scaling_i, d->scaling_w};
+  const TailArgs base{nullptr, nullptr, nullptr, d->delta, d->attenuate ? d->hmap_lowres : nullptr, 0, 0, 0, d->S_h, d->S_w, d->Cd, d->step,
+                      d->video_mode, 0, d->attenuate, d->clamp, d->antialias, d->scaling_i, d->scaling_w};
+  tail_args_t<MODE> a;
+  if constexpr (MODE == TAIL_BLEND) a = base;
+  else a = TailArgsX{base, scale, partials};
   JndTaps k{};
   if (d->taps43) k = taps_from(d->taps43);
   const bool full_jnd = d->attenuate && !d->hmap_lowres;
   const bool sep = full_jnd && standard_jnd_taps(d->taps43);
   return vs_clips_walk(d->clips, d->n, VS_IMAGES_TAIL, d->io_u8 ? 1 : 0, d->S_h, d->S_w, d->antialias ? 1 : 0, [&](const vs_images_group_t& grp) {
-    const ClipsArgs g = clips_args(d->clips, grp, VS_IMAGES_TAIL, d->S_h, d->S_w);
+    ClipsArgs g = clips_args(d->clips, grp, VS_IMAGES_TAIL, d->S_h, d->S_w);
+    if (MODE == TAIL_ENERGY)
+      for (int s = 0; s < grp.count; ++s) g.slot[s].out = nullptr, g.slot[s].preds_w = nullptr;
     const dim3 grid((unsigned)grp.first_wg[grp.count]);
     // (uint8 clips keep the 43-tap form, as vs_embed_tail does)
-    if (d->io_u8) hipLaunchKernelGGL((embed_tail_clips_kernel<unsigned char, false>), grid, dim3(256), 0, (hipStream_t)stream, g, a, k);
-    else if (sep) hipLaunchKernelGGL((embed_tail_clips_kernel<float, true>), grid, dim3(256), 0, (hipStream_t)stream, g, a, k);
-    else hipLaunchKernelGGL((embed_tail_clips_kernel<float, false>), grid, dim3(256), 0, (hipStream_t)stream, g, a, k);
+    if (d->io_u8) hipLaunchKernelGGL((embed_tail_clips_kernel<unsigned char, false, MODE>), grid, dim3(256), 0, (hipStream_t)stream, g, a, k);
+    else if (sep) hipLaunchKernelGGL((embed_tail_clips_kernel<float, true, MODE>), grid, dim3(256), 0, (hipStream_t)stream, g, a, k);
+    else hipLaunchKernelGGL((embed_tail_clips_kernel<float, false, MODE>), grid, dim3(256), 0, (hipStream_t)stream, g, a, k);
+    if constexpr (MODE == TAIL_ENERGY) {
+      if (const int rc = vs_launch_status(); rc != VS_OK) return rc;
+      ListFinishArgs fa{};
+      int most = 1;
+      for (int s = 0; s < grp.count; ++s) {
+        fa.first_wg[s] = grp.first_wg[s];
+        fa.frames[s] = g.slot[s].F;
+        fa.tiles[s] = g.slot[s].tiles;
+        fa.dst[s] = g.slot[s].first_frame;
+        most = g.slot[s].F > most ? g.slot[s].F : most;
+      }
+      hipLaunchKernelGGL(tail_list_energy_finish_kernel, dim3(most, grp.count), dim3(64), 0, (hipStream_t)stream, fa, a.partials, 3.0 / d->Cd, energy);
+      a.partials += grp.first_wg[grp.count];
+    }
     return vs_launch_status();
   });
+}
+
+}  // namespace
+
+extern "C" int vs_embed_tail_clips(const vs_tail_clips_desc_t* d, void* stream) {
+  return tail_clips_launch<TAIL_BLEND>(d, nullptr, nullptr, nullptr, 0, stream);
+}
+
+extern "C" int vs_embed_tail_clips_scaled(const vs_tail_clips_desc_t* d, const float* frame_scale, int n_frames, void* stream) {
+  VS_REQUIRE(frame_scale && n_frames > 0);
+  return tail_clips_launch<TAIL_SCALED>(d, frame_scale, nullptr, nullptr, n_frames, stream);
+}
+
+extern "C" int vs_embed_tail_clips_energy(const vs_tail_clips_desc_t* d, double* partials, double* energy, int n_frames, void* stream) {
+  VS_REQUIRE(partials && energy && n_frames > 0);
+  return tail_clips_launch<TAIL_ENERGY>(d, nullptr, partials, energy, n_frames, stream);
+}
+
+extern "C" int64_t vs_tail_clips_energy_partial_doubles(const vs_clip_desc_t* clips, int n, int io_u8, int S_h, int S_w, int antialias) {
+  if (n < 0 || (n > 0 && !clips) || S_h <= 0 || S_w <= 0) return -1;
+  for (int i = 0; i < n; ++i)
+    if (clips[i].F <= 0 || clips[i].H <= 0 || clips[i].W <= 0) return -1;
+  int64_t total = 0;
+  const int rc = vs_clips_walk(clips, n, VS_IMAGES_TAIL, io_u8 ? 1 : 0, S_h, S_w, antialias ? 1 : 0, [&](const vs_images_group_t& grp) {
+    total += grp.first_wg[grp.count];
+    return (int)VS_OK;
+  });
+  return rc == VS_OK ? total : -1;
+}
+
+extern "C" int vs_psnr_scale_items(const double* energy, const double* elems, const int32_t* first_item, int n_items, int n_groups, float target_db,
+                                   float max_scale, float* scale, void* stream) {
+  VS_REQUIRE(energy && elems && scale && n_items > 0 && std::isfinite(target_db));
+  VS_REQUIRE(!first_item || n_groups > 0);
+  const double amp = std::pow(10.0, -(double)target_db / 20.0);      // (host libm, as vs_psnr_scale)
+  if (first_item)
+    hipLaunchKernelGGL(psnr_scale_groups_kernel, dim3(n_groups), dim3(256), 0, (hipStream_t)stream, energy, elems, first_item, n_items, amp, max_scale,
+                       scale);
+  else
+    hipLaunchKernelGGL(psnr_scale_items_kernel, dim3((n_items + 255) / 256), dim3(256), 0, (hipStream_t)stream, energy, elems, n_items, amp, max_scale,
+                       scale);
+  return vs_launch_status();
 }

@@ -1632,26 +1632,75 @@ class HipEngine:
                        sum(t.numel() * t.element_size() for t in imgs) + 16 * S[0] * S[1] * n * (int(rgb is not None) + int(key is not None)))
         return rgb, key
 
-    def embed_tail_images(self, imgs, outs, delta, *, hmap_low, attenuate, clamp, antialias, scaling_i, scaling_w, preds_w=None):
-        """embed_tail (one frame, step 1) on a list of device images: image i takes frame i of delta [n,Cd,S,S] and of hmap_low; outs[i]
-        (and preds_w[i], fp32 [Cd,H,W]) are written with the bits embed_tail gives that image."""
-        n = len(imgs)
+    def _tail_images_desc(self, imgs, outs, delta, *, hmap_low, attenuate, clamp, antialias, scaling_i, scaling_w, preds_w=None):
+        """vs_tail_images_desc_t of a list of device images -> (descriptor, its HOST array, which the descriptor points into; is uint8)"""
         u8 = imgs[0].dtype == torch.uint8
-        for t, o in zip(imgs, outs):
-            if o.dtype != t.dtype or o.shape != t.shape:
-                raise ValueError("every image needs an output of its own shape and dtype")
         d = N.TailImagesDesc()
         descs = N.image_descs(imgs, outs, preds_w)
-        d.images, d.n = descs, n
+        d.images, d.n = descs, len(imgs)
         d.delta, d.hmap_lowres = N.ptr(delta), N.ptr(hmap_low)
         d.taps43 = C.cast(self.taps43, C.c_void_p)
         d.S_h, d.S_w, d.Cd = delta.shape[-2], delta.shape[-1], delta.shape[1]
         d.attenuate, d.clamp, d.antialias, d.io_u8 = int(attenuate), int(clamp), int(antialias), int(u8)
         d.scaling_i, d.scaling_w = float(scaling_i), float(scaling_w)
+        return d, descs, u8
+
+    def embed_tail_images(self, imgs, outs, delta, *, hmap_low, attenuate, clamp, antialias, scaling_i, scaling_w, preds_w=None,
+                          frame_scale: Optional[torch.Tensor] = None):
+        """embed_tail (one frame, step 1) on a list of device images: image i takes frame i of delta [n,Cd,S,S] and of hmap_low; outs[i]
+        (and preds_w[i], fp32 [Cd,H,W]) are written with the bits embed_tail gives that image.  frame_scale (fp32 [n] on the device): the
+        strength of image i instead of scaling_w (vs_embed_tail_images_scaled)."""
+        for t, o in zip(imgs, outs):
+            if o.dtype != t.dtype or o.shape != t.shape:
+                raise ValueError("every image needs an output of its own shape and dtype")
+        d, descs, u8 = self._tail_images_desc(imgs, outs, delta, hmap_low=hmap_low, attenuate=attenuate, clamp=clamp, antialias=antialias,
+                                              scaling_i=scaling_i, scaling_w=scaling_w, preds_w=preds_w)
+        if frame_scale is not None and (frame_scale.dtype != torch.float32 or frame_scale.numel() != d.n or not frame_scale.is_contiguous()):
+            raise ValueError("frame_scale must be a contiguous fp32 tensor with one strength per image")
         ev = self._shell_t0()
-        N.check(self.lib.vs_embed_tail_images(C.byref(d), N.stream()), "vs_embed_tail_images")
-        self._shell_t1(ev, "embed_tail_images_kernel" + ("<u8>" if u8 else ""), 2 * sum(t.numel() * t.element_size() for t in imgs)
+        if frame_scale is not None:
+            N.check(self.lib.vs_embed_tail_images_scaled(C.byref(d), N.ptr(frame_scale), N.stream()), "vs_embed_tail_images_scaled")
+        else:
+            N.check(self.lib.vs_embed_tail_images(C.byref(d), N.stream()), "vs_embed_tail_images")
+        self._shell_t1(ev, ("embed_tail_images_scaled_kernel" if frame_scale is not None else "embed_tail_images_kernel") + ("<u8>" if u8 else ""),
+                       2 * sum(t.numel() * t.element_size() for t in imgs)
                        + (sum(p.numel() * 4 for p in preds_w) if preds_w is not None else 0) + delta.numel() * 4)
+
+    def tail_energy_images(self, imgs, delta, *, hmap_low, attenuate, antialias, energy: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """vs_embed_tail_images_energy: float64 [n], (3 / Cd) * the sum of d * d over image i, d the perturbation embed_tail_images computes
+        with the same arguments (its preds_w).  No image is stored, nothing is synchronised.  `energy`: where the result goes."""
+        d, descs, u8 = self._tail_images_desc(imgs, None, delta, hmap_low=hmap_low, attenuate=attenuate, clamp=True, antialias=antialias,
+                                              scaling_i=1.0, scaling_w=1.0)
+        if energy is None:
+            energy = torch.empty(d.n, device=self.dev, dtype=torch.float64)
+        if energy.dtype != torch.float64 or energy.numel() != d.n or not energy.is_contiguous():
+            raise ValueError("energy must be a contiguous float64 tensor with one entry per image")
+        n = int(self.lib.vs_tail_images_energy_partial_doubles(descs, d.n, int(u8), d.S_h, d.S_w, d.antialias))
+        if n < 0:
+            raise N.NativeError("vs_tail_images_energy_partial_doubles refused the list")
+        part = self.buf("tail.energy", 2 * n).view(torch.float64)
+        ev = self._shell_t0()
+        N.check(self.lib.vs_embed_tail_images_energy(C.byref(d), N.ptr(part), N.ptr(energy), N.stream()), "vs_embed_tail_images_energy")
+        self._shell_t1(ev, "embed_tail_images_energy_kernel" + ("<u8>" if u8 else ""),
+                       (sum(t.numel() * t.element_size() for t in imgs) if (attenuate and hmap_low is None) else 0) + delta.numel() * 4)
+        return energy
+
+    def psnr_scale_items(self, energy: torch.Tensor, elems: torch.Tensor, target_psnr: float, *, first_item: Optional[torch.Tensor] = None,
+                         max_scale: Optional[float] = None, scale: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """vs_psnr_scale_items: float64 [n] energies of items of elems[i] (float64 [n]) elements -> fp32 [n] strengths that put every item
+        at target_psnr; first_item (int32 [groups + 1] on the device): every run of items [first_item[g], first_item[g + 1]) gets one
+        strength from its summed energy over its summed elements."""
+        n = energy.numel()
+        if scale is None:
+            scale = torch.empty(n, device=self.dev, dtype=torch.float32)
+        if elems.dtype != torch.float64 or elems.numel() != n or energy.dtype != torch.float64 or scale.dtype != torch.float32 or scale.numel() != n:
+            raise ValueError("energy and elems are float64 [n], scale is fp32 [n]")
+        if first_item is not None and (first_item.dtype != torch.int32 or first_item.numel() < 2 or not first_item.is_contiguous()):
+            raise ValueError("first_item must be a contiguous int32 prefix of at least two entries")
+        N.check(self.lib.vs_psnr_scale_items(N.ptr(energy), N.ptr(elems), N.ptr(first_item), n, first_item.numel() - 1 if first_item is not None else 0,
+                                             float(target_psnr), float(max_scale) if max_scale else 0.0, N.ptr(scale), N.stream()),
+                "vs_psnr_scale_items")
+        return scale
 
     def resize_pre_clips(self, slots, S: Tuple[int, int], antialias: bool, *, want_rgb: bool, mul=1.0, add=0.0, want_key: bool = False,
                          key_step: int = 1, tag="rs") -> Tuple[Optional[Act], Optional[Act]]:
@@ -1672,14 +1721,9 @@ class HipEngine:
                        sum(t.numel() * t.element_size() for t, _, _ in slots) + 16 * S[0] * S[1] * ((nf if rgb else 0) + (nk if key else 0)))
         return rgb, key
 
-    def embed_tail_clips(self, slots, outs, delta, *, step, video_mode, hmap_low, attenuate, clamp, antialias, scaling_i, scaling_w, preds_w=None):
-        """embed_tail on a list of slots [(frames, first_frame, first_key)]: slot s is a clip of its own whose delta starts at key frame
-        first_key of delta [keys,Cd,S,S] and whose heat-map at frame first_frame of hmap_low; outs[s] (and preds_w[s], fp32 [F,Cd,H,W]) are
-        written with the bits embed_tail gives that slot."""
+    def _tail_clips_desc(self, slots, outs, delta, *, step, video_mode, hmap_low, attenuate, clamp, antialias, scaling_i, scaling_w, preds_w=None):
+        """vs_tail_clips_desc_t of a list of slots -> (descriptor, its HOST array, which the descriptor points into; is uint8)"""
         u8 = slots[0][0].dtype == torch.uint8
-        for (t, _, _), o in zip(slots, outs):
-            if o.dtype != t.dtype or o.shape != t.shape:
-                raise ValueError("every slot needs an output of its own shape and dtype")
         d = N.TailClipsDesc()
         descs = N.clip_descs(slots, outs, preds_w)
         d.clips, d.n = descs, len(slots)
@@ -1689,10 +1733,47 @@ class HipEngine:
         d.attenuate, d.clamp, d.antialias, d.io_u8 = int(attenuate), int(clamp), int(antialias), int(u8)
         d.scaling_i, d.scaling_w = float(scaling_i), float(scaling_w)
         d.step, d.video_mode = int(step), int(video_mode)
+        return d, descs, u8
+
+    def embed_tail_clips(self, slots, outs, delta, *, step, video_mode, hmap_low, attenuate, clamp, antialias, scaling_i, scaling_w, preds_w=None,
+                         frame_scale: Optional[torch.Tensor] = None):
+        """embed_tail on a list of slots [(frames, first_frame, first_key)]: slot s is a clip of its own whose delta starts at key frame
+        first_key of delta [keys,Cd,S,S] and whose heat-map at frame first_frame of hmap_low; outs[s] (and preds_w[s], fp32 [F,Cd,H,W]) are
+        written with the bits embed_tail gives that slot.  frame_scale (fp32 on the device, indexed like hmap_low: frame f of a slot at
+        first_frame + f): the strength of every frame instead of scaling_w (vs_embed_tail_clips_scaled)."""
+        for (t, _, _), o in zip(slots, outs):
+            if o.dtype != t.dtype or o.shape != t.shape:
+                raise ValueError("every slot needs an output of its own shape and dtype")
+        d, descs, u8 = self._tail_clips_desc(slots, outs, delta, step=step, video_mode=video_mode, hmap_low=hmap_low, attenuate=attenuate,
+                                             clamp=clamp, antialias=antialias, scaling_i=scaling_i, scaling_w=scaling_w, preds_w=preds_w)
+        if frame_scale is not None and (frame_scale.dtype != torch.float32 or not frame_scale.is_contiguous()):
+            raise ValueError("frame_scale must be a contiguous fp32 tensor with one strength per frame of the pass")
         ev = self._shell_t0()
-        N.check(self.lib.vs_embed_tail_clips(C.byref(d), N.stream()), "vs_embed_tail_clips")
-        self._shell_t1(ev, "embed_tail_clips_kernel" + ("<u8>" if u8 else ""), 2 * sum(t.numel() * t.element_size() for t, _, _ in slots)
+        if frame_scale is not None:
+            N.check(self.lib.vs_embed_tail_clips_scaled(C.byref(d), N.ptr(frame_scale), frame_scale.numel(), N.stream()), "vs_embed_tail_clips_scaled")
+        else:
+            N.check(self.lib.vs_embed_tail_clips(C.byref(d), N.stream()), "vs_embed_tail_clips")
+        self._shell_t1(ev, ("embed_tail_clips_scaled_kernel" if frame_scale is not None else "embed_tail_clips_kernel") + ("<u8>" if u8 else ""),
+                       2 * sum(t.numel() * t.element_size() for t, _, _ in slots)
                        + (sum(p.numel() * 4 for p in preds_w) if preds_w is not None else 0) + delta.numel() * 4)
+
+    def tail_energy_clips(self, slots, delta, *, step, video_mode, hmap_low, attenuate, antialias, energy: torch.Tensor) -> torch.Tensor:
+        """vs_embed_tail_clips_energy: energy (float64 on the device, indexed like hmap_low) receives, at first_frame + f, (3 / Cd) * the sum of
+        d * d over frame f of every slot, d the perturbation embed_tail_clips computes with the same arguments.  No frame is stored, nothing
+        is synchronised; entries no slot covers are left alone."""
+        d, descs, u8 = self._tail_clips_desc(slots, None, delta, step=step, video_mode=video_mode, hmap_low=hmap_low, attenuate=attenuate,
+                                             clamp=True, antialias=antialias, scaling_i=1.0, scaling_w=1.0)
+        if energy.dtype != torch.float64 or not energy.is_contiguous():
+            raise ValueError("energy must be a contiguous float64 tensor with one entry per frame of the pass")
+        n = int(self.lib.vs_tail_clips_energy_partial_doubles(descs, d.n, int(u8), d.S_h, d.S_w, d.antialias))
+        if n < 0:
+            raise N.NativeError("vs_tail_clips_energy_partial_doubles refused the list")
+        part = self.buf("tail.energy", 2 * n).view(torch.float64)
+        ev = self._shell_t0()
+        N.check(self.lib.vs_embed_tail_clips_energy(C.byref(d), N.ptr(part), N.ptr(energy), energy.numel(), N.stream()), "vs_embed_tail_clips_energy")
+        self._shell_t1(ev, "embed_tail_clips_energy_kernel" + ("<u8>" if u8 else ""),
+                       (sum(t.numel() * t.element_size() for t, _, _ in slots) if (attenuate and hmap_low is None) else 0) + delta.numel() * 4)
+        return energy
 
     def aggregate_clips(self, logits: torch.Tensor, first_row: torch.Tensor, aggregation: str) -> torch.Tensor:
         """aggregate_bits per clip: logits fp32 [rows, 1+nbits] on the device, first_row int32 [n+1] on the device -> fp32 [n, nbits]"""

@@ -714,6 +714,84 @@ class Wam(nn.Module):
                 "imgs_w": [o.view(ld + tuple(o.shape)) for o, ld in zip(outs, lead)]}
 
     @torch.no_grad()
+    def embed_images_psnr(self, imgs, target_psnr: float, msgs: torch.Tensor = None, max_scaling_w: Optional[float] = None,
+                          interpolation: dict = None, lowres_attenuation: bool = False) -> dict:
+        """`embed_images` with `blender.scaling_w` replaced, image by image, by the strength that puts that image at `target_psnr` dB against
+        its original: with d the perturbation of image i at scaling_w = 1 (its `preds_w`), E_i = (3 / Cd) * sum d^2 in float64 and
+            s_i = 10^(-target_psnr / 20) * sqrt(3 H_i W_i / E_i),   0 where E_i == 0,   at most max_scaling_w when one is given
+        (the formula of `embed_psnr`).  Image i is then image i of `embed_images` at blender.scaling_w = s_i, bit for bit.
+        Returns what `embed_images` returns plus 'scaling_w' (fp32 [n], the strengths applied) and 'energy' (float64 [n]), both on the first
+        image's device.  Per chunk: the resize, the embedder pass and the heat-map of `embed_images`, then an energy pass over the chunk
+        (vs_embed_tail_images_energy: the tail's own d, reduced per image, no image stored), the strengths (vs_psnr_scale_items) and the tail
+        with a strength per image (vs_embed_tail_images_scaled), following each other on the stream without a host synchronisation.  The
+        clamp and uint8 quantisation are not corrected for, as in `embed_psnr`.  Always eager."""
+        check_psnr_args(target_psnr, "frame", max_scaling_w)
+        imgs = list(imgs)
+        views, u8 = self._image_list(imgs, "embed_images_psnr")
+        n = len(views)
+        if u8 and not self.clamp:
+            raise ValueError("uint8 output needs clamp=True ((x * 255).byte() is undefined outside [0, 1])")
+        if msgs is None:
+            msgs = self.get_random_msg(n)
+        elif msgs.shape[0] != n:
+            raise ValueError(f"msgs has {msgs.shape[0]} rows for {n} images")
+        aa = _antialias_flag(interpolation)
+        eng = self._engine()
+        cd = self.embedder.cfg.out_ch
+        if n == 0:
+            return {"msgs": msgs, "preds_w": [], "imgs_w": [], "scaling_w": torch.zeros(0, dtype=torch.float32),
+                    "energy": torch.zeros(0, dtype=torch.float64)}
+        S = (self.img_size, self.img_size)
+        att = self.attenuation is not None
+        lowres = bool(lowres_attenuation)
+        odt = torch.uint8 if u8 else torch.float32
+        hw = [(v.shape[0], v.shape[1]) if u8 else (v.shape[1], v.shape[2]) for v in views]
+        lead = [(1,) if (not u8 and t.dim() == 4) else () for t in imgs]
+        on_dev = all(v.device == eng.dev for v in views)
+        cap = float(max_scaling_w) if max_scaling_w is not None else None
+        outs, pws = [None] * n, [None] * n
+
+        def carve(a, b):
+            """results of images [a, b) as views of one device allocation each"""
+            o = torch.empty(sum(3 * h * w for h, w in hw[a:b]), dtype=odt, device=eng.dev)
+            p = torch.empty(sum(cd * h * w for h, w in hw[a:b]), dtype=torch.float32, device=eng.dev)
+            oo, pp, io, ip = [], [], 0, 0
+            for h, w in hw[a:b]:
+                oo.append(o[io:io + 3 * h * w].view((h, w, 3) if u8 else (3, h, w)))
+                pp.append(p[ip:ip + cd * h * w].view(cd, h, w))
+                io, ip = io + 3 * h * w, ip + cd * h * w
+            return oo, pp
+
+        with torch.cuda.device(eng.dev):
+            mi = self._msgs_dev(msgs, eng.dev)
+            energy = torch.empty(n, device=eng.dev, dtype=torch.float64)
+            scale = torch.empty(n, device=eng.dev, dtype=torch.float32)
+            elems = torch.tensor([3.0 * h * w for h, w in hw], dtype=torch.float64).to(eng.dev)
+            if on_dev:
+                outs, pws = carve(0, n)
+
+            def one(ch, a, b):
+                oo, pp = (outs[a:b], pws[a:b]) if on_dev else carve(a, b)
+                rgb, key = eng.resize_pre_images(ch, S, aa, want_rgb=(att and lowres), want_key=True)
+                delta = eng.embedder_forward(key, mi[a:b], bn_train=self.embedder.training)
+                hmap = eng.jnd_lowres(rgb) if (att and lowres) else None
+                eng.tail_energy_images(ch, delta, hmap_low=hmap, attenuate=int(att), antialias=aa, energy=energy[a:b])
+                eng.psnr_scale_items(energy[a:b], elems[a:b], target_psnr, max_scale=cap, scale=scale[a:b])
+                eng.embed_tail_images(ch, oo, delta, hmap_low=hmap, attenuate=int(att), clamp=self.clamp, antialias=aa,
+                                      scaling_i=self.blender.scaling_i, scaling_w=self.blender.scaling_w, preds_w=pp, frame_scale=scale[a:b])
+                if not on_dev:        # back to where each image came from (_image_chunks synchronises before it returns)
+                    for i in range(a, b):
+                        if outs[i] is None:
+                            outs[i] = _result_buffer(oo[i - a].shape, odt, views[i].device)
+                            pws[i] = _result_buffer(pp[i - a].shape, torch.float32, views[i].device)
+                        outs[i].copy_(oo[i - a], non_blocking=True)
+                        pws[i].copy_(pp[i - a], non_blocking=True)
+            self._image_chunks(eng, views, u8, one)
+        return {"msgs": msgs, "preds_w": [p.view(ld + tuple(p.shape)) for p, ld in zip(pws, lead)],
+                "imgs_w": [o.view(ld + tuple(o.shape)) for o, ld in zip(outs, lead)],
+                "scaling_w": scale.to(views[0].device), "energy": energy.to(views[0].device)}
+
+    @torch.no_grad()
     def detect_images(self, imgs, interpolation: dict = None) -> dict:
         """`detect` (wam.py:206-234) on a list of images of different sizes (see embed_images): one resize launch group and one extractor pass
         per chunk_size images -> {'preds'}: what detect returns for n stacked frames of the processing size, on the first image's device."""
@@ -1116,7 +1194,8 @@ class Videoseal(Wam):
         without a host synchronisation; the call runs eagerly even where VIDEOSEAL_GRAPHS is set.  per="frame" walks the clip in the chunks
         of `embed` (host-resident frames move one chunk at a time); per="clip" keeps the watermark and the low-resolution heat-map of all
         chunks on the device between its two sweeps and needs frames resident on the model's device.
-        The YUV, packed-RGB, image-list and clip-list routes keep the fixed strength: they are not covered here."""
+        Lists of images and of clips have their own calls, `embed_images_psnr` and `embed_clips_psnr`.  The YUV and packed-RGB surface routes
+        keep the fixed strength: they are not covered."""
         check_psnr_args(target_psnr, per, max_scaling_w)
         if not torch.is_tensor(imgs) or imgs.dim() != 4:
             raise ValueError("embed_psnr wants fp32 frames [F, 3, H, W] or a uint8 RGB24 clip [F, H, W, 3]")
@@ -1288,6 +1367,100 @@ class Videoseal(Wam):
                         outs[c][a:a + f].copy_(o, non_blocking=True)
             self._clip_passes(eng, clips, u8, passes, one)
         return {"msgs": msgs, "imgs_w": outs}
+
+    @torch.no_grad()
+    def embed_clips_psnr(self, clips, target_psnr: float, msgs: torch.Tensor = None, per: str = "frame", max_scaling_w: Optional[float] = None,
+                         interpolation: dict = None, lowres_attenuation: bool = False) -> dict:
+        """`embed_clips` with `blender.scaling_w` replaced by the strength that puts every frame (per="frame") or every clip (per="clip") at
+        `target_psnr` dB against its original, by the formula of `embed_psnr`: s = 10^(-target_psnr / 20) * sqrt(n / E) with E the float64
+        energy of the perturbation at strength 1 over n = 3 H_i W_i elements of a frame, or over the 3 F_i H_i W_i elements of clip i with E
+        summed over all its frames -- as a whole, also where chunk_size cut the clip into several spans and passes.  0 where E == 0, at most
+        max_scaling_w when one is given.  Every frame is then that frame of `embed_clips` at blender.scaling_w = its strength, bit for bit.
+        Returns what `embed_clips` returns plus 'scaling_w' (list of fp32 [F_i], the strengths applied) and 'energy' (list of float64 [F_i]),
+        each on its clip's device.
+        per="frame": every pass of `embed_clips` is followed, on the stream, by its energy pass (vs_embed_tail_clips_energy), its strengths
+        (vs_psnr_scale_items) and the tail with a strength per frame (vs_embed_tail_clips_scaled); host-resident clips move pass by pass.
+        per="clip" makes two sweeps: the first runs the network passes and the energy passes and keeps the watermark and the low-resolution
+        heat-map of every pass on the device, one vs_psnr_scale_items call with the clip boundaries sits between them, the second runs the
+        tails.  It needs clips resident on the model's device.  No host synchronisation in either; always eager."""
+        from . import clips as CL
+        check_psnr_args(target_psnr, per, max_scaling_w)
+        if self.video_mode not in N.VIDEO_MODES:
+            raise ValueError(f"unknown video_mode {self.video_mode}")
+        clips, u8 = self._clip_list(clips, "embed_clips_psnr")
+        n = len(clips)
+        if u8 and not self.clamp:
+            raise ValueError("uint8 output needs clamp=True ((x * 255).byte() is undefined outside [0, 1])")
+        if msgs is None:
+            msgs = self.get_random_msg(n)
+        elif msgs.shape[0] != n:
+            raise ValueError(f"msgs has {msgs.shape[0]} rows for {n} clips")
+        aa = _antialias_flag(interpolation)
+        eng = self._engine()
+        if n == 0:
+            return {"msgs": msgs, "imgs_w": [], "scaling_w": [], "energy": []}
+        on_dev = all(t.device == eng.dev for t in clips if t.shape[0])
+        if per == "clip" and not on_dev:
+            raise ValueError('per="clip" keeps the watermark of every pass on the device: it wants clips resident on the model\'s device')
+        S = (self.img_size, self.img_size)
+        att = self.attenuation is not None
+        lowres = bool(lowres_attenuation)
+        step, vm = int(self.step_size), N.VIDEO_MODES[self.video_mode]
+        odt = torch.uint8 if u8 else torch.float32
+        lengths = [t.shape[0] for t in clips]
+        passes = CL.embed_passes(lengths, step, max(1, int(self.chunk_size)))
+        first = CL.first_rows(lengths)          # the frames of the list, clip after clip: the passes walk them in this order
+        total = first[-1]
+        cap = float(max_scaling_w) if max_scaling_w is not None else None
+        with torch.cuda.device(eng.dev):
+            if on_dev:          # one allocation, clip after clip
+                flat = torch.empty(sum(t.numel() for t in clips), dtype=odt, device=eng.dev)
+                outs, pos = [], 0
+                for t in clips:
+                    outs.append(flat[pos:pos + t.numel()].view(t.shape))
+                    pos += t.numel()
+            else:
+                outs = [_result_buffer(t.shape, odt, t.device) if t.shape[0] else torch.empty(t.shape, dtype=odt, device=t.device) for t in clips]
+            energy = torch.empty(total, device=eng.dev, dtype=torch.float64)
+            scale = torch.empty(total, device=eng.dev, dtype=torch.float32)
+            if passes:
+                mi = self._msgs_dev(msgs, eng.dev)
+                hw = [(t.shape[1], t.shape[2]) if u8 else (t.shape[2], t.shape[3]) for t in clips]
+                elems = torch.tensor([3.0 * h * w for (h, w), f in zip(hw, lengths) for _ in range(f)], dtype=torch.float64).to(eng.dev)
+            ekw = dict(step=step, video_mode=vm, attenuate=int(att), antialias=aa)
+            tkw = dict(clamp=self.clamp, scaling_i=self.blender.scaling_i, scaling_w=self.blender.scaling_w, **ekw)
+            kept = []
+
+            def one(slots, rows, frames):
+                # the pass owns a contiguous run of the list's frames: slot s sits at first_frame inside it
+                p0 = first[slots[0][0]] + slots[0][1]
+                p1 = first[slots[-1][0]] + slots[-1][1] + slots[-1][2]
+                desc = [(fr, ff, fk) for (_, _, _, ff, fk), fr in zip(slots, frames)]
+                rgb, key = eng.resize_pre_clips(desc, S, aa, want_rgb=(att and lowres), want_key=True, key_step=step)
+                delta = eng.embedder_forward(key, mi.index_select(0, torch.tensor(rows, device=eng.dev)), bn_train=self.embedder.training)
+                hmap = eng.jnd_lowres(rgb) if (att and lowres) else None
+                if per == "clip":         # the workspaces of the next pass would overwrite them
+                    delta, hmap = delta.clone(), (hmap.clone() if hmap is not None else None)
+                eng.tail_energy_clips(desc, delta, hmap_low=hmap, energy=energy[p0:p1], **ekw)
+                if per == "clip":
+                    kept.append((slots, desc, delta, hmap, p0, p1))
+                    return
+                eng.psnr_scale_items(energy[p0:p1], elems[p0:p1], target_psnr, max_scale=cap, scale=scale[p0:p1])
+                dst = [outs[c][a:a + f] if on_dev else torch.empty_like(fr) for (c, a, f, _, _), fr in zip(slots, frames)]
+                eng.embed_tail_clips(desc, dst, delta, hmap_low=hmap, frame_scale=scale[p0:p1], **tkw)
+                if not on_dev:        # back to where each clip came from (_clip_passes synchronises before it returns)
+                    for (c, a, f, _, _), o in zip(slots, dst):
+                        outs[c][a:a + f].copy_(o, non_blocking=True)
+            self._clip_passes(eng, clips, u8, passes, one)
+            if per == "clip" and kept:
+                eng.psnr_scale_items(energy, elems, target_psnr, first_item=torch.tensor(first, dtype=torch.int32).to(eng.dev), max_scale=cap,
+                                     scale=scale)
+                for slots, desc, delta, hmap, p0, p1 in kept:
+                    dst = [outs[c][a:a + f] for (c, a, f, _, _) in slots]
+                    eng.embed_tail_clips(desc, dst, delta, hmap_low=hmap, frame_scale=scale[p0:p1], **tkw)
+        return {"msgs": msgs, "imgs_w": outs,
+                "scaling_w": [scale[first[i]:first[i + 1]].to(clips[i].device) for i in range(n)],
+                "energy": [energy[first[i]:first[i + 1]].to(clips[i].device) for i in range(n)]}
 
     def _detect_clip_rows(self, eng: HipEngine, clips, u8: bool, aa: bool) -> Optional[torch.Tensor]:
         """the detector's output for every frame of the flattened list, on the device (None for a list without frames): one resize launch group

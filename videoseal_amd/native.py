@@ -58,6 +58,9 @@ EXPORTS = [
 # the entry points of include/videoseal_regions.h (a header of its own: tests/test_host.py holds EXPORTS to what videoseal_hip.h declares)
 REGION_EXPORTS = ["vs_embed_tail_regions", "vs_pixel_vote_regions_partial_doubles", "vs_pixel_vote_regions", "vs_label_boxes"]
 REGIONS_MAX = 8                                              # VS_REGIONS_MAX
+# the entry points of include/videoseal_lists_psnr.h (target PSNR on the image and clip lists; a header of its own for the same reason)
+LIST_PSNR_EXPORTS = ["vs_tail_images_energy_partial_doubles", "vs_embed_tail_images_energy", "vs_embed_tail_images_scaled",
+                     "vs_tail_clips_energy_partial_doubles", "vs_embed_tail_clips_energy", "vs_embed_tail_clips_scaled", "vs_psnr_scale_items"]
 
 
 class NativeError(RuntimeError):
@@ -457,6 +460,11 @@ def lib() -> C.CDLL:
         "vs_embed_tail_regions": [C.POINTER(TailDesc), P, I, P],
         "vs_pixel_vote_regions": [P, I64, P, I, I, I, I, I, I, I, F, P, P, P, P, P],
         "vs_label_boxes": [P, I, I, I, I, P, P],
+        "vs_embed_tail_images_energy": [C.POINTER(TailImagesDesc), P, P, P],
+        "vs_embed_tail_images_scaled": [C.POINTER(TailImagesDesc), P, P],
+        "vs_embed_tail_clips_energy": [C.POINTER(TailClipsDesc), P, P, I, P],
+        "vs_embed_tail_clips_scaled": [C.POINTER(TailClipsDesc), P, I, P],
+        "vs_psnr_scale_items": [P, P, P, I, I, F, F, P, P],
         "vs_disc_input": [P, I, I, I, P, P, P],
         "vs_disc_input_bwd": [P, I, I, I, P, P, P],
         "vs_groupnorm_lrelu": [P, I64, I, I, I, I, P, P, F, F, P, P, P, P, I64, P],
@@ -499,6 +507,10 @@ def lib() -> C.CDLL:
     L.vs_pixel_bce_partial_doubles.argtypes = [I, I, I64]
     L.vs_pixel_vote_regions_partial_doubles.restype = C.c_int64
     L.vs_pixel_vote_regions_partial_doubles.argtypes = [I, I, I64, I]
+    L.vs_tail_images_energy_partial_doubles.restype = C.c_int64
+    L.vs_tail_images_energy_partial_doubles.argtypes = [C.POINTER(ImageDesc), I, I, I, I, I]
+    L.vs_tail_clips_energy_partial_doubles.restype = C.c_int64
+    L.vs_tail_clips_energy_partial_doubles.argtypes = [C.POINTER(ClipDesc), I, I, I, I, I]
     L.vs_groupnorm_partial_doubles.restype = C.c_int64
     L.vs_groupnorm_partial_doubles.argtypes = [I, I, I]
     L.vs_conv4x4_wgrad_partial_floats.restype = C.c_int64
