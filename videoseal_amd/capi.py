@@ -59,6 +59,10 @@ def _bind(L):
     L.vs_model_embed_rgb.restype = I
     L.vs_model_detect_rgb.argtypes = [P, C.POINTER(N.RgbSurface), I, I, I, I, P, P, I64, P]
     L.vs_model_detect_rgb.restype = I
+    L.vs_model_embed_half.argtypes = [P, C.POINTER(N.HalfSurface), C.POINTER(N.HalfSurface), P, I, I, I, I, I, I, I, I, P, I64, P]
+    L.vs_model_embed_half.restype = I
+    L.vs_model_detect_half.argtypes = [P, C.POINTER(N.HalfSurface), I, I, I, I, P, P, I64, P]
+    L.vs_model_detect_half.restype = I
     L._model_api_bound = True
 
 
@@ -261,4 +265,31 @@ class CModel:
         sin = N.rgb_surface(src.tensor, fmt)
         N.check(self._L.vs_model_detect_rgb(self._h, C.byref(sin), F_, H, W, int(antialias), N.ptr(logits), N.ptr(ws), ws.numel(), N.stream()),
                 "vs_model_detect_rgb")
+        return logits
+
+    def embed_half(self, clip: torch.Tensor, msgs: torch.Tensor, *, value_range: str = "unit", layout: str = "nchw", out: Optional[torch.Tensor] = None,
+                   step: int = 1, video_mode: int = 0, lowres_attenuation: bool = False, antialias: bool = True) -> torch.Tensor:
+        """vs_model_embed_half on a device-resident float16 / bfloat16 clip (halfpix.py; any pitch); `out`: where the watermarked clip goes
+        (default: a new compact clip of the same memory form).  msgs [1, k], or [frames, k] with step = 1 (image mode).  Returns the output clip."""
+        from . import halfpix
+        F_, H, W = halfpix.check_clip(clip, layout, value_range)
+        src = halfpix.Clip(clip, layout, value_range)
+        if out is not None:
+            halfpix.check_clip(out, layout, value_range, "out")
+        dst = halfpix.Clip(out, layout, value_range) if out is not None else src.empty_like()
+        m = msgs.to(device=src.device, dtype=torch.int32).contiguous()
+        ws = self._workspace(F_, H, W, step)
+        sin, sout = N.half_surface(src.tensor, layout, value_range), N.half_surface(dst.tensor, layout, value_range)
+        N.check(self._L.vs_model_embed_half(self._h, C.byref(sin), C.byref(sout), N.ptr(m), m.shape[0], F_, H, W, step, video_mode,
+                                            int(lowres_attenuation), int(antialias), N.ptr(ws), ws.numel(), N.stream()), "vs_model_embed_half")
+        return dst.tensor
+
+    def detect_half(self, clip: torch.Tensor, *, value_range: str = "unit", layout: str = "nchw", antialias: bool = True) -> torch.Tensor:
+        from . import halfpix
+        F_, H, W = halfpix.check_clip(clip, layout, value_range)
+        logits = torch.empty(F_, self.cfg.nbits + 1, device=clip.device)
+        ws = self._workspace(F_, H, W, 1)
+        sin = N.half_surface(clip, layout, value_range)
+        N.check(self._L.vs_model_detect_half(self._h, C.byref(sin), F_, H, W, int(antialias), N.ptr(logits), N.ptr(ws), ws.numel(), N.stream()),
+                "vs_model_detect_half")
         return logits

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "vs_common.h"
+#include "videoseal_half.h"
 
 #pragma clang fp contract(off)      // host-side weight folding must round like the torch ops it restates (no fused multiply-add)
 
@@ -330,6 +331,9 @@ struct Runner {
   // io = 4 (vs_model_*_rgb): the packed RGB surfaces
   const vs_rgb_surface_t* psrc = nullptr;
   const vs_rgb_surface_t* pdst = nullptr;
+  // io = 5 (vs_model_*_half): the half-precision surfaces
+  const vs_half_surface_t* hsrc = nullptr;
+  const vs_half_surface_t* hdst = nullptr;
   // vs_model_embed_psnr: the strength of every frame comes from a target PSNR (scale_out: device, [frames])
   struct Psnr { float target_db; int per_clip; float max_scale; float* scale_out; };
   const Psnr* psnr = nullptr;
@@ -788,13 +792,14 @@ struct Runner {
   }
   // model.py::_embed_frames_eager
   // io: 0 = fp32 NCHW, 3 = the YUV surface `ysrc` (io_u8 = 2 arrives here as a contiguous nv12 surface), 4 = the packed RGB surface `psrc`,
-  // any other value = RGB24
+  // 5 = the half-precision surface `hsrc`, any other value = RGB24
   void resize(const void* imgs, int io, int F, int H, int W, int S, int antialias, float* rgb, float mul, float add, float* key, int step,
               const float* ymat) {
     if (!live()) return;
     const bool u8 = io != 0;
     if (io == 3) chk(vs_resize_pre_yuv(ysrc, F, H, W, ydec, S, S, antialias, rgb, mul, add, key, step, ymat, st));
     else if (io == 4) chk(vs_resize_pre_rgb(psrc, F, H, W, S, S, antialias, rgb, mul, add, key, step, ymat, st));
+    else if (io == 5) chk(vs_resize_pre_half(hsrc, F, H, W, S, S, antialias, rgb, mul, add, key, step, ymat, st));
     else if (u8) chk(vs_resize_pre_u8(static_cast<const unsigned char*>(imgs), F, H, W, S, S, antialias, rgb, mul, add, key, step, ymat, st));
     else chk(vs_resize_pre(static_cast<const float*>(imgs), F, 3, H, W, S, S, antialias, rgb, mul, add, key, step, ymat, st));
   }
@@ -835,6 +840,17 @@ struct Runner {
       n.attenuate = att ? 1 : 0; n.clamp = c.clamp; n.antialias = antialias;
       n.scaling_i = c.scaling_i; n.scaling_w = c.scaling_w;
       if (live()) chk(vs_embed_tail_rgb(&n, st));
+      return;
+    }
+    if (io == 5) {
+      vs_tail_half_desc_t n;
+      std::memset(&n, 0, sizeof(n));
+      n.src = *hsrc; n.dst = *hdst; n.preds_w = preds_w; n.delta = delta; n.hmap_lowres = hmap; n.taps43 = m->taps43;
+      n.F = F; n.H = H; n.W = W; n.S_h = Sh; n.S_w = Sw; n.Cd = c.out_ch;
+      n.step = step; n.video_mode = video_mode; n.total_key = nk;
+      n.attenuate = att ? 1 : 0; n.clamp = c.clamp; n.antialias = antialias;
+      n.scaling_i = c.scaling_i; n.scaling_w = c.scaling_w;
+      if (live()) chk(vs_embed_tail_half(&n, st));
       return;
     }
     const bool u8 = io != 0;
@@ -1250,5 +1266,32 @@ extern "C" int vs_model_detect_rgb(vs_model_t* m, const vs_rgb_surface_t* in, in
   Runner r{m, static_cast<char*>(ws), ws_bytes, 0, stream};
   r.psrc = in;
   r.detect(nullptr, 4, frames, H, W, antialias, logits);
+  return r.rc;
+}
+
+// ---- half-precision surfaces (halfpix.hip, include/videoseal_half.h): the same two entry points on vs_half_surface_t.  The formats are
+// checked by vs_resize_pre_half / vs_embed_tail_half; n_msgs = frames with step = 1 is image mode (a message per frame)
+extern "C" int vs_model_embed_half(vs_model_t* m, const vs_half_surface_t* in, const vs_half_surface_t* out, const int32_t* msgs, int n_msgs,
+                                   int frames, int H, int W, int step, int video_mode, int lowres_attenuation, int antialias, void* ws,
+                                   int64_t ws_bytes, void* stream) {
+  VS_REQUIRE(m && in && out && in->plane[0] && out->plane[0] && msgs && ws && frames > 0 && H > 0 && W > 0 && step >= 1 && ((uintptr_t)ws & 255) == 0);
+  const int nk = (frames + step - 1) / step;
+  VS_REQUIRE(n_msgs == 1 || n_msgs == nk);
+  VS_REQUIRE(video_mode >= 0 && video_mode <= 2);
+  VS_REQUIRE(m->c.clamp && in->plane[0] != out->plane[0]);
+  if (in->elem != out->elem || in->layout != out->layout || in->components != out->components || in->value_range != out->value_range)
+    return VS_ERR_UNSUPPORTED;
+  Runner r{m, static_cast<char*>(ws), ws_bytes, 0, stream};
+  r.hsrc = in; r.hdst = out;
+  r.embed(nullptr, 5, msgs, n_msgs, frames, H, W, step, video_mode, lowres_attenuation, antialias, nullptr, nullptr);
+  return r.rc;
+}
+
+extern "C" int vs_model_detect_half(vs_model_t* m, const vs_half_surface_t* in, int frames, int H, int W, int antialias, float* logits, void* ws,
+                                    int64_t ws_bytes, void* stream) {
+  VS_REQUIRE(m && in && in->plane[0] && logits && ws && frames > 0 && H > 0 && W > 0 && ((uintptr_t)ws & 255) == 0);
+  Runner r{m, static_cast<char*>(ws), ws_bytes, 0, stream};
+  r.hsrc = in;
+  r.detect(nullptr, 5, frames, H, W, antialias, logits);
   return r.rc;
 }

@@ -6,7 +6,7 @@
 //   rgba64, bgra64                uint16  [H][W][4]     words R G B A / B G R A
 //   x2rgb10, x2bgr10              uint32  [H][W]        bits 31-30 X, 29-20 R (B), 19-10 G, 9-0 B (R)
 // A format is a layout (bytes per pixel, or the 10:10:10:2 word) and the positions of R, G and B inside the pixel, which travel as kernel
-// arguments.  Not here: packed YUV, big-endian words, half-float RGB, premultiplied alpha.
+// arguments.  Not here: packed YUV, big-endian words, premultiplied alpha; half-float RGB is halfpix.hip.
 #include "rgb_surf.h"
 
 namespace {

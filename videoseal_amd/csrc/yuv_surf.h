@@ -24,14 +24,32 @@ namespace {
 struct YuvSurf { const unsigned char* p[3]; int64_t pitch[3], fs[3]; };       // bytes
 struct YuvGeo { YuvSurf s, d; Nv12Mat dec, enc; };
 
-template <bool PLANAR_, int DEPTH_, bool MSB_, int SX_ = 1, int SY_ = 1>
+// The sample codec of a surface: stored word <-> sample value, sample triple <-> RGB.  For the YUV formats a sample is an integer code and the
+// colour affines stand between codes and RGB; half_surf.h puts floating-point samples (and no matrix) behind the same four functions.
+template <int DEPTH_, bool MSB_>
+struct YuvCodec {
+  static constexpr int BPS = DEPTH_ > 8 ? 2 : 1;            // bytes per sample
+  using S = typename std::conditional<BPS == 2, unsigned short, unsigned char>::type;
+  static __device__ __forceinline__ float val(const unsigned raw) {            // stored word -> code
+    if (BPS == 1) return (float)raw;
+    return MSB_ ? (float)(raw >> 6) : (float)(raw < 1023u ? raw : 1023u);
+  }
+  static __device__ __forceinline__ S word(const float v) {                    // code value -> stored word, the one rounding
+    const int c = (int)floorf(fminf(fmaxf(v, 0.f), (float)((1 << DEPTH_) - 1)) + 0.5f);
+    return (S)(BPS == 2 && MSB_ ? c << 6 : c);
+  }
+  static __device__ __forceinline__ void rgb(const Nv12Mat& k, const float y, const float cb, const float cr, float (&out)[3]) { nv12_rgb(k, y, cb, cr, out); }
+  static __device__ __forceinline__ float aff(const Nv12Mat& k, const int r, const float a, const float b, const float c) { return nv12_aff(k, r, a, b, c); }
+};
+
+template <bool PLANAR_, int DEPTH_, bool MSB_, int SX_ = 1, int SY_ = 1, class CODEC_ = YuvCodec<DEPTH_, MSB_>>
 struct Surf {
   static_assert((SX_ == 1 && (SY_ == 0 || SY_ == 1)) || (SX_ == 0 && SY_ == 0 && PLANAR_), "4:2:0, 4:2:2, or planar 4:4:4");
   static constexpr bool PLANAR = PLANAR_;
   static constexpr int DEPTH = DEPTH_;
   static constexpr int SX = SX_, SY = SY_;                  // chroma subsampling shifts: a chroma sample serves (1 << SX) x (1 << SY) pixels
   static constexpr bool PSUB = PLANAR_ && SX_ == 1;         // planar chroma of half width: a piece serves 2 SPP luma columns
-  static constexpr int BPS = DEPTH_ > 8 ? 2 : 1;            // bytes per sample
+  static constexpr int BPS = CODEC_::BPS;                   // bytes per sample
   static constexpr int SPP = 16 / BPS;                      // samples per 16-byte piece
   static constexpr int NL = PSUB ? 2 : 1;                   // luma pieces per row of a resize chunk
   static constexpr int CW = NL * SPP;                       // luma columns of a resize chunk: one chroma piece per plane and chroma row serves them
@@ -46,18 +64,14 @@ struct Surf {
   static constexpr int PPR = TTW / SPP;                     // pieces of an output row of 256 columns
   static constexpr int OCW = PLANAR_ && !SX_ ? 2 * TTW : TTW;   // samples of an output chroma row of a tile: pairs, U then V halves, or (4:4:4) 256 of U then 256 of V
   static constexpr int OPC = OCW / SPP;                     // its pieces
-  using S = typename std::conditional<BPS == 2, unsigned short, unsigned char>::type;
+  using S = typename CODEC_::S;
   static __host__ __device__ __forceinline__ int crows(const int H) { return SY_ ? H >> 1 : H; }      // rows of a chroma plane
   static __host__ __device__ __forceinline__ int pcols(const int W) { return SX_ ? W >> 1 : W; }      // samples of a planar chroma row
 
-  static __device__ __forceinline__ float val(const unsigned raw) {            // stored word -> code
-    if (BPS == 1) return (float)raw;
-    return MSB_ ? (float)(raw >> 6) : (float)(raw < 1023u ? raw : 1023u);
-  }
-  static __device__ __forceinline__ S word(const float v) {                    // code value -> stored word, the one rounding
-    const int c = (int)floorf(fminf(fmaxf(v, 0.f), (float)((1 << DEPTH_) - 1)) + 0.5f);
-    return (S)(BPS == 2 && MSB_ ? c << 6 : c);
-  }
+  static __device__ __forceinline__ float val(const unsigned raw) { return CODEC_::val(raw); }
+  static __device__ __forceinline__ S word(const float v) { return CODEC_::word(v); }
+  static __device__ __forceinline__ void rgb(const Nv12Mat& k, const float y, const float cb, const float cr, float (&out)[3]) { CODEC_::rgb(k, y, cb, cr, out); }
+  static __device__ __forceinline__ float aff(const Nv12Mat& k, const int r, const float a, const float b, const float c) { return CODEC_::aff(k, r, a, b, c); }
   static __device__ __forceinline__ unsigned gld(const unsigned char* __restrict__ row, const int col) {      // one sample, any address
     if (BPS == 1) return row[col];
     return (unsigned)row[2 * col] | ((unsigned)row[2 * col + 1] << 8);
@@ -261,7 +275,7 @@ __global__ __launch_bounds__(256) void resize_pre_yuv_kernel(YuvSurf s, Nv12Mat 
             const int yy = row + h - y_lo;
             if (yy >= 0 && yy < wh) {                                   // (the window ends inside the frame: yy < wh => row + h < H)
               float rgb[3];
-              nv12_rgb(dec, ch.lum(h, q), ch.cb(h, q), ch.cr(h, q), rgb);
+              SF::rgb(dec, ch.lum(h, q), ch.cb(h, q), ch.cr(h, q), rgb);
 #pragma unroll
               for (int c = 0; c < 3; ++c) Lw[(c * RS_WH + yy) * RS_WW + xx] = rgb[c];
             }
@@ -307,7 +321,7 @@ __global__ __launch_bounds__(256) void resize_pre_yuv_kernel(YuvSurf s, Nv12Mat 
         const int xx = tx.lo + jx;
         float rgb[3], cb, cr;
         SF::gchroma(ur, vr, xx, cb, cr);
-        nv12_rgb(dec, SF::val(SF::gld(yr, xx)), cb, cr, rgb);
+        SF::rgb(dec, SF::val(SF::gld(yr, xx)), cb, cr, rgb);
 #pragma unroll
         for (int c = 0; c < 3; ++c) r3[c].add(wx, rgb[c]);
       }
@@ -329,7 +343,7 @@ __global__ __launch_bounds__(256) void resize_pre_yuv_kernel(YuvSurf s, Nv12Mat 
         const int xx = tx.lo + jx;
         float rgb[3], cb, cr;
         SF::gchroma(ur, vr, xx, cb, cr);
-        nv12_rgb(dec, SF::val(SF::gld(yr, xx)), cb, cr, rgb);
+        SF::rgb(dec, SF::val(SF::gld(yr, xx)), cb, cr, rgb);
 #pragma unroll
         for (int c = 0; c < 3; ++c) r[c] = __builtin_fmaf(wx, rgb[c], r[c]);
       }
@@ -436,7 +450,7 @@ __global__ __launch_bounds__(256) void resize_pre_yuv_stream_kernel(YuvSurf s, N
 #pragma unroll
           for (int h = 0; h < 2; ++h) {
             float rgb[3];
-            nv12_rgb(dec, pv.lum(h, q), SF::SChunk::cb(cu[h % SF::NCR], q), SF::SChunk::cr(cv[h % SF::NCR], q), rgb);
+            SF::rgb(dec, pv.lum(h, q), SF::SChunk::cb(cu[h % SF::NCR], q), SF::SChunk::cr(cv[h % SF::NCR], q), rgb);
 #pragma unroll
             for (int c = 0; c < 3; ++c) px[h][c][e] = rgb[c];
           }
@@ -556,7 +570,7 @@ __global__ __launch_bounds__(256) void embed_tail_yuv_kernel(TailArgs a, JndTaps
   auto pixel = [&](const int rr, const int wc, float (&rgb)[3]) __attribute__((always_inline)) {
     float cb, cr;
     SF::lchroma(CS + (rr >> SY) * CRS, wc, cb, cr);
-    nv12_rgb(g.dec, SF::val(YS[rr * NVW + wc]), cb, cr, rgb);
+    SF::rgb(g.dec, SF::val(YS[rr * NVW + wc]), cb, cr, rgb);
   };
   if (full_jnd) {       // luminance of the tile + halo, zero outside the frame (conv zero padding)
     auto lum_column = [&](const int lxx) __attribute__((always_inline)) {
@@ -664,9 +678,9 @@ __global__ __launch_bounds__(256) void embed_tail_yuv_kernel(TailArgs a, JndTaps
           const float t = blend_px(a.scaling_i, a.scaling_w, px[c], d[a.Cd == 1 ? 0 : c], hm, false);
           v[c] = t <= 0.f ? 0.f : (t >= 1.f ? 1.f : t);
         }
-        Yo[ly * TTW + lx] = SF::word(nv12_aff(g.enc, 0, v[0], v[1], v[2]));
-        cbs += nv12_aff(g.enc, 1, v[0], v[1], v[2]);
-        crs += nv12_aff(g.enc, 2, v[0], v[1], v[2]);
+        Yo[ly * TTW + lx] = SF::word(SF::aff(g.enc, 0, v[0], v[1], v[2]));
+        cbs += SF::aff(g.enc, 1, v[0], v[1], v[2]);
+        crs += SF::aff(g.enc, 2, v[0], v[1], v[2]);
       }
       if (!SY || q == 1) {                                // the block's rows are complete
         SF::ochroma(Co + (ly >> SY) * OCW, lx, live, cbs, crs);
@@ -784,7 +798,7 @@ __global__ __launch_bounds__(256) void embed_tail_yuv_stream_kernel(TailArgs a, 
     const S* B = Bst[slot];
     float cb, cr;
     SF::lchroma(B + SG * NSW + (q >> SY) * CRS, wc, cb, cr);
-    nv12_rgb(g.dec, SF::val(B[q * NSW + wc]), cb, cr, rgb);
+    SF::rgb(g.dec, SF::val(B[q * NSW + wc]), cb, cr, rgb);
   };
   Pieces pv = load_piece(-1);
   stash(0, pv);
@@ -945,9 +959,9 @@ __global__ __launch_bounds__(256) void embed_tail_yuv_stream_kernel(TailArgs a, 
           const float t = blend_px(a.scaling_i, a.scaling_w, p, d[CD == 1 ? 0 : c], hm, false);
           v[c] = t <= 0.f ? 0.f : (t >= 1.f ? 1.f : t);
         }
-        Og[j * TTW + lx] = SF::word(nv12_aff(g.enc, 0, v[0], v[1], v[2]));
-        cbs += nv12_aff(g.enc, 1, v[0], v[1], v[2]);
-        crs += nv12_aff(g.enc, 2, v[0], v[1], v[2]);
+        Og[j * TTW + lx] = SF::word(SF::aff(g.enc, 0, v[0], v[1], v[2]));
+        cbs += SF::aff(g.enc, 1, v[0], v[1], v[2]);
+        crs += SF::aff(g.enc, 2, v[0], v[1], v[2]);
       }
       if (!SY || (j & 1)) {                                    // the block's rows are complete: every lane takes part in the exchange
         SF::ochroma(Og + SG * TTW + (j >> SY) * OCW, lx, live, cbs, crs);

@@ -1533,9 +1533,13 @@ class HipEngine:
         return isinstance(x, Clip)
 
     def _surface_route(self, clip) -> "_SurfaceRoute":
-        """how a non-tensor frames argument reaches the library: a packed RGB clip (rgbpack.Clip: one tensor at any pitch, twelve formats) or
-        a YUV clip of any of the ten formats (a 4:2:0 one reaches the _yuv420 launches through the library's forwarder)"""
+        """how a non-tensor frames argument reaches the library: a half clip (halfpix.Clip: one float16 / bfloat16 tensor, planar or packed), a
+        packed RGB clip (rgbpack.Clip: one tensor at any pitch, twelve formats) or a YUV clip of any of the ten formats (a 4:2:0 one reaches the _yuv420 launches through the library's forwarder)"""
         _, H, W = clip.shape
+        from .halfpix import Clip as HalfClip
+        if isinstance(clip, HalfClip):
+            return _SurfaceRoute("half", "half-precision", lambda c: N.half_surface(c.tensor, c.layout, c.value_range), N.TailHalfDesc,
+                                 H * W * clip.components * 2, None)
         if self._rgb_clip(clip):
             from .rgbpack import pixel_bytes
             return _SurfaceRoute("rgb", "packed RGB", lambda c: N.rgb_surface(c.tensor, c.fmt), N.TailRgbDesc, H * W * pixel_bytes(clip.fmt), None)

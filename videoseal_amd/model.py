@@ -52,6 +52,14 @@ def _raw_frames(x) -> bool:
     return not torch.is_tensor(x) or x.dtype == torch.uint8
 
 
+def _refuse_half(x, what: str, why: str) -> None:
+    """float16 / bfloat16 frames have a fused route of their own (embed_half / detect_half, halfpix.py) and no other: `what` would turn them
+    into fp32 frames silently and answer in fp32"""
+    ts = x if isinstance(x, (list, tuple)) else [x]
+    if any(torch.is_tensor(t) and t.dtype in (torch.float16, torch.bfloat16) for t in ts):
+        raise NotImplementedError(f"{what} does not take half-precision clips: {why} (embed_half / detect_half take one float16 / bfloat16 clip)")
+
+
 def _empty_like(x):
     return torch.empty_like(x) if torch.is_tensor(x) else x.empty_like()
 
@@ -657,6 +665,7 @@ class Wam(nn.Module):
         low-resolution heat-map when asked, one tail over the chunk (vs_embed_tail_images) -- the pieces of `embed`, so image i equals
         what the per-image pieces give up to the batch size of the network pass.  Always eager (no hipGraph route)."""
         imgs = list(imgs)
+        _refuse_half(imgs, "embed_images", "lists of images are fp32 or uint8")
         views, u8 = self._image_list(imgs, "embed_images")
         n = len(views)
         if u8 and not self.clamp:
@@ -727,6 +736,7 @@ class Wam(nn.Module):
         clamp and uint8 quantisation are not corrected for, as in `embed_psnr`.  Always eager."""
         check_psnr_args(target_psnr, "frame", max_scaling_w)
         imgs = list(imgs)
+        _refuse_half(imgs, "embed_images_psnr", "lists of images are fp32 or uint8")
         views, u8 = self._image_list(imgs, "embed_images_psnr")
         n = len(views)
         if u8 and not self.clamp:
@@ -1066,6 +1076,7 @@ class Videoseal(Wam):
         are not on the model's device move chunk by chunk, and their labels with them.  The embedder runs in eval mode.  The strength is
         blender.scaling_w for every region: `embed_psnr` takes no label map (its strength comes from the energy of ONE watermark over the frame)."""
         from . import regions as RG
+        _refuse_half(imgs, "embed_regions", "half clips carry no label maps")
         F_, H, W, u8 = RG.check_frames(imgs, "embed_regions")
         RG.check_labels(labels, F_, H, W)
         R = RG.check_msgs(msgs, F_, is_video)
@@ -1197,6 +1208,7 @@ class Videoseal(Wam):
         Lists of images and of clips have their own calls, `embed_images_psnr` and `embed_clips_psnr`.  The YUV and packed-RGB surface routes
         keep the fixed strength: they are not covered."""
         check_psnr_args(target_psnr, per, max_scaling_w)
+        _refuse_half(imgs, "embed_psnr", "the half surface route keeps the fixed strength")
         if not torch.is_tensor(imgs) or imgs.dim() != 4:
             raise ValueError("embed_psnr wants fp32 frames [F, 3, H, W] or a uint8 RGB24 clip [F, H, W, 3]")
         u8 = imgs.dtype == torch.uint8
@@ -1323,6 +1335,8 @@ class Videoseal(Wam):
         from . import clips as CL
         if self.video_mode not in N.VIDEO_MODES:
             raise ValueError(f"unknown video_mode {self.video_mode}")
+        clips = list(clips)
+        _refuse_half(clips, "embed_clips", "lists of clips are fp32 or uint8")
         clips, u8 = self._clip_list(clips, "embed_clips")
         n = len(clips)
         if u8 and not self.clamp:
@@ -1387,6 +1401,8 @@ class Videoseal(Wam):
         check_psnr_args(target_psnr, per, max_scaling_w)
         if self.video_mode not in N.VIDEO_MODES:
             raise ValueError(f"unknown video_mode {self.video_mode}")
+        clips = list(clips)
+        _refuse_half(clips, "embed_clips_psnr", "lists of clips are fp32 or uint8")
         clips, u8 = self._clip_list(clips, "embed_clips_psnr")
         n = len(clips)
         if u8 and not self.clamp:
@@ -1642,6 +1658,64 @@ class Videoseal(Wam):
         from . import rgbpack
         rgbpack.check_clip(clip, fmt, "detect_rgb")
         return self._detect_yuv(rgbpack.Clip(clip, fmt), "detect_rgb", interpolation)
+
+    # ---- half-precision clips (videoseal_amd/halfpix.py): what an image or video generator's decoder hands over
+    def _half_clip(self, imgs, what: str, value_range: str, layout: str):
+        from . import halfpix
+        if isinstance(imgs, (list, tuple)):
+            raise NotImplementedError(f"{what} takes one clip: lists of images or clips (embed_images / embed_clips) are fp32 or uint8")
+        if torch.is_tensor(imgs) and imgs.dtype not in halfpix.DTYPES:
+            raise ValueError(f"{what} wants a float16 or bfloat16 clip, got {imgs.dtype}: fp32 frames go to embed / detect, integer ones to "
+                             f"embed_rgb / detect_rgb")
+        halfpix.check_clip(imgs, layout, value_range, what)
+        return halfpix.Clip(imgs, layout, value_range)
+
+    @torch.no_grad()
+    def embed_half(self, imgs: torch.Tensor, msgs: torch.Tensor = None, is_video: bool = True, value_range: str = "unit", layout: str = "nchw",
+                   interpolation: dict = None, lowres_attenuation: bool = True) -> dict:
+        """imgs: a float16 or bfloat16 clip (halfpix.py): layout "nchw" [F, 3, H, W], planar or channels-last memory, or "nhwc" [F, H, W, 3 | 4]
+        (the fourth component is alpha); value_range "unit" (values in [0, 1]) or "signed" ([-1, 1], as a VAE decoder leaves them); any row
+        pitch and frame stride -> {'imgs_w': a compact clip of the same dtype, shape and memory form, 'msgs'}.  Means: halfpix.from_rgb(embed(
+        halfpix.to_rgb(imgs), msgs, is_video=..., lowres_attenuation=...)['imgs_w'], like=imgs), bit for bit, with both conversions fused into
+        the resize and tail kernels: no fp32 frame is written; alpha of the result is the clip's, bit for bit.  is_video=False is image mode:
+        a message row per frame (msgs [F, k], or random), the embedder on every frame, no 'preds_w'.  Needs clamp=True."""
+        clip = self._half_clip(imgs, "embed_half", value_range, layout)
+        if is_video:
+            out, msgs = self._embed_yuv(clip, "embed_half", msgs, interpolation, lowres_attenuation)
+            return {"imgs_w": out.tensor, "msgs": msgs}
+        if not self.clamp:
+            raise NotImplementedError("embed_half needs clamp=True (words are undefined outside the value range)")
+        F_ = clip.shape[0]
+        if msgs is None:
+            msgs = self.get_random_msg(F_)
+        elif msgs.shape[0] != F_:
+            raise ValueError(f"msgs has {msgs.shape[0]} rows for {F_} images")
+        if F_ == 0 or clip.numel() == 0:
+            return {"imgs_w": clip.clone().tensor, "msgs": msgs}
+        eng = self._engine()
+        aa = _antialias_flag(interpolation)
+        with torch.cuda.device(eng.dev):
+            mi = self._msgs_dev(msgs, eng.dev)
+            out = self._run_chunks(eng, clip, max(1, int(getattr(self, "chunk_size", 32))),
+                                   lambda fr, oc, a, b: self._embed_frames(eng, fr, mi[a:b], oc, step=1, video_mode=0, antialias=aa,
+                                                                           lowres=lowres_attenuation))
+        return {"imgs_w": out.tensor, "msgs": msgs}
+
+    @torch.no_grad()
+    def detect_half(self, imgs: torch.Tensor, is_video: bool = True, value_range: str = "unit", layout: str = "nchw",
+                    interpolation: dict = None) -> dict:
+        """imgs, value_range, layout as in embed_half -> {'preds': [F, 1+nbits]}: detect(halfpix.to_rgb(imgs), is_video=...)['preds'] with the
+        conversion fused into the resize kernel.  As for fp32 frames, is_video=True walks the clip in chunks of chunk_size frames and
+        is_video=False sends all frames through the extractor in one pass."""
+        clip = self._half_clip(imgs, "detect_half", value_range, layout)
+        if is_video or clip.shape[0] == 0:
+            return self._detect_yuv(clip, "detect_half", interpolation)
+        self._per_frame_rows_only("detect_half")
+        eng = self._engine()
+        aa = _antialias_flag(interpolation)
+        with torch.cuda.device(eng.dev):
+            fr = clip if clip.device == eng.dev else clip.to(eng.dev)
+            return {"preds": self._detect_frames(eng, fr, (self.img_size, self.img_size), aa).to(clip.device)}
 
     def extract_message(self, imgs: torch.Tensor, aggregation: str = "avg",
                         interpolation: dict = {"mode": "bilinear", "align_corners": False, "antialias": False}) -> torch.Tensor:

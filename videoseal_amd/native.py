@@ -61,6 +61,9 @@ REGIONS_MAX = 8                                              # VS_REGIONS_MAX
 # the entry points of include/videoseal_lists_psnr.h (target PSNR on the image and clip lists; a header of its own for the same reason)
 LIST_PSNR_EXPORTS = ["vs_tail_images_energy_partial_doubles", "vs_embed_tail_images_energy", "vs_embed_tail_images_scaled",
                      "vs_tail_clips_energy_partial_doubles", "vs_embed_tail_clips_energy", "vs_embed_tail_clips_scaled", "vs_psnr_scale_items"]
+# the entry points of include/videoseal_half.h (float16 / bfloat16 surfaces; a header of its own for the same reason)
+HALF_EXPORTS = ["vs_sizeof_half_surface", "vs_sizeof_tail_half_desc", "vs_resize_pre_half", "vs_embed_tail_half", "vs_model_embed_half",
+                "vs_model_detect_half"]
 
 
 class NativeError(RuntimeError):
@@ -191,6 +194,39 @@ def rgb_surface(clip, fmt: str) -> RgbSurface:
     s.pitch = clip.stride(1) * clip.element_size()
     s.frame_stride = clip.stride(0) * clip.element_size()
     s.format = fmt_info(fmt)[0]
+    return s
+
+
+class HalfSurface(C.Structure):
+    """mirror of vs_half_surface_t: plane addresses (packed: one), row pitches and frame strides in bytes, element type, layout, components,
+    value range (VS_HALF_*)"""
+    _fields_ = [
+        ("plane", C.c_void_p * 3), ("pitch", C.c_int64 * 3), ("frame_stride", C.c_int64 * 3),
+        ("elem", C.c_int32), ("layout", C.c_int32), ("components", C.c_int32), ("value_range", C.c_int32),
+    ]
+
+
+class TailHalfDesc(C.Structure):
+    """mirror of vs_tail_half_desc_t: two surfaces, then TailDesc's members from preds_w on"""
+    _fields_ = [("src", HalfSurface), ("dst", HalfSurface)] + TailDesc._fields_[2:]
+
+
+def half_surface(clip, layout: str, value_range: str) -> HalfSurface:
+    """the surface of a device-resident half clip (videoseal_amd/halfpix.py) in either memory form: a strided view stays one, nothing is copied"""
+    from . import halfpix
+    s = HalfSurface()
+    form, comps = halfpix.memory_form(clip, layout)
+    s.elem, s.layout, s.components, s.value_range = halfpix.DTYPES[clip.dtype], form, comps, halfpix.RANGES[value_range]
+    es = clip.element_size()
+    if form == halfpix.PLANAR:
+        for i in range(3):
+            s.plane[i] = ptr(clip) + i * clip.stride(1) * es
+            s.pitch[i] = clip.stride(2) * es
+            s.frame_stride[i] = clip.stride(0) * es
+    else:
+        s.plane[0] = ptr(clip)
+        s.pitch[0] = clip.stride(1 if layout == "nhwc" else 2) * es
+        s.frame_stride[0] = clip.stride(0) * es
     return s
 
 
@@ -367,6 +403,8 @@ def lib() -> C.CDLL:
         "vs_embed_tail_yuv": [C.POINTER(TailYuvDesc), P],
         "vs_resize_pre_rgb": [C.POINTER(RgbSurface), I, I, I, I, I, I, P, F, F, P, I, P, P],
         "vs_embed_tail_rgb": [C.POINTER(TailRgbDesc), P],
+        "vs_resize_pre_half": [C.POINTER(HalfSurface), I, I, I, I, I, I, P, F, F, P, I, P, P],
+        "vs_embed_tail_half": [C.POINTER(TailHalfDesc), P],
         "vs_resize_pre_images": [C.POINTER(ImageDesc), I, I, I, I, I, P, F, F, P, P, P],
         "vs_embed_tail_images": [C.POINTER(TailImagesDesc), P],
         "vs_images_plan": [C.POINTER(ImageDesc), I, I, I, I, I, I, C.POINTER(ImagesGroup), I, C.POINTER(C.c_int)],
@@ -521,6 +559,7 @@ def lib() -> C.CDLL:
     L.vs_sizeof_yuv420_surface.restype = L.vs_sizeof_tail_yuv420_desc.restype = C.c_int
     L.vs_sizeof_yuv_surface.restype = L.vs_sizeof_tail_yuv_desc.restype = C.c_int
     L.vs_sizeof_rgb_surface.restype = L.vs_sizeof_tail_rgb_desc.restype = C.c_int
+    L.vs_sizeof_half_surface.restype = L.vs_sizeof_tail_half_desc.restype = C.c_int
     L.vs_sizeof_conv_plan.restype = L.vs_sizeof_cnx_stage_plan.restype = C.c_int
     if L.vs_version() != 3:
         raise NativeError(f"{LIB_PATH} has ABI version {L.vs_version()}, this binding is written for 3: rebuild (make -C videoseal_amd/csrc)")
@@ -529,8 +568,9 @@ def lib() -> C.CDLL:
             L.vs_sizeof_cnx_stage_plan() != C.sizeof(CnxStagePlan) or L.vs_sizeof_yuv420_surface() != C.sizeof(Yuv420Surface) or \
             L.vs_sizeof_tail_yuv420_desc() != C.sizeof(TailYuv420Desc) or L.vs_sizeof_yuv_surface() != C.sizeof(YuvSurface) or \
             L.vs_sizeof_tail_yuv_desc() != C.sizeof(TailYuvDesc) or L.vs_sizeof_rgb_surface() != C.sizeof(RgbSurface) or \
-            L.vs_sizeof_tail_rgb_desc() != C.sizeof(TailRgbDesc):
-        raise NativeError("ctypes mirrors of vs_conv_desc_t / vs_tail_desc_t / vs_tail_nv12_desc_t / vs_tail_yuv420_desc_t / vs_tail_yuv_desc_t / vs_tail_rgb_desc_t / the plan structs are out of date with the shared library")
+            L.vs_sizeof_tail_rgb_desc() != C.sizeof(TailRgbDesc) or L.vs_sizeof_half_surface() != C.sizeof(HalfSurface) or \
+            L.vs_sizeof_tail_half_desc() != C.sizeof(TailHalfDesc):
+        raise NativeError("ctypes mirrors of vs_conv_desc_t / vs_tail_desc_t / vs_tail_nv12_desc_t / vs_tail_yuv420_desc_t / vs_tail_yuv_desc_t / vs_tail_rgb_desc_t / vs_tail_half_desc_t / the plan structs are out of date with the shared library")
     _lib = L
     return L
 

@@ -17,7 +17,7 @@ Rules, with top = 2^depth - 1 and depth 8, 16 or 10:
              floor((c / top) * top) == c in fp32 for every code of the three depths, so an unwatermarked pixel comes back unchanged.
     Alpha    the alpha component (the two X bits) of an output pixel is the source pixel's, bit for bit; it never enters arithmetic.
              RGB is straight, not premultiplied.  Without a source (`like=None`) alpha is opaque (all ones) and X is 3.
-Not supported: big-endian words, half-float RGB, premultiplied alpha, packed YUV.
+Not supported: big-endian words, premultiplied alpha, packed YUV.  Half-float RGB (float16 / bfloat16) has a module of its own: halfpix.py.
 """
 from __future__ import annotations
 
