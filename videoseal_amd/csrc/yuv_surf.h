@@ -1,6 +1,7 @@
 // YUV frames as a decoder delivers them: vs_resize_pre and vs_embed_tail (shell.hip) with the colour conversion fused in, each way.  Four
 // kernels (resize and tail, each as a tile form and a row-streaming form), one body per kernel, a surface trait per format.  This header holds
-// the trait, the kernel bodies and their launchers; yuv420.hip instantiates the 4:2:0 traits, yuv4xx.hip the 4:2:2 and 4:4:4 ones.
+// the trait, the kernel bodies and their launchers; yuv420.hip instantiates the 4:2:0 traits, yuv4xx.hip the 4:2:2 and 4:4:4 ones, yuv_clips.hip
+// the list forms of three of the kernels (lists of clips: the same bodies behind another prologue, see "Where a workgroup works" below).
 //   nv12       uint8   Y plane + interleaved CbCr plane           i420       uint8   Y, U, V planes
 //   p010       uint16  as nv12, code = word >> 6                  yuv420p10  uint16  as i420, code = min(word, 1023)
 //   nv16 / p210: as nv12 / p010 with a chroma row per luma row;  yuv422p / yuv422p10: as i420 / yuv420p10 with a chroma row per luma row;
@@ -234,18 +235,90 @@ struct Surf {
   };
 };
 
+// ---- Where a workgroup works: the prologue of the three kernels that have a list form (the two tile kernels and the row-streaming resize).
+// Grid form: the launch has ONE surface; blockIdx.{x, y, z} are (tile column, tile row, frame) and H, W, the destinations and the tail's
+// arguments are the launch's.  List form (vs_resize_pre_yuv_clips / vs_embed_tail_yuv_clips, videoseal_yuv_clips.h): the launch is a flat
+// grid over at most VS_YUV_CLIPS_PER_LAUNCH slots whose descriptors and prefix table of first workgroups travel in the kernel arguments; a
+// workgroup finds its slot by the halving search of images_find (shell.hip) -- four steps -- and (frame, tile row, tile column) as clips_item
+// does, frame-major.  Everything it finds is workgroup-uniform: scalar loads and scalar compares, the slot's pointers and sizes stay in SGPRs.
+// The body sees a slot as a clip of its own: dst_rgb / hmap_lowres moved to the slot's first frame, dst_key / delta to its first key frame,
+// total_key = ceil(F / step).  The kernels take the source (and the tail's geometry) as a template parameter and ask the overloads below;
+// for the grid form every one of them is the identity, so the grid instantiations compile to the instructions they had before the list
+// forms existed, and the statements after the prologue are one text for both.
+constexpr int YUV_CLIPS = 16;      // VS_YUV_CLIPS_PER_LAUNCH (yuv_clips.hip holds the two together)
+struct YuvClipSlot { YuvSurf s, d; int F, H, W, first_frame, first_key, cols, tiles, pad_; };      // cols: tiles per tile row; tiles: per frame
+struct YuvClipsArgs {
+  int first_wg[YUV_CLIPS + 1];       // entries past the launch's slot count hold the grid size: never reached by a workgroup
+  int pad_;
+  YuvClipSlot slot[YUV_CLIPS];
+};
+struct YuvClipsGeo { YuvClipsArgs c; Nv12Mat dec, enc; };
+struct YuvGeoRef { const YuvSurf& s; const YuvSurf& d; const Nv12Mat& dec; const Nv12Mat& enc; };      // a slot's YuvGeo, in place
+
+struct YuvAt { int k, f; unsigned bx, by; };       // slot, frame of the slot, tile column, tile row (unsigned, as blockIdx is: x0 = bx * TTW is the grid form's expression)
+__device__ __forceinline__ YuvAt yuv_at(const YuvSurf&) { return YuvAt{0, (int)blockIdx.z, blockIdx.x, blockIdx.y}; }
+__device__ __forceinline__ YuvAt yuv_at(const YuvGeo&) { return YuvAt{0, (int)blockIdx.z, blockIdx.x, blockIdx.y}; }
+__device__ __forceinline__ YuvAt yuv_at(const YuvClipsArgs& g) {
+  const int wg = blockIdx.x;
+  int k = 0;
+#pragma unroll
+  for (int s = YUV_CLIPS / 2; s >= 1; s >>= 1)
+    if (wg >= g.first_wg[k + s]) k += s;
+  const int t = wg - g.first_wg[k];
+  const int tiles = g.slot[k].tiles, cols = g.slot[k].cols;
+  const int f = t / tiles;
+  const int r = t - f * tiles;
+  const int by = r / cols;
+  return YuvAt{k, f, (unsigned)(r - by * cols), (unsigned)by};
+}
+__device__ __forceinline__ YuvAt yuv_at(const YuvClipsGeo& g) { return yuv_at(g.c); }
+__device__ __forceinline__ const YuvSurf& yuv_src(const YuvSurf& s, const int) { return s; }
+__device__ __forceinline__ const YuvSurf& yuv_src(const YuvClipsArgs& g, const int k) { return g.slot[k].s; }
+__device__ __forceinline__ int yuv_h(const YuvSurf&, const int, const int H) { return H; }
+__device__ __forceinline__ int yuv_h(const YuvClipsArgs& g, const int k, const int) { return g.slot[k].H; }
+__device__ __forceinline__ int yuv_w(const YuvSurf&, const int, const int W) { return W; }
+__device__ __forceinline__ int yuv_w(const YuvClipsArgs& g, const int k, const int) { return g.slot[k].W; }
+// the resize's destinations, moved to the slot's first frame / first key frame (frame: oh x ow x 4 floats)
+__device__ __forceinline__ float* yuv_rgb_at(const YuvSurf&, const int, float* p, const int, const int) { return p; }
+__device__ __forceinline__ float* yuv_rgb_at(const YuvClipsArgs& g, const int k, float* p, const int oh, const int ow) {
+  return p ? p + g.slot[k].first_frame * ((int64_t)oh * ow * 4) : nullptr;
+}
+__device__ __forceinline__ float* yuv_key_at(const YuvSurf&, const int, float* p, const int, const int) { return p; }
+__device__ __forceinline__ float* yuv_key_at(const YuvClipsArgs& g, const int k, float* p, const int oh, const int ow) {
+  return p ? p + g.slot[k].first_key * ((int64_t)oh * ow * 4) : nullptr;
+}
+// the tail's arguments and geometry of the slot (as embed_tail_clips_kernel of shell.hip sets them)
+__device__ __forceinline__ void yuv_tail_args(const YuvGeo&, const int, TailArgs&) {}
+__device__ __forceinline__ void yuv_tail_args(const YuvClipsGeo& g, const int k, TailArgs& a) {
+  a.F = g.c.slot[k].F;
+  a.H = g.c.slot[k].H;
+  a.W = g.c.slot[k].W;
+  a.total_key = (a.F + a.step - 1) / a.step;
+  const int64_t splane = (int64_t)a.Sh * a.Sw;
+  a.delta += g.c.slot[k].first_key * splane * a.Cd;
+  if (a.hmap_lowres) a.hmap_lowres += g.c.slot[k].first_frame * splane;
+}
+__device__ __forceinline__ const YuvGeo& yuv_geo(const YuvGeo& g, const int) { return g; }
+__device__ __forceinline__ YuvGeoRef yuv_geo(const YuvClipsGeo& g, const int k) { return YuvGeoRef{g.c.slot[k].s, g.c.slot[k].d, g.dec, g.enc}; }
+
 // Tile form of the resize: resize_pre_kernel (shell.hip) on YUV frames -- conversion and clamp per source pixel in front of the filter, then
 // the same taps in the same order.  A workgroup owns 32 x 8 output pixels.  Staging: a task is one chunk of CW columns x one row PAIR (the luma
 // pieces of both rows and the chroma they share), converted from registers into the fp32 window in LDS; the window of at most RS_WW x RS_WH
 // pixels spans <= 15 chunks x 17 pairs, tasks taken in turn by the 256 threads.  A window that does not fit is filtered straight from the frame.
-template <class SF>
-__global__ __launch_bounds__(256) void resize_pre_yuv_kernel(YuvSurf s, Nv12Mat dec, int B, int H, int W, int oh, int ow, int antialias,
-                                                             float* __restrict__ dst_rgb, float mul, float add, float* __restrict__ dst_key,
+// SRC: YuvSurf (grid form) or YuvClipsArgs (list form: B, H_ and W_ are not used, the destinations are the whole tensors).
+template <class SF, class SRC = YuvSurf>
+__global__ __launch_bounds__(256) void resize_pre_yuv_kernel(SRC src, Nv12Mat dec, int B, int H_, int W_, int oh, int ow, int antialias,
+                                                             float* __restrict__ dst_rgb_, float mul, float add, float* __restrict__ dst_key_,
                                                              int key_step, int key_mode, float y0, float y1, float y2) {
   __shared__ float Lw[3 * RS_WH * RS_WW];
   constexpr int CW = SF::CW;
-  const int ox0 = blockIdx.x * 32, oy0 = blockIdx.y * 8;
-  const int b = blockIdx.z;
+  const YuvAt at = yuv_at(src);
+  const YuvSurf& s = yuv_src(src, at.k);
+  const int H = yuv_h(src, at.k, H_), W = yuv_w(src, at.k, W_);
+  float* __restrict__ dst_rgb = yuv_rgb_at(src, at.k, dst_rgb_, oh, ow);
+  float* __restrict__ dst_key = yuv_key_at(src, at.k, dst_key_, oh, ow);
+  const int ox0 = at.bx * 32, oy0 = at.by * 8;
+  const int b = at.f;
   const unsigned char* base = s.p[0] + (int64_t)b * s.fs[0];
   const unsigned char* ubase = s.p[1] + (int64_t)b * s.fs[1];
   const unsigned char* vbase = SF::PLANAR ? s.p[2] + (int64_t)b * s.fs[2] : ubase;
@@ -378,8 +451,8 @@ __global__ __launch_bounds__(256) void resize_pre_yuv_kernel(YuvSurf s, Nv12Mat 
 // registers into the [8][3][INW] fp32 window; the horizontal and vertical passes, their expressions and their order are resize_stream_body's
 // and the tile kernel's: the same bits.
 template <class SF> constexpr int yuv_rs_align() { return SF::CW > 16 ? SF::CW : 16; }      // window start, in columns: the margin of vs_rs::rs_pick
-template <class SF, int OW>
-__global__ __launch_bounds__(256) void resize_pre_yuv_stream_kernel(YuvSurf s, Nv12Mat dec, int H, int W, int oh, int ow, int antialias,
+template <class SF, int OW, class SRC = YuvSurf>
+__global__ __launch_bounds__(256) void resize_pre_yuv_stream_kernel(SRC src, Nv12Mat dec, int H_, int W_, int oh, int ow, int antialias,
                                                                     ResizePreEpi epi, int strip) {
   using namespace vs_rs;
   extern __shared__ __attribute__((aligned(16))) float rs_smem[];
@@ -391,7 +464,12 @@ __global__ __launch_bounds__(256) void resize_pre_yuv_stream_kernel(YuvSurf s, N
   float* Wy = Hr + RING * 3 * OW;                        // [RS_WTAB_ROWS][MT] vertical weights | first row | tap count
   int* WyLo = reinterpret_cast<int*>(Wy + RS_WTAB_ROWS * MT);
   int* WyN = WyLo + RS_WTAB_ROWS;
-  const int ox0 = blockIdx.x * OW, oy0 = blockIdx.y * strip, b = blockIdx.z;
+  const YuvAt at = yuv_at(src);
+  const YuvSurf& s = yuv_src(src, at.k);
+  const int H = yuv_h(src, at.k, H_), W = yuv_w(src, at.k, W_);
+  epi.dst_rgb = yuv_rgb_at(src, at.k, epi.dst_rgb, oh, ow);
+  epi.dst_key = yuv_key_at(src, at.k, epi.dst_key, oh, ow);
+  const int ox0 = at.bx * OW, oy0 = at.by * strip, b = at.f;
   const int oy_end = min(oh, oy0 + strip);
   const unsigned char* base = s.p[0] + (int64_t)b * s.fs[0];
   const unsigned char* ubase = s.p[1] + (int64_t)b * s.fs[1];
@@ -520,8 +598,9 @@ __global__ __launch_bounds__(256) void resize_pre_yuv_stream_kernel(YuvSurf s, N
 // With SY = 0 the window holds a chroma row per luma row (20) and the tile leaves 16 chroma rows; 4:4:4 rows hold 2 x NVW / 2 x 256 samples.
 // LDS: 55 - 69 KB for 4:2:0, up to 98 KB for yuv444p10 (one workgroup per CU): this form serves frames too small for the row-streaming one.
 constexpr int NVR = TTH + 2 * HALO;
-template <class SF>
-__global__ __launch_bounds__(256) void embed_tail_yuv_kernel(TailArgs a, JndTaps k, YuvGeo g) {
+// GEO: YuvGeo (grid form) or YuvClipsGeo (list form: F, H, W, total_key and the first frames of delta / hmap_lowres are the slot's).
+template <class SF, class GEO = YuvGeo>
+__global__ __launch_bounds__(256) void embed_tail_yuv_kernel(TailArgs a, JndTaps k, GEO geo) {
   using S = typename SF::S;
   constexpr int SPP = SF::SPP, NVW = SF::NVW, NPY = SF::NPY, NPC = SF::NPC, CRS = SF::CRS, PPR = SF::PPR, OCW = SF::OCW, OPC = SF::OPC;
   constexpr int SY = SF::SY, NVC = NVR >> SY, NOC = TTH >> SY;       // chroma rows of the window, of the output tile
@@ -534,7 +613,10 @@ __global__ __launch_bounds__(256) void embed_tail_yuv_kernel(TailArgs a, JndTaps
   __shared__ int ty_lo[TTH], ty_n[TTH];
   __shared__ float ty_w[TTH][4];
   __shared__ int s_xhi, s_nmax, s_xlo;
-  const int x0 = blockIdx.x * TTW, y0 = blockIdx.y * TTH, f = blockIdx.z;
+  const YuvAt at = yuv_at(geo);
+  yuv_tail_args(geo, at.k, a);
+  const auto& g = yuv_geo(geo, at.k);
+  const int x0 = at.bx * TTW, y0 = at.by * TTH, f = at.f;
   const bool full_jnd = a.attenuate && !a.hmap_lowres;
   if (threadIdx.x == 0) { s_xhi = 0; s_nmax = 0; }
   {     // frame samples -> LDS: NVR x NPY luma pieces, then NVC x NPC chroma pieces; all loads of a thread issued before its stores

@@ -1710,7 +1710,10 @@ class HipEngine:
                          key_step: int = 1, tag="rs") -> Tuple[Optional[Act], Optional[Act]]:
         """resize_pre on a list of slots [(frames, first_frame, first_key)] (clips.py; frames a device tensor fp32 [F,3,H,W] or uint8 RGB24
         [F,H,W,3], contiguous, all of one dtype) -> (rgb Act [frames of the pass,S,S,4] or None, key Act [key frames of the pass,S,S,4] or None),
-        every frame with the bits resize_pre gives its clip."""
+        every frame with the bits resize_pre gives its clip.  Slots whose frames are yuv.Clip objects (device-resident planes at any pitch, one
+        format and colour choice per call) take vs_resize_pre_yuv_clips: the decode is fused into the kernels."""
+        if not torch.is_tensor(slots[0][0]):
+            return self._resize_pre_yuv_clips(slots, S, antialias, want_rgb=want_rgb, mul=mul, add=add, want_key=want_key, key_step=key_step, tag=tag)
         u8 = slots[0][0].dtype == torch.uint8
         nf = max(ff + t.shape[0] for t, ff, _ in slots)
         nk = max(fk + (t.shape[0] + key_step - 1) // key_step for t, _, fk in slots)
@@ -1724,6 +1727,58 @@ class HipEngine:
         self._shell_t1(ev, "resize_pre_clips_kernel" + ("<u8>" if u8 else ""),
                        sum(t.numel() * t.element_size() for t, _, _ in slots) + 16 * S[0] * S[1] * ((nf if rgb else 0) + (nk if key else 0)))
         return rgb, key
+
+    def _yuv_clip_slots(self, slots):
+        """the checks of a list of YUV slots [(yuv.Clip, first_frame, first_key)] -> (format, colour affines, bytes of all frames)"""
+        first = slots[0][0]
+        depth, _ = self._yuv_clip(first)
+        from .yuv import Clip
+        if type(first) is not Clip:
+            raise TypeError("lists of clips take yuv.Clip slots, not packed RGB or half-precision clips")
+        nbytes = 0
+        for c, _, _ in slots:
+            _, nsamp = self._yuv_clip(c)
+            if type(c) is not type(first) or c.fmt != first.fmt or c.color != first.color:
+                raise ValueError(f"the YUV clips of one call share a format and a colour choice, got {c.fmt} {c.color} beside {first.fmt} {first.color}")
+            nbytes += c.shape[0] * nsamp * c.planes[0].element_size()
+        return first.fmt, self.yuv_arrays(first.color, depth), nbytes
+
+    def _resize_pre_yuv_clips(self, slots, S, antialias, *, want_rgb, mul, add, want_key, key_step, tag):
+        """resize_pre_clips on YUV slots (vs_resize_pre_yuv_clips)"""
+        fmt, affines, nbytes = self._yuv_clip_slots(slots)
+        nf = max(ff + c.shape[0] for c, ff, _ in slots)
+        nk = max(fk + (c.shape[0] + key_step - 1) // key_step for c, _, fk in slots)
+        rgb = self.new_act(tag + ".rgb", nf, S[0], S[1], 3, 4) if want_rgb else None
+        key = self.new_act(tag + ".key", nk, S[0], S[1], self.cfg.in_ch, 4) if want_key else None
+        descs = N.yuv_clip_descs(slots)
+        ev = self._shell_t0()
+        N.check(self.lib.vs_resize_pre_yuv_clips(descs, len(slots), affines[0], S[0], S[1], 1 if antialias else 0, N.ptr(rgb.t) if rgb else None, mul, add,
+                                                 N.ptr(key.t) if key else None, key_step, self.ymat if self.cfg.yuv else None, N.stream()),
+                "vs_resize_pre_yuv_clips")
+        self._shell_t1(ev, f"resize_pre_yuv_clips_kernel<{fmt}>", nbytes + 16 * S[0] * S[1] * ((nf if rgb else 0) + (nk if key else 0)))
+        return rgb, key
+
+    def _embed_tail_yuv_clips(self, slots, outs, delta, *, step, video_mode, hmap_low, attenuate, clamp, antialias, scaling_i, scaling_w):
+        """embed_tail_clips on YUV slots (vs_embed_tail_yuv_clips)"""
+        fmt, affines, nbytes = self._yuv_clip_slots(slots)
+        if int(attenuate) == 2:
+            raise NotImplementedError("the YUV tail has no training order of operations")
+        for (c, _, _), o in zip(slots, outs):
+            if type(o) is not type(c) or o.fmt != c.fmt or o.shape != c.shape:
+                raise ValueError("YUV frames need an output clip of the same format and size")
+        d = N.TailYuvClipsDesc()
+        descs = N.yuv_clip_descs(slots, outs)
+        d.clips, d.n = descs, len(slots)
+        d.delta, d.hmap_lowres = N.ptr(delta), N.ptr(hmap_low)
+        d.taps43 = C.cast(self.taps43, C.c_void_p)
+        d.S_h, d.S_w, d.Cd = delta.shape[-2], delta.shape[-1], delta.shape[1]
+        d.attenuate, d.clamp, d.antialias = int(attenuate), int(clamp), int(antialias)
+        d.scaling_i, d.scaling_w = float(scaling_i), float(scaling_w)
+        d.step, d.video_mode = int(step), int(video_mode)
+        d.yuv2rgb12, d.rgb2yuv12 = affines
+        ev = self._shell_t0()
+        N.check(self.lib.vs_embed_tail_yuv_clips(C.byref(d), N.stream()), "vs_embed_tail_yuv_clips")
+        self._shell_t1(ev, f"embed_tail_yuv_clips_kernel<{fmt}>", 2 * nbytes + delta.numel() * 4)
 
     def _tail_clips_desc(self, slots, outs, delta, *, step, video_mode, hmap_low, attenuate, clamp, antialias, scaling_i, scaling_w, preds_w=None):
         """vs_tail_clips_desc_t of a list of slots -> (descriptor, its HOST array, which the descriptor points into; is uint8)"""
@@ -1744,7 +1799,13 @@ class HipEngine:
         """embed_tail on a list of slots [(frames, first_frame, first_key)]: slot s is a clip of its own whose delta starts at key frame
         first_key of delta [keys,Cd,S,S] and whose heat-map at frame first_frame of hmap_low; outs[s] (and preds_w[s], fp32 [F,Cd,H,W]) are
         written with the bits embed_tail gives that slot.  frame_scale (fp32 on the device, indexed like hmap_low: frame f of a slot at
-        first_frame + f): the strength of every frame instead of scaling_w (vs_embed_tail_clips_scaled)."""
+        first_frame + f): the strength of every frame instead of scaling_w (vs_embed_tail_clips_scaled).  Slots of yuv.Clip objects (outs:
+        clips of the same format and sizes) take vs_embed_tail_yuv_clips: always the tile kernel, whatever tail_variant says."""
+        if not torch.is_tensor(slots[0][0]):
+            if preds_w is not None or frame_scale is not None:
+                raise NotImplementedError("lists of YUV clips have no preds_w and no per-frame strength")
+            return self._embed_tail_yuv_clips(slots, outs, delta, step=step, video_mode=video_mode, hmap_low=hmap_low, attenuate=attenuate, clamp=clamp,
+                                              antialias=antialias, scaling_i=scaling_i, scaling_w=scaling_w)
         for (t, _, _), o in zip(slots, outs):
             if o.dtype != t.dtype or o.shape != t.shape:
                 raise ValueError("every slot needs an output of its own shape and dtype")

@@ -1636,6 +1636,158 @@ class Videoseal(Wam):
         from . import yuv
         return self._detect_yuv(self._yuv_clip(planes, fmt, "detect_yuv", matrix, full_range, yuv), "detect_yuv", interpolation)
 
+    # ---- lists of YUV clips: the clip lists above on decoder surfaces (vs_resize_pre_yuv_clips / vs_embed_tail_yuv_clips)
+    def _yuv_clip_list(self, clips, fmt: str, what: str, matrix: str, full_range: bool):
+        """the clips as yuv.Clip objects after the checks: plane tuples of ONE format, each a valid clip of it (F may be 0)"""
+        from . import yuv
+        clips = list(clips)
+        if any(torch.is_tensor(c) for c in clips):
+            raise TypeError(f"{what} wants a sequence of plane tuples of format {fmt!r}; fp32 and uint8 RGB24 tensors go to {what[:-len('_yuv')]}")
+        yuv.fmt_info(fmt)
+        if matrix not in yuv.MATRICES:
+            raise ValueError(f"{what}: matrix must be one of {sorted(yuv.MATRICES)}, got {matrix!r}")
+        out = []
+        for i, planes in enumerate(clips):
+            if isinstance(planes, yuv.Clip):
+                if planes.fmt != fmt:
+                    raise ValueError(f"{what}: the clips of one call share a format, clip {i} is {planes.fmt}, not {fmt}")
+                planes = planes.planes
+            yuv.check_clip(planes, fmt, f"{what}: clip {i}")
+            out.append(yuv.Clip(planes, fmt, (matrix, bool(full_range))))
+        return out
+
+    def _yuv_clip_passes(self, eng: HipEngine, clips, passes, fn, restart=None) -> None:
+        """_clip_passes for yuv.Clip objects: device-resident planes are sliced in place at their own pitches, others move pass by pass"""
+        on_dev = all(c.device == eng.dev for c in clips if c.shape[0])
+        for attempt in range(2):
+            for slots, extra in passes:
+                frames = []
+                for s in slots:
+                    ch = clips[s[0]][s[1]:s[1] + s[2]]
+                    frames.append(ch if ch.device == eng.dev else ch.to(eng.dev))
+                fn(slots, extra, frames)
+            if on_dev:
+                break
+            torch.cuda.current_stream(eng.dev).synchronize()
+            if attempt or not eng.guard_tripped_after_sync():
+                break
+            if restart is not None:
+                restart()
+
+    @torch.no_grad()
+    def embed_clips_yuv(self, clips, fmt: str, msgs: torch.Tensor = None, interpolation: dict = None, lowres_attenuation: bool = True,
+                        matrix: str = "bt709", full_range: bool = False) -> dict:
+        """`embed_yuv(clip_i, fmt, msgs[i:i+1])` for every clip of a list whose clips differ in size and length, with the key frames of many
+        clips going through the U-Net as one batch, as embed_clips does for fp32 and RGB24 clips.  clips: n plane tuples as embed_yuv takes
+        them, all of format `fmt` and one colour choice (planes at any pitch and frame stride: views of decoder surfaces are fine), F_i >= 0;
+        msgs [n, k] or None (random).  -> {'planes_w': [plane tuple per clip], 'imgs_w': [the packed buffer [F_i, samples per frame] each
+        tuple views], 'msgs'}; for device-resident clips the buffers are views of one allocation per call, clip after clip.  Per pass
+        (clips.embed_passes): one resize launch set (vs_resize_pre_yuv_clips), one embedder pass with a message row per key frame, one
+        low-resolution heat-map when asked, one tail launch set (vs_embed_tail_yuv_clips, always the 16-row tile kernel).  No RGB or fp32 frame
+        is written and a 10-bit clip keeps its 10 bits.  Needs clamp=True.  Always eager (no hipGraph route)."""
+        from . import clips as CL
+        from . import yuv
+        if self.video_mode not in N.VIDEO_MODES:
+            raise ValueError(f"unknown video_mode {self.video_mode}")
+        clips = self._yuv_clip_list(clips, fmt, "embed_clips_yuv", matrix, full_range)
+        n = len(clips)
+        if not self.clamp:
+            raise NotImplementedError("embed_clips_yuv needs clamp=True (codes are undefined outside [0, 1])")
+        if msgs is None:
+            msgs = self.get_random_msg(n)
+        elif msgs.shape[0] != n:
+            raise ValueError(f"msgs has {msgs.shape[0]} rows for {n} clips")
+        if n == 0:
+            return {"msgs": msgs, "planes_w": [], "imgs_w": []}
+        eng = self._engine()
+        aa = _antialias_flag(interpolation)
+        S = (self.img_size, self.img_size)
+        att = self.attenuation is not None
+        lowres = bool(lowres_attenuation)
+        step, vm = int(self.step_size), N.VIDEO_MODES[self.video_mode]
+        passes = CL.embed_passes([c.shape[0] for c in clips], step, max(1, int(self.chunk_size)))
+        on_dev = all(c.device == eng.dev for c in clips if c.shape[0])
+        with torch.cuda.device(eng.dev):
+            if on_dev:          # one allocation, clip after clip
+                sizes = [c.shape[0] * yuv.frame_samples(fmt, c.shape[1], c.shape[2]) for c in clips]
+                flat = torch.empty(sum(sizes), dtype=yuv.fmt_dtype(fmt), device=eng.dev)
+                outs, pos = [], 0
+                for c, sz in zip(clips, sizes):
+                    buf = flat[pos:pos + sz].view(c.shape[0], -1) if c.shape[0] else flat[pos:pos].view(0, yuv.frame_samples(fmt, c.shape[1], c.shape[2]))
+                    outs.append(yuv.Clip(yuv.planes_of(buf, fmt, c.shape[1], c.shape[2]), fmt, c.color, buf))
+                    pos += sz
+            else:
+                outs = [c.empty_like() for c in clips]
+            if passes:
+                mi = self._msgs_dev(msgs, eng.dev)
+
+            def one(slots, rows, frames):
+                dst = [outs[c][a:a + f] if on_dev else fr.empty_like() for (c, a, f, _, _), fr in zip(slots, frames)]
+                desc = [(fr, ff, fk) for (_, _, _, ff, fk), fr in zip(slots, frames)]
+                rgb, key = eng.resize_pre_clips(desc, S, aa, want_rgb=(att and lowres), want_key=True, key_step=step)
+                delta = eng.embedder_forward(key, mi.index_select(0, torch.tensor(rows, device=eng.dev)), bn_train=self.embedder.training)
+                hmap = eng.jnd_lowres(rgb) if (att and lowres) else None
+                eng.embed_tail_clips(desc, dst, delta, step=step, video_mode=vm, hmap_low=hmap, attenuate=int(att), clamp=self.clamp, antialias=aa,
+                                     scaling_i=self.blender.scaling_i, scaling_w=self.blender.scaling_w)
+                if not on_dev:        # back to where each clip came from (_yuv_clip_passes synchronises before it returns)
+                    for (c, a, f, _, _), o in zip(slots, dst):
+                        outs[c][a:a + f].copy_(o, non_blocking=True)
+            self._yuv_clip_passes(eng, clips, passes, one)
+        return {"msgs": msgs, "planes_w": [o.planes for o in outs], "imgs_w": [o.buf for o in outs]}
+
+    def _detect_yuv_clip_rows(self, eng: HipEngine, clips, aa: bool) -> Optional[torch.Tensor]:
+        """_detect_clip_rows for yuv.Clip objects"""
+        from . import clips as CL
+        S = (self.img_size, self.img_size)
+        preds = []
+
+        def one(slots, _, frames):
+            rgb, _ = eng.resize_pre_clips([(fr, ff, 0) for (_, _, _, ff), fr in zip(slots, frames)], S, aa, want_rgb=True, mul=2.0, add=-1.0, tag="det.in")
+            p = eng.extractor_forward(rgb)
+            preds.append(p if eng.preds_owned else p.clone())
+        self._yuv_clip_passes(eng, clips, [(s, None) for s in CL.detect_passes([c.shape[0] for c in clips])], one, restart=preds.clear)
+        return torch.cat(preds, dim=0) if preds else None
+
+    @torch.no_grad()
+    def detect_clips_yuv(self, clips, fmt: str, interpolation: dict = None, matrix: str = "bt709", full_range: bool = False) -> dict:
+        """`detect_yuv(clip_i, fmt)` for every clip of a list (see embed_clips_yuv) -> {'preds': list of [F_i, 1+nbits]}, entry i on clip i's
+        device; the extractor runs on up to streaming.DET_BATCH frames of the flattened list at a time (clips.detect_passes)."""
+        from . import clips as CL
+        clips = self._yuv_clip_list(clips, fmt, "detect_clips_yuv", matrix, full_range)
+        if not clips:
+            return {"preds": []}
+        eng = self._engine()
+        aa = _antialias_flag(interpolation)
+        with torch.cuda.device(eng.dev):
+            rows = self._detect_yuv_clip_rows(eng, clips, aa)
+            first = CL.first_rows([c.shape[0] for c in clips])
+            return {"preds": [rows[first[i]:first[i + 1]].to(c.device) if c.shape[0] else torch.zeros(self._empty_preds_shape(), device=c.device)
+                              for i, c in enumerate(clips)]}
+
+    @torch.no_grad()
+    def extract_messages_yuv(self, clips, fmt: str, aggregation: str = "avg",
+                             interpolation: dict = {"mode": "bilinear", "align_corners": False, "antialias": False},
+                             matrix: str = "bt709", full_range: bool = False) -> torch.Tensor:
+        """`extract_message(yuv.to_rgb(clip_i, fmt), aggregation, interpolation)` for every clip of a list -> bool [n, nbits], row i for clip i
+        (on the first clip's device): detect_clips_yuv's passes, then the frame aggregation of all clips in one launch (vs_aggregate_clips); a
+        clip without frames aggregates to zeros, i.e. to all-False."""
+        from . import clips as CL
+        self._per_frame_rows_only("extract_messages_yuv")
+        if aggregation not in N.AGGREGATIONS:
+            raise ValueError(f"unknown aggregation {aggregation}")
+        clips = self._yuv_clip_list(clips, fmt, "extract_messages_yuv", matrix, full_range)
+        n, k = len(clips), self.embedder.cfg.nbits
+        if n == 0:
+            return torch.zeros((0, k), dtype=torch.bool)
+        eng = self._engine()
+        aa = _antialias_flag(interpolation)
+        with torch.cuda.device(eng.dev):
+            rows = self._detect_yuv_clip_rows(eng, clips, aa)
+            if rows is None:
+                return torch.zeros((n, k), dtype=torch.bool, device=clips[0].device)
+            first = torch.tensor(CL.first_rows([c.shape[0] for c in clips]), dtype=torch.int32, device=eng.dev)
+            return (eng.aggregate_clips(rows.contiguous(), first, aggregation) > 0).to(clips[0].device)
+
     # ---- packed RGB clips (videoseal_amd/rgbpack.py): what capture, compositors and image decoders hold, alpha / X carried through
     @torch.no_grad()
     def embed_rgb(self, clip: torch.Tensor, fmt: str, msgs: torch.Tensor = None, interpolation: dict = None,

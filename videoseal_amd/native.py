@@ -64,6 +64,10 @@ LIST_PSNR_EXPORTS = ["vs_tail_images_energy_partial_doubles", "vs_embed_tail_ima
 # the entry points of include/videoseal_half.h (float16 / bfloat16 surfaces; a header of its own for the same reason)
 HALF_EXPORTS = ["vs_sizeof_half_surface", "vs_sizeof_tail_half_desc", "vs_resize_pre_half", "vs_embed_tail_half", "vs_model_embed_half",
                 "vs_model_detect_half"]
+# the entry points of include/videoseal_yuv_clips.h (lists of YUV clips; a header of its own for the same reason)
+YUV_CLIPS_EXPORTS = ["vs_sizeof_yuv_clip_desc", "vs_sizeof_tail_yuv_clips_desc", "vs_sizeof_yuv_clips_group", "vs_resize_pre_yuv_clips",
+                     "vs_embed_tail_yuv_clips", "vs_yuv_clips_plan"]
+YUV_CLIPS_PER_LAUNCH = 16                                    # VS_YUV_CLIPS_PER_LAUNCH
 
 
 class NativeError(RuntimeError):
@@ -325,6 +329,60 @@ def clips_plan(sizes, kind: int, io_u8: bool, oh: int, ow: int, antialias: bool)
     return [(g.form, g.strip, list(g.image[:g.count]), list(g.first_wg[:g.count + 1])) for g in groups[:n.value]]
 
 
+class YuvClipDesc(C.Structure):
+    """mirror of vs_yuv_clip_desc_t: one slot of a list of YUV clips -- the surfaces of a run of frames of one clip and where it sits in the
+    processing-size tensors"""
+    _fields_ = [("src", YuvSurface), ("dst", YuvSurface), ("F", C.c_int32), ("H", C.c_int32), ("W", C.c_int32),
+                ("first_frame", C.c_int32), ("first_key", C.c_int32)]
+
+
+class TailYuvClipsDesc(C.Structure):
+    """mirror of vs_tail_yuv_clips_desc_t: TailClipsDesc's members that apply to surfaces, then the two colour affines"""
+    _fields_ = [
+        ("clips", C.POINTER(YuvClipDesc)), ("delta", C.c_void_p), ("hmap_lowres", C.c_void_p), ("taps43", C.c_void_p),
+        ("n", C.c_int32), ("S_h", C.c_int32), ("S_w", C.c_int32), ("Cd", C.c_int32),
+        ("attenuate", C.c_int32), ("clamp", C.c_int32), ("antialias", C.c_int32),
+        ("scaling_i", C.c_float), ("scaling_w", C.c_float), ("step", C.c_int32), ("video_mode", C.c_int32),
+        ("yuv2rgb12", C.c_float * 12), ("rgb2yuv12", C.c_float * 12),
+    ]
+
+
+class YuvClipsGroup(C.Structure):
+    """mirror of vs_yuv_clips_group_t: one launch of the plan"""
+    _fields_ = [("form", C.c_int32), ("count", C.c_int32), ("strip", C.c_int32), ("reserved_", C.c_int32),
+                ("slot", C.c_int32 * YUV_CLIPS_PER_LAUNCH), ("first_wg", C.c_int32 * (YUV_CLIPS_PER_LAUNCH + 1))]
+
+
+def yuv_clip_descs(slots, outs=None):
+    """the HOST descriptor array of a list of slots [(clip, first_frame, first_key)]: clip a yuv.Clip of device-resident planes at any pitch;
+    outs: one clip per slot or None.  Addresses, pitches and sizes, nothing is copied"""
+    arr = (YuvClipDesc * max(1, len(slots)))()
+    for i, (c, first_frame, first_key) in enumerate(slots):
+        arr[i].src = yuv_surface(c.planes, c.fmt)
+        if outs is not None:
+            arr[i].dst = yuv_surface(outs[i].planes, outs[i].fmt)
+        arr[i].F, arr[i].H, arr[i].W = c.shape
+        arr[i].first_frame, arr[i].first_key = first_frame, first_key
+    return arr
+
+
+def yuv_clips_plan(sizes, fmt: str, kind: int, oh: int, ow: int, antialias: bool):
+    """vs_yuv_clips_plan on a list of (F, H, W) of format `fmt`: the launches as [(form, strip, [slot indices], [first workgroups ..., grid])]
+    (no GPU involved)"""
+    from .yuv import fmt_info
+    L = lib()
+    planar, depth, msb, chroma = fmt_info(fmt)
+    arr = (YuvClipDesc * max(1, len(sizes)))()
+    for i, (F_, H, W) in enumerate(sizes):
+        arr[i].F, arr[i].H, arr[i].W = F_, H, W
+        arr[i].src.planar, arr[i].src.depth, arr[i].src.msb_aligned, arr[i].src.chroma = int(planar), depth, int(msb), chroma
+    n = C.c_int(0)
+    check(L.vs_yuv_clips_plan(arr, len(sizes), kind, oh, ow, int(antialias), None, 0, C.byref(n)), "vs_yuv_clips_plan")
+    groups = (YuvClipsGroup * max(1, n.value))()
+    check(L.vs_yuv_clips_plan(arr, len(sizes), kind, oh, ow, int(antialias), groups, n.value, C.byref(n)), "vs_yuv_clips_plan")
+    return [(g.form, g.strip, list(g.slot[:g.count]), list(g.first_wg[:g.count + 1])) for g in groups[:n.value]]
+
+
 class ResblockThinDesc(C.Structure):
     """mirror of vs_resblock_thin_desc_t"""
     _fields_ = [
@@ -412,6 +470,9 @@ def lib() -> C.CDLL:
         "vs_embed_tail_clips": [C.POINTER(TailClipsDesc), P],
         "vs_clips_plan": [C.POINTER(ClipDesc), I, I, I, I, I, I, C.POINTER(ImagesGroup), I, C.POINTER(C.c_int)],
         "vs_aggregate_clips": [P, I64, P, I, I, I, P, P],
+        "vs_resize_pre_yuv_clips": [C.POINTER(YuvClipDesc), I, P, I, I, I, P, F, F, P, I, P, P],
+        "vs_embed_tail_yuv_clips": [C.POINTER(TailYuvClipsDesc), P],
+        "vs_yuv_clips_plan": [C.POINTER(YuvClipDesc), I, I, I, I, I, C.POINTER(YuvClipsGroup), I, C.POINTER(C.c_int)],
         "vs_aug_color": [P, P, I, I, I, I, F, P, P],
         "vs_aug_crop_flip": [P, P, I, I, I, I, I, I, I, I, P],
         "vs_aug_color_chain": [P, P, I, I, I, I, C.POINTER(C.c_int), C.POINTER(C.c_float), P, P],
